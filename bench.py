@@ -13,8 +13,12 @@ in HBM.  Ranks own disjoint problem slices; the only collective is the all-gathe
   python bench.py --gpus 8 --workload gait-sweep                               configs[4]: 8 gaits x 512 commands, horizon 150, gaits split over ranks
   python bench.py --robot g1 --gait standing_trot --batch 1024                 configs[3]: G1 walk (self-defined configuration)
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (linearisation sweep) and, at N = 1,
-`cpu_baseline` (the single-thread C++ oracle timed on this box's host cores).
+Prints ONE JSON line on rank 0: the headline figure (`value`, `ms_per_step`) of the --steps timed steps and the configuration.  A plain
+run does only that: set-up, --settle and --warmup steps, the timed steps (no kernel carries an event pair), --dump-outputs.
+  python bench.py --full               also the per-kernel breakdown, four more timed regions (`timing_spread`), the fused solve mode, the job
+                                       report and gather checks, `roofline*` (linearisation sweep; the timed region then carries the events of
+                                       the roofline kernel) and, at N = 1, `cpu_baseline` (the single-thread C++ oracle timed on the host cores)
+  python bench.py --dump-outputs DIR   writes the solution of the last timed step as DIR/*.npy (float64), see dump_outputs()
 """
 import argparse
 import json
@@ -61,9 +65,14 @@ def parse_args():
                     help="trot: perturbed initial states on one gait (configs[1..3]); gait-sweep: 8 gaits x 512 velocity commands, "
                          "horizon 150, generated on the device, gaits split over the ranks (configs[4])")
     ap.add_argument("--intervals", type=int, default=None, help="horizon in shooting intervals of dt = 0.015 s (default 100; gait-sweep 150)")
-    ap.add_argument("--cpu-sample", type=int, default=256, help="problems solved by the CPU baseline (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="do not wrap kernels in HIP events")
-    ap.add_argument("--profile-all", action="store_true", help="time every kernel class inside the timed region (default: the linearisation kernel only)")
+    ap.add_argument("--full", action="store_true", help="besides the headline figure: per-kernel times, timing spread, fused solve mode, job report, "
+                    "roofline figures and CPU baselines (off: set-up, warm-up, timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the solution of the last step as DIR/<name>.npy (float64, at most 64 MB: a fixed sample of the "
+                         "problems beyond that)")
+    ap.add_argument("--cpu-sample", type=int, default=256, help="--full: problems solved by the CPU baseline (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: do not wrap kernels in HIP events")
+    ap.add_argument("--profile-all", action="store_true", help="--full: time every kernel class inside the timed region (default: the linearisation kernel only)")
     ap.add_argument("--robot", default="h1", choices=["h1", "openloong", "g1", "hunter", "h1:hard", "hunter:hard"],
                     help="h1 = the headline workload (nx = nu = 22); g1 = BASELINE.json configs[3] (nx = nu = 24, self-defined configuration); "
                          "openloong = the reference's own 12-joint robot")
@@ -71,7 +80,7 @@ def parse_args():
     ap.add_argument("--gait-start", type=float, default=0.0,
                     help="time at which the gait template of the trot workload is inserted (default 0 = SURVEY 8(d) config 2 to the letter: the template tiled "
                          "from t = 0, the solve starts on a mode switch; -1.225 = the rounds 1-4 scenario, t0 = 0 falls mid-swing)")
-    ap.add_argument("--no-fused", action="store_true", help="skip the second timed region (fused solve mode)")
+    ap.add_argument("--no-fused", action="store_true", help="--full: skip the second timed region (fused solve mode)")
     ap.add_argument("--gather", default="auto", choices=["auto", "all", "root"],
                     help="collective of the solved trajectories per step: all-gather (every rank holds every block) or gather to rank 0; auto = "
                          "root for --scaling strong and --workload gait-sweep (the north-star's \"final gather\": one job, one owner of the "
@@ -193,27 +202,30 @@ def main():
     s = torch.cuda.Stream(device=device)
     # The timed region runs the MATERIALISED formulation (the lineariser writes the reference's complete per-node LQ model): that is the
     # sweep the north-star asks to profile and the one the roofline unit (algorithmic bytes per node linearisation) is defined on.
-    # The engine's default, fused solve mode (the lineariser leaves only what the solve reads; identical solution bits) is timed in a
-    # second region of the same length and reported as `fused` ("report both").
+    # With --full, the engine's default, fused solve mode (the lineariser leaves only what the solve reads; identical solution bits) is timed
+    # in a second region of the same length and reported as `fused` ("report both").
     ddp = args.solver == "ddp"
     if ddp and sweep:
         raise SystemExit("--solver ddp runs the trot workload")
     global KERNEL_CLASSES
     if ddp:
         KERNEL_CLASSES = DDP_KERNEL_CLASSES
-    mpc = (bp.BatchedDdpMpc if ddp else bp.BatchedSqpMpc)(itf, max_batch=B, max_nodes=max_nodes, profile=(0 if args.no_profile else (1 if args.profile_all else 2)), device=device,
+    full = args.full
+    profile = (0 if args.no_profile else (1 if args.profile_all else 2)) if full else 0
+    mpc = (bp.BatchedDdpMpc if ddp else bp.BatchedSqpMpc)(itf, max_batch=B, max_nodes=max_nodes, profile=profile, device=device,
                                                           stream=s.cuda_stream, pipeline_chunks=args.chunks, materialize_lq=True)
     if sweep:
         lay = mpc.setup_commands(cp["t0"], cp["x0"], cp["gaits"], cp["gait_of_problem"], cp["gait_start"], cp["cmd_vel"], horizon=cp["horizon"])
     else:
         lay = mpc.setup(prob["t0"], prob["x0"], prob["schedule"], prob["targets"], horizon=prob["horizon"])
     n_nodes = lay["n_nodes_max"]
-    # intermediate (= linearised) nodes of this rank: per grid, times the problems on it
-    kinds = mpc.read("g_kind").reshape(B, max_nodes)          # [grid][node]; grid index < n_grids <= B
-    g_nodes = mpc.read("g_nodes")[:lay["n_grids"]].astype(int)
-    p_grid = mpc.read("p_grid")[:B].astype(int)
-    inter_of_grid = np.array([int((kinds[g, :g_nodes[g]] == 0).sum()) for g in range(lay["n_grids"])])
-    n_intermediate_total = int(inter_of_grid[p_grid].sum())     # node linearisations per launch on this rank
+    if full:
+        # intermediate (= linearised) nodes of this rank: per grid, times the problems on it
+        kinds = mpc.read("g_kind").reshape(B, max_nodes)          # [grid][node]; grid index < n_grids <= B
+        g_nodes = mpc.read("g_nodes")[:lay["n_grids"]].astype(int)
+        p_grid = mpc.read("p_grid")[:B].astype(int)
+        inter_of_grid = np.array([int((kinds[g, :g_nodes[g]] == 0).sum()) for g in range(lay["n_grids"])])
+        n_intermediate_total = int(inter_of_grid[p_grid].sum())     # node linearisations per launch on this rank
 
     with torch.cuda.stream(s):
         gather = bd.TrajectoryGather(capacity, max_nodes, nx, nu, torch.device("cuda", device), mode=args.gather)
@@ -263,82 +275,119 @@ def main():
         else:
             rank_ms_min = rank_ms
         mpc.synchronize()
-
-        t, x, u, _, stats = mpc.fetch()
-        ok = sum(1 for st in stats if st.status == 0)
-        if ddp:     # status 1 = no step length passed the Armijo test, the baseline roll-out (new gains, no feedforward increment) is the solution: a valid solve
-            ok = sum(1 for st in stats if st.status in (0, 1))
-        lin_timed = mpc.kernel_time("linearize", reset=False)         # HIP events attached to the kernel's dispatches on the launch stream, over exactly the timed steps
-        # error bar of `value`: the same region of `steps` steps four more times (the line's value stays the FIRST region, the contract's)
-        spread = [elapsed / args.steps * 1e3]
-        if world == 1:
-            mpc.set_profile(0)
-            for _ in range(4):
+        if full or args.dump_outputs:
+            t, x, u, _, stats = mpc.fetch()
+        if args.dump_outputs:
+            gathered = None
+            if world > 1 and rank == 0:         # what the per-step gather delivered to rank 0, every rank's problems in order
+                def problems_of(r):
+                    lo, hi = bd.shard_range(len(lib) if sweep else total, world, r)
+                    return (hi - lo) * (per_gait if sweep else 1)
+                blocks = [gather.block(r) for r in range(world)]
+                gathered = [torch.cat([b[i][:problems_of(r)] for r, b in enumerate(blocks)]).cpu().numpy() for i in (0, 1)]
+            if rank == 0:
+                dump_outputs(args.dump_outputs, t, x, u, stats, gathered)
+        if full:
+            ok = sum(1 for st in stats if st.status == 0)
+            if ddp:     # status 1 = no step length passed the Armijo test, the baseline roll-out (new gains, no feedforward increment) is the solution: a valid solve
+                ok = sum(1 for st in stats if st.status in (0, 1))
+            lin_timed = mpc.kernel_time("linearize", reset=False)         # HIP events attached to the kernel's dispatches on the launch stream, over exactly the timed steps
+            # error bar of `value`: the same region of `steps` steps four more times (the line's value stays the FIRST region, the contract's)
+            spread = [elapsed / args.steps * 1e3]
+            if world == 1:
+                mpc.set_profile(0)
+                for _ in range(4):
+                    fence()
+                    ts0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        step()
+                    fence(barrier=False)
+                    spread.append((time.perf_counter() - ts0) / args.steps * 1e3)
+                mpc.set_profile(0 if args.no_profile else (1 if args.profile_all else 2))
+            kt_steps = args.steps
+            if not args.no_profile and not args.profile_all:
+                # per-kernel breakdown from a short extra pass with every kernel class timed (each event pair costs 1-2 us of stream time,
+                # so the timed region itself only carries the pair around the roofline kernel)
+                mpc.set_profile(1)
+                for k in KERNEL_CLASSES:
+                    mpc.kernel_time(k, reset=True)
+                extra = kt_steps = max(3, min(args.steps, 10))
+                for _ in range(extra):
+                    step()
                 fence()
-                ts0 = time.perf_counter()
+                mpc.synchronize()
+            # whole-job report: one 40-byte all-reduce of {merit, dynamics SSE, equality SSE, failures, node
+            # linearisations}, outside the timed region
+            report = [sum(st.merit_after for st in stats), sum(st.dynamics_sse_after for st in stats), sum(st.equality_sse_after for st in stats),
+                      float(len(stats) - ok), float(n_intermediate_total)]
+            gathered_ok = gather.own_block_consistent()
+            if use_dist:
+                report = [float(v) for v in bd.reduce_stats(report).tolist()]
+                # every rank holds everybody's result: rank 0's copy of the last rank's block must be what that rank computed
+                # (checksum of the BIT PATTERNS, folded to 52 bits so that it travels exactly in a double: a floating-point sum of the same numbers
+                #  depends on the reduction order torch picks for the alignment of the view - 1 ulp apart between the local block and its gathered copy)
+                def bit_checksum(tv):
+                    w = tv.contiguous().view(torch.int64)
+                    return float(int(((w & 0xFFFFFFFF).sum() + (w >> 32).sum()).item()) % (1 << 52))
+                probe = torch.zeros(2, dtype=torch.float64)
+                if rank == world - 1:
+                    probe = torch.tensor([bit_checksum(gather.x_local), bit_checksum(gather.u_local)], dtype=torch.float64)
+                probe = bd.reduce_stats(probe.tolist())
+                if args.gather == "all" or rank == 0:       # (gather to root: only rank 0 holds the other ranks' blocks)
+                    xb, ub = gather.block(world - 1)
+                    gathered_ok = gathered_ok and bit_checksum(xb) == float(probe[0]) and bit_checksum(ub) == float(probe[1])
+            ktimes = {k: mpc.kernel_time(k, reset=False) for k in KERNEL_CLASSES}
+            # ---- second timed region: the fused solve mode, same problems, same number of steps, no kernel carries an event pair
+            fused = None
+            if not args.no_fused:
+                mpc.set_materialize(False)
+                mpc.set_profile(0)
+                for _ in range(max(1, args.warmup)):
+                    step()
+                fence()
+                tf0 = time.perf_counter()
                 for _ in range(args.steps):
                     step()
                 fence(barrier=False)
-                spread.append((time.perf_counter() - ts0) / args.steps * 1e3)
-            mpc.set_profile(0 if args.no_profile else (1 if args.profile_all else 2))
-        kt_steps = args.steps
-        if not args.no_profile and not args.profile_all:
-            # per-kernel breakdown from a short extra pass with every kernel class timed (each event pair costs 1-2 us of stream time,
-            # so the timed region itself only carries the pair around the roofline kernel)
-            mpc.set_profile(1)
-            for k in KERNEL_CLASSES:
-                mpc.kernel_time(k, reset=True)
-            extra = kt_steps = max(3, min(args.steps, 10))
-            for _ in range(extra):
-                step()
-            fence()
-            mpc.synchronize()
-        # whole-job report: one 40-byte all-reduce of {merit, dynamics SSE, equality SSE, failures, node
-        # linearisations}, outside the timed region
-        report = [sum(st.merit_after for st in stats), sum(st.dynamics_sse_after for st in stats), sum(st.equality_sse_after for st in stats),
-                  float(len(stats) - ok), float(n_intermediate_total)]
-        gathered_ok = gather.own_block_consistent()
-        if use_dist:
-            report = [float(v) for v in bd.reduce_stats(report).tolist()]
-            # every rank holds everybody's result: rank 0's copy of the last rank's block must be what that rank computed
-            # (checksum of the BIT PATTERNS, folded to 52 bits so that it travels exactly in a double: a floating-point sum of the same numbers
-            #  depends on the reduction order torch picks for the alignment of the view - 1 ulp apart between the local block and its gathered copy)
-            def bit_checksum(tv):
-                w = tv.contiguous().view(torch.int64)
-                return float(int(((w & 0xFFFFFFFF).sum() + (w >> 32).sum()).item()) % (1 << 52))
-            probe = torch.zeros(2, dtype=torch.float64)
-            if rank == world - 1:
-                probe = torch.tensor([bit_checksum(gather.x_local), bit_checksum(gather.u_local)], dtype=torch.float64)
-            probe = bd.reduce_stats(probe.tolist())
-            if args.gather == "all" or rank == 0:       # (gather to root: only rank 0 holds the other ranks' blocks)
-                xb, ub = gather.block(world - 1)
-                gathered_ok = gathered_ok and bit_checksum(xb) == float(probe[0]) and bit_checksum(ub) == float(probe[1])
-        ktimes = {k: mpc.kernel_time(k, reset=False) for k in KERNEL_CLASSES}
-        # ---- second timed region: the fused solve mode, same problems, same number of steps, no kernel carries an event pair
-        fused = None
-        if not args.no_fused:
-            mpc.set_materialize(False)
-            mpc.set_profile(0)
-            for _ in range(max(1, args.warmup)):
-                step()
-            fence()
-            tf0 = time.perf_counter()
-            for _ in range(args.steps):
-                step()
-            fence(barrier=False)
-            f_elapsed = time.perf_counter() - tf0
-            if use_dist:
-                f_elapsed = float(bd.reduce_stats([f_elapsed], op="max")[0])
-            _, xf, uf, _, _ = mpc.fetch()
-            same = bool(np.array_equal(xf, x) and np.array_equal(uf, u))
-            if use_dist:
-                same = bool(bd.reduce_stats([0.0 if same else 1.0])[0] == 0.0)
-            fused = {"value": round(total * args.steps / f_elapsed, 2), "unit": "solves/s", "ms_per_step": round(1e3 * f_elapsed / args.steps, 4),
-                     "solution_bits_equal_materialised": same, "hbm_bytes_per_step": None}
+                f_elapsed = time.perf_counter() - tf0
+                if use_dist:
+                    f_elapsed = float(bd.reduce_stats([f_elapsed], op="max")[0])
+                _, xf, uf, _, _ = mpc.fetch()
+                same = bool(np.array_equal(xf, x) and np.array_equal(uf, u))
+                if use_dist:
+                    same = bool(bd.reduce_stats([0.0 if same else 1.0])[0] == 0.0)
+                fused = {"value": round(total * args.steps / f_elapsed, 2), "unit": "solves/s", "ms_per_step": round(1e3 * f_elapsed / args.steps, 4),
+                         "solution_bits_equal_materialised": same, "hbm_bytes_per_step": None}
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         value = total * args.steps / elapsed
+        headline = (args.robot, gait, sweep, NI) == ("h1", "trot", False, 100)
+        if sweep:
+            wl = "%s gait-library sweep: %d gaits (%s) x %d velocity commands, horizon=%d intervals (dt 0.015), generated on the device, " \
+                 "gaits split over the ranks, cold start, 1 SQP iteration (BASELINE.json configs[4])" % (ROBOT_LABEL[args.robot], len(lib), ", ".join(names), per_gait, NI)
+        else:
+            wl = "%s %s (template tiled from t = %g), horizon=%d intervals (dt 0.015), %s perturbed initial states, cold start, 1 SQP iteration (%s)" % (
+                ROBOT_LABEL[args.robot], gait, args.gait_start, NI, ("batch=%d per GPU" % args.batch) if scaling == "weak" else ("global batch %d in contiguous slices" % total),
+                "the shape of BASELINE.json configs[1] through the reference's second solver, GaussNewtonDDP_MPC: 1 ILQR iteration, %d policy roll-outs per problem in the line search" % (
+                    1 + sum(1 for k in range(16) if 0.5 ** k >= 1e-2)) if ddp else
+                "BASELINE.json configs[1]" if headline and scaling == "weak" and args.batch == 256 else
+                "BASELINE.json configs[2]" if headline and scaling == "strong" and total == 4096 else
+                "BASELINE.json configs[3]" if (args.robot, gait, NI) == ("g1", "standing_trot", 100) else "not the headline workload")
+        out = {"metric": ("DDP (ILQR) " if ddp else "") + "MPC solves/s (%s, horizon=%d)" % ({"h1": "H1", "g1": "G1", "h1:hard": "H1 hard cones"}.get(args.robot, args.robot), NI), "value": round(value, 2), "unit": "solves/s", "n_gpus": world,
+               "steps": args.steps, "warmup": args.warmup, "settle_steps": max(0, args.settle), "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
+               "dtype": "f64", "data": "synthetic",
+               "config": {"workload": wl, "gait_start": (None if sweep else args.gait_start), "solver": args.solver, "global_batch": total, "problems_on_rank0": B, "shooting_nodes": n_nodes,
+                          "nx": nx, "nu": nu,
+                          "parallelism": "problem-sharded x%d, one %s of trajectories per solve (%s), overlapped with the next solve" % (
+                              world, "all-gather" if args.gather == "all" else "gather to rank 0", backend if use_dist else "none at N = 1"),
+                          "distributed": {"backend": (dist.get_backend() if use_dist else None), "world_size_seen": (dist.get_world_size() if use_dist else 1),
+                                          "gather": args.gather if use_dist else None, "devices": ("one shared device" if one_device and world > 1 else "one per rank"),
+                                          "rank_ms_per_step_min": round(rank_ms_min, 4), "rank_ms_per_step_max": round(elapsed / args.steps * 1e3, 4),
+                                          "gather_algo_requested": args.gather_algo, "gather_proto_requested": args.gather_proto,
+                                          "collective": collective_report(nccl_log, backend if use_dist else None, args.gather_report)}},
+               "ms_per_solve": round(ms_per_step / max(1, total // world), 6)}
+    if rank == 0 and full:
         lin_ms, lin_n = lin_timed
         roofline = None
         if lin_n > 0:
@@ -366,39 +415,14 @@ def main():
             # calibration of `frac` for a kernel whose HBM traffic is 97 % stores: what a write-only stream of the same bytes achieves on this
             # device, measured here, outside the timed region (tools/probes/write_roof.hip: the lineariser's own store pattern without arithmetic)
             roofline["write_roof"] = write_roof(B, int(round(n_intermediate_total / max(1.0, launches_per_step) / B)), nx, achieved)
-        headline = (args.robot, gait, sweep, NI) == ("h1", "trot", False, 100)
-        if sweep:
-            wl = "%s gait-library sweep: %d gaits (%s) x %d velocity commands, horizon=%d intervals (dt 0.015), generated on the device, " \
-                 "gaits split over the ranks, cold start, 1 SQP iteration (BASELINE.json configs[4])" % (ROBOT_LABEL[args.robot], len(lib), ", ".join(names), per_gait, NI)
-        else:
-            wl = "%s %s (template tiled from t = %g), horizon=%d intervals (dt 0.015), %s perturbed initial states, cold start, 1 SQP iteration (%s)" % (
-                ROBOT_LABEL[args.robot], gait, args.gait_start, NI, ("batch=%d per GPU" % args.batch) if scaling == "weak" else ("global batch %d in contiguous slices" % total),
-                "the shape of BASELINE.json configs[1] through the reference's second solver, GaussNewtonDDP_MPC: 1 ILQR iteration, %d policy roll-outs per problem in the line search" % (
-                    1 + sum(1 for k in range(16) if 0.5 ** k >= 1e-2)) if ddp else
-                "BASELINE.json configs[1]" if headline and scaling == "weak" and args.batch == 256 else
-                "BASELINE.json configs[2]" if headline and scaling == "strong" and total == 4096 else
-                "BASELINE.json configs[3]" if (args.robot, gait, NI) == ("g1", "standing_trot", 100) else "not the headline workload")
-        out = {"metric": ("DDP (ILQR) " if ddp else "") + "MPC solves/s (%s, horizon=%d)" % ({"h1": "H1", "g1": "G1", "h1:hard": "H1 hard cones"}.get(args.robot, args.robot), NI), "value": round(value, 2), "unit": "solves/s", "n_gpus": world,
-               "steps": args.steps, "warmup": args.warmup, "settle_steps": max(0, args.settle), "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
-               "dtype": "f64", "data": "synthetic",
-               "config": {"workload": wl, "gait_start": (None if sweep else args.gait_start), "solver": args.solver, "global_batch": total, "problems_on_rank0": B, "shooting_nodes": n_nodes,
-                          "node_linearizations_per_step": int(report[4]), "nx": nx, "nu": nu,
-                          "parallelism": "problem-sharded x%d, one %s of trajectories per solve (%s), overlapped with the next solve" % (
-                              world, "all-gather" if args.gather == "all" else "gather to rank 0", backend if use_dist else "none at N = 1"),
-                          "accepted_steps_rank0": ok,
-                          "distributed": {"backend": (dist.get_backend() if use_dist else None), "world_size_seen": (dist.get_world_size() if use_dist else 1),
-                                          "gather": args.gather if use_dist else None, "devices": ("one shared device" if one_device and world > 1 else "one per rank"),
-                                          "rank_ms_per_step_min": round(rank_ms_min, 4), "rank_ms_per_step_max": round(elapsed / args.steps * 1e3, 4),
-                                          "gather_algo_requested": args.gather_algo, "gather_proto_requested": args.gather_proto,
-                                          "collective": collective_report(nccl_log, backend if use_dist else None, args.gather_report)},
-                          "job_report": {"merit_sum": report[0], "dynamics_sse_sum": report[1], "equality_sse_sum": report[2], "failures": int(report[3]),
-                                         "gather_consistent": bool(gathered_ok)}},
-               "ms_per_solve": round(ms_per_step / max(1, total // world), 6),
-               "kernel_ms_per_step": {k: round(v[0] / max(1, kt_steps), 4) for k, v in ktimes.items()},
-               "timing_spread": {"regions": len(spread), "steps_per_region": args.steps, "ms_per_step_min": round(min(spread), 4),
-                                 "ms_per_step_median": round(float(np.median(spread)), 4), "ms_per_step_max": round(max(spread), 4),
-                                 "note": "region 1 carries the events of the roofline kernel and is `ms_per_step`; regions 2.. run without them"},
-               "roofline": roofline, "fused": fused}
+        out["config"].update({"node_linearizations_per_step": int(report[4]), "accepted_steps_rank0": ok,
+                              "job_report": {"merit_sum": report[0], "dynamics_sse_sum": report[1], "equality_sse_sum": report[2], "failures": int(report[3]),
+                                             "gather_consistent": bool(gathered_ok)}})
+        out.update({"kernel_ms_per_step": {k: round(v[0] / max(1, kt_steps), 4) for k, v in ktimes.items()},
+                    "timing_spread": {"regions": len(spread), "steps_per_region": args.steps, "ms_per_step_min": round(min(spread), 4),
+                                      "ms_per_step_median": round(float(np.median(spread)), 4), "ms_per_step_max": round(max(spread), 4),
+                                      "note": "region 1 carries the events of the roofline kernel and is `ms_per_step`; regions 2.. run without them"},
+                    "roofline": roofline, "fused": fused})
         kms = out["kernel_ms_per_step"]
         n_all_nodes = int(sum(g_nodes[p_grid])) if world == 1 else None
         if world == 1:
@@ -439,11 +463,43 @@ def main():
                         out["cpu_baseline_analytic"] = cpu_baseline_analytic(prob, min(args.cpu_sample, B), x, stats, args.robot)
                     except Exception as e:
                         out["cpu_baseline_analytic"] = {"value": None, "why": "%s: %s" % (type(e).__name__, e)}
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if use_dist:
-        assert gathered_ok, "gathered trajectories differ from the local result"
+        assert not full or gathered_ok, "gathered trajectories differ from the local result"
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60 << 20          # --dump-outputs: 64 MB in all with the sample's index files
+
+
+def dump_outputs(path, t, x, u, stats, gathered=None):
+    """--dump-outputs: what the caller of the timed solve receives after its last step, one float64 .npy per array, so that two builds
+    can be compared output for output on the same seeded problems:
+      t [B, nodes + 1], x [B, nodes + 1, nx], u [B, nodes, nu]   the solution of rank 0's problems on their shooting grids (entries past
+                                                                  stats.n_nodes are zeroed: the solver leaves them unspecified)
+      stats_<field> [B]                                           the per-problem statistics of bpmpc Stats (n_nodes, status, merit_after, ...)
+      x_gathered, u_gathered                                      N > 1: every rank's trajectories as the per-step gather delivered them
+    Beyond 64 MB in all, every array keeps the same fixed (seeded) sample of its problems, listed in problems[_gathered].npy."""
+    import numpy as np
+    from bipedal_control_amd.api import Stats
+    n = np.array([st.n_nodes for st in stats])
+    t, x, u = t.copy(), x.copy(), u.copy()
+    for b, nb in enumerate(n):
+        t[b, nb + 1:], x[b, nb + 1:], u[b, nb:] = 0.0, 0.0, 0.0
+    arrays = {"t": t, "x": x, "u": u}
+    arrays.update({"stats_" + f: np.array([getattr(st, f) for st in stats], dtype=np.float64) for f, _ in Stats._fields_ if f != "reserved"})
+    if gathered is not None:
+        arrays["x_gathered"], arrays["u_gathered"] = gathered
+    keep = min(1.0, DUMP_LIMIT_BYTES / sum(a.size * 8 for a in arrays.values()))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if keep < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(len(a), int(len(a) * keep), replace=False))
+            a = a[rows]
+            np.save(os.path.join(path, "problems_gathered.npy" if name.endswith("_gathered") else "problems.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def sq_counters_file():

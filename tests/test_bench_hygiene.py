@@ -50,3 +50,25 @@ def test_default_bench_scenario_is_config_2_to_the_letter(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     args = bench.parse_args()
     assert args.gait_start == 0.0 and args.batch == 256 and args.gpus == 1     # the trot template tiled from t = 0
+
+
+def test_dumped_outputs_are_float64_and_bounded(tmp_path):
+    """bench.py --dump-outputs: float64 arrays, entries past n_nodes zeroed, at most 64 MB in all (beyond that a fixed sample of the problems)."""
+    import numpy as np
+    from bipedal_control_amd.api import Stats
+    bench = importlib.import_module("bench")
+
+    def dump(d, B):
+        rng = np.random.default_rng(1)
+        st = (Stats * B)()
+        for b in range(B):
+            st[b].n_nodes = 100 + b % 7
+        bench.dump_outputs(str(d), rng.random((B, 117)), rng.random((B, 117, 22)) + 1.0, rng.random((B, 116, 22)) + 1.0, list(st))
+        return {p.name[:-4]: np.load(p) for p in d.iterdir()}
+    small = dump(tmp_path / "small", 8)
+    assert all(a.dtype == np.float64 for a in small.values()) and "problems" not in small and small["x"].shape == (8, 117, 22)
+    assert small["x"][1, :102].all() and not small["x"][1, 102:].any() and not small["u"][1, 101:].any() and not small["t"][1, 102:].any()
+    big = dump(tmp_path / "big", 4096)
+    assert sum(a.nbytes for a in big.values()) <= 64e6 and len(big["x"]) == len(big["problems"]) < 4096
+    assert np.array_equal(big["stats_n_nodes"], 100 + big["problems"] % 7)
+    assert np.array_equal(dump(tmp_path / "again", 4096)["problems"], big["problems"])

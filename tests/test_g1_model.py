@@ -1,5 +1,5 @@
 """Unitree G1 (BASELINE.json configs[3]) on the CPU tier: both ingests agree on the authored assets, the reduced URDF equals the
-reference's g1.urdf (when the reference tree is present), hand-derived known answers, and the oracle's dynamics on this model pass
+reference's g1.urdf (a copy under tests/golden/reference/), hand-derived known answers, and the oracle's dynamics on this model pass
 the same invariants / finite-difference checks that pin it for H1.  G1 exercises what H1 and OpenLoong do not: joint frames with a
 fixed pitch (hip pitch -0.34907, knee +0.5096, ankle -0.16053), a hip order pitch-roll-yaw, massless contact frames.
 The configuration is authored here (tools/make_assets.py): self-defined, not reference parity."""
@@ -14,7 +14,7 @@ from tests import oracle_bridge as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = os.path.join(ROOT, "assets", "g1")
-REF_URDF = "/root/reference/bipedal_robot_example/unitree_g1/g1_description/g1.urdf"
+REF_URDF = os.path.join(ROOT, "tests", "golden", "reference", "bipedal_robot_example", "unitree_g1", "g1_description", "g1.urdf")      # tests/golden/make_reference_fixtures.py
 LEG = ["hip_pitch", "hip_roll", "hip_yaw", "knee", "ankle_pitch", "ankle_roll"]
 
 
@@ -73,7 +73,6 @@ def test_g1_product_matches_oracle_ingest(both):
         assert np.abs(got - ref).max() <= 1e-15 * max(1.0, np.abs(ref).max()), name
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_URDF), reason="reference tree not present (GPU box)")
 def test_g1_reduced_urdf_equals_reference_file(both):
     """Kinematic tree and inertias parsed from the reference's g1.urdf equal those of the reduced asset (the sole frames are the
     only addition and carry no mass)."""

@@ -83,7 +83,7 @@ def test_iterations_and_convergence_flags(ctx):
 
 def test_bench_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "32", "--intervals", "40",
-                          "--cpu-sample", "4"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cpu-sample", "4", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -107,6 +107,35 @@ def test_bench_contract():
     assert abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-4
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["max_abs_x_diff_vs_gpu"] < 1e-8
     assert "workload" in d["config"] and d["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(ctx, tmp_path):
+    """Without --full the line carries the headline figure of exactly --steps timed steps and nothing measured beside it; --dump-outputs
+    writes the solution of the last timed step: the same numbers from run to run, and what the solver returns for the same problems."""
+    bp, sc, _, _ = ctx
+    itf = sc.interface("h1")            # as bench.py builds it
+
+    def bench(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--batch", "32", "--intervals", "40",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    a, b = bench(tmp_path / "a"), bench(tmp_path / "b")
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(a) and a["steps"] == 4 and a["dtype"] == "f64"
+    assert not {"roofline", "roofline_all", "cpu_baseline", "fused", "kernel_ms_per_step", "timing_spread"} & set(a)
+    assert abs(a["value"] - 32 * 1e3 / a["ms_per_step"]) <= 1e-3 * a["value"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert {"t.npy", "x.npy", "u.npy", "stats_n_nodes.npy", "stats_status.npy"} <= set(names) and names == sorted(p.name for p in (tmp_path / "b").iterdir())
+    for n in names:
+        da, db = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert da.dtype == np.float64 and np.array_equal(da, db), n
+    prob = sc.trot_problem(itf, batch=32, n_intervals=40, gait_start=0.0)
+    _, x, u, _, st = bp.BatchedSqpMpc(itf, max_batch=32, max_nodes=56).run(prob["t0"], prob["x0"], prob["schedule"], prob["targets"], horizon=prob["horizon"])
+    xd, ud, nd = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "u.npy"), np.load(tmp_path / "a" / "stats_n_nodes.npy")
+    assert xd.shape == x.shape and np.array_equal(nd, [s.n_nodes for s in st])
+    for k in range(32):
+        n = st[k].n_nodes
+        assert rel_x(xd[k, :n + 1], x[k, :n + 1]) < 1e-12 and rel_u(ud[k, :n], u[k, :n]) < 1e-12 and not xd[k, n + 1:].any()
 
 
 @pytest.mark.parametrize("feedback", [True, False])

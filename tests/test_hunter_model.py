@@ -11,7 +11,7 @@ from tests import oracle_bridge as ob
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = os.path.join(ROOT, "assets", "hunter")
-REF = "/root/reference/bipedal_robot_example/hunter"
+REF = os.path.join(ROOT, "tests", "golden", "reference", "bipedal_robot_example", "hunter")      # the reference's own files (tests/golden/make_reference_fixtures.py)
 
 
 @pytest.fixture(scope="module")
@@ -46,7 +46,6 @@ def test_product_matches_oracle_ingest(both):
     assert abs(itf.robotMass() - m["robot_mass"]) < 1e-12
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_reduced_assets_equal_reference_files():
     urdf = os.path.join(REF, "legged_hunter_description/urdf/hunter.urdf")
     task = os.path.join(REF, "legged_hunter_config/config/task/task.info")

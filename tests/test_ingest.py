@@ -9,7 +9,7 @@ from oracle import ingest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 A = os.path.join(ROOT, "assets", "h1")
-REF = "/root/reference/bipedal_robot_example/unitree_h1"
+REF = os.path.join(ROOT, "tests", "golden", "reference", "bipedal_robot_example", "unitree_h1")      # the reference's own files (tests/golden/make_reference_fixtures.py)
 
 
 @pytest.fixture(scope="module")
@@ -67,7 +67,6 @@ def test_product_matches_oracle_ingest(both):
     assert nb == 11
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present (GPU box)")
 def test_reduced_assets_equal_reference_files():
     """The reduced assets and the reference's full data files give the identical flat model (both ingests)."""
     import bipedal_control_amd as bp

@@ -7,7 +7,7 @@ IFS='|' read -ra SHAPES <<< "${ABARGS:---batch 256|--batch 4096}"
 for rep in 1 2; do
 for V in "X=0" ${ABENV:-}; do
 for ARGS in "${SHAPES[@]}"; do
-  env $V timeout 300 python bench.py $ARGS --cpu-sample 0 --no-fused > $O/line.json 2>$O/err.log
+  env $V timeout 300 python bench.py --full $ARGS --cpu-sample 0 --no-fused > $O/line.json 2>$O/err.log
   python -c "
 import json
 d=json.loads(open('$O/line.json').read().strip().splitlines()[-1]); print('[$V] $ARGS', d['value'], d['ms_per_step'], d['kernel_ms_per_step'])" 2>&1 | tail -1

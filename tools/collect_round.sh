@@ -22,15 +22,15 @@ for s in "" b4096_ g1_ sweep_; do cp gpurun_out/${TAG}_${s}traffic.json profiles
 cp gpurun_out/${TAG}_counters.json profiles/${PUB}_sq_counters.json
 sed -i "s/r0[0-9][a-z]*_traffic/${PUB}_traffic/; s/r0[0-9][a-z]*_\(b4096\|g1\|sweep\)_traffic/${PUB}_\1_traffic/; s/r0[0-9][a-z]*_sq_counters/${PUB}_sq_counters/" profiles/traffic_index.json
 timeout 300 python bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-fused > /dev/null 2>&1    # warm-up: the first bench after the test suite runs ~2 % slow (clocks)
-timeout 600 python bench.py > $O/bench_h1.json 2> $O/bench_h1.err
-timeout 600 python bench.py --robot g1 --batch 1024 --cpu-sample 16 > $O/bench_g1.json 2>> $O/bench_h1.err
-timeout 600 python bench.py --workload gait-sweep --batch 4096 --cpu-sample 16 > $O/bench_sweep.json 2>> $O/bench_h1.err
-timeout 600 python bench.py --batch 4096 --cpu-sample 0 > $O/bench_4096.json 2>> $O/bench_h1.err
-timeout 600 python bench.py --batch 512 --cpu-sample 0 > $O/bench_512.json 2>> $O/bench_h1.err
-timeout 600 python bench.py --robot hunter --cpu-sample 16 > $O/bench_hunter.json 2>> $O/bench_h1.err
-timeout 600 python bench.py --robot h1:hard --cpu-sample 16 > $O/bench_h1_hard.json 2>> $O/bench_h1.err
-timeout 600 python bench.py --gait-start -1.225 --cpu-sample 0 > $O/bench_h1_midswing.json 2>> $O/bench_h1.err      # round 4's input: nobody back-tracks
-timeout 600 python bench.py --solver ddp --cpu-sample 2 > $O/bench_ddp.json 2>> $O/bench_h1.err                          # the reference's second solver at the configs[1] shape
+timeout 600 python bench.py --full > $O/bench_h1.json 2> $O/bench_h1.err
+timeout 600 python bench.py --full --robot g1 --batch 1024 --cpu-sample 16 > $O/bench_g1.json 2>> $O/bench_h1.err
+timeout 600 python bench.py --full --workload gait-sweep --batch 4096 --cpu-sample 16 > $O/bench_sweep.json 2>> $O/bench_h1.err
+timeout 600 python bench.py --full --batch 4096 --cpu-sample 0 > $O/bench_4096.json 2>> $O/bench_h1.err
+timeout 600 python bench.py --full --batch 512 --cpu-sample 0 > $O/bench_512.json 2>> $O/bench_h1.err
+timeout 600 python bench.py --full --robot hunter --cpu-sample 16 > $O/bench_hunter.json 2>> $O/bench_h1.err
+timeout 600 python bench.py --full --robot h1:hard --cpu-sample 16 > $O/bench_h1_hard.json 2>> $O/bench_h1.err
+timeout 600 python bench.py --full --gait-start -1.225 --cpu-sample 0 > $O/bench_h1_midswing.json 2>> $O/bench_h1.err      # round 4's input: nobody back-tracks
+timeout 600 python bench.py --full --solver ddp --cpu-sample 2 > $O/bench_ddp.json 2>> $O/bench_h1.err                          # the reference's second solver at the configs[1] shape
 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_ddp_stats -o run -- python bench.py --solver ddp --steps 5 --warmup 2 --cpu-sample 0 --no-fused > gpurun_out/${TAG}_ddp_bench_under_rocprof.json 2> gpurun_out/${TAG}_ddp_stats.log
 python tools/summarize_rocpd.py "$(find gpurun_out/${TAG}_ddp_stats -name '*.db' | head -1)" gpurun_out/${TAG}_ddp_kernel_stats.csv > /dev/null
 tools/probes/write_roof.bin 256 103 > $O/write_roof.json 2>&1; tools/probes/write_roof.bin 4096 103 >> $O/write_roof.json 2>&1; tools/probes/write_roof.bin 1024 103 24 >> $O/write_roof.json 2>&1

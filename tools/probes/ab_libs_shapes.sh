@@ -7,7 +7,7 @@ timeout 300 python bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-fused >/de
 for rep in 1 2; do for v in $1; do
   cp tools/probes/lib_$v.bin bipedal_control_amd/libbpmpc.so
   for ARGS in "${SHAPES[@]}"; do
-    timeout 300 python bench.py $ARGS --cpu-sample 0 --no-fused --profile-all 2>/tmp/err.log | tail -1 | python -c "
+    timeout 300 python bench.py --full $ARGS --cpu-sample 0 --no-fused --profile-all 2>/tmp/err.log | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$v [$ARGS]', d['value'], d['ms_per_step'], d['kernel_ms_per_step'])"
   done

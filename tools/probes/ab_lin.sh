@@ -9,7 +9,7 @@ for v in $1; do
   cp tools/probes/lib_$v.bin bipedal_control_amd/libbpmpc.so
   timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_g1.py tests/test_gpu_hunter.py -m gpu -q -x -k "linearize or lq or fused or matches_oracle" 2>&1 | tail -2 | tr '\n' ' '; echo
   for rep in 1 2; do for ARGS in "${SHAPES[@]}"; do
-    timeout 300 python bench.py $ARGS --cpu-sample 0 2>/tmp/err.log | tail -1 | python -c "
+    timeout 300 python bench.py --full $ARGS --cpu-sample 0 2>/tmp/err.log | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; print('$v [$ARGS]', d['value'], d['ms_per_step'], 'fused', (d.get('fused') or {}).get('value'), 'lin', k.get('linearize'), 'frac', d['roofline']['frac'])

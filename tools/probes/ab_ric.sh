@@ -7,7 +7,7 @@ NAMES=$1; shift
 timeout 300 python bench.py --steps 10 --warmup 3 --cpu-sample 0 --no-fused >/dev/null 2>&1
 for rep in 1 2; do for v in $NAMES; do
   cp tools/probes/lib_$v.bin bipedal_control_amd/libbpmpc.so
-  timeout 300 python bench.py --cpu-sample 0 --no-fused --profile-all "$@" 2>/tmp/err.log | tail -1 | python -c "
+  timeout 300 python bench.py --full --cpu-sample 0 --no-fused --profile-all "$@" 2>/tmp/err.log | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; print('$v', d['value'], d['ms_per_step'], k)

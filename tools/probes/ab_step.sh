@@ -8,7 +8,7 @@ IFS='|' read -ra SHAPES <<< "${3:---batch 256|--batch 4096|--robot g1 --batch 10
 for rep in 1 2; do for v in $1; do
   cp tools/probes/lib_$v.bin bipedal_control_amd/libbpmpc.so
   for ARGS in "${SHAPES[@]}"; do
-    timeout 300 python bench.py $ARGS --cpu-sample 0 2>/tmp/err.log | tail -1 | python -c "
+    timeout 300 python bench.py --full $ARGS --cpu-sample 0 2>/tmp/err.log | tail -1 | python -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; print('$v [$ARGS]', d['value'], d['ms_per_step'], 'fused', (d.get('fused') or {}).get('value'), k)

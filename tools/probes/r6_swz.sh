@@ -6,7 +6,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_g1.py -m gp
 bash tools/probes/ab_ric.sh "base swz" 2>&1 | tee $O/ab.txt
 bash tools/probes/ab_ric.sh "base swz" --robot g1 --batch 256 2>&1 | tee -a $O/ab.txt
 B="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM"
-rocprofv3 --kernel-trace --pmc $B --output-format csv -d $O/pmc_sqB -o run -- python bench.py --steps 3 --warmup 1 --settle 0 --cpu-sample 0 > /dev/null 2> $O/pmc.log || tail -5 $O/pmc.log
+rocprofv3 --kernel-trace --pmc $B --output-format csv -d $O/pmc_sqB -o run -- python bench.py --full --steps 3 --warmup 1 --settle 0 --cpu-sample 0 > /dev/null 2> $O/pmc.log || tail -5 $O/pmc.log
 python - <<PY 2>&1 | tee $O/lds.txt
 import csv, glob, collections
 f = glob.glob("$O/pmc_sqB/**/*counter_collection.csv", recursive=True)

@@ -51,7 +51,7 @@ def main(fetch_dir, write_dir, out, extra=""):
     res = {"csrc_hash": csrc_hash(), "batch": int(mb.group(1)) if mb else 256, "intervals": int(mi.group(1)) if mi else (150 if "gait-sweep" in extra else 100), "bench_arguments": extra, "kernel": lin,
            "materialised_hbm_bytes_per_step": int(per_step_common + kernels[lin]["hbm_bytes_per_launch"]) if lin and steps else None,
            "fused_hbm_bytes_per_step": int(per_step_common + kernels[lin_f]["hbm_bytes_per_launch"]) if lin_f and steps else None,
-           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python bench.py --steps 3 --warmup 1 --cpu-sample 0 " + extra,
+           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) --output-format csv -- python bench.py --full --steps 3 --warmup 1 --cpu-sample 0 " + extra,
            "hbm_bytes_per_launch": kernels[lin]["hbm_bytes_per_launch"] if lin else None,
            "note": "FETCH_SIZE doubled (gfx950 reports half of the streamed read bytes, MI355X_MICROARCH.md); WRITE_SIZE as reported.",
            "all_kernels": kernels}
