@@ -475,6 +475,16 @@ class BatchedSqpMpc:
         """Async D2D copy of the iterate into device buffers given by raw pointers (e.g. torch tensors' data_ptr())."""
         _check(load_library().bpmpc_solver_export_trajectories(self._h, C.c_void_p(x_dst_ptr), C.c_void_p(u_dst_ptr)))
 
+    def evaluatePolicy(self, t, x):
+        """MRT_BASE::evaluatePolicy(t, x) for every problem of the last run (bpmpc_solver_evaluate_policy): t[batch], x[batch, nx] ->
+        (x_opt [batch, nx], u_opt [batch, nu], planned mode [batch])."""
+        B = self.batch
+        t = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
+        x = _f64(x).reshape(B, self.nx)
+        x_opt, u_opt, mode = np.zeros((B, self.nx)), np.zeros((B, self.nu)), np.zeros(B, np.int32)
+        _check(load_library().bpmpc_solver_evaluate_policy(self._h, B, _d(t), _d(x), _d(x_opt), _d(u_opt), _i(mode)))
+        return x_opt, u_opt, mode
+
 
 class WeightedWbc:
     """A batch of WeightedWbc instances on one MI355X (bipedal_wbc/include/bipedal_wbc/WeightedWbc.h; construction + loadTasksSetting as
@@ -511,6 +521,86 @@ class WeightedWbc:
 
     def reset(self):
         _check(load_library().bpmpc_wbc_reset(self._h))
+
+
+class _TickOutputs(C.Structure):
+    _fields_ = [("x_obs", _dp), ("x_opt", _dp), ("u_opt", _dp), ("joint_cmd", _dp), ("wbc_solution", _dp), ("planned_mode", _ip), ("wbc_status", _ip),
+                ("safe", _ip)]
+
+
+class DeviceArray:
+    """A device buffer of the library seen through __cuda_array_interface__: torch.as_tensor(view, device="cuda") wraps it without a copy
+    (`.torch()` does that).  The memory belongs to the handle that returned it."""
+
+    def __init__(self, ptr, shape, typestr):
+        self.ptr, self.shape, self.typestr = int(ptr), tuple(int(n) for n in shape), typestr
+        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": typestr, "data": (self.ptr, False), "version": 3, "strides": None}
+
+    def torch(self):
+        import torch
+        return torch.as_tensor(self, device="cuda")
+
+
+class BatchedController:
+    """BipedalController::update (bipedal_controllers/src/BipedalController.cpp:186-262) for the batch of a BatchedSqpMpc and a WeightedWbc
+    (bpmpc_controller_tick): measured rigid-body state -> observation (centroidal state, yaw unwrap), evaluatePolicy of the last run, the WBC,
+    SafetyChecker, joint commands - three kernels on the solver's stream.  `tick` takes numpy arrays (host) or device tensors (e.g. torch
+    tensors of a GPU simulator; order their producer against the solver's stream, e.g. by creating the solver on a torch stream)."""
+
+    NAMES = ("x_obs", "x_opt", "u_opt", "joint_cmd", "wbc_solution", "planned_mode", "wbc_status", "safe")
+
+    def __init__(self, mpc, wbc):
+        self.mpc, self.wbc = mpc, wbc
+        self._h = C.c_void_p()
+        _check(load_library().bpmpc_controller_create(mpc._h, wbc._h, C.byref(self._h)))
+        self.nx, self.nu, self.nj = mpc.nx, mpc.nu, mpc.interface.actuatedDofNum
+        self.max_batch = wbc.max_batch
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.bpmpc_controller_destroy(self._h)
+            self._h = None
+
+    def _shapes(self, B):
+        return {"x_obs": (B, self.nx), "x_opt": (B, self.nx), "u_opt": (B, self.nu), "joint_cmd": (B, 3, self.nj),
+                "wbc_solution": (B, self.wbc.numDecisionVars), "planned_mode": (B,), "wbc_status": (B,), "safe": (B,)}
+
+    def tick(self, t, rbd, period=0.0025, fetch=True):
+        """One tick for the solver's batch.  t: [batch] (or a scalar), rbd: [batch, 2 (6 + nj)].  fetch=True: returns a dict of numpy arrays
+        (x_obs, x_opt, u_opt, joint_cmd [batch, 3, nj] = position, velocity, torque, wbc_solution, planned_mode, wbc_status, safe); False: only
+        enqueues (see device_outputs)."""
+        B = self.mpc.batch
+        on_device = hasattr(rbd, "data_ptr") and getattr(rbd, "is_cuda", False)
+        if on_device:
+            if not (hasattr(t, "data_ptr") and t.is_cuda):
+                raise ValueError("t and rbd must both be device tensors or both host arrays")
+            for a, n in ((t, B), (rbd, B * 2 * self.wbc.generalizedCoordinatesNum)):
+                if str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.numel() != n:
+                    raise ValueError("device inputs must be contiguous float64 tensors of the batch's size")
+            tp, rp, keep = C.cast(C.c_void_p(t.data_ptr()), _dp), C.cast(C.c_void_p(rbd.data_ptr()), _dp), None
+        else:
+            tt = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
+            rr = _f64(rbd).reshape(B, 2 * self.wbc.generalizedCoordinatesNum)
+            tp, rp, keep = _d(tt), _d(rr), (tt, rr)
+        out, ptrs = None, None
+        if fetch:
+            out = {k: np.zeros(shp, np.int32 if k in ("planned_mode", "wbc_status", "safe") else np.float64) for k, shp in self._shapes(B).items()}
+            ptrs = _TickOutputs(*[(_i if out[k].dtype == np.int32 else _d)(out[k]) for k in self.NAMES])
+        _check(load_library().bpmpc_controller_tick(self._h, B, tp, rp, int(on_device), C.c_double(period), C.byref(ptrs) if fetch else None))
+        del keep
+        return out
+
+    def reset(self):
+        """yaw_last = 0 for every robot (BipedalController::starting)."""
+        _check(load_library().bpmpc_controller_reset(self._h))
+
+    def device_outputs(self):
+        """The results of the last tick where they live: a dict of DeviceArray (zero-copy; `.torch()` wraps one as a tensor) over the solver's batch."""
+        o = _TickOutputs()
+        _check(load_library().bpmpc_controller_device_outputs(self._h, C.byref(o)))
+        B = self.mpc.batch
+        return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k in ("planned_mode", "wbc_status", "safe") else "<f8")
+                for k, shp in self._shapes(B).items()}
 
 
 class BatchedDdpMpc(BatchedSqpMpc):

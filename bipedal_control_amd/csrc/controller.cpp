@@ -1,0 +1,196 @@
+// Host side of the controller tick (kernels/tick.h, k_tick.hip) and of MRT_BASE::evaluatePolicy: the C ABI of include/bpmpc.h.
+//   BipedalController::update          bipedal_controllers/src/BipedalController.cpp:186-262
+//   observation                         :397-403 (computeCentroidalStateFromRbdModel, yaw unwrap)
+//   evaluatePolicy / WBC / safety       :199, :229, SafetyChecker.h:39-52;  commands :237-252
+// One tick = k_tick_observe_policy, k_wbc (the WBC handle's kernel and its per-robot last solutions), k_tick_commands, all on the solver's
+// stream; nothing is synchronised unless outputs are asked for on the host.
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <stdexcept>
+#include <string>
+
+#include "../../include/bpmpc.h"
+#include "capi_internal.h"
+#include "kernel_launchers.h"
+#include "kernels/tick.h"
+
+using namespace bpmpc;
+
+struct bpmpc_controller {
+  bpmpc_solver* s = nullptr;
+  bpmpc_wbc* w = nullptr;
+  int device = 0, max_batch = 0, nj = 0, nx = 0, nv = 0, n = 0;
+  double *d_yaw = nullptr, *d_t = nullptr, *d_rbd = nullptr, *d_xobs = nullptr, *d_xopt = nullptr, *d_uopt = nullptr, *d_cmd = nullptr;
+  int *d_mode = nullptr, *d_safe = nullptr;
+};
+
+namespace {
+
+struct TickDeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
+void tick_hip(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw TickDeviceError(std::string(what) + ": " + hipGetErrorString(e));
+}
+#define TICK_HIP(expr) tick_hip((expr), #expr)
+
+int translate(const std::exception& e) {
+  if (dynamic_cast<const TickDeviceError*>(&e)) { set_last_error(e.what()); return BPMPC_ERR_DEVICE; }
+  int rc = solver_translate(e);              // the solver's own classes (its Unsupported for the DDP solver included)
+  if (rc == BPMPC_ERR_IO) rc = wbc_translate(e);
+  return rc == BPMPC_ERR_IO ? BPMPC_ERR_DEVICE : rc;
+}
+
+TickArgs policy_args(const SolverTickView& v, int batch) {
+  TickArgs a{};
+  a.batch = batch; a.N = v.N; a.feedback = v.feedback;
+  a.p_grid = v.p_grid; a.g_nodes = v.g_nodes; a.g_kind = v.g_kind; a.g_mode = v.g_mode; a.g_time = v.g_time; a.x = v.x; a.u = v.u; a.K = v.K;
+  return a;
+}
+
+void free_all(bpmpc_controller* c) {
+  for (void* p : {(void*)c->d_yaw, (void*)c->d_t, (void*)c->d_rbd, (void*)c->d_xobs, (void*)c->d_xopt, (void*)c->d_uopt, (void*)c->d_cmd, (void*)c->d_mode,
+                  (void*)c->d_safe})
+    if (p) (void)hipFree(p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpmpc_solver_evaluate_policy(bpmpc_solver* s, int batch, const double* t, const double* x, double* x_opt, double* u_opt, int* planned_mode) {
+  if (!s || !t || !x || !x_opt || !u_opt || !planned_mode) { set_last_error("bpmpc_solver_evaluate_policy: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  void* block = nullptr;
+  int rc = BPMPC_OK;
+  try {
+    const SolverTickView v = solver_tick_view(s);
+    if (batch != v.batch) throw std::invalid_argument("bpmpc_solver_evaluate_policy: batch differs from the batch of the last setup");
+    TICK_HIP(hipSetDevice(v.device));
+    const size_t B = batch, nx = v.nx, nu = v.nu;
+    const size_t bytes = B * (1 + 2 * nx + nu) * sizeof(double) + B * sizeof(int);
+    TICK_HIP(hipMalloc(&block, bytes));
+    double* d_t = static_cast<double*>(block);
+    double* d_x = d_t + B;
+    double* d_xopt = d_x + B * nx;
+    double* d_uopt = d_xopt + B * nx;
+    int* d_mode = reinterpret_cast<int*>(d_uopt + B * nu);
+    TICK_HIP(hipMemcpyAsync(d_t, t, B * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    TICK_HIP(hipMemcpyAsync(d_x, x, B * nx * sizeof(double), hipMemcpyHostToDevice, v.stream));
+    TickArgs a = policy_args(v, batch);
+    a.t = d_t; a.x_in = d_x; a.x_opt = d_xopt; a.u_opt = d_uopt; a.mode = d_mode;
+    kl::tick_observe_policy(v.nj, batch, v.stream, v.d_model, a);
+    TICK_HIP(hipGetLastError());
+    TICK_HIP(hipMemcpyAsync(x_opt, d_xopt, B * nx * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    TICK_HIP(hipMemcpyAsync(u_opt, d_uopt, B * nu * sizeof(double), hipMemcpyDeviceToHost, v.stream));
+    TICK_HIP(hipMemcpyAsync(planned_mode, d_mode, B * sizeof(int), hipMemcpyDeviceToHost, v.stream));
+    TICK_HIP(hipStreamSynchronize(v.stream));
+  } catch (const std::exception& e) { rc = translate(e); }
+  if (block) (void)hipFree(block);
+  return rc;
+}
+
+int bpmpc_controller_create(bpmpc_solver* s, bpmpc_wbc* w, bpmpc_controller** out) {
+  if (!s || !w || !out) { set_last_error("bpmpc_controller_create: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  *out = nullptr;
+  std::unique_ptr<bpmpc_controller> c(new bpmpc_controller);
+  try {
+    int nx = 0, nu = 0;
+    if (bpmpc_solver_layout(s, nullptr, nullptr, nullptr, &nx, &nu) != BPMPC_OK) throw std::invalid_argument("bpmpc_controller_create: bad solver handle");
+    const WbcTickView wv = wbc_tick_view(w);
+    if (nx != 12 + wv.nj) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC are built for different robots");
+    if (solver_device(s) != wv.device) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC live on different devices");
+    c->s = s; c->w = w; c->device = wv.device; c->max_batch = wv.max_batch; c->nj = wv.nj; c->nx = nx; c->nv = wv.nv; c->n = wv.n;
+    TICK_HIP(hipSetDevice(c->device));
+    const size_t B = c->max_batch;
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_yaw), B * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_t), B * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_rbd), B * 2 * c->nv * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_xobs), B * c->nx * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_xopt), B * c->nx * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_uopt), B * c->nx * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_cmd), B * 3 * c->nj * sizeof(double)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_mode), B * sizeof(int)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_safe), B * sizeof(int)));
+    TICK_HIP(hipMemset(c->d_yaw, 0, B * sizeof(double)));       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
+    TICK_HIP(hipDeviceSynchronize());
+  } catch (const std::exception& e) {
+    const int rc = translate(e);
+    free_all(c.get());
+    return rc;
+  }
+  *out = c.release();
+  return BPMPC_OK;
+}
+
+void bpmpc_controller_destroy(bpmpc_controller* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->device);
+  (void)hipDeviceSynchronize();           // a tick may still be in flight on the solver's stream
+  free_all(c);
+  delete c;
+}
+
+int bpmpc_controller_reset(bpmpc_controller* c) {
+  if (!c) { set_last_error("null controller handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  try {
+    TICK_HIP(hipSetDevice(c->device));
+    TICK_HIP(hipDeviceSynchronize());
+    TICK_HIP(hipMemset(c->d_yaw, 0, (size_t)c->max_batch * sizeof(double)));
+    TICK_HIP(hipDeviceSynchronize());
+  } catch (const std::exception& e) { return translate(e); }
+  return BPMPC_OK;
+}
+
+int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const double* rbd, int inputs_on_device, double period,
+                          const bpmpc_tick_outputs* host_out) {
+  (void)period;      // WeightedWbc::update takes it and does not use it (WbcBase.cpp:242-243), as bpmpc_wbc_update
+  if (!c || !t || !rbd) { set_last_error("bpmpc_controller_tick: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  try {
+    const SolverTickView v = solver_tick_view(c->s);
+    if (batch != v.batch) throw std::invalid_argument("bpmpc_controller_tick: batch differs from the batch of the solver's last setup");
+    if (batch > c->max_batch) throw std::length_error("bpmpc_controller_tick: batch exceeds the WBC's max_batch");
+    TICK_HIP(hipSetDevice(c->device));
+    const size_t B = batch;
+    const double *dt = t, *drbd = rbd;
+    if (!inputs_on_device) {
+      TICK_HIP(hipMemcpyAsync(c->d_t, t, B * sizeof(double), hipMemcpyHostToDevice, v.stream));
+      TICK_HIP(hipMemcpyAsync(c->d_rbd, rbd, B * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, v.stream));
+      dt = c->d_t; drbd = c->d_rbd;
+    }
+    TickArgs a = policy_args(v, batch);
+    a.t = dt; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs; a.x_loop = v.loop_x; a.safe = c->d_safe;
+    a.x_opt = c->d_xopt; a.u_opt = c->d_uopt; a.mode = c->d_mode;
+    kl::tick_observe_policy(c->nj, batch, v.stream, v.d_model, a);
+    TICK_HIP(hipGetLastError());
+    solver_tick_done(c->s);
+    wbc_launch_on(c->w, batch, c->d_xopt, c->d_uopt, drbd, c->d_mode, v.stream);
+    const WbcTickView wv = wbc_tick_view(c->w);
+    kl::tick_commands(c->nj, batch, v.stream, c->d_xopt, c->d_uopt, wv.sol, c->d_cmd);
+    TICK_HIP(hipGetLastError());
+    if (host_out) {
+      const bpmpc_tick_outputs& o = *host_out;
+      auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) TICK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, v.stream)); };
+      down(o.x_obs, c->d_xobs, B * c->nx * sizeof(double));
+      down(o.x_opt, c->d_xopt, B * c->nx * sizeof(double));
+      down(o.u_opt, c->d_uopt, B * c->nx * sizeof(double));
+      down(o.joint_cmd, c->d_cmd, B * 3 * c->nj * sizeof(double));
+      down(o.wbc_solution, wv.sol, B * c->n * sizeof(double));
+      down(o.planned_mode, c->d_mode, B * sizeof(int));
+      down(o.wbc_status, wv.status, B * sizeof(int));
+      down(o.safe, c->d_safe, B * sizeof(int));
+      TICK_HIP(hipStreamSynchronize(v.stream));
+    }
+  } catch (const std::exception& e) { return translate(e); }
+  return BPMPC_OK;
+}
+
+int bpmpc_controller_device_outputs(bpmpc_controller* c, bpmpc_tick_outputs* o) {
+  if (!c || !o) { set_last_error("bpmpc_controller_device_outputs: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  try {
+    const WbcTickView wv = wbc_tick_view(c->w);
+    o->x_obs = c->d_xobs; o->x_opt = c->d_xopt; o->u_opt = c->d_uopt; o->joint_cmd = c->d_cmd; o->wbc_solution = wv.sol;
+    o->planned_mode = c->d_mode; o->wbc_status = wv.status; o->safe = c->d_safe;
+  } catch (const std::exception& e) { return translate(e); }
+  return BPMPC_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// Host-side entry points of the kernel translation units (k_node.hip, k_project.hip, k_riccati.hip, k_riccati_wave.hip): the solver
+// Host-side entry points of the kernel translation units (k_node.hip, k_project.hip, k_riccati.hip, k_riccati_wave.hip, k_ddp.hip, k_tick.hip): the solver
 // (solver.hip, host code) launches every kernel through these, so the kernel families compile in parallel and a change to one of them
 // rebuilds one translation unit.  `nj` selects the instantiation (10: nx = nu = 22, 12: nx = nu = 24); every function only enqueues.
 #pragma once
@@ -12,6 +12,7 @@ struct Launch;
 struct DeviceModel;
 struct RolloutArgs;
 struct DdpBuffers;
+struct TickArgs;
 
 namespace kl {
 
@@ -52,6 +53,10 @@ void ddp_select(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuf
 void ddp_nominal(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d);
 void ddp_finish(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d);
 void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid);
+
+// ---- k_tick.hip: the controller tick (observation + policy evaluation in one launch; the joint commands behind k_wbc)
+void tick_observe_policy(int nj, int batch, hipStream_t st, const DeviceModel* model, const TickArgs& a);
+void tick_commands(int nj, int batch, hipStream_t st, const double* x_opt, const double* u_opt, const double* sol, double* cmd);
 
 }  // namespace kl
 }  // namespace bpmpc

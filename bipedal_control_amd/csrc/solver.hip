@@ -123,6 +123,10 @@ struct bpmpc_solver {
   bool has_solution = false;                               // a solve has completed on the current setup
   bool has_rollout = false;                                // roll_x holds the end states of a rollout
   bool rollout_unchecked = false;                          // ... whose status flags have not been read back yet
+  // closed loop through the controller tick (k_tick.hip): tick_x holds the observations of the last bpmpc_controller_tick; loop_from_tick says
+  // that the tick, not a rollout, ran last on the handle - bpmpc_solver_setup_commands(x0 = NULL) then starts from tick_x instead of roll_x
+  double* tick_x = nullptr;
+  bool loop_from_tick = false;
   std::vector<int> grid_kind;                               // host copy of the node kinds of the current setup [n_grids][N]
   int max_rows = kMaxEqRows;                                // largest number of equality rows over the nodes of the current setup
   int max_vel_rows = 12;                                    // ... of rows that constrain a contact velocity (12 double stance, 8 single support, 4 flight)
@@ -462,6 +466,7 @@ void allocate(bpmpc_solver* s) {
   b.zero_page = s->alloc<double>(nullptr, 4 + 32);     // {0.0, 1.0, 0.0, 0.0}: zeros and ones of the generated force rows, a 16-byte pair of zeros; then a whole row of zeros (alloc zero-fills)
   { const double one = 1.0; HIP_CHECK(hipMemcpyAsync(b.zero_page + 1, &one, sizeof(double), hipMemcpyHostToDevice, s->stream)); HIP_CHECK(hipStreamSynchronize(s->stream)); }
   b.roll_t = s->alloc<double>(nullptr, B); b.roll_x0 = s->alloc<double>(nullptr, B * NX); b.roll_x = s->alloc<double>("roll_x", B * NX);
+  s->tick_x = s->alloc<double>("tick_x", B * NX);
   b.roll_u = s->alloc<double>("roll_u", B * NU); b.roll_steps = s->alloc<int>(nullptr, B * 2); b.roll_status = s->alloc<int>(nullptr, B);
   b.g_time = s->alloc<double>("g_time", B * (N + 1)); b.rg_t0 = s->alloc<double>(nullptr, B); b.rg_start = s->alloc<double>(nullptr, B);
   b.p_t0 = s->alloc<double>(nullptr, B); b.p_cmd = s->alloc<double>(nullptr, B * 4); b.lib_d = s->alloc<double>(nullptr, kRefLibCapacity);
@@ -791,8 +796,9 @@ void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0
                     bool from_previous) {
   if (batch < 1 || batch > s->settings.max_batch) throw std::length_error("batch exceeds the solver's max_batch");
   if (!(horizon > 0) || !t0 || !cmd_vel || n_gaits < 0 || (n_gaits > 0 && !gaits)) throw std::invalid_argument("setup_commands: null or invalid argument");
-  if (!x0 && (!s->has_rollout || batch != s->batch)) throw std::invalid_argument("setup_commands: x0 == NULL needs a rollout of the same batch on the handle");
-  if (!x0 && s->rollout_unchecked) check_rollout_status(s, nullptr);
+  if (!x0 && (!(s->has_rollout || s->loop_from_tick) || batch != s->batch))
+    throw std::invalid_argument("setup_commands: x0 == NULL needs a rollout of the same batch on the handle (or a controller tick)");
+  if (!x0 && !s->loop_from_tick && s->rollout_unchecked) check_rollout_status(s, nullptr);
   if (command_kind != 0 && command_kind != 1) throw std::invalid_argument("setup_commands: command_kind is 0 (velocity) or 1 (goal pose)");
   if (n_gaits > 0 && (!gait_of_problem || !gait_start)) throw std::invalid_argument("setup_commands: gait_of_problem and gait_start are needed with templates");
   const int N = s->settings.max_nodes, NX = s->nx;
@@ -844,7 +850,8 @@ void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0
                                  {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
     upload_batch(s, up, 9);
   }
-  if (!x0) HIP_CHECK(hipMemcpyAsync(bf.p_x0, bf.roll_x, (size_t)batch * NX * sizeof(double), hipMemcpyDeviceToDevice, s->stream));   // closed loop on the device
+  if (!x0) HIP_CHECK(hipMemcpyAsync(bf.p_x0, s->loop_from_tick ? s->tick_x : bf.roll_x, (size_t)batch * NX * sizeof(double), hipMemcpyDeviceToDevice,
+                                    s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
   ReferenceGenArgs a{};
   a.lib.switching = bf.lib_d; a.lib.first_mode = bf.lib_i; a.lib.modes = bf.lib_i + first_mode.size(); a.lib.n_templates = n_gaits + 1;
   a.lib.init_events = bf.lib_d + sw_count; a.lib.init_modes = bf.lib_i + first_mode.size() + mode_count; a.lib.init_n_events = (int)init.event_times.size();
@@ -934,6 +941,7 @@ void rollout(bpmpc_solver* s, const double* t_start, const double* x_start, doub
   kl::rollout(s->rm.nj, s->dm.serial_legs && !s->force_tables, B, s->stream, s->d_model, a);
   HIP_CHECK(hipGetLastError());
   s->has_rollout = true;
+  s->loop_from_tick = false;
   if (!x_end && !u_end && !steps) {                 // nothing to hand back: stay asynchronous; the status is looked at by the next
     s->rollout_unchecked = true;                    // setup_commands(x0 = NULL), which reads its own flags back anyway
     return;
@@ -1275,3 +1283,31 @@ int bpmpc_solver_layout(const bpmpc_solver* s, int* batch, int* n_nodes_max, int
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ controller tick (k_tick.hip, controller.cpp)
+namespace bpmpc {
+
+SolverTickView solver_tick_view(bpmpc_solver* s) {
+  if (!s) throw std::invalid_argument("null solver handle");
+  if (s->is_ddp())
+    throw Unsupported("controller tick / evaluate_policy: the DDP solution is a FeedforwardController on the time points of its own roll-out, not on the shooting grid "
+                      "the policy is interpolated on");
+  if (s->batch < 1 || !s->has_solution) throw std::invalid_argument("controller tick / evaluate_policy needs a completed bpmpc_solver_run since the last setup");
+  const Buffers& bf = s->buf;
+  const int feedback = s->feedback();
+  if (feedback && !bf.K) throw std::invalid_argument("controller tick / evaluate_policy: the feedback policy needs the gains (return_gains with reference kernels)");
+  SolverTickView v;
+  v.device = s->settings.device; v.batch = s->batch; v.N = s->settings.max_nodes; v.nx = s->nx; v.nu = s->nu; v.nj = s->rm.nj; v.feedback = feedback;
+  v.stream = s->stream; v.d_model = s->d_model;
+  v.p_grid = bf.p_grid; v.g_nodes = bf.g_nodes; v.g_kind = bf.g_kind; v.g_mode = bf.g_mode; v.g_time = bf.g_time;
+  v.x = bf.x; v.u = bf.u; v.K = bf.K; v.loop_x = s->tick_x;
+  return v;
+}
+
+void solver_tick_done(bpmpc_solver* s) { s->loop_from_tick = true; }
+
+int solver_device(const bpmpc_solver* s) { return s->settings.device; }
+
+int solver_translate(const std::exception& e) { return translate(e); }
+
+}  // namespace bpmpc

@@ -38,6 +38,7 @@ struct bpmpc_wbc {
   hipStream_t stream = nullptr;
   double *d_x = nullptr, *d_u = nullptr, *d_rbd = nullptr, *d_sol = nullptr, *d_debug = nullptr;
   int *d_mode = nullptr, *d_status = nullptr;
+  hipEvent_t ev_foreign = nullptr;      // k_wbc enqueued on another handle's stream (controller tick): this handle's stream waits for it
 };
 
 namespace {
@@ -77,6 +78,31 @@ int translate(const std::exception& e) {
   return BPMPC_ERR_IO;
 }
 }  // namespace
+
+namespace bpmpc {
+
+int wbc_translate(const std::exception& e) { return translate(e); }
+
+WbcTickView wbc_tick_view(const bpmpc_wbc* w) {
+  if (!w) throw std::invalid_argument("null wbc handle");
+  return WbcTickView{w->device, w->max_batch, w->n, w->nv, w->rm.nj, w->d_sol, w->d_status};
+}
+
+// The launch of bpmpc_wbc_update without its transfers: device inputs, the handle's last solutions and statuses, on the caller's stream.
+void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const double* input_des, const double* rbd_meas, const int* mode, hipStream_t stream) {
+  if (batch < 1 || batch > w->max_batch) throw std::length_error("controller tick: batch exceeds the WBC's max_batch");
+  WbcArgs a{};
+  a.batch = batch; a.nx = w->rm.nx; a.state_des = state_des; a.input_des = input_des; a.rbd_meas = rbd_meas; a.mode = mode;
+  a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr;
+  if (w->rm.nj == 10) hipLaunchKernelGGL(k_wbc<10>, dim3(batch), dim3(kWave), 0, stream, w->d_model, w->st, a);
+  else hipLaunchKernelGGL(k_wbc<12>, dim3(batch), dim3(kWave), 0, stream, w->d_model, w->st, a);
+  WBC_HIP(hipGetLastError());
+  if (!w->ev_foreign) WBC_HIP(hipEventCreateWithFlags(&w->ev_foreign, hipEventDisableTiming));
+  WBC_HIP(hipEventRecord(w->ev_foreign, stream));
+  WBC_HIP(hipStreamWaitEvent(w->stream, w->ev_foreign, 0));
+}
+
+}  // namespace bpmpc
 
 extern "C" {
 
@@ -120,6 +146,7 @@ int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int d
 void bpmpc_wbc_destroy(bpmpc_wbc* w) {
   if (!w) return;
   if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
+  if (w->ev_foreign) (void)hipEventDestroy(w->ev_foreign);
   for (void* p : {(void*)w->d_model, (void*)w->d_x, (void*)w->d_u, (void*)w->d_rbd, (void*)w->d_sol, (void*)w->d_debug, (void*)w->d_mode, (void*)w->d_status})
     if (p) (void)hipFree(p);
   delete w;

@@ -322,6 +322,55 @@ int bpmpc_wbc_update(bpmpc_wbc* wbc, int batch, const double* state_desired, con
                      const int* mode, double period, double* solution, int* status, double* debug);
 int bpmpc_wbc_reset(bpmpc_wbc* wbc);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Controller tick = BipedalController::update for a BATCH of robots, on the device (bipedal_controllers/src/BipedalController.cpp:186-262)
+ *   observation   :397-403  computeCentroidalStateFromRbdModel(measured rbd state) + yaw unwrap: from rbd[b] (the layout of
+ *                           bpmpc_wbc_update) q = [base position, zyx, joints], v = [linear velocity, E(zyx)^-1 angular velocity, joint
+ *                           velocities], x_obs = [A(q) v / m, q] (A: centroidal momentum matrix in Euler-rate base coordinates, m: robot mass),
+ *                           then x_obs[9] = yaw_last + shortest_angular_distance(yaw_last, x_obs[9]) (distance in (-pi, pi]); yaw_last is kept
+ *                           per robot on the handle, 0 after create / reset (BipedalController::starting)
+ *   policy        :199      evaluatePolicy(t, x_obs) of the last completed bpmpc_solver_run, see bpmpc_solver_evaluate_policy
+ *   WBC           :229      the WBC handle's WeightedWbc::update(x*, u*, rbd, planned mode): the same kernel and the same per-robot last QP
+ *                           solutions as bpmpc_wbc_update (the fallback of WeightedWbc.cpp:68-81 is the same whichever entry point ran)
+ *   safety        SafetyChecker::check (SafetyChecker.h:39-52): safe = 0 when |x_obs[10]| > pi/3 or |x_obs[11]| > pi/3 (the limit passes)
+ *   commands      :237-252  joint_cmd[b] = [posDes = x*[12:], velDes = u*[12:], torque = last nj entries of the WBC solution] ([3][nj];
+ *                           the joint gains kp / kd stay the caller's)
+ * Everything runs on the solver's stream (three launches: k_tick_observe_policy, k_wbc, k_tick_commands).  The observations also close the
+ * loop: bpmpc_solver_setup_commands(x0 = NULL) starts from the states of the last rollout OR the last tick, whichever ran last on the solver.
+ * ------------------------------------------------------------------------------------------------------------- */
+/* MRT_BASE::evaluatePolicy for every problem of the last completed bpmpc_solver_run (host in / out; synchronises): t[batch], x[batch*nx] ->
+ * x_opt[batch*nx] = LinearInterpolation of the solution's states at t (clamped before the first and after the last node),
+ * u_opt[batch*nu] = uff(t) + K(t) x with the feedback policy (the input and gain of a pre-event node and of the terminal node repeat the
+ * previous one, uff_j = u_j - K_j x_j: multiple_shooting::toPrimalSolution [OCS2-upstream, recalled]) or u(t) without it, planned_mode[batch]
+ * = ModeSchedule::modeAtTime(t) (a time exactly on an event belongs to the earlier mode; before the first / after the last node the mode of
+ * the first / last interval of the solution - a clamp to its time span).  batch must equal the batch of the last setup.
+ * BPMPC_ERR_INVALID_ARGUMENT: no completed run since the last setup, batch mismatch; BPMPC_ERR_UNSUPPORTED: the DDP solver. */
+int bpmpc_solver_evaluate_policy(bpmpc_solver* solver, int batch, const double* t, const double* x, double* x_opt, double* u_opt, int* planned_mode);
+
+typedef struct bpmpc_controller bpmpc_controller;
+/* Per-robot outputs of a tick (row-major, strides of the WBC's max_batch do not apply: [batch] leading):
+ * x_obs[batch*nx], x_opt[batch*nx], u_opt[batch*nu], joint_cmd[batch*3*nj], wbc_solution[batch*n] (bpmpc_wbc_dims), planned_mode[batch],
+ * wbc_status[batch], safe[batch]. */
+typedef struct {
+  double *x_obs, *x_opt, *u_opt, *joint_cmd, *wbc_solution;
+  int *planned_mode, *wbc_status, *safe;
+} bpmpc_tick_outputs;
+/* Solver and WBC of the same robot on the same device; the handles must outlive the controller. */
+int bpmpc_controller_create(bpmpc_solver* solver, bpmpc_wbc* wbc, bpmpc_controller** out);
+void bpmpc_controller_destroy(bpmpc_controller* controller);
+int bpmpc_controller_reset(bpmpc_controller* controller);   /* yaw_last = 0 for every robot */
+/* One tick for `batch` robots: t[batch] (policy time), rbd[batch*2*(6+nj)] measured rigid-body state.  inputs_on_device != 0: t and rbd are
+ * device pointers (e.g. the tensors of a GPU simulator).  host_out NULL: nothing is copied back or synchronised (read the results through
+ * bpmpc_controller_device_outputs); otherwise every non-NULL member receives its block and the call synchronises.  batch must equal the
+ * batch of the solver's last setup (else BPMPC_ERR_INVALID_ARGUMENT) and be at most the WBC's max_batch (else BPMPC_ERR_CAPACITY); a tick
+ * needs a completed bpmpc_solver_run since that setup (BPMPC_ERR_INVALID_ARGUMENT) and an SQP solver (DDP: BPMPC_ERR_UNSUPPORTED).
+ * period: as in bpmpc_wbc_update (unused by the reference). */
+int bpmpc_controller_tick(bpmpc_controller* controller, int batch, const double* t, const double* rbd, int inputs_on_device, double period,
+                          const bpmpc_tick_outputs* host_out);
+/* Device pointers of the outputs of the last tick (same shapes as above, leading dimension the WBC's max_batch).  wbc_solution / wbc_status
+ * are the WBC handle's own buffers: a later bpmpc_wbc_update overwrites them. */
+int bpmpc_controller_device_outputs(bpmpc_controller* controller, bpmpc_tick_outputs* dev_out);
+
 #ifdef __cplusplus
 }
 #endif
