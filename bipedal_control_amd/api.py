@@ -3,6 +3,7 @@
 Names follow the reference so that code reads like its call sites:
   BipedalRobotInterface(taskFile, urdfFile, referenceFile)   ocs2_bipedal_robot/include/ocs2_bipedal_robot/BipedalRobotInterface.h:56-127
   GaitSchedule.insertModeSequenceTemplate / getModeSchedule  ocs2_bipedal_robot/src/gait/GaitSchedule.cpp:46-102
+  BatchedGaitSchedule.command                                one GaitReceiver per robot, ocs2_bipedal_robot/src/gait/GaitReceiver.cpp:49-59
   loadModeSequenceTemplate                                   ocs2_bipedal_robot/src/gait/ModeSequenceTemplate.cpp:50-71
   cmdVelToTargetTrajectories / goalToTargetTrajectories      bipedal_controllers/src/TargetTrajectoriesPublisher.cpp:60-99
   BatchedSqpMpc(interface, ...)                              the SqpMpc construction sites bipedal_controllers/src/BipedalController.cpp:303-306
@@ -239,6 +240,63 @@ class GaitSchedule:
         return ModeSchedule(ev[:n.value].copy(), ms[:n.value + 1].copy())
 
 
+class BatchedGaitSchedule:
+    """One GaitSchedule per robot of a BatchedSqpMpc, kept on the device (bpmpc_gait_batch): gait commands with the semantics of
+    GaitReceiver (GaitReceiver.cpp:49-59) take effect in the solver's setup_gaits.  `gaits` is the template library (a list of
+    ModeSequenceTemplate); robots refer to a template by its index."""
+
+    def __init__(self, mpc, gaits):
+        self.mpc, self.gaits, self.max_batch = mpc, list(gaits), mpc.max_batch
+        keep, tm = [], (_GaitTemplate * max(1, len(self.gaits)))()
+        for i, g in enumerate(self.gaits):
+            sw, mo = _f64(g.switchingTimes), np.ascontiguousarray(g.modeSequence, np.int32)
+            keep += [sw, mo]
+            tm[i] = _GaitTemplate(len(mo), _d(sw), _i(mo))
+        self._h = C.c_void_p()
+        _check(load_library().bpmpc_gait_batch_create(mpc._h, tm, len(self.gaits), C.byref(self._h)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.bpmpc_gait_batch_destroy(self._h)
+            self._h = None
+
+    def _robots(self, *arrays):
+        shape = np.broadcast(*[np.asarray(a) for a in arrays]).shape
+        return (self.max_batch,) if shape == () else shape
+
+    def insertModeSequenceTemplate(self, gait, startTime, finalTime):
+        """GaitSchedule::insertModeSequenceTemplate(gaits[gait[b]], startTime[b], finalTime[b]) for robots 0 .. len - 1 (scalars: every
+        robot), applied by the next setup before its getModeSchedule; gait[b] < 0 leaves robot b's pending insert as it is."""
+        shape = self._robots(gait, startTime, finalTime)
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(gait, np.int32), shape))
+        st, fi = _f64(np.broadcast_to(np.asarray(startTime, float), shape)), _f64(np.broadcast_to(np.asarray(finalTime, float), shape))
+        _check(load_library().bpmpc_gait_batch_insert(self._h, len(g), _i(g), _d(st), _d(fi)))
+
+    def command(self, gait):
+        """GaitReceiver::mpcModeSequenceCallback for robots 0 .. len(gait) - 1: gait[b] >= 0 becomes robot b's pending template (the latest
+        wins), < 0 leaves it as it is.  A numpy array, or a contiguous int32 device array: a torch.int32 tensor on the GPU or any object with
+        __cuda_array_interface__ (order its producer against the solver's stream)."""
+        iface = getattr(gait, "__cuda_array_interface__", None)
+        if iface is not None:
+            shape = tuple(iface["shape"])
+            if iface["typestr"] != "<i4" or len(shape) != 1 or iface.get("strides") not in (None, (4,)):
+                raise ValueError("device gait commands must be a contiguous one-dimensional int32 array")
+            _check(load_library().bpmpc_gait_batch_command(self._h, int(shape[0]), C.cast(C.c_void_p(iface["data"][0]), _ip), 1))
+            return
+        g = np.ascontiguousarray(np.broadcast_to(np.asarray(gait, np.int32), self._robots(gait)))
+        _check(load_library().bpmpc_gait_batch_command(self._h, len(g), _i(g), 0))
+
+    def reset(self):
+        """Every robot back to GaitSchedule(initialModeSchedule, defaultModeSequenceTemplate); nothing pending."""
+        _check(load_library().bpmpc_gait_batch_reset(self._h))
+
+    def modeSchedule(self, robot, capacity=1024):
+        """Robot's schedule after the last setup (does not mutate anything, unlike the reference's getModeSchedule)."""
+        ev, ms, n = np.zeros(capacity), np.zeros(capacity, np.int32), C.c_int()
+        _check(load_library().bpmpc_gait_batch_mode_schedule(self._h, int(robot), _d(ev), _i(ms), capacity, C.byref(n)))
+        return ModeSchedule(ev[:n.value].copy(), ms[:n.value + 1].copy())
+
+
 def swing_reference(interface, modeSchedule, times):
     """SwingTrajectoryPlanner::update + getZpositionConstraint / getZvelocityConstraint (SwingTrajectoryPlanner.cpp:50-118)."""
     ev, ms, t = _f64(modeSchedule.eventTimes), np.ascontiguousarray(modeSchedule.modeSequence, np.int32), _f64(times)
@@ -362,6 +420,23 @@ class BatchedSqpMpc:
             tm[i] = _GaitTemplate(len(mo), _d(sw), _i(mo))
         _check(load_library().bpmpc_solver_setup_commands(self._h, B, C.c_double(horizon), _d(t0), _d(x0), tm, len(gaits), _i(gop), _d(gst), _d(cmd),
                                                           int(bool(goal)), C.c_double(time_to_target), int(bool(from_previous))))
+        self.batch = B
+        return self.layout()
+
+    def setup_gaits(self, gait_schedules, t0, x0, cmd_vel, horizon=None, time_to_target=0.0, from_previous=False, goal=False):
+        """setup_commands with every robot's schedule taken from a BatchedGaitSchedule of this solver (bpmpc_solver_setup_gaits): its pending
+        inserts, getModeSchedule(t0 - H, t0 + 2 H) as the window of this setup, then its pending commands at (t0 + H, H)."""
+        if horizon is None:
+            horizon = self.interface.mpcSettings()["timeHorizon"]
+        if x0 is None:                      # continue from the end states of the last rollout or tick (device-resident)
+            B = self.batch
+        else:
+            x0 = _f64(x0).reshape(-1, self.nx)
+            B = x0.shape[0]
+        t0 = _f64(np.broadcast_to(np.asarray(t0, float), (B,)))
+        cmd = _f64(np.broadcast_to(np.asarray(cmd_vel, float), (B, 4)))
+        _check(load_library().bpmpc_solver_setup_gaits(self._h, gait_schedules._h, B, C.c_double(horizon), _d(t0), _d(x0), _d(cmd), int(bool(goal)),
+                                                       C.c_double(time_to_target), int(bool(from_previous))))
         self.batch = B
         return self.layout()
 

@@ -92,6 +92,48 @@ __device__ inline void ref_tile(DevSchedule& s, const double* sw, const int* mod
   ref_push_ms(s, 3);
 }
 
+// GaitSchedule::insertModeSequenceTemplate(lib[tmpl], start, final_time) (GaitSchedule.cpp:46-73) on the schedule in LDS
+__device__ inline void ref_insert(DevSchedule& s, const GaitLibraryView& lib, int tmpl, double start, double final_time) {
+  EXACT_FP_BODY
+  const int cut = ref_lower_bound(s.ev, s.ne, start);
+  if (cut < s.ne) { s.ne = cut; s.nm = cut + 1; }
+  double transition = lib.transition_stance_time;
+  if (s.nm > 0 && s.ms[s.nm - 1] == 3) transition = 0.0;
+  if (transition > 0.0) { ref_push_ev(s, start); ref_push_ms(s, 3); }
+  const int f = lib.first_mode[tmpl];
+  ref_tile(s, lib.switching + f + tmpl, lib.modes + f, lib.first_mode[tmpl + 1] - f, start + transition, final_time);
+}
+
+// GaitSchedule::getModeSchedule(lower, upper) (GaitSchedule.cpp:78-102), tiling template `tmpl`.  The erased front is not moved:
+// the returned offset is where the kept schedule starts (s.ev, s.ms, s.cap already point there).
+__device__ inline int ref_window(DevSchedule& s, const GaitLibraryView& lib, int tmpl, double lower, double upper) {
+  EXACT_FP_BODY
+  int base = 0;
+  const int first = ref_lower_bound(s.ev, s.ne, lower);
+  if (first > 0) {                     // forget the past but keep one phase, relabelled STANCE, in front of `lower`
+    base = first - 1;
+    s.ev += base; s.ms += base; s.ne -= base; s.nm -= base; s.cap -= base;
+    s.ms[0] = 3;
+  }
+  const double resume = s.ne == 0 ? upper : s.ev[s.ne - 1];
+  if (s.ne > 0) --s.ne;
+  if (s.nm > 0) --s.nm;
+  const int f = lib.first_mode[tmpl];
+  ref_tile(s, lib.switching + f + tmpl, lib.modes + f, lib.first_mode[tmpl + 1] - f, resume, upper);
+  return base;
+}
+
+// SwingTrajectoryPlanner::update: every swing phase needs a stance phase of that leg before and after it
+__device__ inline void ref_check_swings(DevSchedule& s) {
+  for (int c = 0; c < 4 && s.status == kRefOk; ++c) {
+    int fc = -1, lc = -1;
+    for (int p = 0; p < s.nm; ++p)
+      if (ref_contact(s.ms[p], c)) { if (fc < 0) fc = p; lc = p; }
+    if (s.nm > 0 && fc != 0) s.status = kRefNoTakeOff + c;
+    else if (s.nm > 0 && lc != s.nm - 1) s.status = kRefNoTouchDown + c;
+  }
+}
+
 // GaitSchedule(initial, default template).insert_template(gait, start, t0 + 2 H) [if gait >= 0] followed by
 // mode_schedule(t0 - H, t0 + 2 H): what SwitchedModelReferenceManager::modifyReferences asks for at solve time.
 __device__ inline void ref_build_schedule(RefGenLds& w, const GaitLibraryView& lib, int gait, double start, double t0, double horizon) {
@@ -103,37 +145,11 @@ __device__ inline void ref_build_schedule(RefGenLds& w, const GaitLibraryView& l
   const double upper = t0 + 2 * horizon, lower = t0 - horizon;
   if (gait >= 0) {
     tmpl = gait;
-    const int cut = ref_lower_bound(s.ev, s.ne, start);
-    if (cut < s.ne) { s.ne = cut; s.nm = cut + 1; }
-    double transition = lib.transition_stance_time;
-    if (s.nm > 0 && s.ms[s.nm - 1] == 3) transition = 0.0;
-    if (transition > 0.0) { ref_push_ev(s, start); ref_push_ms(s, 3); }
-    const int f = lib.first_mode[tmpl];
-    ref_tile(s, lib.switching + f + tmpl, lib.modes + f, lib.first_mode[tmpl + 1] - f, start + transition, upper);
+    ref_insert(s, lib, tmpl, start, upper);
   }
   int base = 0;
-  if (s.status == kRefOk) {
-    const int first = ref_lower_bound(s.ev, s.ne, lower);
-    if (first > 0) {                     // forget the past but keep one phase, relabelled STANCE, in front of `lower`
-      base = first - 1;
-      s.ev += base; s.ms += base; s.ne -= base; s.nm -= base; s.cap -= base;
-      s.ms[0] = 3;
-    }
-    const double resume = s.ne == 0 ? upper : s.ev[s.ne - 1];
-    if (s.ne > 0) --s.ne;
-    if (s.nm > 0) --s.nm;
-    const int f = lib.first_mode[tmpl];
-    ref_tile(s, lib.switching + f + tmpl, lib.modes + f, lib.first_mode[tmpl + 1] - f, resume, upper);
-  }
-  // SwingTrajectoryPlanner::update: every swing phase needs a stance phase of that leg before and after it
-  if (s.status == kRefOk)
-    for (int c = 0; c < 4 && s.status == kRefOk; ++c) {
-      int fc = -1, lc = -1;
-      for (int p = 0; p < s.nm; ++p)
-        if (ref_contact(s.ms[p], c)) { if (fc < 0) fc = p; lc = p; }
-      if (s.nm > 0 && fc != 0) s.status = kRefNoTakeOff + c;
-      else if (s.nm > 0 && lc != s.nm - 1) s.status = kRefNoTouchDown + c;
-    }
+  if (s.status == kRefOk) base = ref_window(s, lib, tmpl, lower, upper);
+  if (s.status == kRefOk) ref_check_swings(s);
   w.base = base; w.ne = s.ne; w.nm = s.nm; w.status = s.status;
 }
 
@@ -201,23 +217,20 @@ __device__ inline void ref_swing(const RefGenLds& w, const ReferenceGenArgs& a, 
   else ref_cubic_eval(ref_cubic(mid, z_mid, 0.0, t_td, terrain, scale * a.touch_down_velocity), t, z, zd);
 }
 
-__global__ __launch_bounds__(64) void k_reference_grids(ReferenceGenArgs a) {
+// Shooting grid of the schedule in LDS (one lane): what k_reference_grids and k_gait_advance lay after the schedule.
+__device__ inline void ref_lay_grid(RefGenLds& w, const ReferenceGenArgs& a, double t0) {
   EXACT_FP_BODY
-  __shared__ RefGenLds w;
-  const int g = blockIdx.x, l = threadIdx.x;
-  const double t0 = a.t0[g];
-  if (l == 0) {
-    w.rows = 12;
-    w.vrows = 4;
-    ref_build_schedule(w, a.lib, a.gait[g], a.gait_start[g], t0, a.horizon);
-    int n = 0;
-    if (w.status == kRefOk) {
-      n = ref_shooting_grid(w, t0, t0 + a.horizon, a.dt, a.dt_min);
-      if (n > a.N) w.status = kRefGridTooLong;
-    }
-    w.n_grid = n;
+  int n = 0;
+  if (w.status == kRefOk) {
+    n = ref_shooting_grid(w, t0, t0 + a.horizon, a.dt, a.dt_min);
+    if (n > a.N) w.status = kRefGridTooLong;
   }
-  __syncthreads();
+  w.n_grid = n;
+}
+
+// Node table g from the grid and schedule in LDS, whole stride (every lane of the workgroup; the caller synchronises before).
+__device__ inline void ref_fill_tables(RefGenLds& w, const ReferenceGenArgs& a, int g, int l) {
+  EXACT_FP_BODY
   const int n = w.n_grid, N = a.N;
   const bool ok = w.status == kRefOk;
   const double* ev = w.ev + w.base;
@@ -247,8 +260,23 @@ __global__ __launch_bounds__(64) void k_reference_grids(ReferenceGenArgs a) {
     for (int c = 0; c < 4; ++c) { a.zref[4 * i + c] = z[c]; a.zdref[4 * i + c] = zd[c]; }
   }
   for (int k = l; k <= N; k += 64) a.node_time[(size_t)g * (N + 1) + k] = (ok && k <= n) ? w.time[k] : 0.0;
+}
+
+__global__ __launch_bounds__(64) void k_reference_grids(ReferenceGenArgs a) {
+  EXACT_FP_BODY
+  __shared__ RefGenLds w;
+  const int g = blockIdx.x, l = threadIdx.x;
+  const double t0 = a.t0[g];
+  if (l == 0) {
+    w.rows = 12;
+    w.vrows = 4;
+    ref_build_schedule(w, a.lib, a.gait[g], a.gait_start[g], t0, a.horizon);
+    ref_lay_grid(w, a, t0);
+  }
   __syncthreads();
-  if (l == 0) { a.nodes[g] = n; a.status[g] = w.status; a.rows[g] = w.rows | (w.vrows << 8); }
+  ref_fill_tables(w, a, g, l);
+  __syncthreads();
+  if (l == 0) { a.nodes[g] = w.n_grid; a.status[g] = w.status; a.rows[g] = w.rows | (w.vrows << 8); }
 }
 
 struct CommandTargetArgs {

@@ -28,6 +28,7 @@
 #include "kernel_launchers.h"
 #include "reference_gen.h"
 #include "kernels/reference_device.h"
+#include "kernels/gait_state.h"
 #include "kernels/rollout.h"
 
 namespace bpmpc {
@@ -441,6 +442,27 @@ void bpmpc_solver::ddp_nominal_rollout() {
   HIP_CHECK(hipGetLastError());
 }
 
+// One GaitSchedule per robot on the device (include/bpmpc.h, bpmpc_gait_batch): the schedules live in state slots of a double buffer,
+// robots of one slot share their whole history (create / reset, inserts, commands, the t0 of every setup) and so their schedule and their grid.
+// bpmpc_solver_setup_gaits advances the front buffer into the back one and swaps them only when every robot was accepted.
+struct bpmpc_gait_batch {
+  bpmpc_solver* solver = nullptr;
+  int max_batch = 0, n_gaits = 0;
+  GaitLibraryView lib{};                                    // on the device, uploaded once
+  double* ev[2] = {nullptr, nullptr};                      // [slot][kRefMaxEvents]
+  int* ms[2] = {nullptr, nullptr};                         // [slot][kRefMaxEvents + 1]
+  int* meta[2] = {nullptr, nullptr};                       // [slot][kGaitMeta]
+  int front = 0;
+  int* grp_i = nullptr;                                    // per group of a setup: source slot, insert gait, command [3][max_batch]
+  double* grp_d = nullptr;                                 // ... t0, insert start, insert final [3][max_batch]
+  int* cmd_dev = nullptr;                                  // pending commands while device-side commands are outstanding
+  bool cmd_on_device = false;                              // cmd_dev, not cmd, holds the pending commands
+  std::vector<int> slot;                                   // per robot: state slot in the front buffer, < 0 = the state after create / reset
+  std::vector<int> cmd, ins_gait;                          // per robot: pending command / insert (< 0: none)
+  std::vector<double> ins_start, ins_final;
+  std::vector<void*> allocations;
+};
+
 namespace {
 
 int translate(const std::exception& e) {
@@ -789,88 +811,93 @@ void setup(bpmpc_solver* s, int batch, double horizon, const double* t0, const d
 
 void check_rollout_status(bpmpc_solver* s, int* steps);
 
-// Device-side reference generation (SURVEY.md section 8(f) rank 2): the same tables as setup(), built on the GPU from gait
-// templates and velocity commands; the host only groups problems by (t0, gait, gait start) and reads the grid sizes back.
-void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_gait_template* gaits, int n_gaits,
-                    const int* gait_of_problem, const double* gait_start, const double* cmd_vel, int command_kind, double time_to_target,
-                    bool from_previous) {
-  if (batch < 1 || batch > s->settings.max_batch) throw std::length_error("batch exceeds the solver's max_batch");
-  if (!(horizon > 0) || !t0 || !cmd_vel || n_gaits < 0 || (n_gaits > 0 && !gaits)) throw std::invalid_argument("setup_commands: null or invalid argument");
-  if (!x0 && (!(s->has_rollout || s->loop_from_tick) || batch != s->batch))
-    throw std::invalid_argument("setup_commands: x0 == NULL needs a rollout of the same batch on the handle (or a controller tick)");
-  if (!x0 && !s->loop_from_tick && s->rollout_unchecked) check_rollout_status(s, nullptr);
-  if (command_kind != 0 && command_kind != 1) throw std::invalid_argument("setup_commands: command_kind is 0 (velocity) or 1 (goal pose)");
-  if (n_gaits > 0 && (!gait_of_problem || !gait_start)) throw std::invalid_argument("setup_commands: gait_of_problem and gait_start are needed with templates");
-  const int N = s->settings.max_nodes, NX = s->nx;
-  const double dt = s->settings.dt > 0 ? s->settings.dt : s->rm.sqp.dt;
-  std::vector<int> pgrid(batch), ggait;
-  std::vector<double> gt0, gstart;
-  {
-    std::map<std::tuple<double, int, double>, int> seen;
-    for (int b = 0; b < batch; ++b) {
-      const int gi = gait_of_problem ? gait_of_problem[b] : -1;
-      if (gi >= n_gaits) throw std::invalid_argument("gait_of_problem refers to a template that was not passed");
-      const double st = gi >= 0 ? gait_start[b] : 0.0;
-      auto key = std::make_tuple(t0[b], gi < 0 ? -1 : gi, st);
-      auto it = seen.find(key);
-      if (it == seen.end()) { it = seen.emplace(key, (int)gt0.size()).first; gt0.push_back(t0[b]); ggait.push_back(gi < 0 ? -1 : gi); gstart.push_back(st); }
-      pgrid[b] = it->second;
-    }
+// Host image of the device gait library: the passed templates, then defaultModeSequenceTemplate; initialModeSchedule behind them
+struct GaitLibrary {
+  std::vector<double> d;
+  std::vector<int> i;
+  int n_templates = 0, init_n_events = 0;
+  size_t first_mode_count = 0, sw_count = 0, mode_count = 0;
+  GaitLibraryView view(const double* dev_d, const int* dev_i, double transition_stance_time) const {
+    GaitLibraryView v{};
+    v.switching = dev_d; v.first_mode = dev_i; v.modes = dev_i + first_mode_count; v.n_templates = n_templates;
+    v.init_events = dev_d + sw_count; v.init_modes = dev_i + first_mode_count + mode_count; v.init_n_events = init_n_events;
+    v.transition_stance_time = transition_stance_time;
+    return v;
   }
-  const int G = (int)gt0.size();
-  // gait library: the passed templates, then defaultModeSequenceTemplate; initialModeSchedule behind them
-  std::vector<double> lib_d;
+};
+GaitLibrary gait_library(const RobotModel& rm, const bpmpc_gait_template* gaits, int n_gaits) {
+  GaitLibrary L;
   std::vector<int> first_mode{0}, lib_modes;
   auto add_template = [&](const double* sw, const int* modes, int n) {
     if (n < 0 || (n > 0 && (!sw || !modes))) throw std::invalid_argument("invalid gait template");
-    lib_d.insert(lib_d.end(), sw, sw + (n > 0 ? n + 1 : 0));
-    if (n == 0) lib_d.push_back(0.0);
+    L.d.insert(L.d.end(), sw, sw + (n > 0 ? n + 1 : 0));
+    if (n == 0) L.d.push_back(0.0);
     lib_modes.insert(lib_modes.end(), modes, modes + n);
     first_mode.push_back((int)lib_modes.size());
   };
   for (int g = 0; g < n_gaits; ++g) add_template(gaits[g].switching_times, gaits[g].modes, gaits[g].n_modes);
-  const ModeTemplate& dflt = s->rm.default_template;
+  const ModeTemplate& dflt = rm.default_template;
   if (!dflt.modes.empty() && dflt.switching_times.size() != dflt.modes.size() + 1) throw std::invalid_argument("default gait template is malformed");
   add_template(dflt.switching_times.data(), dflt.modes.data(), (int)dflt.modes.size());
-  const ModeSchedule& init = s->rm.initial_mode_schedule;
-  const size_t sw_count = lib_d.size(), mode_count = lib_modes.size();
-  lib_d.insert(lib_d.end(), init.event_times.begin(), init.event_times.end());
-  std::vector<int> lib_i = first_mode;
-  lib_i.insert(lib_i.end(), lib_modes.begin(), lib_modes.end());
-  lib_i.insert(lib_i.end(), init.modes.begin(), init.modes.end());
-  if (lib_d.size() > (size_t)kRefLibCapacity || lib_i.size() > (size_t)kRefLibCapacity) throw std::length_error("gait library exceeds the device capacity");
-  if (from_previous) preserve_previous(s, batch, false);
-  Buffers& bf = s->buf;
-  s->pin_up.reset();                                      // the previous call waited for its transfers (the synchronisation below)
-  {
-    const TransferPiece up[9] = {{bf.rg_t0, gt0.data(), nullptr, gt0.size() * sizeof(double)}, {bf.rg_gait, ggait.data(), nullptr, ggait.size() * sizeof(int)},
-                                 {bf.rg_start, gstart.data(), nullptr, gstart.size() * sizeof(double)}, {bf.lib_d, lib_d.data(), nullptr, lib_d.size() * sizeof(double)},
-                                 {bf.lib_i, lib_i.data(), nullptr, lib_i.size() * sizeof(int)}, {bf.p_grid, pgrid.data(), nullptr, pgrid.size() * sizeof(int)},
-                                 {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)}, {bf.p_cmd, cmd_vel, nullptr, (size_t)batch * 4 * sizeof(double)},
-                                 {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
-    upload_batch(s, up, 9);
-  }
-  if (!x0) HIP_CHECK(hipMemcpyAsync(bf.p_x0, s->loop_from_tick ? s->tick_x : bf.roll_x, (size_t)batch * NX * sizeof(double), hipMemcpyDeviceToDevice,
-                                    s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
+  const ModeSchedule& init = rm.initial_mode_schedule;
+  L.n_templates = n_gaits + 1; L.init_n_events = (int)init.event_times.size();
+  L.first_mode_count = first_mode.size(); L.sw_count = L.d.size(); L.mode_count = lib_modes.size();
+  L.d.insert(L.d.end(), init.event_times.begin(), init.event_times.end());
+  L.i = first_mode;
+  L.i.insert(L.i.end(), lib_modes.begin(), lib_modes.end());
+  L.i.insert(L.i.end(), init.modes.begin(), init.modes.end());
+  if (L.d.size() > (size_t)kRefLibCapacity || L.i.size() > (size_t)kRefLibCapacity) throw std::length_error("gait library exceeds the device capacity");
+  return L;
+}
+
+// argument checks shared by the device-side setups (`what` names the entry point in the messages)
+void check_device_setup(bpmpc_solver* s, const char* what, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
+                        int command_kind, bool invalid_other) {
+  const std::string w(what);
+  if (batch < 1 || batch > s->settings.max_batch) throw std::length_error("batch exceeds the solver's max_batch");
+  if (!(horizon > 0) || !t0 || !cmd_vel || invalid_other) throw std::invalid_argument(w + ": null or invalid argument");
+  if (!x0 && (!(s->has_rollout || s->loop_from_tick) || batch != s->batch))
+    throw std::invalid_argument(w + ": x0 == NULL needs a rollout of the same batch on the handle (or a controller tick)");
+  if (!x0 && !s->loop_from_tick && s->rollout_unchecked) check_rollout_status(s, nullptr);
+  if (command_kind != 0 && command_kind != 1) throw std::invalid_argument(w + ": command_kind is 0 (velocity) or 1 (goal pose)");
+}
+
+// grid settings and node-table outputs of k_reference_grids / k_gait_advance
+ReferenceGenArgs reference_args(bpmpc_solver* s, const GaitLibraryView& lib, int G, double horizon) {
+  const Buffers& bf = s->buf;
   ReferenceGenArgs a{};
-  a.lib.switching = bf.lib_d; a.lib.first_mode = bf.lib_i; a.lib.modes = bf.lib_i + first_mode.size(); a.lib.n_templates = n_gaits + 1;
-  a.lib.init_events = bf.lib_d + sw_count; a.lib.init_modes = bf.lib_i + first_mode.size() + mode_count; a.lib.init_n_events = (int)init.event_times.size();
-  a.lib.transition_stance_time = s->rm.phase_transition_stance_time;
-  a.n_grids = G; a.N = N; a.horizon = horizon; a.dt = dt; a.dt_min = 1e-8;
-  a.t0 = bf.rg_t0; a.gait = bf.rg_gait; a.gait_start = bf.rg_start;
+  a.lib = lib;
+  a.n_grids = G; a.N = s->settings.max_nodes; a.horizon = horizon; a.dt = s->settings.dt > 0 ? s->settings.dt : s->rm.sqp.dt; a.dt_min = 1e-8;
   a.lift_off_velocity = s->rm.swing.lift_off_velocity; a.touch_down_velocity = s->rm.swing.touch_down_velocity;
   a.swing_height = s->rm.swing.swing_height; a.swing_time_scale = s->rm.swing.swing_time_scale;
   a.kind = bf.g_kind; a.mode = bf.g_mode; a.nodes = bf.g_nodes; a.status = bf.rg_status; a.rows = bf.rg_rows;
   a.gdt = bf.g_dt; a.gstart = bf.g_start; a.zref = bf.g_zref; a.zdref = bf.g_zdref; a.node_time = bf.g_time;
-  hipLaunchKernelGGL(k_reference_grids, dim3(G), dim3(64), 0, s->stream, a);
-  HIP_CHECK(hipGetLastError());
+  return a;
+}
+
+// x0 == NULL: the start states are already on the device
+void copy_loop_x0(bpmpc_solver* s, int batch, const double* x0) {
+  if (!x0) HIP_CHECK(hipMemcpyAsync(s->buf.p_x0, s->loop_from_tick ? s->tick_x : s->buf.roll_x, (size_t)batch * s->nx * sizeof(double), hipMemcpyDeviceToDevice,
+                                    s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
+}
+
+// the target trajectories of the velocity commands / goal poses (k_command_targets)
+void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int command_kind, double time_to_target) {
+  Buffers& bf = s->buf;
   CommandTargetArgs c{};
-  c.batch = batch; c.nx = NX; c.nj = s->rm.nj; c.time_to_target = time_to_target > 0 ? time_to_target : horizon; c.com_height = s->rm.com_height;
+  c.batch = batch; c.nx = s->nx; c.nj = s->rm.nj; c.time_to_target = time_to_target > 0 ? time_to_target : horizon; c.com_height = s->rm.com_height;
   c.goal = command_kind; c.displacement_velocity = s->rm.target_displacement_velocity; c.rotation_velocity = s->rm.target_rotation_velocity;
   for (int j = 0; j < s->rm.nj; ++j) c.default_joint_state[j] = s->rm.default_joint_state[j];
   c.t0 = bf.p_t0; c.x0 = bf.p_x0; c.cmd_vel = bf.p_cmd; c.tgt_t = bf.p_tgt_t; c.tgt_x = bf.p_tgt_x; c.tgt_n = bf.p_tgt_n;
   hipLaunchKernelGGL(k_command_targets, dim3((batch + 63) / 64), dim3(64), 0, s->stream, c);
   HIP_CHECK(hipGetLastError());
+}
+
+// Reads the grid sizes of the G grids the device just laid back (synchronises), reports a rejected grid like the host path and takes the
+// accepted ones over into the handle; the caller then runs finish_setup.  A rejected setup leaves the solver without a usable setup.
+void accept_reference_grids(bpmpc_solver* s, int batch, int G, const std::vector<int>& pgrid) {
+  const int N = s->settings.max_nodes;
+  const Buffers& bf = s->buf;
   std::vector<int> nodes(G), status(G), rows(G), kind((size_t)G * N);
   std::vector<double> node_times((size_t)G * (N + 1), 0.0);   // becomes the handle's copy once every grid has been accepted
   {
@@ -898,9 +925,202 @@ void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0
   s->node_times.swap(node_times);
   s->batch = batch; s->n_grids = G; s->n_nodes_max = nmax; s->cold = true; s->max_rows = rows_max; s->max_vel_rows = vrows_max;
   s->grid_nodes = nodes; s->grid_of_problem = pgrid; s->grid_kind = kind;
+}
+
+// Device-side reference generation (SURVEY.md section 8(f) rank 2): the same tables as setup(), built on the GPU from gait
+// templates and velocity commands; the host only groups problems by (t0, gait, gait start) and reads the grid sizes back.
+void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_gait_template* gaits, int n_gaits,
+                    const int* gait_of_problem, const double* gait_start, const double* cmd_vel, int command_kind, double time_to_target,
+                    bool from_previous) {
+  check_device_setup(s, "setup_commands", batch, horizon, t0, x0, cmd_vel, command_kind, n_gaits < 0 || (n_gaits > 0 && !gaits));
+  if (n_gaits > 0 && (!gait_of_problem || !gait_start)) throw std::invalid_argument("setup_commands: gait_of_problem and gait_start are needed with templates");
+  const int NX = s->nx;
+  std::vector<int> pgrid(batch), ggait;
+  std::vector<double> gt0, gstart;
+  {
+    std::map<std::tuple<double, int, double>, int> seen;
+    for (int b = 0; b < batch; ++b) {
+      const int gi = gait_of_problem ? gait_of_problem[b] : -1;
+      if (gi >= n_gaits) throw std::invalid_argument("gait_of_problem refers to a template that was not passed");
+      const double st = gi >= 0 ? gait_start[b] : 0.0;
+      auto key = std::make_tuple(t0[b], gi < 0 ? -1 : gi, st);
+      auto it = seen.find(key);
+      if (it == seen.end()) { it = seen.emplace(key, (int)gt0.size()).first; gt0.push_back(t0[b]); ggait.push_back(gi < 0 ? -1 : gi); gstart.push_back(st); }
+      pgrid[b] = it->second;
+    }
+  }
+  const int G = (int)gt0.size();
+  const GaitLibrary lib = gait_library(s->rm, gaits, n_gaits);
+  if (from_previous) preserve_previous(s, batch, false);
+  Buffers& bf = s->buf;
+  s->pin_up.reset();                                      // the previous call waited for its transfers (the synchronisation below)
+  {
+    const TransferPiece up[9] = {{bf.rg_t0, gt0.data(), nullptr, gt0.size() * sizeof(double)}, {bf.rg_gait, ggait.data(), nullptr, ggait.size() * sizeof(int)},
+                                 {bf.rg_start, gstart.data(), nullptr, gstart.size() * sizeof(double)}, {bf.lib_d, lib.d.data(), nullptr, lib.d.size() * sizeof(double)},
+                                 {bf.lib_i, lib.i.data(), nullptr, lib.i.size() * sizeof(int)}, {bf.p_grid, pgrid.data(), nullptr, pgrid.size() * sizeof(int)},
+                                 {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)}, {bf.p_cmd, cmd_vel, nullptr, (size_t)batch * 4 * sizeof(double)},
+                                 {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
+    upload_batch(s, up, 9);
+  }
+  ReferenceGenArgs a = reference_args(s, lib.view(bf.lib_d, bf.lib_i, s->rm.phase_transition_stance_time), G, horizon);
+  a.t0 = bf.rg_t0; a.gait = bf.rg_gait; a.gait_start = bf.rg_start;
+  copy_loop_x0(s, batch, x0);
+  hipLaunchKernelGGL(k_reference_grids, dim3(G), dim3(64), 0, s->stream, a);
+  HIP_CHECK(hipGetLastError());
+  launch_command_targets(s, batch, horizon, command_kind, time_to_target);
+  accept_reference_grids(s, batch, G, pgrid);
   finish_setup(s, batch, nullptr, nullptr, from_previous);
 }
 
+void check_gait_batch(const bpmpc_gait_batch* g, int batch, const int* gait, bool host_gaits) {
+  if (!g) throw std::invalid_argument("null gait batch handle");
+  if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("batch exceeds the gait batch's max_batch");
+  if (!gait) throw std::invalid_argument("null gait array");
+  if (host_gaits)
+    for (int b = 0; b < batch; ++b)
+      if (gait[b] >= g->n_gaits) throw std::invalid_argument("gait index refers to a template that was not passed");
+}
+
+void gait_batch_reset(bpmpc_gait_batch* g) {
+  std::fill(g->slot.begin(), g->slot.end(), -1);
+  std::fill(g->cmd.begin(), g->cmd.end(), -1);
+  std::fill(g->ins_gait.begin(), g->ins_gait.end(), -1);
+  std::fill(g->ins_start.begin(), g->ins_start.end(), 0.0);
+  std::fill(g->ins_final.begin(), g->ins_final.end(), 0.0);
+  g->cmd_on_device = false;
+}
+
+// the pending commands back on the host (synchronises; only after a device-side command)
+void gait_commands_to_host(bpmpc_gait_batch* g) {
+  if (!g->cmd_on_device) return;
+  bpmpc_solver* s = g->solver;
+  HIP_CHECK(hipMemcpyAsync(g->cmd.data(), g->cmd_dev, g->max_batch * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIP_CHECK(hipStreamSynchronize(s->stream));
+  g->cmd_on_device = false;
+}
+
+void gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, bool on_device) {
+  check_gait_batch(g, batch, gait, !on_device);
+  bpmpc_solver* s = g->solver;
+  if (!on_device) {
+    gait_commands_to_host(g);
+    for (int b = 0; b < batch; ++b) if (gait[b] >= 0) g->cmd[b] = gait[b];
+    return;
+  }
+  if (!g->cmd_on_device) {                                // the device copy takes over: it starts from the host's pending commands
+    if (std::all_of(g->cmd.begin(), g->cmd.end(), [](int c) { return c < 0; })) {
+      HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)g->cmd_dev, -1, g->max_batch, s->stream));
+    } else {
+      HIP_CHECK(hipMemcpyAsync(g->cmd_dev, g->cmd.data(), g->max_batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
+      HIP_CHECK(hipStreamSynchronize(s->stream));
+    }
+  }
+  hipLaunchKernelGGL(k_gait_command, dim3((batch + 255) / 256), dim3(256), 0, s->stream, batch, gait, g->cmd_dev);
+  HIP_CHECK(hipGetLastError());
+  g->cmd_on_device = true;
+}
+
+// GaitSchedule state of one robot after the last setup (synchronises)
+void gait_batch_mode_schedule(bpmpc_gait_batch* g, int robot, double* event_times, int* modes, int capacity, int* n_events) {
+  if (!g || !event_times || !modes || !n_events) throw std::invalid_argument("bpmpc_gait_batch_mode_schedule: null argument");
+  if (robot < 0 || robot >= g->max_batch) throw std::invalid_argument("bpmpc_gait_batch_mode_schedule: robot out of range");
+  const int slot = g->slot[robot];
+  if (slot < 0) {
+    const ModeSchedule& init = g->solver->rm.initial_mode_schedule;
+    if ((int)init.modes.size() > capacity || (int)init.event_times.size() > capacity) throw std::length_error("mode schedule capacity too small");
+    std::copy(init.event_times.begin(), init.event_times.end(), event_times);
+    std::copy(init.modes.begin(), init.modes.end(), modes);
+    *n_events = (int)init.event_times.size();
+    return;
+  }
+  bpmpc_solver* s = g->solver;
+  int meta[kGaitMeta];
+  HIP_CHECK(hipMemcpyAsync(meta, g->meta[g->front] + (size_t)slot * kGaitMeta, sizeof(meta), hipMemcpyDeviceToHost, s->stream));
+  HIP_CHECK(hipStreamSynchronize(s->stream));
+  if (meta[0] > capacity || meta[1] > capacity) throw std::length_error("mode schedule capacity too small");
+  HIP_CHECK(hipMemcpyAsync(event_times, g->ev[g->front] + (size_t)slot * kRefMaxEvents, meta[0] * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+  HIP_CHECK(hipMemcpyAsync(modes, g->ms[g->front] + (size_t)slot * (kRefMaxEvents + 1), meta[1] * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIP_CHECK(hipStreamSynchronize(s->stream));
+  *n_events = meta[0];
+}
+
+// setup_commands with the schedules of the gait batch: the pending inserts, getModeSchedule(t0 - H, t0 + 2 H) as the window of this setup,
+// then the pending commands at (t0 + H, H) - per group of robots with one history, in k_gait_advance
+void setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
+                 int command_kind, double time_to_target, bool from_previous) {
+  if (!g || g->solver != s) throw std::invalid_argument("setup_gaits: the gait batch belongs to another solver");
+  if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("setup_gaits: batch exceeds the gait batch's max_batch");
+  check_device_setup(s, "setup_gaits", batch, horizon, t0, x0, cmd_vel, command_kind, false);
+  gait_commands_to_host(g);
+  for (int b = 0; b < batch; ++b)
+    if (g->cmd[b] >= g->n_gaits) throw std::invalid_argument("setup_gaits: a gait command refers to a template that was not passed");
+  const int NX = s->nx, B = g->max_batch;
+  // groups: robots of the batch with one (history, t0, pending insert, pending command) advance together; robots behind the batch
+  // keep their state (one group per slot in use)
+  std::vector<int> pgrid(batch), new_slot(B, -1), src, ins_g, cmd;
+  std::vector<double> gt0, ins_s, ins_f;
+  {
+    std::map<std::tuple<int, double, int, double, double, int>, int> seen;
+    for (int b = 0; b < batch; ++b) {
+      const bool ins = g->ins_gait[b] >= 0;
+      auto key = std::make_tuple(g->slot[b], t0[b], ins ? g->ins_gait[b] : -1, ins ? g->ins_start[b] : 0.0, ins ? g->ins_final[b] : 0.0, g->cmd[b] < 0 ? -1 : g->cmd[b]);
+      auto it = seen.find(key);
+      if (it == seen.end()) {
+        it = seen.emplace(key, (int)src.size()).first;
+        src.push_back(g->slot[b]); gt0.push_back(t0[b]); ins_g.push_back(std::get<2>(key)); ins_s.push_back(std::get<3>(key)); ins_f.push_back(std::get<4>(key));
+        cmd.push_back(std::get<5>(key));
+      }
+      pgrid[b] = new_slot[b] = it->second;
+    }
+  }
+  const int G = (int)src.size();
+  {
+    std::map<int, int> kept;
+    for (int b = batch; b < B; ++b) {
+      if (g->slot[b] < 0) continue;
+      auto it = kept.find(g->slot[b]);
+      if (it == kept.end()) {
+        it = kept.emplace(g->slot[b], (int)src.size()).first;
+        src.push_back(g->slot[b]); gt0.push_back(0.0); ins_g.push_back(-1); ins_s.push_back(0.0); ins_f.push_back(0.0); cmd.push_back(-1);
+      }
+      new_slot[b] = it->second;
+    }
+  }
+  const int groups = (int)src.size();
+  std::vector<int> gi(3 * (size_t)B, -1);
+  std::vector<double> gd(3 * (size_t)B, 0.0);
+  std::copy(src.begin(), src.end(), gi.begin()); std::copy(ins_g.begin(), ins_g.end(), gi.begin() + B); std::copy(cmd.begin(), cmd.end(), gi.begin() + 2 * B);
+  std::copy(gt0.begin(), gt0.end(), gd.begin()); std::copy(ins_s.begin(), ins_s.end(), gd.begin() + B); std::copy(ins_f.begin(), ins_f.end(), gd.begin() + 2 * B);
+  if (from_previous) preserve_previous(s, batch, false);
+  Buffers& bf = s->buf;
+  s->pin_up.reset();                                      // the previous call waited for its transfers (the synchronisation below)
+  {
+    const TransferPiece up[6] = {{g->grp_i, gi.data(), nullptr, gi.size() * sizeof(int)}, {g->grp_d, gd.data(), nullptr, gd.size() * sizeof(double)},
+                                 {bf.p_grid, pgrid.data(), nullptr, pgrid.size() * sizeof(int)}, {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)},
+                                 {bf.p_cmd, cmd_vel, nullptr, (size_t)batch * 4 * sizeof(double)}, {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
+    upload_batch(s, up, 6);
+  }
+  GaitAdvanceArgs a{};
+  a.ref = reference_args(s, g->lib, G, horizon);
+  a.ref.t0 = g->grp_d;
+  a.n_advance = G;
+  a.src = g->grp_i; a.insert_gait = g->grp_i + B; a.command = g->grp_i + 2 * B;
+  a.insert_start = g->grp_d + B; a.insert_final = g->grp_d + 2 * B;
+  const int f = g->front, k = 1 - f;
+  a.ev_in = g->ev[f]; a.ms_in = g->ms[f]; a.meta_in = g->meta[f];
+  a.ev_out = g->ev[k]; a.ms_out = g->ms[k]; a.meta_out = g->meta[k];
+  copy_loop_x0(s, batch, x0);
+  hipLaunchKernelGGL(k_gait_advance, dim3(groups), dim3(64), 0, s->stream, a);
+  HIP_CHECK(hipGetLastError());
+  launch_command_targets(s, batch, horizon, command_kind, time_to_target);
+  accept_reference_grids(s, batch, G, pgrid);
+  // every robot was accepted: the new schedules become the front buffer, the applied inserts and commands are no longer pending
+  g->front = k;
+  g->slot.swap(new_slot);
+  std::fill(g->cmd.begin(), g->cmd.begin() + batch, -1);
+  std::fill(g->ins_gait.begin(), g->ins_gait.begin() + batch, -1);
+  finish_setup(s, batch, nullptr, nullptr, from_previous);
+}
 
 // reads the per-problem flags of the last rollout back (synchronises) and reports failures like the reference's integrator does
 void check_rollout_status(bpmpc_solver* s, int* steps) {
@@ -1132,6 +1352,74 @@ int bpmpc_solver_setup_commands(bpmpc_solver* s, int batch, double horizon, cons
                                 int n_gaits, const int* gait_of_problem, const double* gait_start, const double* cmd_vel, int command_kind,
                                 double time_to_target, int from_previous) {
   API_GUARD(s, { setup_commands(s, batch, horizon, t0, x0, gaits, n_gaits, gait_of_problem, gait_start, cmd_vel, command_kind, time_to_target, from_previous != 0); })
+}
+int bpmpc_solver_setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
+                             int command_kind, double time_to_target, int from_previous) {
+  API_GUARD(s, { setup_gaits(s, g, batch, horizon, t0, x0, cmd_vel, command_kind, time_to_target, from_previous != 0); })
+}
+int bpmpc_gait_batch_create(bpmpc_solver* s, const bpmpc_gait_template* gaits, int n_gaits, bpmpc_gait_batch** out) {
+  if (!out) { set_last_error("bpmpc_gait_batch_create: null output"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  *out = nullptr;
+  if (!s) { set_last_error("bpmpc_gait_batch_create: null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  std::unique_ptr<bpmpc_gait_batch> g(new bpmpc_gait_batch);
+  try {
+    if (n_gaits < 0 || (n_gaits > 0 && !gaits)) throw std::invalid_argument("bpmpc_gait_batch_create: null or invalid gait templates");
+    HIP_CHECK(hipSetDevice(s->settings.device));
+    const GaitLibrary lib = gait_library(s->rm, gaits, n_gaits);
+    const int B = s->settings.max_batch;
+    g->solver = s; g->max_batch = B; g->n_gaits = n_gaits;
+    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); g->allocations.push_back(p); return p; };
+    double* lib_d = static_cast<double*>(alloc(lib.d.size() * sizeof(double)));
+    int* lib_i = static_cast<int*>(alloc(lib.i.size() * sizeof(int)));
+    for (int k = 0; k < 2; ++k) {
+      g->ev[k] = static_cast<double*>(alloc((size_t)B * kRefMaxEvents * sizeof(double)));
+      g->ms[k] = static_cast<int*>(alloc((size_t)B * (kRefMaxEvents + 1) * sizeof(int)));
+      g->meta[k] = static_cast<int*>(alloc((size_t)B * kGaitMeta * sizeof(int)));
+    }
+    g->grp_i = static_cast<int*>(alloc(3 * (size_t)B * sizeof(int)));
+    g->grp_d = static_cast<double*>(alloc(3 * (size_t)B * sizeof(double)));
+    g->cmd_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
+    HIP_CHECK(hipMemcpyAsync(lib_d, lib.d.data(), lib.d.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipMemcpyAsync(lib_i, lib.i.data(), lib.i.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    g->lib = lib.view(lib_d, lib_i, s->rm.phase_transition_stance_time);
+    g->slot.resize(B); g->cmd.resize(B); g->ins_gait.resize(B); g->ins_start.resize(B); g->ins_final.resize(B);
+    gait_batch_reset(g.get());
+  } catch (const std::exception& e) {
+    const int rc = translate(e);
+    bpmpc_gait_batch_destroy(g.release());
+    return rc;
+  }
+  *out = g.release();
+  return BPMPC_OK;
+}
+void bpmpc_gait_batch_destroy(bpmpc_gait_batch* g) {
+  if (!g) return;
+  if (g->solver && g->solver->stream) (void)hipStreamSynchronize(g->solver->stream);
+  for (void* p : g->allocations) (void)hipFree(p);
+  delete g;
+}
+int bpmpc_gait_batch_reset(bpmpc_gait_batch* g) {
+  if (!g) { set_last_error("bpmpc_gait_batch_reset: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  gait_batch_reset(g);
+  return BPMPC_OK;
+}
+int bpmpc_gait_batch_insert(bpmpc_gait_batch* g, int batch, const int* gait, const double* start_time, const double* final_time) {
+  try {
+    check_gait_batch(g, batch, gait, true);
+    if (!start_time || !final_time) throw std::invalid_argument("bpmpc_gait_batch_insert: null start or final times");
+    for (int b = 0; b < batch; ++b)
+      if (gait[b] >= 0) { g->ins_gait[b] = gait[b]; g->ins_start[b] = start_time[b]; g->ins_final[b] = final_time[b]; }
+  } catch (const std::exception& e) { return translate(e); }
+  return BPMPC_OK;
+}
+int bpmpc_gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, int inputs_on_device) {
+  if (!g) { set_last_error("bpmpc_gait_batch_command: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  API_GUARD(g->solver, { gait_batch_command(g, batch, gait, inputs_on_device != 0); })
+}
+int bpmpc_gait_batch_mode_schedule(bpmpc_gait_batch* g, int robot, double* event_times, int* modes, int capacity, int* n_events) {
+  if (!g) { set_last_error("bpmpc_gait_batch_mode_schedule: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  API_GUARD(g->solver, { gait_batch_mode_schedule(g, robot, event_times, modes, capacity, n_events); })
 }
 int bpmpc_solver_rollout(bpmpc_solver* s, const double* t_start, const double* x_start, double duration, double* x_end, double* u_end, int* steps) {
   API_GUARD(s, { rollout(s, t_start, x_start, duration, x_end, u_end, steps); })

@@ -240,6 +240,45 @@ int bpmpc_solver_setup_commands(bpmpc_solver* solver, int batch, double horizon,
                                 const bpmpc_gait_template* gaits, int n_gaits, const int* gait_of_problem, const double* gait_start,
                                 const double* cmd_vel /* [batch][4]: vx, vy, vz, yaw rate */, int command_kind, double time_to_target,
                                 int from_previous);
+/* Device-resident gait schedules: one GaitSchedule per robot kept on the device between setups, changed at run time by gait
+ * commands with the semantics of GaitReceiver (ocs2_bipedal_robot/src/gait/GaitReceiver.cpp:49-59), so that every robot runs on
+ * its own gait clock and its schedule is the result of its whole command history (GaitSchedule.cpp:46-137, owned by
+ * SwitchedModelReferenceManager.cpp:62-69 and shared with the GaitReceiver).  Per robot b, horizon H:
+ *   create / reset   GaitSchedule(initialModeSchedule, defaultModeSequenceTemplate, phaseTransitionStanceTime) of reference.info
+ *                    (what bpmpc_gait_create builds); nothing pending.  The template library gaits[0 .. n_gaits) is uploaded once.
+ *   insert           insertModeSequenceTemplate(gaits[g], start, final), recorded per robot (a second insert before the setup
+ *                    replaces the first; g < 0 leaves the robot's pending insert as it is) and applied by the next setup BEFORE its
+ *                    getModeSchedule: tiling from a start far in the past (a phase offset) only fits the event capacity once the
+ *                    compaction bound t0 - H of that setup is known.
+ *   command          GaitReceiver::mpcModeSequenceCallback: g >= 0 becomes the robot's pending template (the latest command before a
+ *                    setup wins), g < 0 leaves the robot's pending command as it is.  gait may be a device array (inputs_on_device:
+ *                    ordered on the solver's stream; its template indices are checked by the next setup).
+ *   setup at t0[b]   SolverBase::preRun [OCS2-upstream, recalled]: the reference manager first, then the synchronized modules -
+ *                    1. getModeSchedule(t0 - H, t0 + 2 H) (mutating): its window feeds this setup's grid, swing references, node tables;
+ *                    2. a pending command: insertModeSequenceTemplate(gaits[g], t0 + H, H) - GaitReceiver's literal (finalTime,
+ *                       timeHorizon) - and the command is no longer pending.
+ *                    A command therefore shapes the NEXT setup's window, from t0 + H on, behind a phaseTransitionStanceTime STANCE
+ *                    phase unless the last phase already is STANCE.
+ *   rejected setup   (tiling order, event capacity, grid longer than max_nodes, undefined take-off / touch-down; the statuses and
+ *                    messages of bpmpc_solver_setup_commands) changes no robot's schedule nor pending insert / command: the schedules
+ *                    are double-buffered and the new ones are kept only when every robot was accepted.
+ *   capacity         the per-robot event capacity and compaction of bpmpc_solver_setup_commands (only what getModeSchedule would erase
+ *                    is dropped), so t0 may jump arbitrarily far ahead.
+ * Robots with one history (create / reset, inserts, commands and the t0 of every setup alike) share a grid; a fleet that never
+ * diverged keeps a single grid.  Robots behind `batch` keep their schedules.  Destroy the gait batch before its solver.
+ * bpmpc_solver_setup_gaits is bpmpc_solver_setup_commands with the schedules taken from the gait batch (x0 = NULL, from_previous,
+ * command kinds, errors alike); bpmpc_gait_batch_mode_schedule reports robot's schedule after the last setup (not mutating; it
+ * synchronises).  Invalid handles, a handle of another solver, batch > max_batch, an unknown template index or robot, NULL
+ * pointers: BPMPC_ERR_INVALID_ARGUMENT. */
+typedef struct bpmpc_gait_batch bpmpc_gait_batch;
+int bpmpc_gait_batch_create(bpmpc_solver* solver, const bpmpc_gait_template* gaits, int n_gaits, bpmpc_gait_batch** out);
+void bpmpc_gait_batch_destroy(bpmpc_gait_batch* gaits);
+int bpmpc_gait_batch_reset(bpmpc_gait_batch* gaits);
+int bpmpc_gait_batch_insert(bpmpc_gait_batch* gaits, int batch, const int* gait, const double* start_time, const double* final_time);
+int bpmpc_gait_batch_command(bpmpc_gait_batch* gaits, int batch, const int* gait, int inputs_on_device);
+int bpmpc_gait_batch_mode_schedule(bpmpc_gait_batch* gaits, int robot, double* event_times, int* modes, int capacity, int* n_events);
+int bpmpc_solver_setup_gaits(bpmpc_solver* solver, bpmpc_gait_batch* gaits, int batch, double horizon, const double* t0, const double* x0,
+                             const double* cmd_vel /* [batch][4] */, int command_kind, double time_to_target, int from_previous);
 /* MRT side: MRT_BASE::rolloutPolicy for every problem of the batch - TimeTriggeredRollout::run from
  * (t_start[b], x_start[b]) over `duration` under the LinearController of the last solve (u = uff(t) + K(t) x), ODE45 with the
  * rollout block of task.info (AbsTolODE, RelTolODE, timeStep, maxNumStepsPerSecond), restarted at the mode-schedule events inside
