@@ -96,6 +96,38 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _restart_arg(a, ctype, count):
+    """(pointer, on_device, keep-alive) of a restart argument of `count` int32 (ctype c_int) or float64 entries: a contiguous torch tensor on the
+    GPU or any object with __cuda_array_interface__ of that type and size (order its producer against the handle's stream), or a host array."""
+    typestr, tname = ("<i4", "torch.int32") if ctype is C.c_int else ("<f8", "torch.float64")
+    if hasattr(a, "data_ptr") and getattr(a, "is_cuda", False):
+        if str(a.dtype) != tname or not a.is_contiguous() or a.numel() != count:
+            raise ValueError("device restart inputs must be contiguous %s tensors of %d elements" % (tname, count))
+        return C.cast(C.c_void_p(a.data_ptr()), C.POINTER(ctype)), True, a
+    iface = getattr(a, "__cuda_array_interface__", None)
+    if iface is not None:
+        if iface["typestr"] != typestr or int(np.prod(iface["shape"])) != count or iface.get("strides") not in (None, (int(typestr[-1]),)):
+            raise ValueError("device restart inputs must be contiguous %s arrays of %d elements" % (typestr, count))
+        return C.cast(C.c_void_p(iface["data"][0]), C.POINTER(ctype)), True, a
+    h = np.ascontiguousarray(np.asarray(a).reshape(-1), np.int32 if ctype is C.c_int else np.float64)
+    if h.size != count:
+        raise ValueError("restart inputs need %d entries, got %d" % (count, h.size))
+    return h.ctypes.data_as(C.POINTER(ctype)), False, h
+
+
+def _count(a):
+    return int(np.prod(getattr(a, "shape", np.shape(a))))
+
+
+def _restart_args(*specs):
+    """_restart_arg of every (array, ctype, count) that is not None; all on the device or all on the host."""
+    out = [None if a is None else _restart_arg(a, ct, n) for a, ct, n in specs]
+    kinds = {o[1] for o in out if o is not None}
+    if len(kinds) > 1:
+        raise ValueError("restart inputs must all be device tensors or all host arrays")
+    return [None if o is None else o[0] for o in out], int(kinds.pop()) if kinds else 0, out
+
+
 class BipedalRobotInterface:
     """Problem definition: model constants + settings (BipedalRobotInterface.cpp:67-204)."""
 
@@ -289,6 +321,15 @@ class BatchedGaitSchedule:
     def reset(self):
         """Every robot back to GaitSchedule(initialModeSchedule, defaultModeSequenceTemplate); nothing pending."""
         _check(load_library().bpmpc_gait_batch_reset(self._h))
+
+    def restart(self, mask):
+        """Robots with mask[b] != 0 (robots 0 .. len(mask) - 1) back to their state after create / reset, their pending insert and command dropped
+        (bpmpc_gait_batch_restart); applied by the next setup_gaits before anything recorded after this call.  A numpy array or an int32 device
+        tensor (its read-back waits for that setup)."""
+        n = _count(mask)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, n))
+        _check(load_library().bpmpc_gait_batch_restart(self._h, n, mp, dev))
+        del keep
 
     def modeSchedule(self, robot, capacity=1024):
         """Robot's schedule after the last setup (does not mutate anything, unlike the reference's getModeSchedule)."""
@@ -550,6 +591,16 @@ class BatchedSqpMpc:
         """Async D2D copy of the iterate into device buffers given by raw pointers (e.g. torch tensors' data_ptr())."""
         _check(load_library().bpmpc_solver_export_trajectories(self._h, C.c_void_p(x_dst_ptr), C.c_void_p(u_dst_ptr)))
 
+    def restart(self, mask, x=None):
+        """MPC_BASE::reset for the problems with mask[b] != 0 (bpmpc_solver_restart): the next setup gives them the initializer's guess instead of the
+        shifted solution; x (nullable, [batch, nx]) replaces their rows of the closed-loop start that x0=None reads.  Until the first run after
+        that setup, evaluatePolicy, rollout and a controller tick are refused.  numpy arrays, or int32 / float64 device tensors; len(mask) must be
+        the batch of the last setup."""
+        B = _count(mask)
+        (mp, xp), dev, keep = _restart_args((mask, C.c_int, B), (x, C.c_double, B * self.nx))
+        _check(load_library().bpmpc_solver_restart(self._h, B, mp, xp, dev))
+        del keep
+
     def evaluatePolicy(self, t, x):
         """MRT_BASE::evaluatePolicy(t, x) for every problem of the last run (bpmpc_solver_evaluate_policy): t[batch], x[batch, nx] ->
         (x_opt [batch, nx], u_opt [batch, nu], planned mode [batch])."""
@@ -596,6 +647,13 @@ class WeightedWbc:
 
     def reset(self):
         _check(load_library().bpmpc_wbc_reset(self._h))
+
+    def restart(self, mask):
+        """clearLastQpSol for the robots with mask[b] != 0 (robots 0 .. len(mask) - 1; bpmpc_wbc_restart): their last solution and status become 0."""
+        n = _count(mask)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, n))
+        _check(load_library().bpmpc_wbc_restart(self._h, n, mp, dev))
+        del keep
 
 
 class _TickOutputs(C.Structure):
@@ -668,6 +726,15 @@ class BatchedController:
     def reset(self):
         """yaw_last = 0 for every robot (BipedalController::starting)."""
         _check(load_library().bpmpc_controller_reset(self._h))
+
+    def restart(self, mask, rbd):
+        """BipedalController::starting for the robots with mask[b] != 0 (bpmpc_controller_restart): their observation from rbd [batch, 2 (6 + nj)]
+        with the yaw unwrapped against 0, MPC_BASE::reset from it, clearLastQpSol; the other robots are not touched.  numpy arrays, or an int32 and
+        a float64 device tensor (e.g. (safe == 0).int() of device_outputs: then the call only enqueues); len(mask) must be the solver's batch."""
+        B = _count(mask)
+        (mp, rp), dev, keep = _restart_args((mask, C.c_int, B), (rbd, C.c_double, B * 2 * self.wbc.generalizedCoordinatesNum))
+        _check(load_library().bpmpc_controller_restart(self._h, B, mp, rp, dev))
+        del keep
 
     def device_outputs(self):
         """The results of the last tick where they live: a dict of DeviceArray (zero-copy; `.torch()` wraps one as a tensor) over the solver's batch."""

@@ -4,6 +4,8 @@
 //   evaluatePolicy / WBC / safety       :199, :229, SafetyChecker.h:39-52;  commands :237-252
 // One tick = k_tick_observe_policy, k_wbc (the WBC handle's kernel and its per-robot last solutions), k_tick_commands, all on the solver's
 // stream; nothing is synchronised unless outputs are asked for on the host.
+// A restart (BipedalController::starting, :123-179) for the robots of a mask = k_restart_observe, bpmpc_solver_restart with the observations,
+// k_wbc_restart, on the same stream.
 #include <hip/hip_runtime.h>
 
 #include <memory>
@@ -22,7 +24,7 @@ struct bpmpc_controller {
   bpmpc_wbc* w = nullptr;
   int device = 0, max_batch = 0, nj = 0, nx = 0, nv = 0, n = 0;
   double *d_yaw = nullptr, *d_t = nullptr, *d_rbd = nullptr, *d_xobs = nullptr, *d_xopt = nullptr, *d_uopt = nullptr, *d_cmd = nullptr;
-  int *d_mode = nullptr, *d_safe = nullptr;
+  int *d_mode = nullptr, *d_safe = nullptr, *d_mask = nullptr;
 };
 
 namespace {
@@ -49,7 +51,7 @@ TickArgs policy_args(const SolverTickView& v, int batch) {
 
 void free_all(bpmpc_controller* c) {
   for (void* p : {(void*)c->d_yaw, (void*)c->d_t, (void*)c->d_rbd, (void*)c->d_xobs, (void*)c->d_xopt, (void*)c->d_uopt, (void*)c->d_cmd, (void*)c->d_mode,
-                  (void*)c->d_safe})
+                  (void*)c->d_safe, (void*)c->d_mask})
     if (p) (void)hipFree(p);
 }
 
@@ -110,6 +112,7 @@ int bpmpc_controller_create(bpmpc_solver* s, bpmpc_wbc* w, bpmpc_controller** ou
     TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_cmd), B * 3 * c->nj * sizeof(double)));
     TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_mode), B * sizeof(int)));
     TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_safe), B * sizeof(int)));
+    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_mask), B * sizeof(int)));
     TICK_HIP(hipMemset(c->d_yaw, 0, B * sizeof(double)));       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
     TICK_HIP(hipDeviceSynchronize());
   } catch (const std::exception& e) {
@@ -179,6 +182,32 @@ int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const
       down(o.safe, c->d_safe, B * sizeof(int));
       TICK_HIP(hipStreamSynchronize(v.stream));
     }
+  } catch (const std::exception& e) { return translate(e); }
+  return BPMPC_OK;
+}
+
+// BipedalController::starting for the robots of `mask`: the observation unwrapped against yawLast = 0 (:126-127), MPC_BASE::reset from it (:147-148),
+// clearLastQpSol (:179).  The refusals of bpmpc_solver_restart (DDP, batch of the last setup) and the tick's (the WBC's max_batch) come first.
+int bpmpc_controller_restart(bpmpc_controller* c, int batch, const int* mask, const double* rbd, int inputs_on_device) {
+  if (!c || !mask || !rbd) { set_last_error("bpmpc_controller_restart: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  try {
+    const SolverRestartView v = solver_restart_view(c->s, batch);
+    if (batch > c->max_batch) throw std::length_error("bpmpc_controller_restart: batch exceeds the WBC's max_batch");
+    TICK_HIP(hipSetDevice(c->device));
+    const int* dmask = mask;
+    const double* drbd = rbd;
+    if (!inputs_on_device) {
+      TICK_HIP(hipMemcpyAsync(c->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, v.stream));
+      TICK_HIP(hipMemcpyAsync(c->d_rbd, rbd, (size_t)batch * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, v.stream));
+      dmask = c->d_mask; drbd = c->d_rbd;
+    }
+    RestartArgs a{};
+    a.batch = batch; a.mask = dmask; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs;
+    kl::restart_observe(c->nj, batch, v.stream, v.d_model, a);
+    TICK_HIP(hipGetLastError());
+    solver_restart(c->s, batch, dmask, c->d_xobs, true);
+    wbc_restart_on(c->w, batch, dmask, v.stream);
+    if (!inputs_on_device) TICK_HIP(hipStreamSynchronize(v.stream));     // the caller's host arrays
   } catch (const std::exception& e) { return translate(e); }
   return BPMPC_OK;
 }

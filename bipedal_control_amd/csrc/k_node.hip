@@ -150,13 +150,15 @@ __global__ __launch_bounds__(lin_waves<NJ>() * kWave) __attribute__((amdgpu_wave
 // state), which every node finds on its own - no sequential sweep (the first version, one wavefront per problem walking the
 // horizon, took 0.53 ms at batch 256 and was the longest kernel of a closed-loop tick).
 // Oracle: oracle/reference_py.py warm_start_from_previous.
+// restarted (nullable, bpmpc_solver_restart): a problem with restarted[b] != 0 keeps k_prepare's guess, the cold start of MPC_BASE::reset.
 template <int NJ>
-__global__ __launch_bounds__(kWave) void k_warm_shift(Launch L) {
+__global__ __launch_bounds__(kWave) void k_warm_shift(Launch L, const int* restarted) {
   constexpr int NX = 12 + NJ, NU = 12 + NJ;
   __shared__ double xi[NX];
   __shared__ double Ks[2][NU * NX];
   const int b = blockIdx.x / L.N, i = blockIdx.x % L.N, l = threadIdx.x;
   const int N = L.N;
+  if (restarted && restarted[b]) return;
   const int g = L.buf.p_grid[b], n = L.buf.g_nodes[g];
   if (i >= n) return;
   const int gp = L.buf.tp_grid[b], np = L.buf.tp_nodes[gp];
@@ -428,7 +430,9 @@ void linearize_fast(int nj, bool materialise, int nodes, hipStream_t st, const L
     }
   });
 }
-void warm_shift(int nj, int slots, hipStream_t st, const Launch& L) { KL_NJ(nj, hipLaunchKernelGGL(k_warm_shift<NJ>, dim3(slots), dim3(kWave), 0, st, L)); }
+void warm_shift(int nj, int slots, hipStream_t st, const Launch& L, const int* restarted) {
+  KL_NJ(nj, hipLaunchKernelGGL(k_warm_shift<NJ>, dim3(slots), dim3(kWave), 0, st, L, restarted));
+}
 void ls_begin(int nj, int batch, hipStream_t st, const Launch& L) { KL_NJ(nj, hipLaunchKernelGGL(k_ls_begin<NJ>, dim3(batch), dim3(kWave), 0, st, L)); }
 void trial_reference(int nj, int slots, hipStream_t st, const Launch& L) { KL_NJ(nj, hipLaunchKernelGGL(k_trial<NJ>, dim3(slots), dim3(kWave), 0, st, L)); }
 int trial_fast_workgroups(int nj, int nodes) {

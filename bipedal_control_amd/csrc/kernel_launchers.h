@@ -13,6 +13,7 @@ struct DeviceModel;
 struct RolloutArgs;
 struct DdpBuffers;
 struct TickArgs;
+struct RestartArgs;
 
 namespace kl {
 
@@ -20,7 +21,7 @@ namespace kl {
 void prepare(int nj, int slots, hipStream_t st, const Launch& L);
 void linearize_reference(int nj, int slots, hipStream_t st, const Launch& L);
 void linearize_fast(int nj, bool materialise, int nodes, hipStream_t st, const Launch& L, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-void warm_shift(int nj, int slots, hipStream_t st, const Launch& L);
+void warm_shift(int nj, int slots, hipStream_t st, const Launch& L, const int* restarted = nullptr);   // restarted[b] != 0: problem b keeps k_prepare's guess
 void ls_begin(int nj, int batch, hipStream_t st, const Launch& L);
 void trial_reference(int nj, int slots, hipStream_t st, const Launch& L);
 int trial_fast_workgroups(int nj, int nodes);
@@ -54,9 +55,10 @@ void ddp_nominal(int nj, int batch, hipStream_t st, const Launch& L, const DdpBu
 void ddp_finish(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d);
 void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid);
 
-// ---- k_tick.hip: the controller tick (observation + policy evaluation in one launch; the joint commands behind k_wbc)
+// ---- k_tick.hip: the controller tick (observation + policy evaluation in one launch; the joint commands behind k_wbc), the restart's observation
 void tick_observe_policy(int nj, int batch, hipStream_t st, const DeviceModel* model, const TickArgs& a);
 void tick_commands(int nj, int batch, hipStream_t st, const double* x_opt, const double* u_opt, const double* sol, double* cmd);
+void restart_observe(int nj, int batch, hipStream_t st, const DeviceModel* model, const RestartArgs& a);
 
 }  // namespace kl
 }  // namespace bpmpc

@@ -3,7 +3,8 @@
 //   policy        MRT_BASE::evaluatePolicy (:199) of the last solution at t: x* = LinearInterpolation of x, u* = uff(t) + K(t) x_obs
 //                 (LinearController) or u(t) (FeedforwardController), planned mode = ModeSchedule::modeAtTime
 //   safety        SafetyChecker::check (SafetyChecker.h:39-52): |pitch|, |roll| of the observation at most pi/3
-// (the WBC between policy and commands is k_wbc, kernels/wbc.h; k_tick_commands only gathers its joint block).
+// (the WBC between policy and commands is k_wbc, kernels/wbc.h; k_tick_commands only gathers its joint block).  The observation alone, for the
+// robots of a restart, is k_restart_observe (restart_observe below).
 //
 // Mapping: the lane-per-coordinate layout of linearize_fast.h / rollout.h - lane g of a robot carries generalised coordinate g
 // (q = [base position, Euler ZYX, joints], v = [base linear velocity, Euler rates, joint rates]), 16 lanes per robot at nj = 10, 32 at nj = 12,
@@ -46,139 +47,149 @@ __device__ __forceinline__ double tick_normalize_angle(double a) {
   return r <= 0.0 ? r + M_PI : r - M_PI;
 }
 
+// The observation of one robot (BipedalController.cpp:397-403) into w.xo of its lane group: x_obs = [A(q) v / m, q] from the measured state rb,
+// the yaw unwrapped against yl; the yaw lane also stores the unwrapped yaw to *yaw_out (nullable).  Every lane of the group takes part (DPP
+// reductions); returns behind the LDS barrier that follows the writes of xo.
+template <int NJ>
+__device__ __forceinline__ void tick_observation(const DeviceModel& md, TickLds<NJ>& w, const double* rb, double yl, double* yaw_out) {
+  using C = LinFastCfg<NJ>;
+  constexpr int G = C::G, NB = C::NB, LPN = C::LPN;
+  static_assert(C::G0 == 0, "one lane per coordinate");
+  const int sub = threadIdx.x / LPN, g = threadIdx.x % LPN;
+  double* xo = w.xo[sub];
+  // ---- measured state (WbcBase::updateMeasured / CentroidalModelRbdConversions layout): q_g, v_g of this lane
+  const double pb[3] = {rb[3], rb[4], rb[5]};
+  double sy, cy, sp, cp, sr, cr;
+  sincos(rb[0], &sy, &cy);
+  sincos(rb[1], &sp, &cp);
+  sincos(rb[2], &sr, &cr);
+  double qg = 0.0, vg = 0.0;
+  if (g < 3) { qg = rb[3 + g]; vg = rb[G + 3 + g]; }
+  else if (g < 6) {
+    qg = rb[g - 3];
+    // Euler-angle rates from the world angular velocity: E thetadot = omega, E = [e_z, Rz e_y, Rz Ry e_x] (as k_wbc)
+    const double wx = rb[G], wy = rb[G + 1], wz = rb[G + 2];
+    const double rr = (cy * wx + sy * wy) / cp, pr = -sy * wx + cy * wy;
+    vg = g == 3 ? wz + sp * rr : (g == 4 ? pr : rr);
+  } else if (g < G) { qg = rb[g]; vg = rb[G + g]; }
+  const bool is_joint = g >= 6 && g < G, is_body = g >= 5 && g < G;
+  const int body = is_body ? g - 5 : 0;
+  // ---- joint-local rotations, then the chain walk of every body lane (wbc_rbd_pass's composition, per lane)
+  if (is_joint) {
+    double sg, cg;
+    sincos(qg, &sg, &cg);
+    const double* ax = md.axis[body];
+    const double vv = 1.0 - cg;
+    const double rot[9] = {cg + vv * ax[0] * ax[0],         vv * ax[0] * ax[1] - sg * ax[2], vv * ax[0] * ax[2] + sg * ax[1],
+                           vv * ax[1] * ax[0] + sg * ax[2], cg + vv * ax[1] * ax[1],         vv * ax[1] * ax[2] - sg * ax[0],
+                           vv * ax[2] * ax[0] - sg * ax[1], vv * ax[2] * ax[1] + sg * ax[0], cg + vv * ax[2] * ax[2]};
+    double E[9];
+    mat3_mul(md.Rfix[body], rot, E);
+    for (int i = 0; i < 9; ++i) w.T[sub][body - 1][i] = E[i];
+  }
+  lds_wave_sync();
+  double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
+  double o[3] = {pb[0], pb[1], pb[2]};
+  if (is_joint) {
+    const int depth = md.depth[body];
+    for (int d = 0; d < depth; ++d) {
+      const int j = md.path[body][d];
+      double t[3], E[9], Rn[9];
+      mat3_vec(R, md.pfix[j], t);
+      for (int i = 0; i < 3; ++i) o[i] += t[i];
+      for (int i = 0; i < 9; ++i) E[i] = w.T[sub][j - 1][i];
+      mat3_mul(R, E, Rn);
+      for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+    }
+  }
+  // ---- inertia of the lane's body about the base origin (eval_lane's composite form)
+  if (is_body) {
+    double cb[3], dv[3];
+    mat3_vec(R, md.com[body], cb);
+    for (int i = 0; i < 3; ++i) dv[i] = o[i] + cb[i] - pb[i];
+    const double* I = md.inertia[body];
+    const double Ib[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
+    double Tm[9];
+    mat3_mul(R, Ib, Tm);
+    double Iw[6];
+    Iw[0] = Tm[0] * R[0] + Tm[1] * R[1] + Tm[2] * R[2];
+    Iw[1] = Tm[0] * R[3] + Tm[1] * R[4] + Tm[2] * R[5];
+    Iw[2] = Tm[0] * R[6] + Tm[1] * R[7] + Tm[2] * R[8];
+    Iw[3] = Tm[3] * R[3] + Tm[4] * R[4] + Tm[5] * R[5];
+    Iw[4] = Tm[3] * R[6] + Tm[4] * R[7] + Tm[5] * R[8];
+    Iw[5] = Tm[6] * R[6] + Tm[7] * R[7] + Tm[8] * R[8];
+    const double m = md.mass[body], dd = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
+    double* cm = w.comp[sub][body];
+    cm[0] = m; cm[1] = m * dv[0]; cm[2] = m * dv[1]; cm[3] = m * dv[2];
+    cm[4] = Iw[0] + m * (dd - dv[0] * dv[0]); cm[5] = Iw[1] - m * dv[0] * dv[1]; cm[6] = Iw[2] - m * dv[0] * dv[2];
+    cm[7] = Iw[3] + m * (dd - dv[1] * dv[1]); cm[8] = Iw[4] - m * dv[1] * dv[2]; cm[9] = Iw[5] + m * (dd - dv[2] * dv[2]);
+  }
+  lds_wave_sync();
+  // ---- composite of the subtree moved by this coordinate (the base coordinates move the whole robot), column g of A
+  double s[10];
+  for (int c = 0; c < 10; ++c) s[c] = 0.0;
+  {
+    const unsigned mask = g < G ? md.subtree[body] : 0u;
+    for (int m = 0; m < NB; ++m) {
+      const double sel = ((mask >> m) & 1u) ? 1.0 : 0.0;
+      for (int c = 0; c < 10; ++c) s[c] += sel * w.comp[sub][m][c];
+    }
+  }
+  const double Mc = s[0];
+  const double invM = Mc > 0.0 ? 1.0 / Mc : 0.0;
+  const double Dv[3] = {s[1] * invM, s[2] * invM, s[3] * invM};
+  const double DD = Dv[0] * Dv[0] + Dv[1] * Dv[1] + Dv[2] * Dv[2];
+  const double Cc[3] = {pb[0] + Dv[0], pb[1] + Dv[1], pb[2] + Dv[2]};
+  const double Ic[6] = {s[4] - Mc * (DD - Dv[0] * Dv[0]), s[5] + Mc * Dv[0] * Dv[1], s[6] + Mc * Dv[0] * Dv[2],
+                        s[7] - Mc * (DD - Dv[1] * Dv[1]), s[8] + Mc * Dv[1] * Dv[2], s[9] - Mc * (DD - Dv[2] * Dv[2])};
+  const double Mtot = node_bcast<C, 5>(Mc);          // lane 5 (roll) sees the whole robot
+  const double com[3] = {node_bcast<C, 5>(Cc[0]), node_bcast<C, 5>(Cc[1]), node_bcast<C, 5>(Cc[2])};
+  double ah[3] = {0.0, 0.0, 0.0};
+  if (g < 3) { ah[0] = g == 0 ? 1.0 : 0.0; ah[1] = g == 1 ? 1.0 : 0.0; ah[2] = g == 2 ? 1.0 : 0.0; }
+  else if (g == 3) ah[2] = 1.0;
+  else if (g == 4) { ah[0] = -sy; ah[1] = cy; }
+  else if (g == 5) { ah[0] = cy * cp; ah[1] = sy * cp; ah[2] = -sp; }
+  else if (g < G) mat3_vec(R, md.axis[body], ah);
+  double Ac[6];
+  if (g < 3) {
+    for (int i = 0; i < 3; ++i) { Ac[i] = ah[i] * Mtot; Ac[3 + i] = 0.0; }
+  } else {
+    const double rC[3] = {Cc[0] - o[0], Cc[1] - o[1], Cc[2] - o[2]};
+    double vC[3], t[3], Iw[3];
+    cross3(ah, rC, vC);
+    const double dC[3] = {Cc[0] - com[0], Cc[1] - com[1], Cc[2] - com[2]};
+    cross3(dC, vC, t);
+    sym3_mul(Ic, ah, Iw);
+    for (int i = 0; i < 3; ++i) { Ac[i] = Mc * vC[i]; Ac[3 + i] = Iw[i] + Mc * t[i]; }
+  }
+  // ---- h = A v (a reduction over the robot's lanes), normalised by the robot mass; q; the yaw unwrap of BipedalController.cpp:400-403
+  double hn[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) hn[i] = node_allreduce_add<LPN>(g < G ? Ac[i] * vg : 0.0) / md.robot_mass;
+  lds_wave_sync();                                   // earlier readers of xo (none in this launch; the order of the phases stays explicit)
+  if (g < 6) xo[g] = lane_pick6(hn, g);
+  if (g < G) {
+    double qo = qg;
+    if (g == 3) {
+      qo = yl + tick_normalize_angle(qg - yl);
+      if (yaw_out) *yaw_out = qo;
+    }
+    xo[6 + g] = qo;
+  }
+  lds_wave_sync();
+}
+
 template <int NJ>
 __device__ __forceinline__ void tick_observe_policy(const DeviceModel& md, TickLds<NJ>& w, const TickArgs& a) {
   using C = LinFastCfg<NJ>;
-  constexpr int G = C::G, NX = C::NX, NU = C::NU, NB = C::NB, LPN = C::LPN, NPW = C::NPW;
-  static_assert(C::G0 == 0, "one lane per coordinate");
+  constexpr int G = C::G, NX = C::NX, NU = C::NU, LPN = C::LPN, NPW = C::NPW;
   const int sub = threadIdx.x / LPN, g = threadIdx.x % LPN;
   const int bq = blockIdx.x * NPW + sub;
   const bool valid = bq < a.batch;
   const int b = valid ? bq : 0;            // lane groups beyond the batch compute robot 0 and write nothing (the DPP reductions need every lane)
   double* xo = w.xo[sub];
   if (a.rbd) {
-    // ---- measured state (WbcBase::updateMeasured / CentroidalModelRbdConversions layout): q_g, v_g of this lane
-    const double* rb = a.rbd + (size_t)b * 2 * G;
-    const double pb[3] = {rb[3], rb[4], rb[5]};
-    double sy, cy, sp, cp, sr, cr;
-    sincos(rb[0], &sy, &cy);
-    sincos(rb[1], &sp, &cp);
-    sincos(rb[2], &sr, &cr);
-    double qg = 0.0, vg = 0.0;
-    if (g < 3) { qg = rb[3 + g]; vg = rb[G + 3 + g]; }
-    else if (g < 6) {
-      qg = rb[g - 3];
-      // Euler-angle rates from the world angular velocity: E thetadot = omega, E = [e_z, Rz e_y, Rz Ry e_x] (as k_wbc)
-      const double wx = rb[G], wy = rb[G + 1], wz = rb[G + 2];
-      const double rr = (cy * wx + sy * wy) / cp, pr = -sy * wx + cy * wy;
-      vg = g == 3 ? wz + sp * rr : (g == 4 ? pr : rr);
-    } else if (g < G) { qg = rb[g]; vg = rb[G + g]; }
-    const bool is_joint = g >= 6 && g < G, is_body = g >= 5 && g < G;
-    const int body = is_body ? g - 5 : 0;
-    // ---- joint-local rotations, then the chain walk of every body lane (wbc_rbd_pass's composition, per lane)
-    if (is_joint) {
-      double sg, cg;
-      sincos(qg, &sg, &cg);
-      const double* ax = md.axis[body];
-      const double vv = 1.0 - cg;
-      const double rot[9] = {cg + vv * ax[0] * ax[0],         vv * ax[0] * ax[1] - sg * ax[2], vv * ax[0] * ax[2] + sg * ax[1],
-                             vv * ax[1] * ax[0] + sg * ax[2], cg + vv * ax[1] * ax[1],         vv * ax[1] * ax[2] - sg * ax[0],
-                             vv * ax[2] * ax[0] - sg * ax[1], vv * ax[2] * ax[1] + sg * ax[0], cg + vv * ax[2] * ax[2]};
-      double E[9];
-      mat3_mul(md.Rfix[body], rot, E);
-      for (int i = 0; i < 9; ++i) w.T[sub][body - 1][i] = E[i];
-    }
-    lds_wave_sync();
-    double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
-    double o[3] = {pb[0], pb[1], pb[2]};
-    if (is_joint) {
-      const int depth = md.depth[body];
-      for (int d = 0; d < depth; ++d) {
-        const int j = md.path[body][d];
-        double t[3], E[9], Rn[9];
-        mat3_vec(R, md.pfix[j], t);
-        for (int i = 0; i < 3; ++i) o[i] += t[i];
-        for (int i = 0; i < 9; ++i) E[i] = w.T[sub][j - 1][i];
-        mat3_mul(R, E, Rn);
-        for (int i = 0; i < 9; ++i) R[i] = Rn[i];
-      }
-    }
-    // ---- inertia of the lane's body about the base origin (eval_lane's composite form)
-    if (is_body) {
-      double cb[3], dv[3];
-      mat3_vec(R, md.com[body], cb);
-      for (int i = 0; i < 3; ++i) dv[i] = o[i] + cb[i] - pb[i];
-      const double* I = md.inertia[body];
-      const double Ib[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
-      double Tm[9];
-      mat3_mul(R, Ib, Tm);
-      double Iw[6];
-      Iw[0] = Tm[0] * R[0] + Tm[1] * R[1] + Tm[2] * R[2];
-      Iw[1] = Tm[0] * R[3] + Tm[1] * R[4] + Tm[2] * R[5];
-      Iw[2] = Tm[0] * R[6] + Tm[1] * R[7] + Tm[2] * R[8];
-      Iw[3] = Tm[3] * R[3] + Tm[4] * R[4] + Tm[5] * R[5];
-      Iw[4] = Tm[3] * R[6] + Tm[4] * R[7] + Tm[5] * R[8];
-      Iw[5] = Tm[6] * R[6] + Tm[7] * R[7] + Tm[8] * R[8];
-      const double m = md.mass[body], dd = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
-      double* cm = w.comp[sub][body];
-      cm[0] = m; cm[1] = m * dv[0]; cm[2] = m * dv[1]; cm[3] = m * dv[2];
-      cm[4] = Iw[0] + m * (dd - dv[0] * dv[0]); cm[5] = Iw[1] - m * dv[0] * dv[1]; cm[6] = Iw[2] - m * dv[0] * dv[2];
-      cm[7] = Iw[3] + m * (dd - dv[1] * dv[1]); cm[8] = Iw[4] - m * dv[1] * dv[2]; cm[9] = Iw[5] + m * (dd - dv[2] * dv[2]);
-    }
-    lds_wave_sync();
-    // ---- composite of the subtree moved by this coordinate (the base coordinates move the whole robot), column g of A
-    double s[10];
-    for (int c = 0; c < 10; ++c) s[c] = 0.0;
-    {
-      const unsigned mask = g < G ? md.subtree[body] : 0u;
-      for (int m = 0; m < NB; ++m) {
-        const double sel = ((mask >> m) & 1u) ? 1.0 : 0.0;
-        for (int c = 0; c < 10; ++c) s[c] += sel * w.comp[sub][m][c];
-      }
-    }
-    const double Mc = s[0];
-    const double invM = Mc > 0.0 ? 1.0 / Mc : 0.0;
-    const double Dv[3] = {s[1] * invM, s[2] * invM, s[3] * invM};
-    const double DD = Dv[0] * Dv[0] + Dv[1] * Dv[1] + Dv[2] * Dv[2];
-    const double Cc[3] = {pb[0] + Dv[0], pb[1] + Dv[1], pb[2] + Dv[2]};
-    const double Ic[6] = {s[4] - Mc * (DD - Dv[0] * Dv[0]), s[5] + Mc * Dv[0] * Dv[1], s[6] + Mc * Dv[0] * Dv[2],
-                          s[7] - Mc * (DD - Dv[1] * Dv[1]), s[8] + Mc * Dv[1] * Dv[2], s[9] - Mc * (DD - Dv[2] * Dv[2])};
-    const double Mtot = node_bcast<C, 5>(Mc);          // lane 5 (roll) sees the whole robot
-    const double com[3] = {node_bcast<C, 5>(Cc[0]), node_bcast<C, 5>(Cc[1]), node_bcast<C, 5>(Cc[2])};
-    double ah[3] = {0.0, 0.0, 0.0};
-    if (g < 3) { ah[0] = g == 0 ? 1.0 : 0.0; ah[1] = g == 1 ? 1.0 : 0.0; ah[2] = g == 2 ? 1.0 : 0.0; }
-    else if (g == 3) ah[2] = 1.0;
-    else if (g == 4) { ah[0] = -sy; ah[1] = cy; }
-    else if (g == 5) { ah[0] = cy * cp; ah[1] = sy * cp; ah[2] = -sp; }
-    else if (g < G) mat3_vec(R, md.axis[body], ah);
-    double Ac[6];
-    if (g < 3) {
-      for (int i = 0; i < 3; ++i) { Ac[i] = ah[i] * Mtot; Ac[3 + i] = 0.0; }
-    } else {
-      const double rC[3] = {Cc[0] - o[0], Cc[1] - o[1], Cc[2] - o[2]};
-      double vC[3], t[3], Iw[3];
-      cross3(ah, rC, vC);
-      const double dC[3] = {Cc[0] - com[0], Cc[1] - com[1], Cc[2] - com[2]};
-      cross3(dC, vC, t);
-      sym3_mul(Ic, ah, Iw);
-      for (int i = 0; i < 3; ++i) { Ac[i] = Mc * vC[i]; Ac[3 + i] = Iw[i] + Mc * t[i]; }
-    }
-    // ---- h = A v (a reduction over the robot's lanes), normalised by the robot mass; q; the yaw unwrap of BipedalController.cpp:400-403
-    double hn[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) hn[i] = node_allreduce_add<LPN>(g < G ? Ac[i] * vg : 0.0) / md.robot_mass;
-    lds_wave_sync();                                   // earlier readers of xo (none in this launch; the order of the phases stays explicit)
-    if (g < 6) xo[g] = lane_pick6(hn, g);
-    if (g < G) {
-      double qo = qg;
-      if (g == 3) {
-        const double yl = a.yaw_last[b];
-        qo = yl + tick_normalize_angle(qg - yl);
-        if (valid) a.yaw_last[b] = qo;
-      }
-      xo[6 + g] = qo;
-    }
-    lds_wave_sync();
+    tick_observation<NJ>(md, w, a.rbd + (size_t)b * 2 * G, a.yaw_last[b], valid ? a.yaw_last + b : nullptr);
     if (valid) {
       for (int c = g; c < NX; c += LPN) {
         a.x_obs[(size_t)b * NX + c] = xo[c];
@@ -240,6 +251,30 @@ __device__ __forceinline__ void tick_commands(int batch, const double* x_opt, co
   c[j] = x_opt[(size_t)b * NX + 12 + j];
   c[NJ + j] = u_opt[(size_t)b * NU + 12 + j];
   c[2 * NJ + j] = sol[(size_t)b * NSOL + NSOL - NJ + j];
+}
+
+// The observation of a restart (BipedalController::starting, :126-127: the observation is zeroed, then set from the estimator): for every robot
+// with mask[b] != 0 x_obs[b] and yaw_last[b] from rbd[b], the yaw unwrapped against 0 (wrapped to (-pi, pi]); other robots are not written.
+// The tick's mapping and device functions; a wavefront without a restarted robot leaves at once.
+struct RestartArgs {
+  int batch;
+  const int* mask;                    // [batch] non-zero: restart
+  const double* rbd;                  // [batch][2 (6 + NJ)]
+  double *yaw_last, *x_obs;           // [batch], [batch][NX]
+};
+
+template <int NJ>
+__device__ __forceinline__ void restart_observe(const DeviceModel& md, TickLds<NJ>& w, const RestartArgs& a) {
+  using C = LinFastCfg<NJ>;
+  constexpr int G = C::G, NX = C::NX, LPN = C::LPN, NPW = C::NPW;
+  const int sub = threadIdx.x / LPN, g = threadIdx.x % LPN;
+  const int bq = blockIdx.x * NPW + sub;
+  const bool mine = bq < a.batch && a.mask[bq] != 0;
+  if (__ballot(mine) == 0) return;       // one wavefront per workgroup: it leaves as a whole
+  const int b = bq < a.batch ? bq : 0;   // the other lane groups compute a robot in range and write nothing (the DPP reductions need every lane)
+  tick_observation<NJ>(md, w, a.rbd + (size_t)b * 2 * G, 0.0, mine ? a.yaw_last + b : nullptr);
+  if (mine)
+    for (int c = g; c < NX; c += LPN) a.x_obs[(size_t)b * NX + c] = w.xo[sub][c];
 }
 
 }  // namespace bpmpc

@@ -128,6 +128,13 @@ struct bpmpc_solver {
   // that the tick, not a rollout, ran last on the handle - bpmpc_solver_setup_commands(x0 = NULL) then starts from tick_x instead of roll_x
   double* tick_x = nullptr;
   bool loop_from_tick = false;
+  // per-problem restarts (bpmpc_solver_restart, MPC_BASE::reset per problem): restart_flag[b] != 0 from the restart to the next accepted setup,
+  // which keeps k_prepare's guess for those problems instead of the shifted solution.  restart_pending: flags recorded and not consumed yet;
+  // restart_wait: tick, evaluate_policy and rollout are refused until the first run after that setup (a fresh handle before its first run)
+  int* restart_flag = nullptr;                             // [max_batch]
+  int* restart_mask = nullptr;                             // [max_batch] device copy of a host mask
+  double* restart_x = nullptr;                             // [max_batch][nx] device copy of host states
+  bool restart_pending = false, restart_wait = false;
   std::vector<int> grid_kind;                               // host copy of the node kinds of the current setup [n_grids][N]
   int max_rows = kMaxEqRows;                                // largest number of equality rows over the nodes of the current setup
   int max_vel_rows = 12;                                    // ... of rows that constrain a contact velocity (12 double stance, 8 single support, 4 flight)
@@ -389,6 +396,7 @@ void bpmpc_solver::run_iterations() {
     stage_linesearch();
   }
   has_solution = true;
+  if (!restart_pending) restart_wait = false;              // the first run after the setup that consumed a restart
 }
 
 // One ILQR iteration of the DDP solver (k_ddp.hip; oracle/ddp_py.py is its restatement, step for step).  Everything is enqueued on the solver's
@@ -460,6 +468,13 @@ struct bpmpc_gait_batch {
   std::vector<int> slot;                                   // per robot: state slot in the front buffer, < 0 = the state after create / reset
   std::vector<int> cmd, ins_gait;                          // per robot: pending command / insert (< 0: none)
   std::vector<double> ins_start, ins_final;
+  // restarts (bpmpc_gait_batch_restart): restart[b] != 0 - the next accepted setup advances robot b from the state after create / reset.  A device
+  // mask writes the number of its call (restart_epoch) to restart_dev[b]; entries above restart_base are read back by the next setup.  Inserts
+  // and host-side commands keep the number of device restarts recorded before them (ins_epoch, cmd_epoch): a restart drops only what came first
+  std::vector<int> restart, cmd_epoch, ins_epoch;
+  int* restart_dev = nullptr;
+  int restart_epoch = 0, restart_base = 0;
+  bool restart_on_device = false;
   std::vector<void*> allocations;
 };
 
@@ -489,6 +504,7 @@ void allocate(bpmpc_solver* s) {
   { const double one = 1.0; HIP_CHECK(hipMemcpyAsync(b.zero_page + 1, &one, sizeof(double), hipMemcpyHostToDevice, s->stream)); HIP_CHECK(hipStreamSynchronize(s->stream)); }
   b.roll_t = s->alloc<double>(nullptr, B); b.roll_x0 = s->alloc<double>(nullptr, B * NX); b.roll_x = s->alloc<double>("roll_x", B * NX);
   s->tick_x = s->alloc<double>("tick_x", B * NX);
+  s->restart_flag = s->alloc<int>(nullptr, B); s->restart_mask = s->alloc<int>(nullptr, B); s->restart_x = s->alloc<double>(nullptr, B * NX);
   b.roll_u = s->alloc<double>("roll_u", B * NU); b.roll_steps = s->alloc<int>(nullptr, B * 2); b.roll_status = s->alloc<int>(nullptr, B);
   b.g_time = s->alloc<double>("g_time", B * (N + 1)); b.rg_t0 = s->alloc<double>(nullptr, B); b.rg_start = s->alloc<double>(nullptr, B);
   b.p_t0 = s->alloc<double>(nullptr, B); b.p_cmd = s->alloc<double>(nullptr, B * 4); b.lib_d = s->alloc<double>(nullptr, kRefLibCapacity);
@@ -694,9 +710,13 @@ void finish_setup(bpmpc_solver* s, int batch, const double* warm_x, const double
   s->stage_prepare();
   if (from_previous) {
     const Launch L = s->launch_params();
-    kl::warm_shift(s->rm.nj, batch * L.N, s->stream, L);
+    kl::warm_shift(s->rm.nj, batch * L.N, s->stream, L, s->restart_pending ? s->restart_flag : nullptr);   // restarted problems keep the cold guess
     HIP_CHECK(hipGetLastError());
     if (s->is_ddp()) s->ddp_nominal_rollout();      // the nominal state trajectory of a DDP tick is the roll-out of the previous controller from the measured state
+  }
+  if (s->restart_pending) {                         // an accepted setup of any kind consumes the pending restarts (a cold or caller-given start wins)
+    HIP_CHECK(hipMemsetAsync(s->restart_flag, 0, (size_t)s->settings.max_batch * sizeof(int), s->stream));
+    s->restart_pending = false;
   }
   copy_pairs(s, bf.x, bf.x_init, (size_t)batch * (N + 1) * NX, bf.u, bf.u_init, (size_t)batch * N * NU, true);
   // only the caller's warm-start arrays are still being read at this point: everything else was uploaded before the callers' own
@@ -988,6 +1008,9 @@ void gait_batch_reset(bpmpc_gait_batch* g) {
   std::fill(g->ins_start.begin(), g->ins_start.end(), 0.0);
   std::fill(g->ins_final.begin(), g->ins_final.end(), 0.0);
   g->cmd_on_device = false;
+  std::fill(g->restart.begin(), g->restart.end(), 0);
+  g->restart_base = g->restart_epoch;
+  g->restart_on_device = false;
 }
 
 // the pending commands back on the host (synchronises; only after a device-side command)
@@ -997,6 +1020,48 @@ void gait_commands_to_host(bpmpc_gait_batch* g) {
   HIP_CHECK(hipMemcpyAsync(g->cmd.data(), g->cmd_dev, g->max_batch * sizeof(int), hipMemcpyDeviceToHost, s->stream));
   HIP_CHECK(hipStreamSynchronize(s->stream));
   g->cmd_on_device = false;
+  std::fill(g->cmd_epoch.begin(), g->cmd_epoch.end(), g->restart_epoch);   // k_gait_restart already dropped what the device restarts drop
+}
+
+// the pending device restarts back on the host (synchronises; only after a device mask): each drops the insert / host command recorded before it
+void gait_restarts_to_host(bpmpc_gait_batch* g) {
+  if (!g->restart_on_device) return;
+  bpmpc_solver* s = g->solver;
+  std::vector<int> epoch(g->max_batch);
+  HIP_CHECK(hipMemcpyAsync(epoch.data(), g->restart_dev, g->max_batch * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+  HIP_CHECK(hipStreamSynchronize(s->stream));
+  for (int b = 0; b < g->max_batch; ++b) {
+    if (epoch[b] <= g->restart_base) continue;
+    g->restart[b] = 1;
+    if (g->cmd_epoch[b] < epoch[b]) g->cmd[b] = -1;
+    if (g->ins_epoch[b] < epoch[b]) g->ins_gait[b] = -1;
+  }
+  g->restart_base = g->restart_epoch;
+  g->restart_on_device = false;
+}
+
+__global__ __launch_bounds__(256) void k_gait_restart(int batch, const int* mask, int epoch, int* restart, int* cmd) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch || !mask[b]) return;
+  restart[b] = epoch;
+  if (cmd) cmd[b] = -1;                                   // device-side pending commands are dropped in stream order
+}
+
+void gait_batch_restart(bpmpc_gait_batch* g, int batch, const int* mask, bool on_device) {
+  if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("bpmpc_gait_batch_restart: batch exceeds the gait batch's max_batch");
+  bpmpc_solver* s = g->solver;
+  if (!on_device) {
+    gait_commands_to_host(g);
+    gait_restarts_to_host(g);
+    for (int b = 0; b < batch; ++b)
+      if (mask[b]) { g->restart[b] = 1; g->cmd[b] = -1; g->ins_gait[b] = -1; }
+    return;
+  }
+  ++g->restart_epoch;
+  hipLaunchKernelGGL(k_gait_restart, dim3((batch + 255) / 256), dim3(256), 0, s->stream, batch, mask, g->restart_epoch, g->restart_dev,
+                     g->cmd_on_device ? g->cmd_dev : nullptr);
+  HIP_CHECK(hipGetLastError());
+  g->restart_on_device = true;
 }
 
 void gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, bool on_device) {
@@ -1004,10 +1069,11 @@ void gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, bool on
   bpmpc_solver* s = g->solver;
   if (!on_device) {
     gait_commands_to_host(g);
-    for (int b = 0; b < batch; ++b) if (gait[b] >= 0) g->cmd[b] = gait[b];
+    for (int b = 0; b < batch; ++b) if (gait[b] >= 0) { g->cmd[b] = gait[b]; g->cmd_epoch[b] = g->restart_epoch; }
     return;
   }
   if (!g->cmd_on_device) {                                // the device copy takes over: it starts from the host's pending commands
+    if (g->restart_on_device && std::any_of(g->cmd.begin(), g->cmd.end(), [](int c) { return c >= 0; })) gait_restarts_to_host(g);   // ... as a restart left them
     if (std::all_of(g->cmd.begin(), g->cmd.end(), [](int c) { return c < 0; })) {
       HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)g->cmd_dev, -1, g->max_batch, s->stream));
     } else {
@@ -1052,6 +1118,7 @@ void setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon
   if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("setup_gaits: batch exceeds the gait batch's max_batch");
   check_device_setup(s, "setup_gaits", batch, horizon, t0, x0, cmd_vel, command_kind, false);
   gait_commands_to_host(g);
+  gait_restarts_to_host(g);
   for (int b = 0; b < batch; ++b)
     if (g->cmd[b] >= g->n_gaits) throw std::invalid_argument("setup_gaits: a gait command refers to a template that was not passed");
   const int NX = s->nx, B = g->max_batch;
@@ -1063,11 +1130,11 @@ void setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon
     std::map<std::tuple<int, double, int, double, double, int>, int> seen;
     for (int b = 0; b < batch; ++b) {
       const bool ins = g->ins_gait[b] >= 0;
-      auto key = std::make_tuple(g->slot[b], t0[b], ins ? g->ins_gait[b] : -1, ins ? g->ins_start[b] : 0.0, ins ? g->ins_final[b] : 0.0, g->cmd[b] < 0 ? -1 : g->cmd[b]);
+      auto key = std::make_tuple(g->restart[b] ? -1 : g->slot[b], t0[b], ins ? g->ins_gait[b] : -1, ins ? g->ins_start[b] : 0.0, ins ? g->ins_final[b] : 0.0, g->cmd[b] < 0 ? -1 : g->cmd[b]);
       auto it = seen.find(key);
       if (it == seen.end()) {
         it = seen.emplace(key, (int)src.size()).first;
-        src.push_back(g->slot[b]); gt0.push_back(t0[b]); ins_g.push_back(std::get<2>(key)); ins_s.push_back(std::get<3>(key)); ins_f.push_back(std::get<4>(key));
+        src.push_back(std::get<0>(key)); gt0.push_back(t0[b]); ins_g.push_back(std::get<2>(key)); ins_s.push_back(std::get<3>(key)); ins_f.push_back(std::get<4>(key));
         cmd.push_back(std::get<5>(key));
       }
       pgrid[b] = new_slot[b] = it->second;
@@ -1119,7 +1186,18 @@ void setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon
   g->slot.swap(new_slot);
   std::fill(g->cmd.begin(), g->cmd.begin() + batch, -1);
   std::fill(g->ins_gait.begin(), g->ins_gait.begin() + batch, -1);
+  std::fill(g->restart.begin(), g->restart.begin() + batch, 0);
   finish_setup(s, batch, nullptr, nullptr, from_previous);
+}
+
+void refuse_while_restarting(const bpmpc_solver* s, const char* what) {
+  if (s->restart_wait)
+    throw std::invalid_argument(std::string(what) + ": a restart (bpmpc_solver_restart) waits for the next setup and run; the policy of the previous episode is gone");
+}
+
+void check_restart(const bpmpc_solver* s, int batch) {
+  if (s->is_ddp()) throw Unsupported("restart: not implemented for the DDP solver");
+  if (s->batch < 1 || batch != s->batch) throw std::invalid_argument("restart: batch must equal the batch of the last setup");
 }
 
 // reads the per-problem flags of the last rollout back (synchronises) and reports failures like the reference's integrator does
@@ -1141,6 +1219,7 @@ void check_rollout_status(bpmpc_solver* s, int* steps) {
 // MRT_BASE::rolloutPolicy for the whole batch (kernels/rollout.h): integrates every problem from (t_start, x_start) over `duration`
 // under the LinearController of the last solve.  NULL t_start / x_start: the initial time / measured state of that solve.
 void rollout(bpmpc_solver* s, const double* t_start, const double* x_start, double duration, double* x_end, double* u_end, int* steps) {
+  refuse_while_restarting(s, "bpmpc_solver_rollout");
   if (!s->has_solution) throw std::invalid_argument("bpmpc_solver_rollout needs a completed solve on the handle");
   if (s->is_ddp()) throw Unsupported("bpmpc_solver_rollout: the DDP solution is a FeedforwardController on the time points of its own roll-out (fetch them with bpmpc_solver_fetch), not on the shooting grid this roll-out interpolates on");
   if (!(duration >= 0)) throw std::invalid_argument("bpmpc_solver_rollout: negative duration");
@@ -1169,6 +1248,33 @@ void rollout(bpmpc_solver* s, const double* t_start, const double* x_start, doub
   check_rollout_status(s, steps);
   if (x_end) HIP_CHECK(hipMemcpy(x_end, bf.roll_x, (size_t)B * NX * sizeof(double), hipMemcpyDeviceToHost));
   if (u_end) HIP_CHECK(hipMemcpy(u_end, bf.roll_u, (size_t)B * NU * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+// MPC_BASE::reset for the problems of `mask` (bpmpc_solver_restart): flags for the next setup, their rows of x_new into the closed-loop start
+__global__ __launch_bounds__(256) void k_restart_mark(int batch, int nx, const int* mask, int* flag, const double* x_new, double* loop_x) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= batch * nx) return;
+  const int b = i / nx;
+  if (!mask[b]) return;
+  if (i % nx == 0) flag[b] = 1;
+  if (x_new) loop_x[i] = x_new[i];
+}
+
+void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device) {
+  check_restart(s, batch);
+  const size_t NX = s->nx;
+  if (!on_device) {
+    HIP_CHECK(hipMemcpyAsync(s->restart_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    if (x_new) HIP_CHECK(hipMemcpyAsync(s->restart_x, x_new, (size_t)batch * NX * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    mask = s->restart_mask;
+    if (x_new) x_new = s->restart_x;
+  }
+  // the start that setup(x0 = NULL) reads (copy_loop_x0); neither a tick nor a rollout can replace it before that setup (both are refused)
+  double* loop_x = s->loop_from_tick ? s->tick_x : s->buf.roll_x;
+  hipLaunchKernelGGL(k_restart_mark, dim3((unsigned)((batch * NX + 255) / 256)), dim3(256), 0, s->stream, batch, (int)NX, mask, s->restart_flag, x_new, loop_x);
+  HIP_CHECK(hipGetLastError());
+  s->restart_pending = s->restart_wait = true;
+  if (!on_device) HIP_CHECK(hipStreamSynchronize(s->stream));   // the caller's host arrays
 }
 
 void reset(bpmpc_solver* s) {
@@ -1341,6 +1447,10 @@ int bpmpc_solver_setup_from_previous(bpmpc_solver* s, int batch, double horizon,
   API_GUARD(s, setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, nullptr, nullptr, true))
 }
 int bpmpc_solver_reset(bpmpc_solver* s) { API_GUARD(s, reset(s)) }
+int bpmpc_solver_restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, int inputs_on_device) {
+  if (!mask) { set_last_error("bpmpc_solver_restart: null mask"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  API_GUARD(s, restart(s, batch, mask, x_new, inputs_on_device != 0))
+}
 int bpmpc_solver_run(bpmpc_solver* s) {
   API_GUARD(s, { if (s->batch < 1) throw std::invalid_argument("bpmpc_solver_run before bpmpc_solver_setup"); s->run_iterations(); })
 }
@@ -1379,11 +1489,14 @@ int bpmpc_gait_batch_create(bpmpc_solver* s, const bpmpc_gait_template* gaits, i
     g->grp_i = static_cast<int*>(alloc(3 * (size_t)B * sizeof(int)));
     g->grp_d = static_cast<double*>(alloc(3 * (size_t)B * sizeof(double)));
     g->cmd_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
+    g->restart_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
+    HIP_CHECK(hipMemsetAsync(g->restart_dev, 0, (size_t)B * sizeof(int), s->stream));
     HIP_CHECK(hipMemcpyAsync(lib_d, lib.d.data(), lib.d.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_CHECK(hipMemcpyAsync(lib_i, lib.i.data(), lib.i.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
     HIP_CHECK(hipStreamSynchronize(s->stream));
     g->lib = lib.view(lib_d, lib_i, s->rm.phase_transition_stance_time);
     g->slot.resize(B); g->cmd.resize(B); g->ins_gait.resize(B); g->ins_start.resize(B); g->ins_final.resize(B);
+    g->restart.resize(B); g->cmd_epoch.resize(B); g->ins_epoch.resize(B);
     gait_batch_reset(g.get());
   } catch (const std::exception& e) {
     const int rc = translate(e);
@@ -1409,13 +1522,17 @@ int bpmpc_gait_batch_insert(bpmpc_gait_batch* g, int batch, const int* gait, con
     check_gait_batch(g, batch, gait, true);
     if (!start_time || !final_time) throw std::invalid_argument("bpmpc_gait_batch_insert: null start or final times");
     for (int b = 0; b < batch; ++b)
-      if (gait[b] >= 0) { g->ins_gait[b] = gait[b]; g->ins_start[b] = start_time[b]; g->ins_final[b] = final_time[b]; }
+      if (gait[b] >= 0) { g->ins_gait[b] = gait[b]; g->ins_start[b] = start_time[b]; g->ins_final[b] = final_time[b]; g->ins_epoch[b] = g->restart_epoch; }
   } catch (const std::exception& e) { return translate(e); }
   return BPMPC_OK;
 }
 int bpmpc_gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, int inputs_on_device) {
   if (!g) { set_last_error("bpmpc_gait_batch_command: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
   API_GUARD(g->solver, { gait_batch_command(g, batch, gait, inputs_on_device != 0); })
+}
+int bpmpc_gait_batch_restart(bpmpc_gait_batch* g, int batch, const int* mask, int inputs_on_device) {
+  if (!g || !mask) { set_last_error("bpmpc_gait_batch_restart: null handle or mask"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  API_GUARD(g->solver, { gait_batch_restart(g, batch, mask, inputs_on_device != 0); })
 }
 int bpmpc_gait_batch_mode_schedule(bpmpc_gait_batch* g, int robot, double* event_times, int* modes, int capacity, int* n_events) {
   if (!g) { set_last_error("bpmpc_gait_batch_mode_schedule: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
@@ -1580,6 +1697,7 @@ SolverTickView solver_tick_view(bpmpc_solver* s) {
   if (s->is_ddp())
     throw Unsupported("controller tick / evaluate_policy: the DDP solution is a FeedforwardController on the time points of its own roll-out, not on the shooting grid "
                       "the policy is interpolated on");
+  refuse_while_restarting(s, "controller tick / evaluate_policy");
   if (s->batch < 1 || !s->has_solution) throw std::invalid_argument("controller tick / evaluate_policy needs a completed bpmpc_solver_run since the last setup");
   const Buffers& bf = s->buf;
   const int feedback = s->feedback();
@@ -1595,6 +1713,14 @@ SolverTickView solver_tick_view(bpmpc_solver* s) {
 void solver_tick_done(bpmpc_solver* s) { s->loop_from_tick = true; }
 
 int solver_device(const bpmpc_solver* s) { return s->settings.device; }
+
+SolverRestartView solver_restart_view(bpmpc_solver* s, int batch) {
+  if (!s) throw std::invalid_argument("null solver handle");
+  check_restart(s, batch);
+  return SolverRestartView{s->settings.device, s->rm.nj, s->stream, s->d_model};
+}
+
+void solver_restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool inputs_on_device) { restart(s, batch, mask, x_new, inputs_on_device); }
 
 int solver_translate(const std::exception& e) { return translate(e); }
 

@@ -25,6 +25,16 @@ __global__ __launch_bounds__(kWave) void k_wbc(const DeviceModel* model, WbcSett
   wbc_robot<NJ>(*model, st, w, a, b, threadIdx.x);
 }
 
+// WeightedWbc::clearLastQpSol for the robots of `mask` (bpmpc_wbc_restart): their last solution and status become 0
+__global__ __launch_bounds__(256) void k_wbc_restart(int batch, int n, const int* mask, double* sol, int* status) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= batch * n) return;
+  const int b = i / n;
+  if (!mask[b]) return;
+  sol[i] = 0.0;
+  if (i % n == 0) status[b] = 0;
+}
+
 }  // namespace bpmpc
 
 using namespace bpmpc;
@@ -39,6 +49,9 @@ struct bpmpc_wbc {
   double *d_x = nullptr, *d_u = nullptr, *d_rbd = nullptr, *d_sol = nullptr, *d_debug = nullptr;
   int *d_mode = nullptr, *d_status = nullptr;
   hipEvent_t ev_foreign = nullptr;      // k_wbc enqueued on another handle's stream (controller tick): this handle's stream waits for it
+  hipEvent_t ev_own = nullptr;          // ... and the other way round: a restart only enqueued on this handle's stream, waited for by the next foreign launch
+  bool own_pending = false;
+  int* d_mask = nullptr;                // [max_batch] device copy of a host restart mask
 };
 
 namespace {
@@ -91,6 +104,7 @@ WbcTickView wbc_tick_view(const bpmpc_wbc* w) {
 // The launch of bpmpc_wbc_update without its transfers: device inputs, the handle's last solutions and statuses, on the caller's stream.
 void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const double* input_des, const double* rbd_meas, const int* mode, hipStream_t stream) {
   if (batch < 1 || batch > w->max_batch) throw std::length_error("controller tick: batch exceeds the WBC's max_batch");
+  if (w->own_pending) WBC_HIP(hipStreamWaitEvent(stream, w->ev_own, 0));
   WbcArgs a{};
   a.batch = batch; a.nx = w->rm.nx; a.state_des = state_des; a.input_des = input_des; a.rbd_meas = rbd_meas; a.mode = mode;
   a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr;
@@ -100,6 +114,20 @@ void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const doubl
   if (!w->ev_foreign) WBC_HIP(hipEventCreateWithFlags(&w->ev_foreign, hipEventDisableTiming));
   WBC_HIP(hipEventRecord(w->ev_foreign, stream));
   WBC_HIP(hipStreamWaitEvent(w->stream, w->ev_foreign, 0));
+}
+
+// k_wbc_restart on a device mask, enqueued on `stream` under the rule of wbc_launch_on (the handle's own stream: no events)
+void wbc_restart_on(bpmpc_wbc* w, int batch, const int* mask, hipStream_t stream) {
+  if (batch < 1 || batch > w->max_batch) throw std::length_error("restart: batch exceeds the WBC's max_batch");
+  const bool foreign = stream != w->stream;
+  if (foreign && w->own_pending) WBC_HIP(hipStreamWaitEvent(stream, w->ev_own, 0));
+  hipLaunchKernelGGL(k_wbc_restart, dim3((batch * w->n + 255) / 256), dim3(256), 0, stream, batch, w->n, mask, w->d_sol, w->d_status);
+  WBC_HIP(hipGetLastError());
+  if (foreign) {
+    if (!w->ev_foreign) WBC_HIP(hipEventCreateWithFlags(&w->ev_foreign, hipEventDisableTiming));
+    WBC_HIP(hipEventRecord(w->ev_foreign, stream));
+    WBC_HIP(hipStreamWaitEvent(w->stream, w->ev_foreign, 0));
+  }
 }
 
 }  // namespace bpmpc
@@ -133,6 +161,7 @@ int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int d
     WBC_HIP(hipMalloc(reinterpret_cast<void**>(&w->d_debug), B * kWbcDebugStride * sizeof(double)));
     WBC_HIP(hipMalloc(reinterpret_cast<void**>(&w->d_mode), B * sizeof(int)));
     WBC_HIP(hipMalloc(reinterpret_cast<void**>(&w->d_status), B * sizeof(int)));
+    WBC_HIP(hipMalloc(reinterpret_cast<void**>(&w->d_mask), B * sizeof(int)));
     WBC_HIP(hipMemset(w->d_sol, 0, B * w->n * sizeof(double)));      // lastQpSol_ starts at zero (WeightedWbc.h)
   } catch (const std::exception& e) {
     const int rc = translate(e);
@@ -147,7 +176,9 @@ void bpmpc_wbc_destroy(bpmpc_wbc* w) {
   if (!w) return;
   if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
   if (w->ev_foreign) (void)hipEventDestroy(w->ev_foreign);
-  for (void* p : {(void*)w->d_model, (void*)w->d_x, (void*)w->d_u, (void*)w->d_rbd, (void*)w->d_sol, (void*)w->d_debug, (void*)w->d_mode, (void*)w->d_status})
+  if (w->ev_own) (void)hipEventDestroy(w->ev_own);
+  for (void* p : {(void*)w->d_model, (void*)w->d_x, (void*)w->d_u, (void*)w->d_rbd, (void*)w->d_sol, (void*)w->d_debug, (void*)w->d_mode, (void*)w->d_status,
+                  (void*)w->d_mask})
     if (p) (void)hipFree(p);
   delete w;
 }
@@ -182,6 +213,7 @@ int bpmpc_wbc_update(bpmpc_wbc* w, int batch, const double* state_desired, const
     if (status) WBC_HIP(hipMemcpyAsync(status, w->d_status, B * sizeof(int), hipMemcpyDeviceToHost, w->stream));
     if (debug) WBC_HIP(hipMemcpyAsync(debug, w->d_debug, B * kWbcDebugStride * sizeof(double), hipMemcpyDeviceToHost, w->stream));
     WBC_HIP(hipStreamSynchronize(w->stream));
+    w->own_pending = false;
   } catch (const std::exception& e) { return translate(e); }
   return BPMPC_OK;
 }
@@ -192,6 +224,27 @@ int bpmpc_wbc_reset(bpmpc_wbc* w) {
     WBC_HIP(hipSetDevice(w->device));
     WBC_HIP(hipMemsetAsync(w->d_sol, 0, (size_t)w->max_batch * w->n * sizeof(double), w->stream));
     WBC_HIP(hipStreamSynchronize(w->stream));
+    w->own_pending = false;
+  } catch (const std::exception& e) { return translate(e); }
+  return BPMPC_OK;
+}
+
+int bpmpc_wbc_restart(bpmpc_wbc* w, int batch, const int* mask, int inputs_on_device) {
+  if (!w || !mask) { set_last_error("bpmpc_wbc_restart: null handle or mask"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  try {
+    if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_restart: batch exceeds max_batch");
+    WBC_HIP(hipSetDevice(w->device));
+    if (!inputs_on_device) {
+      WBC_HIP(hipMemcpyAsync(w->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, w->stream));
+      wbc_restart_on(w, batch, w->d_mask, w->stream);
+      WBC_HIP(hipStreamSynchronize(w->stream));
+      w->own_pending = false;
+    } else {                            // only enqueued: the next launch on another stream (a controller tick) waits for it
+      wbc_restart_on(w, batch, mask, w->stream);
+      if (!w->ev_own) WBC_HIP(hipEventCreateWithFlags(&w->ev_own, hipEventDisableTiming));
+      WBC_HIP(hipEventRecord(w->ev_own, w->stream));
+      w->own_pending = true;
+    }
   } catch (const std::exception& e) { return translate(e); }
   return BPMPC_OK;
 }

@@ -410,6 +410,40 @@ int bpmpc_controller_tick(bpmpc_controller* controller, int batch, const double*
  * are the WBC handle's own buffers: a later bpmpc_wbc_update overwrites them. */
 int bpmpc_controller_device_outputs(bpmpc_controller* controller, bpmpc_tick_outputs* dev_out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-robot restarts: BipedalController::starting (bipedal_controllers/src/BipedalController.cpp:123-179) for the robots of a mask, while
+ * every other robot of the batch goes on untouched (not a single bit of its state changes).  mask[batch]: non-zero = restart this robot.
+ * inputs_on_device != 0: mask and the state arrays are device pointers (e.g. (safe == 0) of bpmpc_controller_device_outputs) and the call only
+ * enqueues work; with host arrays the call synchronises.  Restarts recorded before one setup accumulate: the masks are OR-ed and the latest
+ * state given for a robot wins.  Null handles or masks: BPMPC_ERR_INVALID_ARGUMENT.
+ *   solver      bpmpc_solver_restart = MPC_BASE::reset per problem [OCS2-upstream, recalled] (:147-148).  batch must equal the batch of the last
+ *               setup (before any setup or otherwise: BPMPC_ERR_INVALID_ARGUMENT); the DDP solver: BPMPC_ERR_UNSUPPORTED.  x_new (nullable,
+ *               [batch*nx]): its rows of masked problems replace those of the closed-loop start that setup_commands / setup_gaits(x0 = NULL)
+ *               read (the end states of the last rollout or the observations of the last tick, whichever ran last).  The next accepted setup of
+ *               any kind consumes the restart: with a shifted warm start (setup_from_previous, from_previous != 0) the masked problems keep the
+ *               initializer's guess of a cold setup and the others are shifted as before; a cold setup or the caller's warm arrays win for
+ *               everyone.  A rejected setup leaves the restart pending.  From the restart to the first completed bpmpc_solver_run after that
+ *               setup, bpmpc_solver_evaluate_policy, bpmpc_controller_tick and bpmpc_solver_rollout return BPMPC_ERR_INVALID_ARGUMENT (the state
+ *               of a fresh handle before its first run: the controller waits for the first policy of the new episode, :154).
+ *   WBC         bpmpc_wbc_restart = clearLastQpSol (:179): the masked robots' last solutions and statuses become 0.  Enqueued on the WBC handle's
+ *               stream; a later controller tick on another stream waits for it.  batch > max_batch: BPMPC_ERR_CAPACITY.
+ *   gait batch  bpmpc_gait_batch_restart: the masked robots go back to their state after create / reset; their pending insert and command are
+ *               dropped.  The next accepted bpmpc_solver_setup_gaits applies the restart first, so an insert or command recorded after the
+ *               restart applies to the new episode; a rejected setup leaves it pending; robots restarted together share one grid again.  A
+ *               device mask is read back by that setup (which synchronises anyway).  Separate from the controller restart on purpose: starting()
+ *               leaves the gait schedule alone, whether a new episode starts a new gait clock is the caller's choice.
+ *   controller  bpmpc_controller_restart, on the solver's stream: k_restart_observe (the tick's observation of rbd[b] with the yaw unwrapped
+ *               against 0, :126-127, so wrapped to (-pi, pi]) writes x_obs[b] and yaw_last[b] of the masked robots; then bpmpc_solver_restart
+ *               with those observations as x_new and bpmpc_wbc_restart.  batch: the solver's last setup, at most the WBC's max_batch.
+ * The loop after a fall: restart -> bpmpc_solver_setup_gaits(x0 = NULL, from_previous = 1) -> run -> tick.  Not reproduced: the one-point target
+ * of :145 (the batched setups take their targets from the commands: cmd_vel = 0 holds the pose), the DDP solver, the stop request itself.
+ * ------------------------------------------------------------------------------------------------------------- */
+int bpmpc_solver_restart(bpmpc_solver* solver, int batch, const int* mask, const double* x_new, int inputs_on_device);
+int bpmpc_wbc_restart(bpmpc_wbc* wbc, int batch, const int* mask, int inputs_on_device);
+int bpmpc_gait_batch_restart(bpmpc_gait_batch* gaits, int batch, const int* mask, int inputs_on_device);
+/* rbd[batch*2*(6+nj)]: the measured rigid-body states the restarted robots start from (layout of bpmpc_controller_tick). */
+int bpmpc_controller_restart(bpmpc_controller* controller, int batch, const int* mask, const double* rbd, int inputs_on_device);
+
 #ifdef __cplusplus
 }
 #endif
