@@ -1,4 +1,4 @@
-// Host-only part of the C ABI (include/bpmpc.h): model ingest and the reference-manager pre-pass.
+// Host-only part of the C ABI (include/bpmpc.h): model ingest, the reference-manager pre-pass and the error model (capi_internal.h).
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -18,27 +18,21 @@ thread_local std::string g_last_error;
 }
 void set_last_error(const std::string& message) { g_last_error = message; }
 const RobotModel& model_of(const bpmpc_model* handle) { return handle->rm; }
+
+int translate(const std::exception& e, int fallback) {
+  set_last_error(e.what());
+  if (dynamic_cast<const DeviceError*>(&e)) return BPMPC_ERR_DEVICE;
+  if (dynamic_cast<const Unsupported*>(&e)) return BPMPC_ERR_UNSUPPORTED;
+  if (dynamic_cast<const std::invalid_argument*>(&e)) return BPMPC_ERR_INVALID_ARGUMENT;
+  if (dynamic_cast<const std::length_error*>(&e)) return BPMPC_ERR_CAPACITY;
+  return fallback;
+}
 }  // namespace bpmpc
 
 using namespace bpmpc;
 
 namespace {
 int fail(int code, const std::string& why) { set_last_error(why); return code; }
-
-template <typename F>
-int guarded(F&& body) {
-  try {
-    return body();
-  } catch (const std::length_error& e) {
-    return fail(BPMPC_ERR_CAPACITY, e.what());
-  } catch (const std::invalid_argument& e) {
-    return fail(BPMPC_ERR_INVALID_ARGUMENT, e.what());
-  } catch (const UnsupportedSetting& e) {
-    return fail(BPMPC_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) {
-    return fail(BPMPC_ERR_IO, e.what());
-  }
-}
 
 int copy_out(const double* src, size_t n, double* out, int capacity) {
   if ((size_t)capacity < n) throw std::length_error("output capacity too small");
@@ -55,7 +49,7 @@ const char* bpmpc_version(void) { return "bpmpc 0.1 (gfx950, fp64)"; }
 int bpmpc_model_create(const char* urdf, const char* task, const char* reference, bpmpc_model** out) {
   if (!urdf || !task || !reference || !out) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_model_create: null argument");
   *out = nullptr;
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     auto m = std::make_unique<bpmpc_model>();
     m->rm = load_robot_model(urdf, task, reference);
     *out = m.release();
@@ -80,7 +74,7 @@ int bpmpc_model_dims(const bpmpc_model* m, int* nx, int* nu, int* n_contacts, in
 
 int bpmpc_model_get(const bpmpc_model* m, const char* name, double* out, int capacity) {
   if (!m || !name || !out) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_model_get: null argument");
-  return guarded([&]() -> int {
+  return guarded(BPMPC_ERR_IO, [&]() -> int {
     const RobotModel& r = m->rm;
     const std::string n(name);
     const int nj = r.nj, nb = nj + 1;
@@ -140,7 +134,7 @@ int bpmpc_model_joint_name(const bpmpc_model* m, int j, char* out, int capacity)
 
 int bpmpc_gait_create(const bpmpc_model* m, bpmpc_gait** out) {
   if (!m || !out) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_gait_create: null argument");
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     auto g = std::make_unique<bpmpc_gait>();
     g->schedule = std::make_unique<GaitSchedule>(m->rm.initial_mode_schedule, m->rm.default_template, m->rm.phase_transition_stance_time);
     *out = g.release();
@@ -151,7 +145,7 @@ void bpmpc_gait_destroy(bpmpc_gait* g) { delete g; }
 
 int bpmpc_gait_load_template(const char* path, const char* name, double* switching_times, int* modes, int capacity, int* n_modes) {
   if (!path || !name || !switching_times || !modes || !n_modes) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_gait_load_template: null argument");
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     const ModeTemplate t = load_mode_template(path, name);
     if (t.switching_times.size() != t.modes.size() + 1) throw std::runtime_error("gait template needs one more switching time than modes");
     if ((int)t.modes.size() + 1 > capacity) throw std::length_error("gait template capacity too small");
@@ -164,7 +158,7 @@ int bpmpc_gait_load_template(const char* path, const char* name, double* switchi
 
 int bpmpc_gait_insert_template(bpmpc_gait* g, const double* switching_times, const int* modes, int n_modes, double start_time, double final_time) {
   if (!g || !switching_times || !modes || n_modes < 0) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_gait_insert_template: bad argument");
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     ModeTemplate t;
     t.switching_times.assign(switching_times, switching_times + n_modes + 1);
     t.modes.assign(modes, modes + n_modes);
@@ -175,7 +169,7 @@ int bpmpc_gait_insert_template(bpmpc_gait* g, const double* switching_times, con
 
 int bpmpc_gait_mode_schedule(bpmpc_gait* g, double lower, double upper, double* event_times, int* modes, int capacity, int* n_events) {
   if (!g || !event_times || !modes || !n_events) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_gait_mode_schedule: null argument");
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     const ModeSchedule& s = g->schedule->mode_schedule(lower, upper);
     if ((int)s.modes.size() > capacity) throw std::length_error("mode schedule capacity too small");
     std::copy(s.event_times.begin(), s.event_times.end(), event_times);
@@ -188,7 +182,7 @@ int bpmpc_gait_mode_schedule(bpmpc_gait* g, double lower, double upper, double* 
 int bpmpc_swing_reference(const bpmpc_model* m, const double* event_times, const int* modes, int n_events, const double* t, int n_t, double* z,
                           double* zdot) {
   if (!m || !modes || !t || !z || !zdot || n_events < 0 || (n_events > 0 && !event_times)) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_swing_reference: bad argument");
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     ModeSchedule s;
     s.event_times.assign(event_times, event_times + n_events);
     s.modes.assign(modes, modes + n_events + 1);
@@ -206,7 +200,7 @@ int bpmpc_swing_reference(const bpmpc_model* m, const double* event_times, const
 int bpmpc_time_grid(double t0, double tf, double dt, const double* event_times, int n_events, double* node_times, int* node_events, int capacity,
                     int* n_nodes) {
   if (!node_times || !node_events || !n_nodes || n_events < 0 || (n_events > 0 && !event_times)) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_time_grid: bad argument");
-  return guarded([&] {
+  return guarded(BPMPC_ERR_IO, [&] {
     const std::vector<double> ev(event_times, event_times + n_events);
     const std::vector<GridNode> grid = shooting_grid(t0, tf, dt, ev);
     if ((int)grid.size() > capacity) throw std::length_error("time grid capacity too small");
@@ -219,11 +213,11 @@ int bpmpc_time_grid(double t0, double tf, double dt, const double* event_times, 
 int bpmpc_cmd_vel_to_targets(const bpmpc_model* m, const double cmd_vel[4], double t_now, const double* x_now, double time_to_target, double* times,
                              double* states) {
   if (!m || !cmd_vel || !x_now || !times || !states) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_cmd_vel_to_targets: null argument");
-  return guarded([&] { cmd_vel_to_targets(m->rm, cmd_vel, t_now, x_now, time_to_target, times, states); return (int)BPMPC_OK; });
+  return guarded(BPMPC_ERR_IO, [&] { cmd_vel_to_targets(m->rm, cmd_vel, t_now, x_now, time_to_target, times, states); return (int)BPMPC_OK; });
 }
 int bpmpc_goal_to_targets(const bpmpc_model* m, const double goal[4], double t_now, const double* x_now, double* times, double* states) {
   if (!m || !goal || !x_now || !times || !states) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_goal_to_targets: null argument");
-  return guarded([&] { goal_to_targets(m->rm, goal, t_now, x_now, times, states); return (int)BPMPC_OK; });
+  return guarded(BPMPC_ERR_IO, [&] { goal_to_targets(m->rm, goal, t_now, x_now, times, states); return (int)BPMPC_OK; });
 }
 
 }  // extern "C"

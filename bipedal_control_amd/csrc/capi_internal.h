@@ -1,54 +1,36 @@
-// Shared between the host-only part (capi.cpp) and the device part (solver.hip) of libbpmpc.so.
+// The error model of the C ABI (include/bpmpc.h), shared by every unit of libbpmpc.so that has entry points: exceptions inside, a status code
+// and bpmpc_last_error() outside.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <exception>
 #include <string>
+#include <type_traits>
 
 #include "../../include/bpmpc.h"
+#include "errors.h"
 #include "robot_model.h"
 
 namespace bpmpc {
 void set_last_error(const std::string& message);
 const RobotModel& model_of(const bpmpc_model* handle);
 
-struct DeviceModel;
+#define HIP_CHECK(expr)                                                                                     \
+  do {                                                                                                      \
+    hipError_t err_ = (expr);                                                                               \
+    if (err_ != hipSuccess) throw DeviceError(std::string(#expr) + ": " + hipGetErrorString(err_));         \
+  } while (0)
 
-// ---- controller tick (controller.cpp): what it reads of the solver and the WBC handles
-struct SolverTickView {
-  int device, batch, N, nx, nu, nj, feedback;
-  hipStream_t stream;
-  const DeviceModel* d_model;
-  const int *p_grid, *g_nodes, *g_kind, *g_mode;    // grid tables of the last setup
-  const double *g_time, *x, *u, *K;                 // solution of the last run
-  double* loop_x;                                   // [max_batch][nx]: start of bpmpc_solver_setup_commands(x0 = NULL) after a tick
-};
-// Throws (std::invalid_argument: no completed run since the last setup; the Unsupported error of solver.hip: the DDP solver).
-SolverTickView solver_tick_view(bpmpc_solver* s);
-// The tick wrote loop_x: the next setup_commands(x0 = NULL) starts from it (until the next rollout).
-void solver_tick_done(bpmpc_solver* s);
-int solver_device(const bpmpc_solver* s);
-// ---- restarts (bpmpc_controller_restart): the solver's stream and model after the checks of bpmpc_solver_restart (SQP, batch of the last setup)
-struct SolverRestartView {
-  int device, nj;
-  hipStream_t stream;
-  const DeviceModel* d_model;
-};
-SolverRestartView solver_restart_view(bpmpc_solver* s, int batch);
-// bpmpc_solver_restart without the API wrapper (throws)
-void solver_restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool inputs_on_device);
-// The status solver.hip returns for an exception it threw.
-int solver_translate(const std::exception& e);
+// Sets bpmpc_last_error() to e.what() and returns the status of e's class (errors.h; std::invalid_argument, std::length_error), `fallback` for
+// any other exception: BPMPC_ERR_IO for the solver, WBC, gait batch and model entry points, BPMPC_ERR_DEVICE for the controller's.
+int translate(const std::exception& e, int fallback);
 
-struct WbcTickView {
-  int device, max_batch, n, nv, nj;
-  double* sol;                                      // [max_batch][n]: the last QP solution of every robot (lastQpSol_)
-  int* status;                                      // [max_batch]
-};
-WbcTickView wbc_tick_view(const bpmpc_wbc* w);
-int wbc_translate(const std::exception& e);        // the status wbc.hip returns for an exception it threw
-// k_wbc on device inputs, enqueued on `stream`; later work on the WBC handle's own stream waits for it.
-void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const double* input_des, const double* rbd_meas, const int* mode, hipStream_t stream);
-// bpmpc_wbc_restart on a device mask, enqueued on `stream` with the same cross-stream rule
-void wbc_restart_on(bpmpc_wbc* w, int batch, const int* mask, hipStream_t stream);
+// An entry point's body under the error model: what it returns (BPMPC_OK for a body without a result), or the status of what it throws.
+template <typename F>
+int guarded(int fallback, F&& body) {
+  try {
+    if constexpr (std::is_void_v<std::invoke_result_t<F&>>) { body(); return BPMPC_OK; }
+    else return body();
+  } catch (const std::exception& e) { return translate(e, fallback); }
+}
 }  // namespace bpmpc

@@ -12,9 +12,8 @@
 #include <stdexcept>
 #include <string>
 
-#include "../../include/bpmpc.h"
-#include "capi_internal.h"
-#include "kernel_launchers.h"
+#include "solver.h"
+#include "wbc.h"
 #include "kernels/tick.h"
 
 using namespace bpmpc;
@@ -29,23 +28,11 @@ struct bpmpc_controller {
 
 namespace {
 
-struct TickDeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
-void tick_hip(hipError_t e, const char* what) {
-  if (e != hipSuccess) throw TickDeviceError(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define TICK_HIP(expr) tick_hip((expr), #expr)
-
-int translate(const std::exception& e) {
-  if (dynamic_cast<const TickDeviceError*>(&e)) { set_last_error(e.what()); return BPMPC_ERR_DEVICE; }
-  int rc = solver_translate(e);              // the solver's own classes (its Unsupported for the DDP solver included)
-  if (rc == BPMPC_ERR_IO) rc = wbc_translate(e);
-  return rc == BPMPC_ERR_IO ? BPMPC_ERR_DEVICE : rc;
-}
-
-TickArgs policy_args(const SolverTickView& v, int batch) {
+TickArgs policy_args(const bpmpc_solver* s, int batch) {
+  const Buffers& bf = s->buf;
   TickArgs a{};
-  a.batch = batch; a.N = v.N; a.feedback = v.feedback;
-  a.p_grid = v.p_grid; a.g_nodes = v.g_nodes; a.g_kind = v.g_kind; a.g_mode = v.g_mode; a.g_time = v.g_time; a.x = v.x; a.u = v.u; a.K = v.K;
+  a.batch = batch; a.N = s->settings.max_nodes; a.feedback = s->feedback();
+  a.p_grid = bf.p_grid; a.g_nodes = bf.g_nodes; a.g_kind = bf.g_kind; a.g_mode = bf.g_mode; a.g_time = bf.g_time; a.x = bf.x; a.u = bf.u; a.K = bf.K;
   return a;
 }
 
@@ -62,30 +49,29 @@ extern "C" {
 int bpmpc_solver_evaluate_policy(bpmpc_solver* s, int batch, const double* t, const double* x, double* x_opt, double* u_opt, int* planned_mode) {
   if (!s || !t || !x || !x_opt || !u_opt || !planned_mode) { set_last_error("bpmpc_solver_evaluate_policy: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
   void* block = nullptr;
-  int rc = BPMPC_OK;
-  try {
-    const SolverTickView v = solver_tick_view(s);
-    if (batch != v.batch) throw std::invalid_argument("bpmpc_solver_evaluate_policy: batch differs from the batch of the last setup");
-    TICK_HIP(hipSetDevice(v.device));
-    const size_t B = batch, nx = v.nx, nu = v.nu;
+  const int rc = guarded(BPMPC_ERR_DEVICE, [&] {
+    check_policy(s);
+    if (batch != s->batch) throw std::invalid_argument("bpmpc_solver_evaluate_policy: batch differs from the batch of the last setup");
+    HIP_CHECK(hipSetDevice(s->settings.device));
+    const size_t B = batch, nx = s->nx, nu = s->nu;
     const size_t bytes = B * (1 + 2 * nx + nu) * sizeof(double) + B * sizeof(int);
-    TICK_HIP(hipMalloc(&block, bytes));
+    HIP_CHECK(hipMalloc(&block, bytes));
     double* d_t = static_cast<double*>(block);
     double* d_x = d_t + B;
     double* d_xopt = d_x + B * nx;
     double* d_uopt = d_xopt + B * nx;
     int* d_mode = reinterpret_cast<int*>(d_uopt + B * nu);
-    TICK_HIP(hipMemcpyAsync(d_t, t, B * sizeof(double), hipMemcpyHostToDevice, v.stream));
-    TICK_HIP(hipMemcpyAsync(d_x, x, B * nx * sizeof(double), hipMemcpyHostToDevice, v.stream));
-    TickArgs a = policy_args(v, batch);
+    HIP_CHECK(hipMemcpyAsync(d_t, t, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipMemcpyAsync(d_x, x, B * nx * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    TickArgs a = policy_args(s, batch);
     a.t = d_t; a.x_in = d_x; a.x_opt = d_xopt; a.u_opt = d_uopt; a.mode = d_mode;
-    kl::tick_observe_policy(v.nj, batch, v.stream, v.d_model, a);
-    TICK_HIP(hipGetLastError());
-    TICK_HIP(hipMemcpyAsync(x_opt, d_xopt, B * nx * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    TICK_HIP(hipMemcpyAsync(u_opt, d_uopt, B * nu * sizeof(double), hipMemcpyDeviceToHost, v.stream));
-    TICK_HIP(hipMemcpyAsync(planned_mode, d_mode, B * sizeof(int), hipMemcpyDeviceToHost, v.stream));
-    TICK_HIP(hipStreamSynchronize(v.stream));
-  } catch (const std::exception& e) { rc = translate(e); }
+    kl::tick_observe_policy(s->rm.nj, batch, s->stream, s->d_model, a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(x_opt, d_xopt, B * nx * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipMemcpyAsync(u_opt, d_uopt, B * nu * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipMemcpyAsync(planned_mode, d_mode, B * sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+  });
   if (block) (void)hipFree(block);
   return rc;
 }
@@ -94,32 +80,26 @@ int bpmpc_controller_create(bpmpc_solver* s, bpmpc_wbc* w, bpmpc_controller** ou
   if (!s || !w || !out) { set_last_error("bpmpc_controller_create: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
   *out = nullptr;
   std::unique_ptr<bpmpc_controller> c(new bpmpc_controller);
-  try {
-    int nx = 0, nu = 0;
-    if (bpmpc_solver_layout(s, nullptr, nullptr, nullptr, &nx, &nu) != BPMPC_OK) throw std::invalid_argument("bpmpc_controller_create: bad solver handle");
-    const WbcTickView wv = wbc_tick_view(w);
-    if (nx != 12 + wv.nj) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC are built for different robots");
-    if (solver_device(s) != wv.device) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC live on different devices");
-    c->s = s; c->w = w; c->device = wv.device; c->max_batch = wv.max_batch; c->nj = wv.nj; c->nx = nx; c->nv = wv.nv; c->n = wv.n;
-    TICK_HIP(hipSetDevice(c->device));
+  const int rc = guarded(BPMPC_ERR_DEVICE, [&] {
+    if (s->nx != 12 + w->rm.nj) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC are built for different robots");
+    if (s->settings.device != w->device) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC live on different devices");
+    c->s = s; c->w = w; c->device = w->device; c->max_batch = w->max_batch; c->nj = w->rm.nj; c->nx = s->nx; c->nv = w->nv; c->n = w->n;
+    HIP_CHECK(hipSetDevice(c->device));
     const size_t B = c->max_batch;
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_yaw), B * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_t), B * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_rbd), B * 2 * c->nv * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_xobs), B * c->nx * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_xopt), B * c->nx * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_uopt), B * c->nx * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_cmd), B * 3 * c->nj * sizeof(double)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_mode), B * sizeof(int)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_safe), B * sizeof(int)));
-    TICK_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_mask), B * sizeof(int)));
-    TICK_HIP(hipMemset(c->d_yaw, 0, B * sizeof(double)));       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
-    TICK_HIP(hipDeviceSynchronize());
-  } catch (const std::exception& e) {
-    const int rc = translate(e);
-    free_all(c.get());
-    return rc;
-  }
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_yaw), B * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_t), B * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_rbd), B * 2 * c->nv * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_xobs), B * c->nx * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_xopt), B * c->nx * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_uopt), B * c->nx * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_cmd), B * 3 * c->nj * sizeof(double)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_mode), B * sizeof(int)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_safe), B * sizeof(int)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_mask), B * sizeof(int)));
+    HIP_CHECK(hipMemset(c->d_yaw, 0, B * sizeof(double)));       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+  if (rc != BPMPC_OK) { free_all(c.get()); return rc; }
   *out = c.release();
   return BPMPC_OK;
 }
@@ -134,91 +114,86 @@ void bpmpc_controller_destroy(bpmpc_controller* c) {
 
 int bpmpc_controller_reset(bpmpc_controller* c) {
   if (!c) { set_last_error("null controller handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  try {
-    TICK_HIP(hipSetDevice(c->device));
-    TICK_HIP(hipDeviceSynchronize());
-    TICK_HIP(hipMemset(c->d_yaw, 0, (size_t)c->max_batch * sizeof(double)));
-    TICK_HIP(hipDeviceSynchronize());
-  } catch (const std::exception& e) { return translate(e); }
-  return BPMPC_OK;
+  return guarded(BPMPC_ERR_DEVICE, [&] {
+    HIP_CHECK(hipSetDevice(c->device));
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipMemset(c->d_yaw, 0, (size_t)c->max_batch * sizeof(double)));
+    HIP_CHECK(hipDeviceSynchronize());
+  });
 }
 
 int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const double* rbd, int inputs_on_device, double period,
                           const bpmpc_tick_outputs* host_out) {
   (void)period;      // WeightedWbc::update takes it and does not use it (WbcBase.cpp:242-243), as bpmpc_wbc_update
   if (!c || !t || !rbd) { set_last_error("bpmpc_controller_tick: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  try {
-    const SolverTickView v = solver_tick_view(c->s);
-    if (batch != v.batch) throw std::invalid_argument("bpmpc_controller_tick: batch differs from the batch of the solver's last setup");
+  return guarded(BPMPC_ERR_DEVICE, [&] {
+    bpmpc_solver* s = c->s;
+    check_policy(s);
+    if (batch != s->batch) throw std::invalid_argument("bpmpc_controller_tick: batch differs from the batch of the solver's last setup");
     if (batch > c->max_batch) throw std::length_error("bpmpc_controller_tick: batch exceeds the WBC's max_batch");
-    TICK_HIP(hipSetDevice(c->device));
+    HIP_CHECK(hipSetDevice(c->device));
     const size_t B = batch;
     const double *dt = t, *drbd = rbd;
     if (!inputs_on_device) {
-      TICK_HIP(hipMemcpyAsync(c->d_t, t, B * sizeof(double), hipMemcpyHostToDevice, v.stream));
-      TICK_HIP(hipMemcpyAsync(c->d_rbd, rbd, B * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, v.stream));
+      HIP_CHECK(hipMemcpyAsync(c->d_t, t, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      HIP_CHECK(hipMemcpyAsync(c->d_rbd, rbd, B * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, s->stream));
       dt = c->d_t; drbd = c->d_rbd;
     }
-    TickArgs a = policy_args(v, batch);
-    a.t = dt; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs; a.x_loop = v.loop_x; a.safe = c->d_safe;
+    TickArgs a = policy_args(s, batch);
+    a.t = dt; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs; a.x_loop = s->tick_x; a.safe = c->d_safe;
     a.x_opt = c->d_xopt; a.u_opt = c->d_uopt; a.mode = c->d_mode;
-    kl::tick_observe_policy(c->nj, batch, v.stream, v.d_model, a);
-    TICK_HIP(hipGetLastError());
-    solver_tick_done(c->s);
-    wbc_launch_on(c->w, batch, c->d_xopt, c->d_uopt, drbd, c->d_mode, v.stream);
-    const WbcTickView wv = wbc_tick_view(c->w);
-    kl::tick_commands(c->nj, batch, v.stream, c->d_xopt, c->d_uopt, wv.sol, c->d_cmd);
-    TICK_HIP(hipGetLastError());
+    kl::tick_observe_policy(c->nj, batch, s->stream, s->d_model, a);
+    HIP_CHECK(hipGetLastError());
+    s->loop_from_tick = true;          // the next setup_commands(x0 = NULL) starts from tick_x (until the next rollout)
+    wbc_launch_on(c->w, batch, c->d_xopt, c->d_uopt, drbd, c->d_mode, s->stream);
+    kl::tick_commands(c->nj, batch, s->stream, c->d_xopt, c->d_uopt, c->w->d_sol, c->d_cmd);
+    HIP_CHECK(hipGetLastError());
     if (host_out) {
       const bpmpc_tick_outputs& o = *host_out;
-      auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) TICK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, v.stream)); };
+      auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream)); };
       down(o.x_obs, c->d_xobs, B * c->nx * sizeof(double));
       down(o.x_opt, c->d_xopt, B * c->nx * sizeof(double));
       down(o.u_opt, c->d_uopt, B * c->nx * sizeof(double));
       down(o.joint_cmd, c->d_cmd, B * 3 * c->nj * sizeof(double));
-      down(o.wbc_solution, wv.sol, B * c->n * sizeof(double));
+      down(o.wbc_solution, c->w->d_sol, B * c->n * sizeof(double));
       down(o.planned_mode, c->d_mode, B * sizeof(int));
-      down(o.wbc_status, wv.status, B * sizeof(int));
+      down(o.wbc_status, c->w->d_status, B * sizeof(int));
       down(o.safe, c->d_safe, B * sizeof(int));
-      TICK_HIP(hipStreamSynchronize(v.stream));
+      HIP_CHECK(hipStreamSynchronize(s->stream));
     }
-  } catch (const std::exception& e) { return translate(e); }
-  return BPMPC_OK;
+  });
 }
 
 // BipedalController::starting for the robots of `mask`: the observation unwrapped against yawLast = 0 (:126-127), MPC_BASE::reset from it (:147-148),
 // clearLastQpSol (:179).  The refusals of bpmpc_solver_restart (DDP, batch of the last setup) and the tick's (the WBC's max_batch) come first.
 int bpmpc_controller_restart(bpmpc_controller* c, int batch, const int* mask, const double* rbd, int inputs_on_device) {
   if (!c || !mask || !rbd) { set_last_error("bpmpc_controller_restart: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  try {
-    const SolverRestartView v = solver_restart_view(c->s, batch);
+  return guarded(BPMPC_ERR_DEVICE, [&] {
+    bpmpc_solver* s = c->s;
+    check_restart(s, batch);
     if (batch > c->max_batch) throw std::length_error("bpmpc_controller_restart: batch exceeds the WBC's max_batch");
-    TICK_HIP(hipSetDevice(c->device));
+    HIP_CHECK(hipSetDevice(c->device));
     const int* dmask = mask;
     const double* drbd = rbd;
     if (!inputs_on_device) {
-      TICK_HIP(hipMemcpyAsync(c->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, v.stream));
-      TICK_HIP(hipMemcpyAsync(c->d_rbd, rbd, (size_t)batch * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, v.stream));
+      HIP_CHECK(hipMemcpyAsync(c->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
+      HIP_CHECK(hipMemcpyAsync(c->d_rbd, rbd, (size_t)batch * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, s->stream));
       dmask = c->d_mask; drbd = c->d_rbd;
     }
     RestartArgs a{};
     a.batch = batch; a.mask = dmask; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs;
-    kl::restart_observe(c->nj, batch, v.stream, v.d_model, a);
-    TICK_HIP(hipGetLastError());
-    solver_restart(c->s, batch, dmask, c->d_xobs, true);
-    wbc_restart_on(c->w, batch, dmask, v.stream);
-    if (!inputs_on_device) TICK_HIP(hipStreamSynchronize(v.stream));     // the caller's host arrays
-  } catch (const std::exception& e) { return translate(e); }
-  return BPMPC_OK;
+    kl::restart_observe(c->nj, batch, s->stream, s->d_model, a);
+    HIP_CHECK(hipGetLastError());
+    restart(s, batch, dmask, c->d_xobs, true);
+    wbc_restart_on(c->w, batch, dmask, s->stream);
+    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(s->stream));     // the caller's host arrays
+  });
 }
 
 int bpmpc_controller_device_outputs(bpmpc_controller* c, bpmpc_tick_outputs* o) {
   if (!c || !o) { set_last_error("bpmpc_controller_device_outputs: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  try {
-    const WbcTickView wv = wbc_tick_view(c->w);
-    o->x_obs = c->d_xobs; o->x_opt = c->d_xopt; o->u_opt = c->d_uopt; o->joint_cmd = c->d_cmd; o->wbc_solution = wv.sol;
-    o->planned_mode = c->d_mode; o->wbc_status = wv.status; o->safe = c->d_safe;
-  } catch (const std::exception& e) { return translate(e); }
+  o->x_obs = c->d_xobs; o->x_opt = c->d_xopt; o->u_opt = c->d_uopt; o->joint_cmd = c->d_cmd; o->wbc_solution = c->w->d_sol;
+  o->planned_mode = c->d_mode; o->wbc_status = c->w->d_status; o->safe = c->d_safe;
   return BPMPC_OK;
 }
 

@@ -281,13 +281,6 @@ __global__ void k_ddp_keep_times(DdpBuffers d, int batch, int N, double* tp_time
   if (threadIdx.x == 0) { tp_nodes[b] = n - 1; tp_grid[b] = b; }
 }
 
-#define KL_NJ(nj, ...)                                                          \
-  do {                                                                          \
-    if ((nj) == 10) { constexpr int NJ = 10; __VA_ARGS__; }                     \
-    else if ((nj) == 12) { constexpr int NJ = 12; __VA_ARGS__; }                \
-    else throw std::runtime_error("unsupported joint count");                   \
-  } while (0)
-
 namespace kl {
 
 void ddp_policy(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d) { KL_NJ(nj, hipLaunchKernelGGL(k_ddp_policy<NJ>, dim3(batch), dim3(kWave), 0, st, L, d)); }

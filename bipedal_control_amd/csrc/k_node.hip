@@ -394,13 +394,6 @@ __global__ __launch_bounds__(256) void k_copy_pairs(const double* a_src, double*
   if (iterations) for (size_t i = i0; i < (size_t)batch; i += stride) { iterations[i] = 0; active[i] = 1; }
 }
 
-#define KL_NJ(nj, ...)                                                          \
-  do {                                                                          \
-    if ((nj) == 10) { constexpr int NJ = 10; __VA_ARGS__; }                     \
-    else if ((nj) == 12) { constexpr int NJ = 12; __VA_ARGS__; }                \
-    else throw std::runtime_error("unsupported joint count");                   \
-  } while (0)
-
 namespace kl {
 
 void prepare(int nj, int slots, hipStream_t st, const Launch& L) { KL_NJ(nj, hipLaunchKernelGGL(k_prepare<NJ>, dim3(slots), dim3(kWave), 0, st, L)); }

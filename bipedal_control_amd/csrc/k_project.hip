@@ -100,13 +100,6 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PK ? 3 : 
   project_apply_mfma<NJ, PK, WJ>(ws, in, out, dt, dt * (1.0 / L.model->robot_mass), L.model->Q, L.model->R, L.reg_prim);   // as written by linearize_fast
 }
 
-#define KL_NJ(nj, ...)                                                          \
-  do {                                                                          \
-    if ((nj) == 10) { constexpr int NJ = 10; __VA_ARGS__; }                     \
-    else if ((nj) == 12) { constexpr int NJ = 12; __VA_ARGS__; }                \
-    else throw std::runtime_error("unsupported joint count");                   \
-  } while (0)
-
 namespace kl {
 
 void project_reference(int nj, int slots, hipStream_t st, const Launch& L) { KL_NJ(nj, hipLaunchKernelGGL(k_project<NJ>, dim3(slots), dim3(kWave), 0, st, L)); }

@@ -37,13 +37,6 @@ __global__ __launch_bounds__(kRolloutPairThreads) __attribute__((amdgpu_waves_pe
   riccati_rollout_pair<NJ>(ws, io);
 }
 
-#define KL_NJ(nj, ...)                                                          \
-  do {                                                                          \
-    if ((nj) == 10) { constexpr int NJ = 10; __VA_ARGS__; }                     \
-    else if ((nj) == 12) { constexpr int NJ = 12; __VA_ARGS__; }                \
-    else throw std::runtime_error("unsupported joint count");                   \
-  } while (0)
-
 namespace kl {
 
 // joint_rows false: Wt holds the rows 0..11 only, the sweep completes the joint rows from Vt (k_project_fast<.., false>)

@@ -5,8 +5,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <stdexcept>
 
 namespace bpmpc {
+
+// `body` with the instantiation of `nj` as the constant NJ (a launcher's dispatch; nj is 10 or 12, checked when a handle is created)
+#define KL_NJ(nj, ...)                                                          \
+  do {                                                                          \
+    if ((nj) == 10) { constexpr int NJ = 10; __VA_ARGS__; }                     \
+    else if ((nj) == 12) { constexpr int NJ = 12; __VA_ARGS__; }                \
+    else throw std::runtime_error("unsupported joint count");                   \
+  } while (0)
 
 struct Launch;
 struct DeviceModel;
@@ -40,7 +49,7 @@ void project_fast(int nj, bool packed, bool joint_rows, int nodes, hipStream_t s
 
 // ---- k_riccati.hip: workgroup-per-problem sweeps
 void riccati_reference(int nj, int batch, hipStream_t st, const Launch& L);
-void riccati_fast(int nj, bool double_buffered, bool joint_rows, int batch, hipStream_t st, const Launch& L);
+void riccati_fast(int nj, bool joint_rows, int batch, hipStream_t st, const Launch& L);       // four waves, two problems per CU
 void riccati_fast8(int nj, bool joint_rows, int batch, hipStream_t st, const Launch& L);     // joint_rows: Wt holds them (off: completed from Vt by the loaders)
 
 // ---- k_riccati_wave.hip: wave-per-problem sweeps and their roll-out

@@ -4,7 +4,8 @@
 // the host pre-pass (reference_gen.cpp, which restates GaitSchedule.cpp:40-137, SwingTrajectoryPlanner.cpp / SplineCpg.cpp /
 // CubicSpline.cpp, timeDiscretizationWithEvents and TargetTrajectoriesPublisher.cpp:30-62) operation by operation with
 // floating-point contraction switched off, so the tables are bit-identical to the host path (tests/test_gpu_reference_gen.py);
-// only sin/cos of the targets may differ in the last place.
+// only sin/cos of the targets may differ in the last place.  The kernels, k_reference_grids and k_command_targets, are defined in solver.hip, the
+// one unit that launches them: gait_batch.hip includes this header too (kernels/gait_state.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -262,23 +263,6 @@ __device__ inline void ref_fill_tables(RefGenLds& w, const ReferenceGenArgs& a, 
   for (int k = l; k <= N; k += 64) a.node_time[(size_t)g * (N + 1) + k] = (ok && k <= n) ? w.time[k] : 0.0;
 }
 
-__global__ __launch_bounds__(64) void k_reference_grids(ReferenceGenArgs a) {
-  EXACT_FP_BODY
-  __shared__ RefGenLds w;
-  const int g = blockIdx.x, l = threadIdx.x;
-  const double t0 = a.t0[g];
-  if (l == 0) {
-    w.rows = 12;
-    w.vrows = 4;
-    ref_build_schedule(w, a.lib, a.gait[g], a.gait_start[g], t0, a.horizon);
-    ref_lay_grid(w, a, t0);
-  }
-  __syncthreads();
-  ref_fill_tables(w, a, g, l);
-  __syncthreads();
-  if (l == 0) { a.nodes[g] = w.n_grid; a.status[g] = w.status; a.rows[g] = w.rows | (w.vrows << 8); }
-}
-
 struct CommandTargetArgs {
   int batch, nx, nj;
   int goal;                // 0: cmd = (vx, vy, vz, yaw rate) in the base frame; 1: cmd = goal pose (x, y, unused, yaw)
@@ -291,43 +275,6 @@ struct CommandTargetArgs {
   double* tgt_x;           // [batch][kMaxTargetPoints][nx]
   int* tgt_n;
 };
-
-// cmdVelToTargetTrajectories (TargetTrajectoriesPublisher.cpp:40-62 restated in reference_gen.cpp cmd_vel_to_targets)
-__global__ __launch_bounds__(64) void k_command_targets(CommandTargetArgs a) {
-  EXACT_FP_BODY
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= a.batch) return;
-  const int nx = a.nx;
-  const double* x = a.x0 + (size_t)b * nx;
-  const double* cmd = a.cmd_vel + (size_t)b * 4;
-  const double T = a.time_to_target, t_now = a.t0[b];
-  double v[3] = {0.0, 0.0, 0.0}, pose[6], t_reach;
-  if (a.goal) {            // goalToTargetTrajectories (TargetTrajectoriesPublisher.cpp:64-99 restated in reference_gen.cpp goal_to_targets)
-    pose[0] = cmd[0]; pose[1] = cmd[1]; pose[2] = a.com_height; pose[3] = cmd[3]; pose[4] = 0.0; pose[5] = 0.0;
-    const double dx = pose[0] - x[6], dy = pose[1] - x[7], dyaw = pose[3] - x[9];
-    const double tr = fabs(dyaw) / a.rotation_velocity, td = sqrt(dx * dx + dy * dy) / a.displacement_velocity;
-    t_reach = t_now + (tr < td ? td : tr);
-  } else {
-    const double yz = x[9], yy = x[10], yx = x[11];
-    const double cz = cos(yz), sz = sin(yz), cy = cos(yy), sy = sin(yy), cx = cos(yx), sx = sin(yx);
-    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
-    for (int i = 0; i < 3; ++i) v[i] = R[3 * i] * cmd[0] + R[3 * i + 1] * cmd[1] + R[3 * i + 2] * cmd[2];
-    pose[0] = x[6] + v[0] * T; pose[1] = x[7] + v[1] * T; pose[2] = a.com_height; pose[3] = x[9] + cmd[3] * T; pose[4] = 0.0; pose[5] = 0.0;
-    t_reach = t_now + T;
-  }
-  double* ts = a.tgt_t + (size_t)b * kMaxTargetPoints;
-  double* xs = a.tgt_x + (size_t)b * kMaxTargetPoints * nx;
-  for (int i = 0; i < 2 * nx; ++i) xs[i] = 0.0;
-  ts[0] = t_now;
-  ts[1] = t_reach;
-  for (int i = 0; i < 6; ++i) { xs[6 + i] = x[6 + i]; xs[nx + 6 + i] = pose[i]; }
-  xs[6 + 2] = a.com_height;
-  xs[6 + 4] = 0.0;
-  xs[6 + 5] = 0.0;
-  for (int j = 0; j < a.nj; ++j) xs[12 + j] = xs[nx + 12 + j] = a.default_joint_state[j];
-  if (!a.goal) for (int i = 0; i < 3; ++i) xs[i] = xs[nx + i] = v[i];
-  a.tgt_n[b] = 2;
-}
 
 #undef EXACT_FP_BODY
 

@@ -51,35 +51,31 @@ struct LdsSwz {
   static constexpr int size(int rows) { return ((rows + 1) / 2) * PS; }
 };
 
-// DB: the staged operands are double buffered (stage k-1 is staged while the updates of stage k still read theirs, which
-// saves a barrier per stage).  At nx = 22 that costs 98 KB of LDS (one workgroup per CU) against 66 KB single buffered (two
-// workgroups per CU): the solver double buffers when the batch does not exceed the number of CUs.
-template <int NJ, bool DB>
+// One set of staged operands: 66 KB of LDS at nx = 22, two workgroups per CU.
+template <int NJ>
 struct RiccatiMfmaWorkspace {
   static constexpr int NX = 12 + NJ, NU = 12 + NJ;
   static constexpr int ZR = NX;                                  // a row that is always zero: block rows >= nx are read there
-  // rows: two full 16-row blocks when double buffered (plain block loads / stores), otherwise nx + the zero row(s)
-  // (block rows >= nx are then read from the zero row and not stored)
-  static constexpr int RB = DB ? 32 : ((NX + 2 + 1) / 2) * 2;
-  static constexpr int RCL = DB ? 32 : NX;                       // block rows below this are read as they are
+  // rows: nx + the zero row(s) (block rows >= nx are read from the zero row and not stored)
+  static constexpr int RB = ((NX + 2 + 1) / 2) * 2;
+  static constexpr int RCL = NX;                                 // block rows below this are read as they are
   static constexpr int LDN = 34;                                 // leading dimension of the [.. | vector] blocks (nx + 1 <= 32 columns)
   static constexpr int WC = NX + 1 + NU;                         // packed width [A | b | B]
   static constexpr int LDW = ((WC + 15) / 16) * 16 + 2;
   static_assert(NX + 1 <= 32 && NU <= 32 && ((NX + 3) / 4) * 4 <= RB, "two block rows / columns");
-  static constexpr int NBUF = DB ? 2 : 1;
   alignas(16) double S[RB][LDN];        // [S | s], not symmetrised
-  alignas(16) double Qq[NBUF][RB][LDN]; // [Q~ | q~]
+  alignas(16) double Qq[RB][LDN];       // [Q~ | q~]
   alignas(16) double Sn[RB][LDN];       // [Sn | sn]
   alignas(16) double G0[RB][LDN];       // [G | g] before the elimination
-  alignas(16) double W[NBUF][RB][LDW];  // [A~ | b~ | B~]
-  alignas(16) double PW[NBUF][RB][LDW]; // [Px | Pe | Pu]
+  alignas(16) double W[RB][LDW];        // [A~ | b~ | B~]
+  alignas(16) double PW[RB][LDW];       // [Px | Pe | Pu]
   alignas(16) double SW[RB][LDW];       // sym(S) W
-  // Rows of M = reduced inputs.  The single-buffered nx = 24 variant keeps 16 of them (rows 16.. of [P~ | r~ | R~] are zero whenever a
-  // stage has at most 16 reduced inputs - every mode of this problem family leaves at most nu - 10 = 14) so that two workgroups share
-  // a CU (79 KB each); a stage with more makes the sweep report a numerical failure instead of computing nonsense.
-  static constexpr int RBM = (!DB && NX > 22) ? 16 : RB;
-  alignas(16) double M[NBUF][RBM][LDW]; // [P~ | r~ | R~] -> [G | g | H] -> Y in the first nx + 1 columns
-  double r[NBUF][NU];
+  // Rows of M = reduced inputs.  The nx = 24 variant keeps 16 of them (rows 16.. of [P~ | r~ | R~] are zero whenever a stage has at
+  // most 16 reduced inputs - every mode of this problem family leaves at most nu - 10 = 14) so that two workgroups share a CU (79 KB
+  // each); a stage with more makes the sweep report a numerical failure instead of computing nonsense.
+  static constexpr int RBM = NX > 22 ? 16 : RB;
+  alignas(16) double M[RBM][LDW];       // [P~ | r~ | R~] -> [G | g | H] -> Y in the first nx + 1 columns
+  double r[NU];
   alignas(16) double dx[2][NX];
   int status;
   unsigned char nut[kMaxRiccatiStages]; // reduced input dimensions of all stages (a global load per stage would sit on the critical path)
@@ -788,9 +784,9 @@ __device__ __forceinline__ void riccati_rollout_ring(double* lds /* (2 cap + 2 C
   }
 }
 
-template <int NJ, bool DB, bool JW = true>     // JW: Wt holds its joint rows (off: the loaders complete them from Vt, PackedStageLoader JR)
-__device__ __forceinline__ void riccati_mfma(RiccatiMfmaWorkspace<NJ, DB>& ws, const RiccatiFastIO& io) {
-  using WS = RiccatiMfmaWorkspace<NJ, DB>;
+template <int NJ, bool JW = true>     // JW: Wt holds its joint rows (off: the loaders complete them from Vt, PackedStageLoader JR)
+__device__ __forceinline__ void riccati_mfma(RiccatiMfmaWorkspace<NJ>& ws, const RiccatiFastIO& io) {
+  using WS = RiccatiMfmaWorkspace<NJ>;
   constexpr int NX = WS::NX, NU = WS::NU, NT = kRiccatiThreads, LDN = WS::LDN, LDW = WS::LDW, RB = WS::RB, ZR = WS::ZR, RCL = WS::RCL, RBM = WS::RBM;
   constexpr int NXX = NX * NX, NXU = NX * NU;
   constexpr int KS = (NX + 3) / 4;          // k-steps over the state dimension
@@ -879,12 +875,11 @@ __device__ __forceinline__ void riccati_mfma(RiccatiMfmaWorkspace<NJ, DB>& ws, c
 
   for (int k = k_top; k >= io.k_lo; --k) {
     const int nt = ws.nut[k];        // max_nodes <= kMaxRiccatiStages is checked when the solver is created
-    const int cur = DB ? (k & 1) : 0;
-    double (*const W)[LDW] = ws.W[cur];
-    double (*const PW)[LDW] = ws.PW[cur];
-    double (*const Qq)[LDN] = ws.Qq[cur];
-    double (*const M)[LDW] = ws.M[cur];
-    double* const rvec = ws.r[cur];
+    double (*const W)[LDW] = ws.W;
+    double (*const PW)[LDW] = ws.PW;
+    double (*const Qq)[LDN] = ws.Qq;
+    double (*const M)[LDW] = ws.M;
+    double* const rvec = ws.r;
     const int ksn = (nt + 3) >> 2;                   // k-steps over the reduced input
     const int nbc = (BC + nt + 15) >> 4;             // block columns of the packed width nx + 1 + nt
     const int ntb = (nt + 15) >> 4;                  // block rows of the reduced input
@@ -1079,8 +1074,7 @@ __device__ __forceinline__ void riccati_mfma(RiccatiMfmaWorkspace<NJ, DB>& ws, c
       held_acl = acl; held_kf = kf; held_m = mt; held_k = k;
     }
     RMPROF(5);
-    // double buffered: no barrier here, the next stage stages into the other buffer set and its staging barrier also orders S
-    if (!DB) lds_barrier();
+    lds_barrier();
   }
   flush_held();
 #ifdef BPMPC_RICCATI_PROFILE

@@ -6,6 +6,7 @@
 #include <set>
 #include <stdexcept>
 
+#include "errors.h"
 #include "info_tree.h"
 #include "urdf_tree.h"
 
@@ -214,9 +215,9 @@ RobotModel load_robot_model(const std::string& urdf_path, const std::string& tas
     // does not implement is refused, not ignored: a drop-in must not run a different optimiser silently
     std::string v;
     if (task->get("sqp.integratorType", &v) && v != "RK2")
-      throw UnsupportedSetting("task.info: sqp.integratorType " + v + " is not implemented (RK2 sensitivities only)");
+      throw Unsupported("task.info: sqp.integratorType " + v + " is not implemented (RK2 sensitivities only)");
     if (task->get("sqp.projectStateInputEqualityConstraints", &v) && !(v == "true" || v == "1"))
-      throw UnsupportedSetting("task.info: sqp.projectStateInputEqualityConstraints " + v + " is not implemented (the equality constraints are always projected)");
+      throw Unsupported("task.info: sqp.projectStateInputEqualityConstraints " + v + " is not implemented (the equality constraints are always projected)");
     if (task->get("sqp.useFeedbackPolicy", &v)) m.sqp.use_feedback_policy = (v == "true" || v == "1") ? 1 : 0;
   }
   task->get("sqp.inequalityConstraintMu", &m.sqp_inequality_mu);

@@ -27,8 +27,6 @@ struct ModeTemplate {
 };
 
 struct SwingConfig { double lift_off_velocity = 0, touch_down_velocity = 0, swing_height = 0.1, swing_time_scale = 0.15; };
-// A task.info that asks for a variant of the reference's solver this engine does not implement (load_robot_model): BPMPC_ERR_UNSUPPORTED
-struct UnsupportedSetting : std::runtime_error { using std::runtime_error::runtime_error; };
 
 struct SqpConfig { double dt = 0.015; int sqp_iteration = 1; double delta_tol = 1e-4, g_max = 1e-2, g_min = 1e-6;
                    // keys that select the ARITHMETIC of the solver (task.info:76,80,81): the engine implements integratorType RK2 and

@@ -1,5 +1,6 @@
 // Batched SQP solver on one MI355X: device buffers, kernel launches and the solver part of the C ABI (include/bpmpc.h).
-// Kernel bodies live in kernels/*.h; this file only maps (problem, node) -> workgroup and owns HBM.
+// Kernel bodies live in kernels/*.h; this file only maps (problem, node) -> workgroup and owns HBM.  The handle itself is in solver.h,
+// the gait batch and its setup in gait_batch.hip, the batched small transfers in transfer.hip.
 //
 // HBM layout (FP64; B = problems, N = max_nodes, slot s = b*N + k, nx = nu = 12 + nj):
 //   iterate      x[B][(N+1)][nx], u[B][N][nu]                      coalesced 176-B rows per node
@@ -21,244 +22,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/bpmpc.h"
-#include "capi_internal.h"
-#include "device_model.h"
-#include "launch.h"
-#include "kernel_launchers.h"
+#include "solver.h"
 #include "reference_gen.h"
-#include "kernels/reference_device.h"
-#include "kernels/gait_state.h"
 #include "kernels/rollout.h"
-
-namespace bpmpc {
-
-#define HIP_CHECK(expr)                                                                                     \
-  do {                                                                                                      \
-    hipError_t err_ = (expr);                                                                               \
-    if (err_ != hipSuccess) throw DeviceError(std::string(#expr) + ": " + hipGetErrorString(err_));         \
-  } while (0)
-
-struct DeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
-struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };      // -> BPMPC_ERR_UNSUPPORTED
-
-// ------------------------------------------------------------------------------------------------ solver object
-struct KernelTimer {
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  double total_ms = 0.0;
-  int launches = 0;
-};
-
-}  // namespace bpmpc
-
-using namespace bpmpc;
-
-struct HostStaging {   // host-side images of the tables bpmpc_solver_setup uploads
-  std::vector<int> kind, mode, nodes, pgrid, tgt_n;
-  std::vector<double> gdt, gstart, zref, zdref, tgt_t, tgt_x;
-};
-
-// Page-locked host memory for the small transfers of the MPC loop (setup_commands, fetch): a copy from / to pageable memory is
-// staged by the runtime and blocks the calling thread for ~10 us each; from / to pinned memory it is only enqueued.  Slices stay
-// valid until the next reset(), which the callers issue when everything in flight has been waited for.
-struct PinnedArena {
-  char* base = nullptr;
-  size_t cap = 0, used = 0, demand = 0;
-  // start of a new cycle: nothing of the previous one is in flight any more.  Grows to what the previous cycle asked for.
-  void reset() {
-    if (demand > cap) {
-      if (base) (void)hipHostFree(base);
-      base = nullptr; cap = 0;
-      const size_t want = std::max<size_t>(2 * demand, size_t(1) << 20);
-      if (hipHostMalloc(reinterpret_cast<void**>(&base), want) == hipSuccess) cap = want; else base = nullptr;
-    }
-    used = 0; demand = 0;
-  }
-  void* take(size_t bytes) {                              // nullptr: no room in this cycle, the caller uses the pageable path
-    const size_t at = (used + 63) & ~size_t(63);
-    demand = ((demand + 63) & ~size_t(63)) + bytes;
-    if (!base || at + bytes > cap) return nullptr;
-    used = at + bytes;
-    return base + at;
-  }
-  void release() { if (base) (void)hipHostFree(base); base = nullptr; cap = used = demand = 0; }
-};
-
-struct bpmpc_solver {
-  HostStaging staging;
-  PinnedArena pin_up, pin_down;
-  char* xfer = nullptr;                                     // device staging block of the batched small transfers (upload_batch / Downloads)
-  size_t xfer_cap = 0;
-  RobotModel rm;
-  DeviceModel dm;
-  DeviceModel* d_model = nullptr;
-  bpmpc_settings settings{};
-  int nx = 0, nu = 0;
-  int batch = 0, n_grids = 0, n_nodes_max = 0;
-  int num_cus = 256;                                        // compute units of the device
-  // change of variables reading the packed joint rows of the structured elimination: needs an input weight without force / joint-velocity
-  // cross terms (checked when the solver is created; BipedalRobotInterface.cpp:239-271 builds it so).  BPMPC_DENSE_PROJECT=1 switches it off.
-  bool structured_project = false;
-  // Riccati sweep by regime: eight waves with fixed roles while every problem has a CU to itself; four-wave workgroups up to two problems per CU;
-  // beyond that one wavefront per problem (riccati_wave.h at one wave per SIMD up to four problems per CU, riccati_wave2.h at two beyond).
-  // BPMPC_RICCATI_WAVE: 0 never a wave per problem; 1 (default) as described; 2 riccati_wave.h at every batch size, 4 riccati_wave2.h at every
-  // batch size (tests); 3 riccati_wave2.h whenever a wave per problem is used
-  int riccati_wave = 1;
-  bool lin_compact = true;                                  // BPMPC_LIN_COMPACT=0: the lineariser keeps the event nodes in line (A/B, tests)
-  bool force_tables = false;                                // BPMPC_LIN_TABLES=1: the table walks also on a robot of two serial legs (tests)
-  bool wt_joint_rows = false;                               // BPMPC_WT_JOINT_ROWS=1: the change of variables always writes the joint rows of Wt (A/B of the byte cut below)
-  // which sweep runs the current batch (see launch_riccati)
-  bool sweep_wave_regime() const { return riccati_wave == 2 || riccati_wave == 4 || ((riccati_wave == 1 || riccati_wave == 3) && batch > 2 * num_cus); }
-  bool sweep_two_per_simd() const { return sweep_wave_regime() && (riccati_wave >= 3 || (riccati_wave == 1 && batch > 4 * num_cus)); }
-  // the wave-per-problem sweeps (riccati_wave.h, riccati_wave2.h) and the loaders of the eight-wave sweep (riccati_mfma8.h, PackedStageLoader JR) complete the joint rows of Wt = [At | bt | Bt] from Vt ([I | b | 0] + dt Vt): the change of variables then
-  // neither computes nor writes them (3.8 KB per node less each way at the batch sizes where both kernels stream)
-  bool sweep_completes_joint_rows() const { return !wt_joint_rows && structured_project && !settings.reference_kernels; }     // every fast sweep does
-  // The eight-wave sweep holds a CU per problem; a larger batch runs it in ROUNDS (the dispatcher starts a workgroup as a CU becomes free, so the roll-outs
-  // behind the sweeps no longer stream at the same time).  Since its roll-out goes through the ring (round 6) two and three rounds of it beat what those batch
-  // sizes ran before on the 22-state robots - batch 512: 0.5447 against 0.5837 ms on the four-wave workgroups, 768: 0.807 against 0.878 on a wave per problem;
-  // 1024 in four rounds: 1.075 against 0.917, so from there on the wave sweeps - and lose on nx = 24 (G1 / 512: 0.8545 against 0.7682 on the four-wave
-  // workgroups), whose eight-wave stage is 55 % longer (`experiments/LOG.md`).  BPMPC_R8_ROUNDS overrides (1: the regimes of rounds 3 to 5; tests).
-  int r8_rounds = 0;                                        // 0: by the robot, as measured
-  int eight_wave_rounds() const { return r8_rounds > 0 ? r8_rounds : (rm.nj == 10 ? 3 : 1); }
-  bool riccati_double_buffered() const { return riccati_wave != 2 && riccati_wave != 4 && batch <= eight_wave_rounds() * num_cus; }
-  bool has_solution = false;                               // a solve has completed on the current setup
-  bool has_rollout = false;                                // roll_x holds the end states of a rollout
-  bool rollout_unchecked = false;                          // ... whose status flags have not been read back yet
-  // closed loop through the controller tick (k_tick.hip): tick_x holds the observations of the last bpmpc_controller_tick; loop_from_tick says
-  // that the tick, not a rollout, ran last on the handle - bpmpc_solver_setup_commands(x0 = NULL) then starts from tick_x instead of roll_x
-  double* tick_x = nullptr;
-  bool loop_from_tick = false;
-  // per-problem restarts (bpmpc_solver_restart, MPC_BASE::reset per problem): restart_flag[b] != 0 from the restart to the next accepted setup,
-  // which keeps k_prepare's guess for those problems instead of the shifted solution.  restart_pending: flags recorded and not consumed yet;
-  // restart_wait: tick, evaluate_policy and rollout are refused until the first run after that setup (a fresh handle before its first run)
-  int* restart_flag = nullptr;                             // [max_batch]
-  int* restart_mask = nullptr;                             // [max_batch] device copy of a host mask
-  double* restart_x = nullptr;                             // [max_batch][nx] device copy of host states
-  bool restart_pending = false, restart_wait = false;
-  std::vector<int> grid_kind;                               // host copy of the node kinds of the current setup [n_grids][N]
-  int max_rows = kMaxEqRows;                                // largest number of equality rows over the nodes of the current setup
-  int max_vel_rows = 12;                                    // ... of rows that constrain a contact velocity (12 double stance, 8 single support, 4 flight)
-  bool cold = true;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipStream_t producer_stream = nullptr;                   // linearisation + projection of the pipelined horizon chunks
-  hipEvent_t ev_go = nullptr;
-  std::vector<hipEvent_t> ev_chunk;
-  Buffers buf{};
-  std::vector<void*> allocations;
-  std::map<std::string, std::pair<void*, size_t>> named;   // name -> (device ptr, element count)  (doubles unless in int_named)
-  std::map<std::string, bool> is_int;
-  std::vector<double> node_times;                          // host copy: [n_grids][N+1]
-  std::vector<int> grid_nodes, grid_of_problem;
-  std::map<std::string, KernelTimer> timers;
-  int* h_remaining = nullptr;                              // pinned
-  LineSearchSettings ls{};
-
-  template <typename T>
-  T* alloc(const char* name, size_t count, bool integer = false) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, count * sizeof(T)));
-    HIP_CHECK(hipMemsetAsync(p, 0, count * sizeof(T), stream));
-    allocations.push_back(p);
-    if (name) { named[name] = {p, count}; is_int[name] = integer; }
-    return static_cast<T*>(p);
-  }
-
-  Launch launch_params() const {
-    Launch L;
-    L.model = d_model;
-    L.buf = buf;
-    L.batch = batch;
-    L.N = settings.max_nodes;
-    L.k0 = 0;
-    // node range of a launch: the longest grid of the current setup, not the solver's capacity - the per-node kernels map their
-    // workgroups onto batch x klen node slots and every slot beyond a problem's grid is a lane group that idles
-    L.klen = n_nodes_max > 0 ? n_nodes_max : settings.max_nodes;
-    L.cold = cold ? 1 : 0;
-    L.serial_legs = (dm.serial_legs && !force_tables) ? 1 : 0;
-    L.feedback = feedback();
-    L.ls = ls;
-    L.reg_prim = settings.reg_prim;
-    L.lin_ev_n = -1; L.lin_inter = 0;
-    for (int i = 0; i < kLinMaxEvents; ++i) L.lin_ev[i] = 0;
-    if (n_grids == 1 && lin_compact && !grid_kind.empty() && (int)grid_nodes.size() == 1) {
-      const int n = grid_nodes[0];
-      int ne = 0;
-      for (int k = 0; k < n; ++k)
-        if (grid_kind[k] == 1) { if (ne < kLinMaxEvents) L.lin_ev[ne] = k; ++ne; }
-      if (ne <= kLinMaxEvents && n == L.klen) { L.lin_ev_n = ne; L.lin_inter = n - ne; }
-    }
-    L.ilqr = is_ddp() ? 1 : 0;                                  // the DDP solver: every kernel of the backward pass works on the Euler-discretised model
-    L.ilqr_shift = is_ddp() ? rm.ddp.ls_hessian_correction_multiple : 0.0;
-    return L;
-  }
-
-  // Events that only measure time: no system-scope fence when they complete (hipEventDisableSystemFence: "avoiding the cost of cache writeback and
-  // invalidation, and the performance impact of those actions on the execution of following work") - with the default flags the step that carries
-  // the roofline kernel's events ran 3 % slower than the steps without them (the kernel behind the lineariser found its inputs flushed from L2)
-  static constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
-  // settings.profile: 0 off, 1 every kernel class, 2 the linearisation kernel only (the roofline measurement of bench.py: every
-  // event pair costs one to two microseconds of stream time, ten pairs per solve are 2 % of a step)
-  bool timed(const char* cls) const { return settings.profile == 1 || (settings.profile == 2 && std::strcmp(cls, "linearize") == 0); }
-  void time_begin(const char* cls, hipEvent_t* a, hipEvent_t* b, hipStream_t on = nullptr) {
-    if (!timed(cls)) return;
-    HIP_CHECK(hipEventCreateWithFlags(a, kTimingEventFlags));
-    if (hipEventCreateWithFlags(b, kTimingEventFlags) != hipSuccess) { (void)hipEventDestroy(*a); throw DeviceError("hipEventCreate failed"); }
-    if (hipEventRecord(*a, on ? on : stream) != hipSuccess) { (void)hipEventDestroy(*a); (void)hipEventDestroy(*b); throw DeviceError("hipEventRecord failed"); }
-  }
-  void time_end(const char* cls, hipEvent_t a, hipEvent_t b, hipStream_t on = nullptr) {
-    if (!timed(cls)) return;
-    HIP_CHECK(hipEventRecord(b, on ? on : stream));
-    KernelTimer& t = timers[cls];
-    t.pending.emplace_back(a, b);
-    if (t.pending.size() > 4096) collect_timers();   // a profiled loop that never asks for the times must not grow without bound
-  }
-  // The lineariser's events are attached to its dispatch (kl::linearize_fast): their elapsed time is the kernel's duration, without the barrier
-  // packets and the dispatch latency a pair of hipEventRecord calls brackets as well
-  void launch_linearize_fast(hipStream_t on, const Launch& L, int nodes) {
-    if (!timed("linearize")) { kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L); return; }
-    hipEvent_t a, b;
-    HIP_CHECK(hipEventCreateWithFlags(&a, kTimingEventFlags));
-    if (hipEventCreateWithFlags(&b, kTimingEventFlags) != hipSuccess) { (void)hipEventDestroy(a); throw DeviceError("hipEventCreate failed"); }
-    kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L, a, b);
-    KernelTimer& t = timers["linearize"];
-    t.pending.emplace_back(a, b);
-    if (t.pending.size() > 4096) collect_timers();
-  }
-  void collect_timers() {
-    for (auto& kv : timers) {
-      hipError_t first_error = hipSuccess;                 // the events are destroyed whatever happens; the first failure is reported afterwards
-      for (auto& pr : kv.second.pending) {
-        float ms = 0.f;
-        hipError_t e = hipEventSynchronize(pr.second);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, pr.first, pr.second);
-        if (e == hipSuccess) { kv.second.total_ms += ms; kv.second.launches += 1; }
-        else if (first_error == hipSuccess) first_error = e;
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-      }
-      kv.second.pending.clear();
-      if (first_error != hipSuccess) throw DeviceError(std::string("kernel timers: ") + hipGetErrorString(first_error));
-    }
-  }
-
-  void stage_prepare();
-  void stage_linearize();
-  void stage_project();
-  void stage_riccati();
-  void launch_project(hipStream_t on, const Launch& L, int nodes);
-  void launch_riccati(const Launch& L);
-  void stage_linesearch();
-  void pipelined_backward();
-  void run_iterations();
-  void run_ddp();
-  void ddp_nominal_rollout();
-  DdpBuffers ddp{};                                       // the DDP slice (settings.solver = BPMPC_SOLVER_DDP)
-  bool is_ddp() const { return settings.solver == BPMPC_SOLVER_DDP; }
-  // one value for the warm start, the policy rollout and the controller a caller builds (sqp.useFeedbackPolicy / ddp.useFeedbackPolicy of task.info, or the override)
-  int feedback() const { return settings.feedback_policy == 1 ? 1 : (settings.feedback_policy == 2 ? 0 : (is_ddp() ? rm.ddp.use_feedback_policy : rm.sqp.use_feedback_policy)); }
-  int nj() const { return rm.nj; }
-};
 
 // One launch (or a short sequence of launches) bracketed by the events of its kernel class
 #define TIMED_ON(on, cls, ...)                                                      \
@@ -270,6 +36,25 @@ struct bpmpc_solver {
     HIP_CHECK(hipGetLastError());                                                   \
   } while (0)
 #define TIMED(cls, ...) TIMED_ON(stream, cls, __VA_ARGS__)
+
+namespace {
+
+// The part of the roll-out arguments that run_ddp, ddp_nominal_rollout and rollout share: grid tables, iterate, tolerances, and max_steps from the
+// longest grid of the setup
+RolloutArgs rollout_args(const bpmpc_solver* s) {
+  const int N = s->settings.max_nodes;
+  const Buffers& bf = s->buf;
+  RolloutArgs a{};
+  a.N = N; a.p_grid = bf.p_grid; a.g_nodes = bf.g_nodes; a.g_kind = bf.g_kind; a.g_time = bf.g_time;
+  a.x = bf.x; a.u = bf.u; a.K = bf.K;
+  a.abs_tol = s->rm.rollout.abs_tol; a.rel_tol = s->rm.rollout.rel_tol; a.time_step = s->rm.rollout.time_step;
+  double longest = 0.0;
+  for (size_t g = 0; g < s->grid_nodes.size(); ++g) longest = std::max(longest, s->node_times[g * (N + 1) + s->grid_nodes[g]] - s->node_times[g * (N + 1)]);
+  a.max_steps = (int)(s->rm.rollout.max_steps_per_second * std::max(1.0, longest));
+  return a;
+}
+
+}  // namespace
 
 void bpmpc_solver::stage_prepare() {
   const Launch L = launch_params();
@@ -293,11 +78,11 @@ void bpmpc_solver::stage_project() {
   else launch_project(stream, L, batch * L.klen);
 }
 void bpmpc_solver::launch_riccati(const Launch& L) {
-  if (riccati_double_buffered()) { TIMED("riccati", kl::riccati_fast8(nj(), !sweep_completes_joint_rows(), batch, stream, L)); return; }
+  if (sweep_eight_waves()) { TIMED("riccati", kl::riccati_fast8(nj(), !sweep_completes_joint_rows(), batch, stream, L)); return; }
   // up to two problems per CU the four-wave workgroups finish in one round (0.61 against 0.91 ms at batch 512); beyond that a wave per
   // problem, four per CU, wins (G1 / 1024: 1.30 against 1.54 ms; 4096: 4.07 against 4.53 ms)
   if (!sweep_wave_regime()) {
-    TIMED("riccati", kl::riccati_fast(nj(), false, !sweep_completes_joint_rows(), batch, stream, L));
+    TIMED("riccati", kl::riccati_fast(nj(), !sweep_completes_joint_rows(), batch, stream, L));
     return;
   }
   // two waves per SIMD (riccati_wave2.h) need eight problems per CU to fill the chip - the dispatcher packs a CU before it opens the next
@@ -412,20 +197,14 @@ void bpmpc_solver::run_ddp() {
   HIP_CHECK(hipGetLastError());
   // line search: the baseline (step length 0: the new gains, no feedforward increment) and maxStepLength, x contractionRate, .. >= minStepLength
   constexpr double kArmijoCoefficient = 1e-4;                                 // [OCS2-upstream] line_search::Settings default (not in task.info)
-  const int N = settings.max_nodes;
-  RolloutArgs a{};
+  RolloutArgs a = rollout_args(this);
   a.batch = batch * ddp.nv; a.n_problems = batch; a.lff = ddp.lff;
   for (int v = 0; v < ddp.nv; ++v) a.alpha[v] = ddp.alpha_v[v];
-  a.N = N; a.p_grid = buf.p_grid; a.g_nodes = buf.g_nodes; a.g_kind = buf.g_kind; a.g_time = buf.g_time;
-  a.x = buf.x; a.u = buf.u; a.K = buf.K; a.x_start = buf.p_x0;
+  a.x_start = buf.p_x0;
   a.t_start = nullptr; a.duration = -1.0;                                      // every problem over its own horizon [t_0, t_N]
-  a.abs_tol = rm.rollout.abs_tol; a.rel_tol = rm.rollout.rel_tol; a.time_step = rm.rollout.time_step;
   a.feedback = 1;                                                            // the search rolls out the FEEDBACK policy whatever controller is handed out
   a.x_end = ddp.end_x; a.u_end = ddp.end_u; a.steps = ddp.roll_steps; a.status = ddp.roll_status;
   a.rec_t = ddp.rec_t; a.rec_x = ddp.rec_x; a.rec_u = ddp.rec_u; a.rec_n = ddp.rec_n; a.rec_cap = ddp.cap;
-  double longest = 0.0;
-  for (size_t g = 0; g < grid_nodes.size(); ++g) longest = std::max(longest, node_times[g * (N + 1) + grid_nodes[g]] - node_times[g * (N + 1)]);
-  a.max_steps = (int)(rm.rollout.max_steps_per_second * std::max(1.0, longest));
   TIMED("ddp_rollout", kl::rollout(rm.nj, dm.serial_legs && !force_tables, batch * ddp.nv, stream, d_model, a));
   TIMED("ddp_search", { kl::ddp_cost(nj(), batch, !settings.reference_kernels, stream, L, ddp); kl::ddp_select(nj(), batch, stream, L, ddp, kArmijoCoefficient); kl::ddp_finish(nj(), batch, stream, L, ddp); });
 }
@@ -433,61 +212,18 @@ void bpmpc_solver::run_ddp() {
 // GaussNewtonDDP::rolloutInitialTrajectory of a warm tick (k_ddp.hip k_ddp_nominal): the shifted previous FeedforwardController integrated from the
 // measured state over the new horizon (TimeTriggeredRollout, ODE45), its states interpolated onto the shooting grid as the nominal trajectory.
 void bpmpc_solver::ddp_nominal_rollout() {
-  const int N = settings.max_nodes;
-  RolloutArgs a{};
-  a.batch = batch; a.N = N; a.p_grid = buf.p_grid; a.g_nodes = buf.g_nodes; a.g_kind = buf.g_kind; a.g_time = buf.g_time;
-  a.x = buf.x; a.u = buf.u; a.K = buf.K; a.x_start = buf.p_x0;
+  RolloutArgs a = rollout_args(this);
+  a.batch = batch; a.x_start = buf.p_x0;
   a.t_start = nullptr; a.duration = -1.0;
-  a.abs_tol = rm.rollout.abs_tol; a.rel_tol = rm.rollout.rel_tol; a.time_step = rm.rollout.time_step;
   a.feedback = 0;                                      // ddp.useFeedbackPolicy false: the previous controller is its input trajectory
   a.x_end = ddp.end_x; a.u_end = ddp.end_u; a.steps = ddp.roll_steps; a.status = ddp.roll_status;
   a.rec_t = ddp.rec_t; a.rec_x = ddp.rec_x; a.rec_u = ddp.rec_u; a.rec_n = ddp.rec_n; a.rec_cap = ddp.cap;
-  double longest = 0.0;
-  for (size_t g = 0; g < grid_nodes.size(); ++g) longest = std::max(longest, node_times[g * (N + 1) + grid_nodes[g]] - node_times[g * (N + 1)]);
-  a.max_steps = (int)(rm.rollout.max_steps_per_second * std::max(1.0, longest));
   kl::rollout(rm.nj, dm.serial_legs && !force_tables, batch, stream, d_model, a);
   kl::ddp_nominal(nj(), batch, stream, launch_params(), ddp);
   HIP_CHECK(hipGetLastError());
 }
 
-// One GaitSchedule per robot on the device (include/bpmpc.h, bpmpc_gait_batch): the schedules live in state slots of a double buffer,
-// robots of one slot share their whole history (create / reset, inserts, commands, the t0 of every setup) and so their schedule and their grid.
-// bpmpc_solver_setup_gaits advances the front buffer into the back one and swaps them only when every robot was accepted.
-struct bpmpc_gait_batch {
-  bpmpc_solver* solver = nullptr;
-  int max_batch = 0, n_gaits = 0;
-  GaitLibraryView lib{};                                    // on the device, uploaded once
-  double* ev[2] = {nullptr, nullptr};                      // [slot][kRefMaxEvents]
-  int* ms[2] = {nullptr, nullptr};                         // [slot][kRefMaxEvents + 1]
-  int* meta[2] = {nullptr, nullptr};                       // [slot][kGaitMeta]
-  int front = 0;
-  int* grp_i = nullptr;                                    // per group of a setup: source slot, insert gait, command [3][max_batch]
-  double* grp_d = nullptr;                                 // ... t0, insert start, insert final [3][max_batch]
-  int* cmd_dev = nullptr;                                  // pending commands while device-side commands are outstanding
-  bool cmd_on_device = false;                              // cmd_dev, not cmd, holds the pending commands
-  std::vector<int> slot;                                   // per robot: state slot in the front buffer, < 0 = the state after create / reset
-  std::vector<int> cmd, ins_gait;                          // per robot: pending command / insert (< 0: none)
-  std::vector<double> ins_start, ins_final;
-  // restarts (bpmpc_gait_batch_restart): restart[b] != 0 - the next accepted setup advances robot b from the state after create / reset.  A device
-  // mask writes the number of its call (restart_epoch) to restart_dev[b]; entries above restart_base are read back by the next setup.  Inserts
-  // and host-side commands keep the number of device restarts recorded before them (ins_epoch, cmd_epoch): a restart drops only what came first
-  std::vector<int> restart, cmd_epoch, ins_epoch;
-  int* restart_dev = nullptr;
-  int restart_epoch = 0, restart_base = 0;
-  bool restart_on_device = false;
-  std::vector<void*> allocations;
-};
-
 namespace {
-
-int translate(const std::exception& e) {
-  set_last_error(e.what());
-  if (dynamic_cast<const DeviceError*>(&e)) return BPMPC_ERR_DEVICE;
-  if (dynamic_cast<const Unsupported*>(&e)) return BPMPC_ERR_UNSUPPORTED;
-  if (dynamic_cast<const std::invalid_argument*>(&e)) return BPMPC_ERR_INVALID_ARGUMENT;
-  if (dynamic_cast<const std::length_error*>(&e)) return BPMPC_ERR_CAPACITY;
-  return BPMPC_ERR_IO;
-}
 
 void allocate(bpmpc_solver* s) {
   const size_t B = s->settings.max_batch, N = s->settings.max_nodes, NX = s->nx, NU = s->nu, S = B * N;
@@ -579,93 +315,6 @@ template <typename T>
 void upload(bpmpc_solver* s, T* dst, const std::vector<T>& src) {
   if (!src.empty()) HIP_CHECK(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, s->stream));
 }
-// the same through the pinned arena (pin_up.reset() by the caller, once nothing of the previous call is in flight)
-inline void upload_pinned(bpmpc_solver* s, void* dst, const void* src, size_t bytes) {
-  if (bytes == 0) return;
-  void* stage = s->pin_up.take(bytes);
-  if (stage) std::memcpy(stage, src, bytes);
-  HIP_CHECK(hipMemcpyAsync(dst, stage ? stage : src, bytes, hipMemcpyHostToDevice, s->stream));
-}
-template <typename T>
-void upload_pinned(bpmpc_solver* s, T* dst, const std::vector<T>& src) { upload_pinned(s, dst, src.data(), src.size() * sizeof(T)); }
-
-// Small transfers in ONE copy.  Every hipMemcpyAsync is a DMA operation of its own on the stream (5 .. 8 us each whatever its size) and a runtime call on the
-// host: the nine uploads and five read-backs of a setup_commands and the four results of a fetch were most of what a batch = 1 MPC tick spent outside its
-// solve.  Here the pieces travel as one block through `xfer`; a kernel scatters the block to (gathers it from) the arrays the other kernels use.
-struct CopyTable {
-  static constexpr int kMax = 16;
-  void* dst[kMax]; const void* src[kMax]; unsigned words[kMax]; int n;
-};
-__global__ __launch_bounds__(256) void k_copy_table(CopyTable t) {
-  const int e = blockIdx.y;
-  const unsigned* src = static_cast<const unsigned*>(t.src[e]);
-  unsigned* dst = static_cast<unsigned*>(t.dst[e]);
-  for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < t.words[e]; i += gridDim.x * 256) dst[i] = src[i];
-}
-void launch_copy_table(bpmpc_solver* s, const CopyTable& t) {
-  if (t.n == 0) return;
-  unsigned most = 0;
-  for (int i = 0; i < t.n; ++i) most = std::max(most, t.words[i]);
-  hipLaunchKernelGGL(k_copy_table, dim3(std::min(64u, (most + 255) / 256), t.n), dim3(256), 0, s->stream, t);
-  HIP_CHECK(hipGetLastError());
-}
-struct TransferPiece { void* device; const void* host_src; void* host_dst; size_t bytes; };
-inline size_t piece_span(size_t bytes) { return (bytes + 15) & ~size_t(15); }
-// host -> device, pieces of whole 4-byte words (pin_up.reset() by the caller)
-void upload_batch(bpmpc_solver* s, const TransferPiece* pc, int n) {
-  size_t total = 0;
-  int live = 0;
-  bool words = true;
-  for (int i = 0; i < n; ++i) if (pc[i].bytes) { total += piece_span(pc[i].bytes); ++live; words = words && pc[i].bytes % 4 == 0; }
-  char* pin = (words && live >= 2 && live <= CopyTable::kMax && total <= s->xfer_cap) ? static_cast<char*>(s->pin_up.take(total)) : nullptr;
-  if (!pin) {                                             // no room in the arena (its first cycle): piece by piece
-    for (int i = 0; i < n; ++i) upload_pinned(s, pc[i].device, pc[i].host_src, pc[i].bytes);
-    return;
-  }
-  CopyTable t{};
-  size_t off = 0;
-  for (int i = 0; i < n; ++i) {
-    if (!pc[i].bytes) continue;
-    std::memcpy(pin + off, pc[i].host_src, pc[i].bytes);
-    t.dst[t.n] = pc[i].device; t.src[t.n] = s->xfer + off; t.words[t.n] = (unsigned)(pc[i].bytes / 4); ++t.n;
-    off += piece_span(pc[i].bytes);
-  }
-  HIP_CHECK(hipMemcpyAsync(s->xfer, pin, off, hipMemcpyHostToDevice, s->stream));
-  launch_copy_table(s, t);
-}
-// device -> host: enqueue() behind the work on the stream, the caller waits for the stream, finish() hands the pieces to their owners
-struct Downloads {
-  static constexpr size_t kPackLimit = size_t(512) << 10;   // larger pieces travel on their own (a packed piece is copied once more on the device)
-  struct Item { TransferPiece pc; void* pin; };
-  std::vector<Item> items;
-  void add(void* host, const void* device, size_t bytes) { if (host && bytes) items.push_back({{const_cast<void*>(device), nullptr, host, bytes}, nullptr}); }
-  void enqueue(bpmpc_solver* s) {
-    s->pin_down.reset();
-    size_t total = 0;
-    int live = 0;
-    for (const Item& it : items) if (it.pc.bytes <= kPackLimit && it.pc.bytes % 4 == 0) { total += piece_span(it.pc.bytes); ++live; }
-    char* pin = (live >= 2 && live <= CopyTable::kMax && total <= s->xfer_cap) ? static_cast<char*>(s->pin_down.take(total)) : nullptr;
-    if (pin) {
-      CopyTable t{};
-      size_t off = 0;
-      for (Item& it : items) {
-        if (!(it.pc.bytes <= kPackLimit && it.pc.bytes % 4 == 0)) continue;
-        t.dst[t.n] = s->xfer + off; t.src[t.n] = it.pc.device; t.words[t.n] = (unsigned)(it.pc.bytes / 4); ++t.n;
-        it.pin = pin + off;
-        off += piece_span(it.pc.bytes);
-      }
-      launch_copy_table(s, t);
-      HIP_CHECK(hipMemcpyAsync(pin, s->xfer, off, hipMemcpyDeviceToHost, s->stream));
-    }
-    for (Item& it : items) {
-      if (it.pin) continue;
-      void* own = it.pc.bytes <= (size_t(4) << 20) ? s->pin_down.take(it.pc.bytes) : nullptr;      // small results land in pinned memory, large ones in the caller's arrays
-      HIP_CHECK(hipMemcpyAsync(own ? own : it.pc.host_dst, it.pc.device, it.pc.bytes, hipMemcpyDeviceToHost, s->stream));
-      it.pin = own;
-    }
-  }
-  void finish() const { for (const Item& it : items) if (it.pin) std::memcpy(it.pc.host_dst, it.pin, it.pc.bytes); }
-};
 
 void copy_pairs(bpmpc_solver* s, const double* a_src, double* a_dst, size_t na, const double* b_src, double* b_dst, size_t nb, bool rearm) {
   const size_t work = (na > nb ? na : nb) / 2;
@@ -673,6 +322,23 @@ void copy_pairs(bpmpc_solver* s, const double* a_src, double* a_dst, size_t na, 
   kl::copy_pairs(grid, s->stream, a_src, a_dst, na, b_src, b_dst, nb, rearm ? s->buf.iterations : nullptr, s->buf.active, s->batch);
   HIP_CHECK(hipGetLastError());
 }
+
+// MPC_BASE::reset for the problems of `mask` (bpmpc_solver_restart): flags for the next setup, their rows of x_new into the closed-loop start
+__global__ __launch_bounds__(256) void k_restart_mark(int batch, int nx, const int* mask, int* flag, const double* x_new, double* loop_x) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= batch * nx) return;
+  const int b = i / nx;
+  if (!mask[b]) return;
+  if (i % nx == 0) flag[b] = 1;
+  if (x_new) loop_x[i] = x_new[i];
+}
+
+void check_rollout_status(bpmpc_solver* s, int* steps);
+
+}  // namespace
+
+// ---- declared in solver.h: the helpers of the device-side setups (gait_batch.hip), the refusals and the restart (controller.cpp)
+namespace bpmpc {
 
 // receding-horizon warm start: keep the previous solution and its grid on the device before anything is overwritten.  The
 // solution buffers trade places with the "previous" ones (x and u are rewritten by k_prepare, K by the Riccati sweep for every node
@@ -723,6 +389,206 @@ void finish_setup(bpmpc_solver* s, int batch, const double* warm_x, const double
   // synchronisation, and whatever follows on the handle is ordered behind these kernels by the stream
   if (!s->cold) HIP_CHECK(hipStreamSynchronize(s->stream));
 }
+
+GaitLibrary gait_library(const RobotModel& rm, const bpmpc_gait_template* gaits, int n_gaits) {
+  GaitLibrary L;
+  std::vector<int> first_mode{0}, lib_modes;
+  auto add_template = [&](const double* sw, const int* modes, int n) {
+    if (n < 0 || (n > 0 && (!sw || !modes))) throw std::invalid_argument("invalid gait template");
+    L.d.insert(L.d.end(), sw, sw + (n > 0 ? n + 1 : 0));
+    if (n == 0) L.d.push_back(0.0);
+    lib_modes.insert(lib_modes.end(), modes, modes + n);
+    first_mode.push_back((int)lib_modes.size());
+  };
+  for (int g = 0; g < n_gaits; ++g) add_template(gaits[g].switching_times, gaits[g].modes, gaits[g].n_modes);
+  const ModeTemplate& dflt = rm.default_template;
+  if (!dflt.modes.empty() && dflt.switching_times.size() != dflt.modes.size() + 1) throw std::invalid_argument("default gait template is malformed");
+  add_template(dflt.switching_times.data(), dflt.modes.data(), (int)dflt.modes.size());
+  const ModeSchedule& init = rm.initial_mode_schedule;
+  L.n_templates = n_gaits + 1; L.init_n_events = (int)init.event_times.size();
+  L.first_mode_count = first_mode.size(); L.sw_count = L.d.size(); L.mode_count = lib_modes.size();
+  L.d.insert(L.d.end(), init.event_times.begin(), init.event_times.end());
+  L.i = first_mode;
+  L.i.insert(L.i.end(), lib_modes.begin(), lib_modes.end());
+  L.i.insert(L.i.end(), init.modes.begin(), init.modes.end());
+  if (L.d.size() > (size_t)kRefLibCapacity || L.i.size() > (size_t)kRefLibCapacity) throw std::length_error("gait library exceeds the device capacity");
+  return L;
+}
+
+// argument checks shared by the device-side setups (`what` names the entry point in the messages)
+void check_device_setup(bpmpc_solver* s, const char* what, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
+                        int command_kind, bool invalid_other) {
+  const std::string w(what);
+  if (batch < 1 || batch > s->settings.max_batch) throw std::length_error("batch exceeds the solver's max_batch");
+  if (!(horizon > 0) || !t0 || !cmd_vel || invalid_other) throw std::invalid_argument(w + ": null or invalid argument");
+  if (!x0 && (!(s->has_rollout || s->loop_from_tick) || batch != s->batch))
+    throw std::invalid_argument(w + ": x0 == NULL needs a rollout of the same batch on the handle (or a controller tick)");
+  if (!x0 && !s->loop_from_tick && s->rollout_unchecked) check_rollout_status(s, nullptr);
+  if (command_kind != 0 && command_kind != 1) throw std::invalid_argument(w + ": command_kind is 0 (velocity) or 1 (goal pose)");
+}
+
+// grid settings and node-table outputs of k_reference_grids / k_gait_advance
+ReferenceGenArgs reference_args(bpmpc_solver* s, const GaitLibraryView& lib, int G, double horizon) {
+  const Buffers& bf = s->buf;
+  ReferenceGenArgs a{};
+  a.lib = lib;
+  a.n_grids = G; a.N = s->settings.max_nodes; a.horizon = horizon; a.dt = s->settings.dt > 0 ? s->settings.dt : s->rm.sqp.dt; a.dt_min = 1e-8;
+  a.lift_off_velocity = s->rm.swing.lift_off_velocity; a.touch_down_velocity = s->rm.swing.touch_down_velocity;
+  a.swing_height = s->rm.swing.swing_height; a.swing_time_scale = s->rm.swing.swing_time_scale;
+  a.kind = bf.g_kind; a.mode = bf.g_mode; a.nodes = bf.g_nodes; a.status = bf.rg_status; a.rows = bf.rg_rows;
+  a.gdt = bf.g_dt; a.gstart = bf.g_start; a.zref = bf.g_zref; a.zdref = bf.g_zdref; a.node_time = bf.g_time;
+  return a;
+}
+
+// x0 == NULL: the start states are already on the device
+void copy_loop_x0(bpmpc_solver* s, int batch, const double* x0) {
+  if (!x0) HIP_CHECK(hipMemcpyAsync(s->buf.p_x0, s->loop_from_tick ? s->tick_x : s->buf.roll_x, (size_t)batch * s->nx * sizeof(double), hipMemcpyDeviceToDevice,
+                                    s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
+}
+
+#define EXACT_FP_BODY _Pragma("clang fp contract(off)")   // first statement of a body: no fused multiply-add, as on the host (kernels/reference_device.h)
+
+__global__ __launch_bounds__(64) void k_reference_grids(ReferenceGenArgs a) {
+  EXACT_FP_BODY
+  __shared__ RefGenLds w;
+  const int g = blockIdx.x, l = threadIdx.x;
+  const double t0 = a.t0[g];
+  if (l == 0) {
+    w.rows = 12;
+    w.vrows = 4;
+    ref_build_schedule(w, a.lib, a.gait[g], a.gait_start[g], t0, a.horizon);
+    ref_lay_grid(w, a, t0);
+  }
+  __syncthreads();
+  ref_fill_tables(w, a, g, l);
+  __syncthreads();
+  if (l == 0) { a.nodes[g] = w.n_grid; a.status[g] = w.status; a.rows[g] = w.rows | (w.vrows << 8); }
+}
+
+// cmdVelToTargetTrajectories (TargetTrajectoriesPublisher.cpp:40-62 restated in reference_gen.cpp cmd_vel_to_targets)
+__global__ __launch_bounds__(64) void k_command_targets(CommandTargetArgs a) {
+  EXACT_FP_BODY
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= a.batch) return;
+  const int nx = a.nx;
+  const double* x = a.x0 + (size_t)b * nx;
+  const double* cmd = a.cmd_vel + (size_t)b * 4;
+  const double T = a.time_to_target, t_now = a.t0[b];
+  double v[3] = {0.0, 0.0, 0.0}, pose[6], t_reach;
+  if (a.goal) {            // goalToTargetTrajectories (TargetTrajectoriesPublisher.cpp:64-99 restated in reference_gen.cpp goal_to_targets)
+    pose[0] = cmd[0]; pose[1] = cmd[1]; pose[2] = a.com_height; pose[3] = cmd[3]; pose[4] = 0.0; pose[5] = 0.0;
+    const double dx = pose[0] - x[6], dy = pose[1] - x[7], dyaw = pose[3] - x[9];
+    const double tr = fabs(dyaw) / a.rotation_velocity, td = sqrt(dx * dx + dy * dy) / a.displacement_velocity;
+    t_reach = t_now + (tr < td ? td : tr);
+  } else {
+    const double yz = x[9], yy = x[10], yx = x[11];
+    const double cz = cos(yz), sz = sin(yz), cy = cos(yy), sy = sin(yy), cx = cos(yx), sx = sin(yx);
+    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
+    for (int i = 0; i < 3; ++i) v[i] = R[3 * i] * cmd[0] + R[3 * i + 1] * cmd[1] + R[3 * i + 2] * cmd[2];
+    pose[0] = x[6] + v[0] * T; pose[1] = x[7] + v[1] * T; pose[2] = a.com_height; pose[3] = x[9] + cmd[3] * T; pose[4] = 0.0; pose[5] = 0.0;
+    t_reach = t_now + T;
+  }
+  double* ts = a.tgt_t + (size_t)b * kMaxTargetPoints;
+  double* xs = a.tgt_x + (size_t)b * kMaxTargetPoints * nx;
+  for (int i = 0; i < 2 * nx; ++i) xs[i] = 0.0;
+  ts[0] = t_now;
+  ts[1] = t_reach;
+  for (int i = 0; i < 6; ++i) { xs[6 + i] = x[6 + i]; xs[nx + 6 + i] = pose[i]; }
+  xs[6 + 2] = a.com_height;
+  xs[6 + 4] = 0.0;
+  xs[6 + 5] = 0.0;
+  for (int j = 0; j < a.nj; ++j) xs[12 + j] = xs[nx + 12 + j] = a.default_joint_state[j];
+  if (!a.goal) for (int i = 0; i < 3; ++i) xs[i] = xs[nx + i] = v[i];
+  a.tgt_n[b] = 2;
+}
+
+#undef EXACT_FP_BODY
+
+// the target trajectories of the velocity commands / goal poses (k_command_targets)
+void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int command_kind, double time_to_target) {
+  Buffers& bf = s->buf;
+  CommandTargetArgs c{};
+  c.batch = batch; c.nx = s->nx; c.nj = s->rm.nj; c.time_to_target = time_to_target > 0 ? time_to_target : horizon; c.com_height = s->rm.com_height;
+  c.goal = command_kind; c.displacement_velocity = s->rm.target_displacement_velocity; c.rotation_velocity = s->rm.target_rotation_velocity;
+  for (int j = 0; j < s->rm.nj; ++j) c.default_joint_state[j] = s->rm.default_joint_state[j];
+  c.t0 = bf.p_t0; c.x0 = bf.p_x0; c.cmd_vel = bf.p_cmd; c.tgt_t = bf.p_tgt_t; c.tgt_x = bf.p_tgt_x; c.tgt_n = bf.p_tgt_n;
+  hipLaunchKernelGGL(k_command_targets, dim3((batch + 63) / 64), dim3(64), 0, s->stream, c);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Reads the grid sizes of the G grids the device just laid back (synchronises), reports a rejected grid like the host path and takes the
+// accepted ones over into the handle; the caller then runs finish_setup.  A rejected setup leaves the solver without a usable setup.
+void accept_reference_grids(bpmpc_solver* s, int batch, int G, const std::vector<int>& pgrid) {
+  const int N = s->settings.max_nodes;
+  const Buffers& bf = s->buf;
+  std::vector<int> nodes(G), status(G), rows(G), kind((size_t)G * N);
+  std::vector<double> node_times((size_t)G * (N + 1), 0.0);   // becomes the handle's copy once every grid has been accepted
+  {
+    Downloads down;
+    down.add(nodes.data(), bf.g_nodes, G * sizeof(int)); down.add(status.data(), bf.rg_status, G * sizeof(int)); down.add(rows.data(), bf.rg_rows, G * sizeof(int));
+    down.add(kind.data(), bf.g_kind, kind.size() * sizeof(int)); down.add(node_times.data(), bf.g_time, node_times.size() * sizeof(double));
+    down.enqueue(s);
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    down.finish();
+  }
+  s->has_solution = false;
+  s->batch = 0;                                           // stays unusable if a grid is rejected below
+  int nmax = 0, rows_max = 12, vrows_max = 4;
+  for (int g = 0; g < G; ++g) {
+    const int st = status[g];
+    if (st == kRefTileOrder) throw std::runtime_error("The initial time for template-tiling is not greater than the last event time.");
+    if (st == kRefCapacity) throw std::length_error("mode schedule exceeds the device capacity of " + std::to_string(kRefMaxEvents) + " events");
+    if (st == kRefGridTooLong) throw std::length_error("time grid has " + std::to_string(nodes[g]) + " intervals, solver max_nodes is " + std::to_string(N));
+    if (st >= kRefNoTouchDown) throw std::runtime_error("The time of touch-down for the last swing of the EE with ID " + std::to_string(st - kRefNoTouchDown) + " is not defined.");
+    if (st >= kRefNoTakeOff) throw std::runtime_error("The time of take-off for the first swing of the EE with ID " + std::to_string(st - kRefNoTakeOff) + " is not defined.");
+    nmax = std::max(nmax, nodes[g]);
+    rows_max = std::max(rows_max, rows[g] & 255);
+    vrows_max = std::max(vrows_max, rows[g] >> 8);
+  }
+  s->node_times.swap(node_times);
+  s->batch = batch; s->n_grids = G; s->n_nodes_max = nmax; s->cold = true; s->max_rows = rows_max; s->max_vel_rows = vrows_max;
+  s->grid_nodes = nodes; s->grid_of_problem = pgrid; s->grid_kind = kind;
+}
+
+void refuse_while_restarting(const bpmpc_solver* s, const char* what) {
+  if (s->restart_wait)
+    throw std::invalid_argument(std::string(what) + ": a restart (bpmpc_solver_restart) waits for the next setup and run; the policy of the previous episode is gone");
+}
+
+void check_restart(const bpmpc_solver* s, int batch) {
+  if (s->is_ddp()) throw Unsupported("restart: not implemented for the DDP solver");
+  if (s->batch < 1 || batch != s->batch) throw std::invalid_argument("restart: batch must equal the batch of the last setup");
+}
+
+void check_policy(const bpmpc_solver* s) {
+  if (s->is_ddp())
+    throw Unsupported("controller tick / evaluate_policy: the DDP solution is a FeedforwardController on the time points of its own roll-out, not on the shooting grid "
+                      "the policy is interpolated on");
+  refuse_while_restarting(s, "controller tick / evaluate_policy");
+  if (s->batch < 1 || !s->has_solution) throw std::invalid_argument("controller tick / evaluate_policy needs a completed bpmpc_solver_run since the last setup");
+  if (s->feedback() && !s->buf.K) throw std::invalid_argument("controller tick / evaluate_policy: the feedback policy needs the gains (return_gains with reference kernels)");
+}
+
+void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device) {
+  check_restart(s, batch);
+  const size_t NX = s->nx;
+  if (!on_device) {
+    HIP_CHECK(hipMemcpyAsync(s->restart_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
+    if (x_new) HIP_CHECK(hipMemcpyAsync(s->restart_x, x_new, (size_t)batch * NX * sizeof(double), hipMemcpyHostToDevice, s->stream));
+    mask = s->restart_mask;
+    if (x_new) x_new = s->restart_x;
+  }
+  // the start that setup(x0 = NULL) reads (copy_loop_x0); neither a tick nor a rollout can replace it before that setup (both are refused)
+  double* loop_x = s->loop_from_tick ? s->tick_x : s->buf.roll_x;
+  hipLaunchKernelGGL(k_restart_mark, dim3((unsigned)((batch * NX + 255) / 256)), dim3(256), 0, s->stream, batch, (int)NX, mask, s->restart_flag, x_new, loop_x);
+  HIP_CHECK(hipGetLastError());
+  s->restart_pending = s->restart_wait = true;
+  if (!on_device) HIP_CHECK(hipStreamSynchronize(s->stream));   // the caller's host arrays
+}
+
+}  // namespace bpmpc
+
+namespace {
 
 void setup(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_mode_schedule* schedules,
            int n_schedules, const bpmpc_target* targets, const double* warm_x, const double* warm_u, bool from_previous = false) {
@@ -829,124 +695,6 @@ void setup(bpmpc_solver* s, int batch, double horizon, const double* t0, const d
   finish_setup(s, batch, warm_x, warm_u, from_previous);
 }
 
-void check_rollout_status(bpmpc_solver* s, int* steps);
-
-// Host image of the device gait library: the passed templates, then defaultModeSequenceTemplate; initialModeSchedule behind them
-struct GaitLibrary {
-  std::vector<double> d;
-  std::vector<int> i;
-  int n_templates = 0, init_n_events = 0;
-  size_t first_mode_count = 0, sw_count = 0, mode_count = 0;
-  GaitLibraryView view(const double* dev_d, const int* dev_i, double transition_stance_time) const {
-    GaitLibraryView v{};
-    v.switching = dev_d; v.first_mode = dev_i; v.modes = dev_i + first_mode_count; v.n_templates = n_templates;
-    v.init_events = dev_d + sw_count; v.init_modes = dev_i + first_mode_count + mode_count; v.init_n_events = init_n_events;
-    v.transition_stance_time = transition_stance_time;
-    return v;
-  }
-};
-GaitLibrary gait_library(const RobotModel& rm, const bpmpc_gait_template* gaits, int n_gaits) {
-  GaitLibrary L;
-  std::vector<int> first_mode{0}, lib_modes;
-  auto add_template = [&](const double* sw, const int* modes, int n) {
-    if (n < 0 || (n > 0 && (!sw || !modes))) throw std::invalid_argument("invalid gait template");
-    L.d.insert(L.d.end(), sw, sw + (n > 0 ? n + 1 : 0));
-    if (n == 0) L.d.push_back(0.0);
-    lib_modes.insert(lib_modes.end(), modes, modes + n);
-    first_mode.push_back((int)lib_modes.size());
-  };
-  for (int g = 0; g < n_gaits; ++g) add_template(gaits[g].switching_times, gaits[g].modes, gaits[g].n_modes);
-  const ModeTemplate& dflt = rm.default_template;
-  if (!dflt.modes.empty() && dflt.switching_times.size() != dflt.modes.size() + 1) throw std::invalid_argument("default gait template is malformed");
-  add_template(dflt.switching_times.data(), dflt.modes.data(), (int)dflt.modes.size());
-  const ModeSchedule& init = rm.initial_mode_schedule;
-  L.n_templates = n_gaits + 1; L.init_n_events = (int)init.event_times.size();
-  L.first_mode_count = first_mode.size(); L.sw_count = L.d.size(); L.mode_count = lib_modes.size();
-  L.d.insert(L.d.end(), init.event_times.begin(), init.event_times.end());
-  L.i = first_mode;
-  L.i.insert(L.i.end(), lib_modes.begin(), lib_modes.end());
-  L.i.insert(L.i.end(), init.modes.begin(), init.modes.end());
-  if (L.d.size() > (size_t)kRefLibCapacity || L.i.size() > (size_t)kRefLibCapacity) throw std::length_error("gait library exceeds the device capacity");
-  return L;
-}
-
-// argument checks shared by the device-side setups (`what` names the entry point in the messages)
-void check_device_setup(bpmpc_solver* s, const char* what, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
-                        int command_kind, bool invalid_other) {
-  const std::string w(what);
-  if (batch < 1 || batch > s->settings.max_batch) throw std::length_error("batch exceeds the solver's max_batch");
-  if (!(horizon > 0) || !t0 || !cmd_vel || invalid_other) throw std::invalid_argument(w + ": null or invalid argument");
-  if (!x0 && (!(s->has_rollout || s->loop_from_tick) || batch != s->batch))
-    throw std::invalid_argument(w + ": x0 == NULL needs a rollout of the same batch on the handle (or a controller tick)");
-  if (!x0 && !s->loop_from_tick && s->rollout_unchecked) check_rollout_status(s, nullptr);
-  if (command_kind != 0 && command_kind != 1) throw std::invalid_argument(w + ": command_kind is 0 (velocity) or 1 (goal pose)");
-}
-
-// grid settings and node-table outputs of k_reference_grids / k_gait_advance
-ReferenceGenArgs reference_args(bpmpc_solver* s, const GaitLibraryView& lib, int G, double horizon) {
-  const Buffers& bf = s->buf;
-  ReferenceGenArgs a{};
-  a.lib = lib;
-  a.n_grids = G; a.N = s->settings.max_nodes; a.horizon = horizon; a.dt = s->settings.dt > 0 ? s->settings.dt : s->rm.sqp.dt; a.dt_min = 1e-8;
-  a.lift_off_velocity = s->rm.swing.lift_off_velocity; a.touch_down_velocity = s->rm.swing.touch_down_velocity;
-  a.swing_height = s->rm.swing.swing_height; a.swing_time_scale = s->rm.swing.swing_time_scale;
-  a.kind = bf.g_kind; a.mode = bf.g_mode; a.nodes = bf.g_nodes; a.status = bf.rg_status; a.rows = bf.rg_rows;
-  a.gdt = bf.g_dt; a.gstart = bf.g_start; a.zref = bf.g_zref; a.zdref = bf.g_zdref; a.node_time = bf.g_time;
-  return a;
-}
-
-// x0 == NULL: the start states are already on the device
-void copy_loop_x0(bpmpc_solver* s, int batch, const double* x0) {
-  if (!x0) HIP_CHECK(hipMemcpyAsync(s->buf.p_x0, s->loop_from_tick ? s->tick_x : s->buf.roll_x, (size_t)batch * s->nx * sizeof(double), hipMemcpyDeviceToDevice,
-                                    s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
-}
-
-// the target trajectories of the velocity commands / goal poses (k_command_targets)
-void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int command_kind, double time_to_target) {
-  Buffers& bf = s->buf;
-  CommandTargetArgs c{};
-  c.batch = batch; c.nx = s->nx; c.nj = s->rm.nj; c.time_to_target = time_to_target > 0 ? time_to_target : horizon; c.com_height = s->rm.com_height;
-  c.goal = command_kind; c.displacement_velocity = s->rm.target_displacement_velocity; c.rotation_velocity = s->rm.target_rotation_velocity;
-  for (int j = 0; j < s->rm.nj; ++j) c.default_joint_state[j] = s->rm.default_joint_state[j];
-  c.t0 = bf.p_t0; c.x0 = bf.p_x0; c.cmd_vel = bf.p_cmd; c.tgt_t = bf.p_tgt_t; c.tgt_x = bf.p_tgt_x; c.tgt_n = bf.p_tgt_n;
-  hipLaunchKernelGGL(k_command_targets, dim3((batch + 63) / 64), dim3(64), 0, s->stream, c);
-  HIP_CHECK(hipGetLastError());
-}
-
-// Reads the grid sizes of the G grids the device just laid back (synchronises), reports a rejected grid like the host path and takes the
-// accepted ones over into the handle; the caller then runs finish_setup.  A rejected setup leaves the solver without a usable setup.
-void accept_reference_grids(bpmpc_solver* s, int batch, int G, const std::vector<int>& pgrid) {
-  const int N = s->settings.max_nodes;
-  const Buffers& bf = s->buf;
-  std::vector<int> nodes(G), status(G), rows(G), kind((size_t)G * N);
-  std::vector<double> node_times((size_t)G * (N + 1), 0.0);   // becomes the handle's copy once every grid has been accepted
-  {
-    Downloads down;
-    down.add(nodes.data(), bf.g_nodes, G * sizeof(int)); down.add(status.data(), bf.rg_status, G * sizeof(int)); down.add(rows.data(), bf.rg_rows, G * sizeof(int));
-    down.add(kind.data(), bf.g_kind, kind.size() * sizeof(int)); down.add(node_times.data(), bf.g_time, node_times.size() * sizeof(double));
-    down.enqueue(s);
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    down.finish();
-  }
-  s->has_solution = false;
-  s->batch = 0;                                           // stays unusable if a grid is rejected below
-  int nmax = 0, rows_max = 12, vrows_max = 4;
-  for (int g = 0; g < G; ++g) {
-    const int st = status[g];
-    if (st == kRefTileOrder) throw std::runtime_error("The initial time for template-tiling is not greater than the last event time.");
-    if (st == kRefCapacity) throw std::length_error("mode schedule exceeds the device capacity of " + std::to_string(kRefMaxEvents) + " events");
-    if (st == kRefGridTooLong) throw std::length_error("time grid has " + std::to_string(nodes[g]) + " intervals, solver max_nodes is " + std::to_string(N));
-    if (st >= kRefNoTouchDown) throw std::runtime_error("The time of touch-down for the last swing of the EE with ID " + std::to_string(st - kRefNoTouchDown) + " is not defined.");
-    if (st >= kRefNoTakeOff) throw std::runtime_error("The time of take-off for the first swing of the EE with ID " + std::to_string(st - kRefNoTakeOff) + " is not defined.");
-    nmax = std::max(nmax, nodes[g]);
-    rows_max = std::max(rows_max, rows[g] & 255);
-    vrows_max = std::max(vrows_max, rows[g] >> 8);
-  }
-  s->node_times.swap(node_times);
-  s->batch = batch; s->n_grids = G; s->n_nodes_max = nmax; s->cold = true; s->max_rows = rows_max; s->max_vel_rows = vrows_max;
-  s->grid_nodes = nodes; s->grid_of_problem = pgrid; s->grid_kind = kind;
-}
-
 // Device-side reference generation: the same tables as setup(), built on the GPU from gait
 // templates and velocity commands; the host only groups problems by (t0, gait, gait start) and reads the grid sizes back.
 void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_gait_template* gaits, int n_gaits,
@@ -990,214 +738,6 @@ void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0
   launch_command_targets(s, batch, horizon, command_kind, time_to_target);
   accept_reference_grids(s, batch, G, pgrid);
   finish_setup(s, batch, nullptr, nullptr, from_previous);
-}
-
-void check_gait_batch(const bpmpc_gait_batch* g, int batch, const int* gait, bool host_gaits) {
-  if (!g) throw std::invalid_argument("null gait batch handle");
-  if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("batch exceeds the gait batch's max_batch");
-  if (!gait) throw std::invalid_argument("null gait array");
-  if (host_gaits)
-    for (int b = 0; b < batch; ++b)
-      if (gait[b] >= g->n_gaits) throw std::invalid_argument("gait index refers to a template that was not passed");
-}
-
-void gait_batch_reset(bpmpc_gait_batch* g) {
-  std::fill(g->slot.begin(), g->slot.end(), -1);
-  std::fill(g->cmd.begin(), g->cmd.end(), -1);
-  std::fill(g->ins_gait.begin(), g->ins_gait.end(), -1);
-  std::fill(g->ins_start.begin(), g->ins_start.end(), 0.0);
-  std::fill(g->ins_final.begin(), g->ins_final.end(), 0.0);
-  g->cmd_on_device = false;
-  std::fill(g->restart.begin(), g->restart.end(), 0);
-  g->restart_base = g->restart_epoch;
-  g->restart_on_device = false;
-}
-
-// the pending commands back on the host (synchronises; only after a device-side command)
-void gait_commands_to_host(bpmpc_gait_batch* g) {
-  if (!g->cmd_on_device) return;
-  bpmpc_solver* s = g->solver;
-  HIP_CHECK(hipMemcpyAsync(g->cmd.data(), g->cmd_dev, g->max_batch * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  HIP_CHECK(hipStreamSynchronize(s->stream));
-  g->cmd_on_device = false;
-  std::fill(g->cmd_epoch.begin(), g->cmd_epoch.end(), g->restart_epoch);   // k_gait_restart already dropped what the device restarts drop
-}
-
-// the pending device restarts back on the host (synchronises; only after a device mask): each drops the insert / host command recorded before it
-void gait_restarts_to_host(bpmpc_gait_batch* g) {
-  if (!g->restart_on_device) return;
-  bpmpc_solver* s = g->solver;
-  std::vector<int> epoch(g->max_batch);
-  HIP_CHECK(hipMemcpyAsync(epoch.data(), g->restart_dev, g->max_batch * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  HIP_CHECK(hipStreamSynchronize(s->stream));
-  for (int b = 0; b < g->max_batch; ++b) {
-    if (epoch[b] <= g->restart_base) continue;
-    g->restart[b] = 1;
-    if (g->cmd_epoch[b] < epoch[b]) g->cmd[b] = -1;
-    if (g->ins_epoch[b] < epoch[b]) g->ins_gait[b] = -1;
-  }
-  g->restart_base = g->restart_epoch;
-  g->restart_on_device = false;
-}
-
-__global__ __launch_bounds__(256) void k_gait_restart(int batch, const int* mask, int epoch, int* restart, int* cmd) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= batch || !mask[b]) return;
-  restart[b] = epoch;
-  if (cmd) cmd[b] = -1;                                   // device-side pending commands are dropped in stream order
-}
-
-void gait_batch_restart(bpmpc_gait_batch* g, int batch, const int* mask, bool on_device) {
-  if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("bpmpc_gait_batch_restart: batch exceeds the gait batch's max_batch");
-  bpmpc_solver* s = g->solver;
-  if (!on_device) {
-    gait_commands_to_host(g);
-    gait_restarts_to_host(g);
-    for (int b = 0; b < batch; ++b)
-      if (mask[b]) { g->restart[b] = 1; g->cmd[b] = -1; g->ins_gait[b] = -1; }
-    return;
-  }
-  ++g->restart_epoch;
-  hipLaunchKernelGGL(k_gait_restart, dim3((batch + 255) / 256), dim3(256), 0, s->stream, batch, mask, g->restart_epoch, g->restart_dev,
-                     g->cmd_on_device ? g->cmd_dev : nullptr);
-  HIP_CHECK(hipGetLastError());
-  g->restart_on_device = true;
-}
-
-void gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, bool on_device) {
-  check_gait_batch(g, batch, gait, !on_device);
-  bpmpc_solver* s = g->solver;
-  if (!on_device) {
-    gait_commands_to_host(g);
-    for (int b = 0; b < batch; ++b) if (gait[b] >= 0) { g->cmd[b] = gait[b]; g->cmd_epoch[b] = g->restart_epoch; }
-    return;
-  }
-  if (!g->cmd_on_device) {                                // the device copy takes over: it starts from the host's pending commands
-    if (g->restart_on_device && std::any_of(g->cmd.begin(), g->cmd.end(), [](int c) { return c >= 0; })) gait_restarts_to_host(g);   // ... as a restart left them
-    if (std::all_of(g->cmd.begin(), g->cmd.end(), [](int c) { return c < 0; })) {
-      HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)g->cmd_dev, -1, g->max_batch, s->stream));
-    } else {
-      HIP_CHECK(hipMemcpyAsync(g->cmd_dev, g->cmd.data(), g->max_batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
-      HIP_CHECK(hipStreamSynchronize(s->stream));
-    }
-  }
-  hipLaunchKernelGGL(k_gait_command, dim3((batch + 255) / 256), dim3(256), 0, s->stream, batch, gait, g->cmd_dev);
-  HIP_CHECK(hipGetLastError());
-  g->cmd_on_device = true;
-}
-
-// GaitSchedule state of one robot after the last setup (synchronises)
-void gait_batch_mode_schedule(bpmpc_gait_batch* g, int robot, double* event_times, int* modes, int capacity, int* n_events) {
-  if (!g || !event_times || !modes || !n_events) throw std::invalid_argument("bpmpc_gait_batch_mode_schedule: null argument");
-  if (robot < 0 || robot >= g->max_batch) throw std::invalid_argument("bpmpc_gait_batch_mode_schedule: robot out of range");
-  const int slot = g->slot[robot];
-  if (slot < 0) {
-    const ModeSchedule& init = g->solver->rm.initial_mode_schedule;
-    if ((int)init.modes.size() > capacity || (int)init.event_times.size() > capacity) throw std::length_error("mode schedule capacity too small");
-    std::copy(init.event_times.begin(), init.event_times.end(), event_times);
-    std::copy(init.modes.begin(), init.modes.end(), modes);
-    *n_events = (int)init.event_times.size();
-    return;
-  }
-  bpmpc_solver* s = g->solver;
-  int meta[kGaitMeta];
-  HIP_CHECK(hipMemcpyAsync(meta, g->meta[g->front] + (size_t)slot * kGaitMeta, sizeof(meta), hipMemcpyDeviceToHost, s->stream));
-  HIP_CHECK(hipStreamSynchronize(s->stream));
-  if (meta[0] > capacity || meta[1] > capacity) throw std::length_error("mode schedule capacity too small");
-  HIP_CHECK(hipMemcpyAsync(event_times, g->ev[g->front] + (size_t)slot * kRefMaxEvents, meta[0] * sizeof(double), hipMemcpyDeviceToHost, s->stream));
-  HIP_CHECK(hipMemcpyAsync(modes, g->ms[g->front] + (size_t)slot * (kRefMaxEvents + 1), meta[1] * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-  HIP_CHECK(hipStreamSynchronize(s->stream));
-  *n_events = meta[0];
-}
-
-// setup_commands with the schedules of the gait batch: the pending inserts, getModeSchedule(t0 - H, t0 + 2 H) as the window of this setup,
-// then the pending commands at (t0 + H, H) - per group of robots with one history, in k_gait_advance
-void setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
-                 int command_kind, double time_to_target, bool from_previous) {
-  if (!g || g->solver != s) throw std::invalid_argument("setup_gaits: the gait batch belongs to another solver");
-  if (batch < 1 || batch > g->max_batch) throw std::invalid_argument("setup_gaits: batch exceeds the gait batch's max_batch");
-  check_device_setup(s, "setup_gaits", batch, horizon, t0, x0, cmd_vel, command_kind, false);
-  gait_commands_to_host(g);
-  gait_restarts_to_host(g);
-  for (int b = 0; b < batch; ++b)
-    if (g->cmd[b] >= g->n_gaits) throw std::invalid_argument("setup_gaits: a gait command refers to a template that was not passed");
-  const int NX = s->nx, B = g->max_batch;
-  // groups: robots of the batch with one (history, t0, pending insert, pending command) advance together; robots behind the batch
-  // keep their state (one group per slot in use)
-  std::vector<int> pgrid(batch), new_slot(B, -1), src, ins_g, cmd;
-  std::vector<double> gt0, ins_s, ins_f;
-  {
-    std::map<std::tuple<int, double, int, double, double, int>, int> seen;
-    for (int b = 0; b < batch; ++b) {
-      const bool ins = g->ins_gait[b] >= 0;
-      auto key = std::make_tuple(g->restart[b] ? -1 : g->slot[b], t0[b], ins ? g->ins_gait[b] : -1, ins ? g->ins_start[b] : 0.0, ins ? g->ins_final[b] : 0.0, g->cmd[b] < 0 ? -1 : g->cmd[b]);
-      auto it = seen.find(key);
-      if (it == seen.end()) {
-        it = seen.emplace(key, (int)src.size()).first;
-        src.push_back(std::get<0>(key)); gt0.push_back(t0[b]); ins_g.push_back(std::get<2>(key)); ins_s.push_back(std::get<3>(key)); ins_f.push_back(std::get<4>(key));
-        cmd.push_back(std::get<5>(key));
-      }
-      pgrid[b] = new_slot[b] = it->second;
-    }
-  }
-  const int G = (int)src.size();
-  {
-    std::map<int, int> kept;
-    for (int b = batch; b < B; ++b) {
-      if (g->slot[b] < 0) continue;
-      auto it = kept.find(g->slot[b]);
-      if (it == kept.end()) {
-        it = kept.emplace(g->slot[b], (int)src.size()).first;
-        src.push_back(g->slot[b]); gt0.push_back(0.0); ins_g.push_back(-1); ins_s.push_back(0.0); ins_f.push_back(0.0); cmd.push_back(-1);
-      }
-      new_slot[b] = it->second;
-    }
-  }
-  const int groups = (int)src.size();
-  std::vector<int> gi(3 * (size_t)B, -1);
-  std::vector<double> gd(3 * (size_t)B, 0.0);
-  std::copy(src.begin(), src.end(), gi.begin()); std::copy(ins_g.begin(), ins_g.end(), gi.begin() + B); std::copy(cmd.begin(), cmd.end(), gi.begin() + 2 * B);
-  std::copy(gt0.begin(), gt0.end(), gd.begin()); std::copy(ins_s.begin(), ins_s.end(), gd.begin() + B); std::copy(ins_f.begin(), ins_f.end(), gd.begin() + 2 * B);
-  if (from_previous) preserve_previous(s, batch, false);
-  Buffers& bf = s->buf;
-  s->pin_up.reset();                                      // the previous call waited for its transfers (the synchronisation below)
-  {
-    const TransferPiece up[6] = {{g->grp_i, gi.data(), nullptr, gi.size() * sizeof(int)}, {g->grp_d, gd.data(), nullptr, gd.size() * sizeof(double)},
-                                 {bf.p_grid, pgrid.data(), nullptr, pgrid.size() * sizeof(int)}, {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)},
-                                 {bf.p_cmd, cmd_vel, nullptr, (size_t)batch * 4 * sizeof(double)}, {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
-    upload_batch(s, up, 6);
-  }
-  GaitAdvanceArgs a{};
-  a.ref = reference_args(s, g->lib, G, horizon);
-  a.ref.t0 = g->grp_d;
-  a.n_advance = G;
-  a.src = g->grp_i; a.insert_gait = g->grp_i + B; a.command = g->grp_i + 2 * B;
-  a.insert_start = g->grp_d + B; a.insert_final = g->grp_d + 2 * B;
-  const int f = g->front, k = 1 - f;
-  a.ev_in = g->ev[f]; a.ms_in = g->ms[f]; a.meta_in = g->meta[f];
-  a.ev_out = g->ev[k]; a.ms_out = g->ms[k]; a.meta_out = g->meta[k];
-  copy_loop_x0(s, batch, x0);
-  hipLaunchKernelGGL(k_gait_advance, dim3(groups), dim3(64), 0, s->stream, a);
-  HIP_CHECK(hipGetLastError());
-  launch_command_targets(s, batch, horizon, command_kind, time_to_target);
-  accept_reference_grids(s, batch, G, pgrid);
-  // every robot was accepted: the new schedules become the front buffer, the applied inserts and commands are no longer pending
-  g->front = k;
-  g->slot.swap(new_slot);
-  std::fill(g->cmd.begin(), g->cmd.begin() + batch, -1);
-  std::fill(g->ins_gait.begin(), g->ins_gait.begin() + batch, -1);
-  std::fill(g->restart.begin(), g->restart.begin() + batch, 0);
-  finish_setup(s, batch, nullptr, nullptr, from_previous);
-}
-
-void refuse_while_restarting(const bpmpc_solver* s, const char* what) {
-  if (s->restart_wait)
-    throw std::invalid_argument(std::string(what) + ": a restart (bpmpc_solver_restart) waits for the next setup and run; the policy of the previous episode is gone");
-}
-
-void check_restart(const bpmpc_solver* s, int batch) {
-  if (s->is_ddp()) throw Unsupported("restart: not implemented for the DDP solver");
-  if (s->batch < 1 || batch != s->batch) throw std::invalid_argument("restart: batch must equal the batch of the last setup");
 }
 
 // reads the per-problem flags of the last rollout back (synchronises) and reports failures like the reference's integrator does
@@ -1248,33 +788,6 @@ void rollout(bpmpc_solver* s, const double* t_start, const double* x_start, doub
   check_rollout_status(s, steps);
   if (x_end) HIP_CHECK(hipMemcpy(x_end, bf.roll_x, (size_t)B * NX * sizeof(double), hipMemcpyDeviceToHost));
   if (u_end) HIP_CHECK(hipMemcpy(u_end, bf.roll_u, (size_t)B * NU * sizeof(double), hipMemcpyDeviceToHost));
-}
-
-// MPC_BASE::reset for the problems of `mask` (bpmpc_solver_restart): flags for the next setup, their rows of x_new into the closed-loop start
-__global__ __launch_bounds__(256) void k_restart_mark(int batch, int nx, const int* mask, int* flag, const double* x_new, double* loop_x) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= batch * nx) return;
-  const int b = i / nx;
-  if (!mask[b]) return;
-  if (i % nx == 0) flag[b] = 1;
-  if (x_new) loop_x[i] = x_new[i];
-}
-
-void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device) {
-  check_restart(s, batch);
-  const size_t NX = s->nx;
-  if (!on_device) {
-    HIP_CHECK(hipMemcpyAsync(s->restart_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    if (x_new) HIP_CHECK(hipMemcpyAsync(s->restart_x, x_new, (size_t)batch * NX * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    mask = s->restart_mask;
-    if (x_new) x_new = s->restart_x;
-  }
-  // the start that setup(x0 = NULL) reads (copy_loop_x0); neither a tick nor a rollout can replace it before that setup (both are refused)
-  double* loop_x = s->loop_from_tick ? s->tick_x : s->buf.roll_x;
-  hipLaunchKernelGGL(k_restart_mark, dim3((unsigned)((batch * NX + 255) / 256)), dim3(256), 0, s->stream, batch, (int)NX, mask, s->restart_flag, x_new, loop_x);
-  HIP_CHECK(hipGetLastError());
-  s->restart_pending = s->restart_wait = true;
-  if (!on_device) HIP_CHECK(hipStreamSynchronize(s->stream));   // the caller's host arrays
 }
 
 void reset(bpmpc_solver* s) {
@@ -1340,7 +853,7 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
     return BPMPC_ERR_NO_DEVICE;
   }
   std::unique_ptr<bpmpc_solver> s(new bpmpc_solver);
-  try {
+  const int rc = guarded(BPMPC_ERR_IO, [&]() -> int {
     s->rm = model_of(model);
     if (s->rm.nj != 10 && s->rm.nj != 12) { set_last_error("only 10- and 12-joint bipeds are instantiated"); return BPMPC_ERR_UNSUPPORTED; }
     if (settings->reg_prim != 0.0 && settings->reference_kernels) { set_last_error("reg_prim is implemented by the fast kernels only"); return BPMPC_ERR_UNSUPPORTED; }
@@ -1402,11 +915,9 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
                                settings->sqp_iterations > 0 ? settings->sqp_iterations : q.sqp_iteration};
     allocate(s.get());
     HIP_CHECK(hipStreamSynchronize(s->stream));
-  } catch (const std::exception& e) {
-    const int rc = translate(e);
-    bpmpc_solver_destroy(s.release());
-    return rc;
-  }
+    return BPMPC_OK;
+  });
+  if (rc != BPMPC_OK) { bpmpc_solver_destroy(s.release()); return rc; }
   *out = s.release();
   return BPMPC_OK;
 }
@@ -1426,120 +937,41 @@ void bpmpc_solver_destroy(bpmpc_solver* s) {
   delete s;
 }
 
-#define API_GUARD(solver, ...)                                                                    \
-  if (!(solver)) { set_last_error("null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }      \
-  try { HIP_CHECK(hipSetDevice((solver)->settings.device)); __VA_ARGS__; }                               \
-  catch (const std::exception& e) {                                                               \
-    /* a call that threw between enqueueing copies from / to the pinned arenas and its own synchronisation: wait for them before the */ \
-    /* next call recycles (or frees) that memory */                                               \
-    if ((solver)->stream) (void)hipStreamSynchronize((solver)->stream);                           \
-    if ((solver)->producer_stream) (void)hipStreamSynchronize((solver)->producer_stream);         \
-    return translate(e);                                                                          \
-  }                                                                                               \
-  return BPMPC_OK;
-
 int bpmpc_solver_setup(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_mode_schedule* schedules,
                        int n_schedules, const bpmpc_target* targets, const double* warm_x, const double* warm_u) {
-  API_GUARD(s, setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, warm_x, warm_u))
+  return guarded(s, [&] { setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, warm_x, warm_u); });
 }
 int bpmpc_solver_setup_from_previous(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0,
                                      const bpmpc_mode_schedule* schedules, int n_schedules, const bpmpc_target* targets) {
-  API_GUARD(s, setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, nullptr, nullptr, true))
+  return guarded(s, [&] { setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, nullptr, nullptr, true); });
 }
-int bpmpc_solver_reset(bpmpc_solver* s) { API_GUARD(s, reset(s)) }
+int bpmpc_solver_reset(bpmpc_solver* s) { return guarded(s, [&] { reset(s); }); }
 int bpmpc_solver_restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, int inputs_on_device) {
   if (!mask) { set_last_error("bpmpc_solver_restart: null mask"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  API_GUARD(s, restart(s, batch, mask, x_new, inputs_on_device != 0))
+  return guarded(s, [&] { restart(s, batch, mask, x_new, inputs_on_device != 0); });
 }
 int bpmpc_solver_run(bpmpc_solver* s) {
-  API_GUARD(s, { if (s->batch < 1) throw std::invalid_argument("bpmpc_solver_run before bpmpc_solver_setup"); s->run_iterations(); })
+  return guarded(s, [&] {
+    if (s->batch < 1) throw std::invalid_argument("bpmpc_solver_run before bpmpc_solver_setup");
+    s->run_iterations();
+  });
 }
-int bpmpc_solver_sync(bpmpc_solver* s) { API_GUARD(s, { HIP_CHECK(hipStreamSynchronize(s->stream)); s->collect_timers(); }) }
+int bpmpc_solver_sync(bpmpc_solver* s) {
+  return guarded(s, [&] {
+    HIP_CHECK(hipStreamSynchronize(s->stream));
+    s->collect_timers();
+  });
+}
 int bpmpc_solver_fetch(bpmpc_solver* s, double* out_t, double* out_x, double* out_u, double* out_K, bpmpc_stats* stats) {
-  API_GUARD(s, fetch(s, out_t, out_x, out_u, out_K, stats))
+  return guarded(s, [&] { fetch(s, out_t, out_x, out_u, out_K, stats); });
 }
 int bpmpc_solver_setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_gait_template* gaits,
                                 int n_gaits, const int* gait_of_problem, const double* gait_start, const double* cmd_vel, int command_kind,
                                 double time_to_target, int from_previous) {
-  API_GUARD(s, { setup_commands(s, batch, horizon, t0, x0, gaits, n_gaits, gait_of_problem, gait_start, cmd_vel, command_kind, time_to_target, from_previous != 0); })
-}
-int bpmpc_solver_setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon, const double* t0, const double* x0, const double* cmd_vel,
-                             int command_kind, double time_to_target, int from_previous) {
-  API_GUARD(s, { setup_gaits(s, g, batch, horizon, t0, x0, cmd_vel, command_kind, time_to_target, from_previous != 0); })
-}
-int bpmpc_gait_batch_create(bpmpc_solver* s, const bpmpc_gait_template* gaits, int n_gaits, bpmpc_gait_batch** out) {
-  if (!out) { set_last_error("bpmpc_gait_batch_create: null output"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  *out = nullptr;
-  if (!s) { set_last_error("bpmpc_gait_batch_create: null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  std::unique_ptr<bpmpc_gait_batch> g(new bpmpc_gait_batch);
-  try {
-    if (n_gaits < 0 || (n_gaits > 0 && !gaits)) throw std::invalid_argument("bpmpc_gait_batch_create: null or invalid gait templates");
-    HIP_CHECK(hipSetDevice(s->settings.device));
-    const GaitLibrary lib = gait_library(s->rm, gaits, n_gaits);
-    const int B = s->settings.max_batch;
-    g->solver = s; g->max_batch = B; g->n_gaits = n_gaits;
-    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); g->allocations.push_back(p); return p; };
-    double* lib_d = static_cast<double*>(alloc(lib.d.size() * sizeof(double)));
-    int* lib_i = static_cast<int*>(alloc(lib.i.size() * sizeof(int)));
-    for (int k = 0; k < 2; ++k) {
-      g->ev[k] = static_cast<double*>(alloc((size_t)B * kRefMaxEvents * sizeof(double)));
-      g->ms[k] = static_cast<int*>(alloc((size_t)B * (kRefMaxEvents + 1) * sizeof(int)));
-      g->meta[k] = static_cast<int*>(alloc((size_t)B * kGaitMeta * sizeof(int)));
-    }
-    g->grp_i = static_cast<int*>(alloc(3 * (size_t)B * sizeof(int)));
-    g->grp_d = static_cast<double*>(alloc(3 * (size_t)B * sizeof(double)));
-    g->cmd_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
-    g->restart_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
-    HIP_CHECK(hipMemsetAsync(g->restart_dev, 0, (size_t)B * sizeof(int), s->stream));
-    HIP_CHECK(hipMemcpyAsync(lib_d, lib.d.data(), lib.d.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    HIP_CHECK(hipMemcpyAsync(lib_i, lib.i.data(), lib.i.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    HIP_CHECK(hipStreamSynchronize(s->stream));
-    g->lib = lib.view(lib_d, lib_i, s->rm.phase_transition_stance_time);
-    g->slot.resize(B); g->cmd.resize(B); g->ins_gait.resize(B); g->ins_start.resize(B); g->ins_final.resize(B);
-    g->restart.resize(B); g->cmd_epoch.resize(B); g->ins_epoch.resize(B);
-    gait_batch_reset(g.get());
-  } catch (const std::exception& e) {
-    const int rc = translate(e);
-    bpmpc_gait_batch_destroy(g.release());
-    return rc;
-  }
-  *out = g.release();
-  return BPMPC_OK;
-}
-void bpmpc_gait_batch_destroy(bpmpc_gait_batch* g) {
-  if (!g) return;
-  if (g->solver && g->solver->stream) (void)hipStreamSynchronize(g->solver->stream);
-  for (void* p : g->allocations) (void)hipFree(p);
-  delete g;
-}
-int bpmpc_gait_batch_reset(bpmpc_gait_batch* g) {
-  if (!g) { set_last_error("bpmpc_gait_batch_reset: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  gait_batch_reset(g);
-  return BPMPC_OK;
-}
-int bpmpc_gait_batch_insert(bpmpc_gait_batch* g, int batch, const int* gait, const double* start_time, const double* final_time) {
-  try {
-    check_gait_batch(g, batch, gait, true);
-    if (!start_time || !final_time) throw std::invalid_argument("bpmpc_gait_batch_insert: null start or final times");
-    for (int b = 0; b < batch; ++b)
-      if (gait[b] >= 0) { g->ins_gait[b] = gait[b]; g->ins_start[b] = start_time[b]; g->ins_final[b] = final_time[b]; g->ins_epoch[b] = g->restart_epoch; }
-  } catch (const std::exception& e) { return translate(e); }
-  return BPMPC_OK;
-}
-int bpmpc_gait_batch_command(bpmpc_gait_batch* g, int batch, const int* gait, int inputs_on_device) {
-  if (!g) { set_last_error("bpmpc_gait_batch_command: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  API_GUARD(g->solver, { gait_batch_command(g, batch, gait, inputs_on_device != 0); })
-}
-int bpmpc_gait_batch_restart(bpmpc_gait_batch* g, int batch, const int* mask, int inputs_on_device) {
-  if (!g || !mask) { set_last_error("bpmpc_gait_batch_restart: null handle or mask"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  API_GUARD(g->solver, { gait_batch_restart(g, batch, mask, inputs_on_device != 0); })
-}
-int bpmpc_gait_batch_mode_schedule(bpmpc_gait_batch* g, int robot, double* event_times, int* modes, int capacity, int* n_events) {
-  if (!g) { set_last_error("bpmpc_gait_batch_mode_schedule: null handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  API_GUARD(g->solver, { gait_batch_mode_schedule(g, robot, event_times, modes, capacity, n_events); })
+  return guarded(s, [&] { setup_commands(s, batch, horizon, t0, x0, gaits, n_gaits, gait_of_problem, gait_start, cmd_vel, command_kind, time_to_target, from_previous != 0); });
 }
 int bpmpc_solver_rollout(bpmpc_solver* s, const double* t_start, const double* x_start, double duration, double* x_end, double* u_end, int* steps) {
-  API_GUARD(s, { rollout(s, t_start, x_start, duration, x_end, u_end, steps); })
+  return guarded(s, [&] { rollout(s, t_start, x_start, duration, x_end, u_end, steps); });
 }
 int bpmpc_solver_set_materialize(bpmpc_solver* s, int materialize_lq) {
   if (!s) { set_last_error("bpmpc_solver_set_materialize: null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
@@ -1554,15 +986,15 @@ int bpmpc_solver_set_profile(bpmpc_solver* s, int level) {
 int bpmpc_solve_batch(bpmpc_solver* s, int batch, double horizon, const double* t0, const double* x0, const bpmpc_mode_schedule* schedules,
                       int n_schedules, const bpmpc_target* targets, const double* warm_x, const double* warm_u, double* out_t, double* out_x,
                       double* out_u, double* out_K, bpmpc_stats* stats) {
-  API_GUARD(s, {
+  return guarded(s, [&] {
     setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, warm_x, warm_u);
     s->run_iterations();
     fetch(s, out_t, out_x, out_u, out_K, stats);
     s->collect_timers();
-  })
+  });
 }
 int bpmpc_solver_stage(bpmpc_solver* s, const char* stage) {
-  API_GUARD(s, {
+  return guarded(s, [&] {
     if (!stage || s->batch < 1) throw std::invalid_argument("bpmpc_solver_stage: no stage name or no setup");
     const std::string n(stage);
     // an explicit stage request always applies to every problem of the batch
@@ -1572,11 +1004,11 @@ int bpmpc_solver_stage(bpmpc_solver* s, const char* stage) {
     else if (n == "riccati") s->stage_riccati();
     else if (n == "linesearch") s->stage_linesearch();
     else throw std::invalid_argument("unknown stage " + n);
-  })
+  });
 }
 int bpmpc_solver_read(bpmpc_solver* s, const char* name, double* out, long capacity) {
   if (!s || !name) { set_last_error("bpmpc_solver_read: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  try {
+  return guarded(BPMPC_ERR_IO, [&]() -> int {      // (no device set for a size query, no streams drained after a failure)
     if (!out) {                                             // size query
 #if defined(BPMPC_EVAL_PROFILE)
       if (std::string(name) == "evprof") return 16;
@@ -1612,7 +1044,7 @@ int bpmpc_solver_read(bpmpc_solver* s, const char* name, double* out, long capac
       HIP_CHECK(hipMemcpy(out, it->second.first, n * sizeof(double), hipMemcpyDeviceToHost));
     }
     return (int)n;
-  } catch (const std::exception& e) { return translate(e); }
+  });
 }
 int bpmpc_solver_device_trajectories(bpmpc_solver* s, double** x_dev, double** u_dev) {
   if (!s) { set_last_error("null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
@@ -1621,7 +1053,7 @@ int bpmpc_solver_device_trajectories(bpmpc_solver* s, double** x_dev, double** u
   return BPMPC_OK;
 }
 int bpmpc_solver_export_trajectories(bpmpc_solver* s, double* x_dst_dev, double* u_dst_dev) {
-  API_GUARD(s, {
+  return guarded(s, [&] {
     const size_t N = s->settings.max_nodes;
     if (x_dst_dev && u_dst_dev && ((uintptr_t)x_dst_dev % 16 == 0) && ((uintptr_t)u_dst_dev % 16 == 0)) {
       copy_pairs(s, s->buf.x, x_dst_dev, (size_t)s->batch * (N + 1) * s->nx, s->buf.u, u_dst_dev, (size_t)s->batch * N * s->nu, false);
@@ -1629,10 +1061,10 @@ int bpmpc_solver_export_trajectories(bpmpc_solver* s, double* x_dst_dev, double*
       if (x_dst_dev) HIP_CHECK(hipMemcpyAsync(x_dst_dev, s->buf.x, (size_t)s->batch * (N + 1) * s->nx * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
       if (u_dst_dev) HIP_CHECK(hipMemcpyAsync(u_dst_dev, s->buf.u, (size_t)s->batch * N * s->nu * sizeof(double), hipMemcpyDeviceToDevice, s->stream));
     }
-  })
+  });
 }
 int bpmpc_solver_constraint_values(bpmpc_solver* s, double* values, int* rows, int* modes) {
-  API_GUARD(s, {
+  return guarded(s, [&] {
     if (!values || s->batch < 1) throw std::invalid_argument("bpmpc_solver_constraint_values: null output or no setup");
     if (s->settings.reference_kernels) throw std::invalid_argument("bpmpc_solver_constraint_values needs the fast kernels");
     if (s->is_ddp() && s->has_solution) throw Unsupported("bpmpc_solver_constraint_values: the DDP solution lives on the time points of its roll-out, not on the shooting grid the constraint rows are evaluated on");
@@ -1664,10 +1096,10 @@ int bpmpc_solver_constraint_values(bpmpc_solver* s, double* values, int* rows, i
         }
       }
     }
-  })
+  });
 }
 int bpmpc_solver_kernel_time(bpmpc_solver* s, const char* kernel, int reset_after, double* total_ms, int* launches) {
-  API_GUARD(s, {
+  return guarded(s, [&] {
     if (!kernel) throw std::invalid_argument("null kernel class");
     HIP_CHECK(hipStreamSynchronize(s->stream));
     s->collect_timers();
@@ -1675,7 +1107,7 @@ int bpmpc_solver_kernel_time(bpmpc_solver* s, const char* kernel, int reset_afte
     if (total_ms) *total_ms = t.total_ms;
     if (launches) *launches = t.launches;
     if (reset_after) { t.total_ms = 0.0; t.launches = 0; }
-  })
+  });
 }
 int bpmpc_solver_layout(const bpmpc_solver* s, int* batch, int* n_nodes_max, int* n_grids, int* nx, int* nu) {
   if (!s) { set_last_error("null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
@@ -1688,40 +1120,3 @@ int bpmpc_solver_layout(const bpmpc_solver* s, int* batch, int* n_nodes_max, int
 }
 
 }  // extern "C"
-
-// ------------------------------------------------------------------------------------------------ controller tick (k_tick.hip, controller.cpp)
-namespace bpmpc {
-
-SolverTickView solver_tick_view(bpmpc_solver* s) {
-  if (!s) throw std::invalid_argument("null solver handle");
-  if (s->is_ddp())
-    throw Unsupported("controller tick / evaluate_policy: the DDP solution is a FeedforwardController on the time points of its own roll-out, not on the shooting grid "
-                      "the policy is interpolated on");
-  refuse_while_restarting(s, "controller tick / evaluate_policy");
-  if (s->batch < 1 || !s->has_solution) throw std::invalid_argument("controller tick / evaluate_policy needs a completed bpmpc_solver_run since the last setup");
-  const Buffers& bf = s->buf;
-  const int feedback = s->feedback();
-  if (feedback && !bf.K) throw std::invalid_argument("controller tick / evaluate_policy: the feedback policy needs the gains (return_gains with reference kernels)");
-  SolverTickView v;
-  v.device = s->settings.device; v.batch = s->batch; v.N = s->settings.max_nodes; v.nx = s->nx; v.nu = s->nu; v.nj = s->rm.nj; v.feedback = feedback;
-  v.stream = s->stream; v.d_model = s->d_model;
-  v.p_grid = bf.p_grid; v.g_nodes = bf.g_nodes; v.g_kind = bf.g_kind; v.g_mode = bf.g_mode; v.g_time = bf.g_time;
-  v.x = bf.x; v.u = bf.u; v.K = bf.K; v.loop_x = s->tick_x;
-  return v;
-}
-
-void solver_tick_done(bpmpc_solver* s) { s->loop_from_tick = true; }
-
-int solver_device(const bpmpc_solver* s) { return s->settings.device; }
-
-SolverRestartView solver_restart_view(bpmpc_solver* s, int batch) {
-  if (!s) throw std::invalid_argument("null solver handle");
-  check_restart(s, batch);
-  return SolverRestartView{s->settings.device, s->rm.nj, s->stream, s->d_model};
-}
-
-void solver_restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool inputs_on_device) { restart(s, batch, mask, x_new, inputs_on_device); }
-
-int solver_translate(const std::exception& e) { return translate(e); }
-
-}  // namespace bpmpc

@@ -1,0 +1,31 @@
+// The handle of the batched whole-body controller (include/bpmpc.h: bpmpc_wbc, wbc.hip) and the launches on another handle's stream that the
+// controller tick (controller.cpp) enqueues.  The QP itself is kernels/wbc.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/bpmpc.h"
+#include "device_model.h"
+#include "robot_model.h"
+#include "kernels/wbc.h"
+
+struct bpmpc_wbc {
+  bpmpc::RobotModel rm;
+  bpmpc::DeviceModel dm;
+  bpmpc::DeviceModel* d_model = nullptr;
+  bpmpc::WbcSettings st{};
+  int device = 0, max_batch = 0, nv = 0, n = 0;
+  hipStream_t stream = nullptr;
+  double *d_x = nullptr, *d_u = nullptr, *d_rbd = nullptr, *d_sol = nullptr, *d_debug = nullptr;
+  int *d_mode = nullptr, *d_status = nullptr;
+  hipEvent_t ev_foreign = nullptr;      // k_wbc enqueued on another handle's stream (controller tick): this handle's stream waits for it
+  hipEvent_t ev_own = nullptr;          // ... and the other way round: a restart only enqueued on this handle's stream, waited for by the next foreign launch
+  bool own_pending = false;
+  int* d_mask = nullptr;                // [max_batch] device copy of a host restart mask
+};
+
+namespace bpmpc {
+// k_wbc on device inputs, enqueued on `stream`; later work on the WBC handle's own stream waits for it.
+void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const double* input_des, const double* rbd_meas, const int* mode, hipStream_t stream);
+// bpmpc_wbc_restart on a device mask, enqueued on `stream` with the same cross-stream rule
+void wbc_restart_on(bpmpc_wbc* w, int batch, const int* mask, hipStream_t stream);
+}  // namespace bpmpc
