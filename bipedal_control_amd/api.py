@@ -128,6 +128,91 @@ def _restart_args(*specs):
     return [None if o is None else o[0] for o in out], int(kinds.pop()) if kinds else 0, out
 
 
+def _shape(a):
+    iface = getattr(a, "__cuda_array_interface__", None)
+    return tuple(int(n) for n in (a.shape if hasattr(a, "shape") else iface["shape"] if iface is not None else np.shape(a)))
+
+
+def _rows_args(mask, arrays, width, max_batch):
+    """Marshals the rows of a masked per-robot write (bpmpc_wbc_set_params, bpmpc_controller_set_joint_gains): every array of `arrays` has the
+    shape [width], [1, width] (one row for every robot written) or [B, width] (a row per robot); mask (None: every robot) has B entries.  B is
+    len(mask), else the number of rows, else max_batch.  Returns (batch, n_rows, [mask pointer, row pointers ...], on_device, keep-alive);
+    through _restart_args, so device and host inputs are never mixed."""
+    shapes = {_shape(a) for a in arrays}
+    if len(shapes) != 1:
+        raise ValueError("the row arrays must have one shape, got %s" % sorted(shapes))
+    shape = shapes.pop()
+    if len(shape) not in (1, 2) or shape[-1] != width:
+        raise ValueError("rows must have the shape [%d], [1, %d] or [B, %d], got %s" % (width, width, width, list(shape)))
+    n_rows = 1 if len(shape) == 1 else shape[0]
+    batch = int(np.prod(_shape(mask))) if mask is not None else (n_rows if n_rows > 1 else max_batch)
+    if n_rows not in (1, batch) or batch < 1:
+        raise ValueError("%d rows for %d robots: one row or a row per robot" % (n_rows, batch))
+    ptrs, dev, keep = _restart_args((mask, C.c_int, batch), *[(a, C.c_double, n_rows * width) for a in arrays])
+    return batch, n_rows, ptrs, dev, keep
+
+
+class WbcParams:
+    """A parameter row of the WBC (include/bpmpc.h "Run-time parameters", BPMPC_WBC_PARAM_*) with named fields, so that no caller writes index
+    arithmetic: baseKp / baseKd [6] (position x, y, z, orientation x, y, z: WbcBase::setBasePDGains), swingKp / swingKd (setSwingLegPDGains),
+    weightSwingLeg / weightBaseAccel / weightContactForce (WeightedWbc::setWeights), and - per robot only in this engine, the reference reads
+    them once in loadTasksSetting - frictionCoefficient, contactTolerance (noContactMotionTask.tolerance), torqueLimits [nj / 2]."""
+
+    STRIDE = 32
+    FIELDS = ("baseKp", "baseKd", "swingKp", "swingKd", "weightSwingLeg", "weightBaseAccel", "weightContactForce", "frictionCoefficient",
+              "contactTolerance", "torqueLimits")
+    # what the reference's dynamic_reconfigure server calls the callback with at start-up (BipedalController.cpp:407-478): there these values
+    # override task.info from the first tick; here every row starts as task.info and this preset is applied by the caller
+    RECONFIGURE_MOTOR_KP, RECONFIGURE_MOTOR_KD = 80.0, 5.0
+
+    def __init__(self, nj, **fields):
+        self.nj = int(nj)
+        if self.nj not in (10, 12):
+            raise ValueError("nj must be 10 or 12")
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name in self.FIELDS:
+            setattr(self, name, fields.get(name))
+
+    @classmethod
+    def fromRow(cls, row, nj):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(nj, baseKp=r[0:6].copy(), baseKd=r[6:12].copy(), swingKp=float(r[12]), swingKd=float(r[13]), weightSwingLeg=float(r[14]),
+                   weightBaseAccel=float(r[15]), weightContactForce=float(r[16]), frictionCoefficient=float(r[17]), contactTolerance=float(r[18]),
+                   torqueLimits=r[19:19 + int(nj) // 2].copy())
+
+    def toRow(self):
+        missing = [n for n in self.FIELDS if getattr(self, n) is None]
+        if missing:
+            raise ValueError("parameter(s) without a value: %s" % missing)
+        r = np.zeros(self.STRIDE)
+        for lo, n, name in ((0, 6, "baseKp"), (6, 6, "baseKd"), (19, self.nj // 2, "torqueLimits")):
+            v = np.asarray(getattr(self, name), float).reshape(-1)
+            if v.size != n:
+                raise ValueError("%s needs %d values" % (name, n))
+            r[lo:lo + n] = v
+        r[12:19] = [self.swingKp, self.swingKd, self.weightSwingLeg, self.weightBaseAccel, self.weightContactForce, self.frictionCoefficient,
+                    self.contactTolerance]
+        return r
+
+    @classmethod
+    def reconfigureDefaults(cls, nj, base=None):
+        """The start-up values of the reference's reconfigure server: base kp 0 for x and y and 20 for z and the three orientation axes, base kd 0
+        / 0 / 3 / 3 / 3 / 3, swing leg 160 / 18, weights 100 (swing leg) / 1 (base acceleration) / 0.1 (contact force); the leg motors get
+        RECONFIGURE_MOTOR_KP / _KD (80 / 5, BatchedController.setLegMotorGains).  The server does not know the friction coefficient, the contact
+        tolerance or the torque limits: they are taken from `base` (a row or a WbcParams, e.g. WeightedWbc.getParams()) and stay unset
+        without one."""
+        rest = {}
+        if base is not None:
+            b = base if isinstance(base, WbcParams) else cls.fromRow(base, nj)
+            rest = dict(frictionCoefficient=b.frictionCoefficient, contactTolerance=b.contactTolerance, torqueLimits=np.array(b.torqueLimits, float))
+        return cls(nj, baseKp=np.array([0.0, 0.0, 20.0, 20.0, 20.0, 20.0]), baseKd=np.array([0.0, 0.0, 3.0, 3.0, 3.0, 3.0]), swingKp=160.0, swingKd=18.0,
+                   weightSwingLeg=100.0, weightBaseAccel=1.0, weightContactForce=0.1, **rest)
+
+
 class BipedalRobotInterface:
     """Problem definition: model constants + settings (BipedalRobotInterface.cpp:67-204)."""
 
@@ -655,6 +740,26 @@ class WeightedWbc:
         _check(load_library().bpmpc_wbc_restart(self._h, n, mp, dev))
         del keep
 
+    def getParams(self, robot=-1):
+        """The parameter row [32] of `robot` (WbcParams.fromRow names its entries), or with robot < 0 the values loadTasksSetting read from
+        task.info, which every row holds until it is set (bpmpc_wbc_get_params; synchronises)."""
+        row = np.zeros(WbcParams.STRIDE)
+        _check(load_library().bpmpc_wbc_get_params(self._h, int(robot), _d(row)))
+        return row
+
+    def setParams(self, rows, mask=None):
+        """dynamicReconfigCallback's setBasePDGains / setSwingLegPDGains / setWeights (BipedalController.cpp:407-478) per robot, and this engine's
+        per-robot friction, contact tolerance and torque limits (bpmpc_wbc_set_params).  rows: [32] or [1, 32] (one row for every robot written)
+        or [B, 32]; mask (None: every robot; else [B], non-zero = write).  numpy arrays are validated and the call synchronises; float64 / int32
+        device tensors are only enqueued on the WBC's stream (a later controller tick waits for it)."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], WbcParams.STRIDE, self.max_batch)
+        _check(load_library().bpmpc_wbc_set_params(self._h, B, mp, rp, n_rows, dev))
+        del keep
+
+    def resetParams(self):
+        """Every row back to the task.info values (bpmpc_wbc_reset_params)."""
+        _check(load_library().bpmpc_wbc_reset_params(self._h))
+
 
 class _TickOutputs(C.Structure):
     _fields_ = [("x_obs", _dp), ("x_opt", _dp), ("u_opt", _dp), ("joint_cmd", _dp), ("wbc_solution", _dp), ("planned_mode", _ip), ("wbc_status", _ip),
@@ -681,6 +786,7 @@ class BatchedController:
     tensors of a GPU simulator; order their producer against the solver's stream, e.g. by creating the solver on a torch stream)."""
 
     NAMES = ("x_obs", "x_opt", "u_opt", "joint_cmd", "wbc_solution", "planned_mode", "wbc_status", "safe")
+    JOINT_NAMES = ("joint_torque", "joint_kp", "joint_kd")      # bpmpc_controller_joint_outputs
 
     def __init__(self, mpc, wbc):
         self.mpc, self.wbc = mpc, wbc
@@ -701,7 +807,8 @@ class BatchedController:
     def tick(self, t, rbd, period=0.0025, fetch=True):
         """One tick for the solver's batch.  t: [batch] (or a scalar), rbd: [batch, 2 (6 + nj)].  fetch=True: returns a dict of numpy arrays
         (x_obs, x_opt, u_opt, joint_cmd [batch, 3, nj] = position, velocity, torque, wbc_solution, planned_mode, wbc_status, safe); False: only
-        enqueues (see device_outputs)."""
+        enqueues (see device_outputs).  joint_torque [batch, nj] = kp (posDes - q) + kd (velDes - v) + torque with the robots' joint gains
+        (setJointGains; the WBC torque while they are zero) and the gains themselves, joint_kp / joint_kd [batch, nj], come with them."""
         B = self.mpc.batch
         on_device = hasattr(rbd, "data_ptr") and getattr(rbd, "is_cuda", False)
         if on_device:
@@ -721,7 +828,31 @@ class BatchedController:
             ptrs = _TickOutputs(*[(_i if out[k].dtype == np.int32 else _d)(out[k]) for k in self.NAMES])
         _check(load_library().bpmpc_controller_tick(self._h, B, tp, rp, int(on_device), C.c_double(period), C.byref(ptrs) if fetch else None))
         del keep
+        if fetch:
+            for k in self.JOINT_NAMES:             # every key of device_outputs has its host copy
+                out[k] = np.zeros((B, self.nj))
+            _check(load_library().bpmpc_controller_joint_outputs(self._h, B, *[_d(out[k]) for k in self.JOINT_NAMES], None, None, None))
         return out
+
+    def setJointGains(self, kp, kd, mask=None):
+        """The joint-level kp / kd of the reference's joint command (HybridJointHandle::setCommand, BipedalController.cpp:250-254; set by
+        dynamicReconfigCallback :423-472) per robot (bpmpc_controller_set_joint_gains): kp, kd [nj], [1, nj] or [B, nj]; mask as
+        WeightedWbc.setParams.  On the solver's stream; all gains are 0 after create and survive restarts and reset."""
+        B, n_rows, (mp, pp, dp), dev, keep = _rows_args(mask, [kp, kd], self.nj, self.max_batch)
+        _check(load_library().bpmpc_controller_set_joint_gains(self._h, B, mp, pp, dp, n_rows, dev))
+        del keep
+
+    def setLegMotorGains(self, kp_leg, kd_leg, mask=None):
+        """setJointGains from nj / 2 values per robot (or one set for all), mirrored onto both legs as dynamicReconfigCallback does (:423-472)."""
+        def both(a):
+            if hasattr(a, "data_ptr"):
+                import torch
+                return torch.cat([a, a], dim=-1).contiguous()
+            a = np.asarray(a, float)
+            return np.concatenate([a, a], axis=-1)
+        if _shape(kp_leg)[-1:] != (self.nj // 2,) or _shape(kd_leg)[-1:] != (self.nj // 2,):
+            raise ValueError("leg gains need %d values per robot" % (self.nj // 2))
+        self.setJointGains(both(kp_leg), both(kd_leg), mask)
 
     def reset(self):
         """yaw_last = 0 for every robot (BipedalController::starting)."""
@@ -741,8 +872,13 @@ class BatchedController:
         o = _TickOutputs()
         _check(load_library().bpmpc_controller_device_outputs(self._h, C.byref(o)))
         B = self.mpc.batch
-        return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k in ("planned_mode", "wbc_status", "safe") else "<f8")
-                for k, shp in self._shapes(B).items()}
+        views = {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k in ("planned_mode", "wbc_status", "safe") else "<f8")
+                 for k, shp in self._shapes(B).items()}
+        ptrs = [_dp() for _ in self.JOINT_NAMES]
+        _check(load_library().bpmpc_controller_joint_outputs(self._h, B, None, None, None, *[C.byref(p) for p in ptrs]))
+        for k, p in zip(self.JOINT_NAMES, ptrs):
+            views[k] = DeviceArray(C.cast(p, C.c_void_p).value, (B, self.nj), "<f8")
+        return views
 
 
 class BatchedDdpMpc(BatchedSqpMpc):

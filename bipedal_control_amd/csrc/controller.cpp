@@ -3,11 +3,13 @@
 //   observation                         :397-403 (computeCentroidalStateFromRbdModel, yaw unwrap)
 //   evaluatePolicy / WBC / safety       :199, :229, SafetyChecker.h:39-52;  commands :237-252
 // One tick = k_tick_observe_policy, k_wbc (the WBC handle's kernel and its per-robot last solutions), k_tick_commands, all on the solver's
-// stream; nothing is synchronised unless outputs are asked for on the host.
+// stream; nothing is synchronised unless outputs are asked for on the host.  k_tick_commands also forms joint_torque from the per-robot joint
+// gains of dynamicReconfigCallback (:423-472, bpmpc_controller_set_joint_gains).
 // A restart (BipedalController::starting, :123-179) for the robots of a mask = k_restart_observe, bpmpc_solver_restart with the observations,
 // k_wbc_restart, on the same stream.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -24,6 +26,8 @@ struct bpmpc_controller {
   int device = 0, max_batch = 0, nj = 0, nx = 0, nv = 0, n = 0;
   double *d_yaw = nullptr, *d_t = nullptr, *d_rbd = nullptr, *d_xobs = nullptr, *d_xopt = nullptr, *d_uopt = nullptr, *d_cmd = nullptr;
   int *d_mode = nullptr, *d_safe = nullptr, *d_mask = nullptr;
+  double *d_kp = nullptr, *d_kd = nullptr, *d_torque = nullptr;      // [max_batch][nj]: joint gains (0 after create), the last tick's joint_torque
+  double *d_kp_in = nullptr, *d_kd_in = nullptr;                     // device copies of host gain rows
 };
 
 namespace {
@@ -38,7 +42,7 @@ TickArgs policy_args(const bpmpc_solver* s, int batch) {
 
 void free_all(bpmpc_controller* c) {
   for (void* p : {(void*)c->d_yaw, (void*)c->d_t, (void*)c->d_rbd, (void*)c->d_xobs, (void*)c->d_xopt, (void*)c->d_uopt, (void*)c->d_cmd, (void*)c->d_mode,
-                  (void*)c->d_safe, (void*)c->d_mask})
+                  (void*)c->d_safe, (void*)c->d_mask, (void*)c->d_kp, (void*)c->d_kd, (void*)c->d_torque, (void*)c->d_kp_in, (void*)c->d_kd_in})
     if (p) (void)hipFree(p);
 }
 
@@ -96,6 +100,10 @@ int bpmpc_controller_create(bpmpc_solver* s, bpmpc_wbc* w, bpmpc_controller** ou
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_mode), B * sizeof(int)));
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_safe), B * sizeof(int)));
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_mask), B * sizeof(int)));
+    for (double** p : {&c->d_kp, &c->d_kd, &c->d_torque, &c->d_kp_in, &c->d_kd_in}) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), B * c->nj * sizeof(double)));
+    HIP_CHECK(hipMemset(c->d_kp, 0, B * c->nj * sizeof(double)));
+    HIP_CHECK(hipMemset(c->d_kd, 0, B * c->nj * sizeof(double)));
+    HIP_CHECK(hipMemset(c->d_torque, 0, B * c->nj * sizeof(double)));
     HIP_CHECK(hipMemset(c->d_yaw, 0, B * sizeof(double)));       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
     HIP_CHECK(hipDeviceSynchronize());
   });
@@ -146,7 +154,10 @@ int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const
     HIP_CHECK(hipGetLastError());
     s->loop_from_tick = true;          // the next setup_commands(x0 = NULL) starts from tick_x (until the next rollout)
     wbc_launch_on(c->w, batch, c->d_xopt, c->d_uopt, drbd, c->d_mode, s->stream);
-    kl::tick_commands(c->nj, batch, s->stream, c->d_xopt, c->d_uopt, c->w->d_sol, c->d_cmd);
+    TickCommandArgs ca{};
+    ca.batch = batch; ca.x_opt = c->d_xopt; ca.u_opt = c->d_uopt; ca.sol = c->w->d_sol; ca.rbd = drbd; ca.kp = c->d_kp; ca.kd = c->d_kd;
+    ca.cmd = c->d_cmd; ca.joint_torque = c->d_torque;
+    kl::tick_commands(c->nj, s->stream, ca);
     HIP_CHECK(hipGetLastError());
     if (host_out) {
       const bpmpc_tick_outputs& o = *host_out;
@@ -187,6 +198,55 @@ int bpmpc_controller_restart(bpmpc_controller* c, int batch, const int* mask, co
     restart(s, batch, dmask, c->d_xobs, true);
     wbc_restart_on(c->w, batch, dmask, s->stream);
     if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(s->stream));     // the caller's host arrays
+  });
+}
+
+// The joint-level kp / kd of dynamicReconfigCallback (:423-472) for the robots of `mask`, on the solver's stream
+int bpmpc_controller_set_joint_gains(bpmpc_controller* c, int batch, const int* mask, const double* kp, const double* kd, int n_rows, int inputs_on_device) {
+  if (!c || !kp || !kd) { set_last_error("bpmpc_controller_set_joint_gains: null handle or gains"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(BPMPC_ERR_DEVICE, [&] {
+    if (batch < 1 || batch > c->max_batch) throw std::length_error("bpmpc_controller_set_joint_gains: batch exceeds the WBC's max_batch");
+    if (n_rows != 1 && n_rows != batch) throw std::invalid_argument("bpmpc_controller_set_joint_gains: n_rows must be 1 or batch");
+    HIP_CHECK(hipSetDevice(c->device));
+    hipStream_t stream = c->s->stream;
+    const int* dmask = mask;
+    const double *dkp = kp, *dkd = kd;
+    if (!inputs_on_device) {
+      for (int r = 0; r < n_rows; ++r) {
+        if (n_rows != 1 && mask && !mask[r]) continue;
+        for (int j = 0; j < c->nj; ++j)
+          for (const double* g : {kp, kd})
+            if (!std::isfinite(g[r * c->nj + j]) || g[r * c->nj + j] < 0.0)
+              throw std::invalid_argument("bpmpc_controller_set_joint_gains: row " + std::to_string(r) + ", joint " + std::to_string(j) + ": " + (g == kp ? "kp" : "kd") +
+                                          " must be finite and not negative");
+      }
+      const size_t bytes = (size_t)n_rows * c->nj * sizeof(double);
+      HIP_CHECK(hipMemcpyAsync(c->d_kp_in, kp, bytes, hipMemcpyHostToDevice, stream));
+      HIP_CHECK(hipMemcpyAsync(c->d_kd_in, kd, bytes, hipMemcpyHostToDevice, stream));
+      if (mask) HIP_CHECK(hipMemcpyAsync(c->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, stream));
+      dmask = mask ? c->d_mask : nullptr; dkp = c->d_kp_in; dkd = c->d_kd_in;
+    }
+    kl::set_joint_gains(c->nj, batch, stream, dmask, dkp, dkd, n_rows, c->d_kp, c->d_kd);
+    HIP_CHECK(hipGetLastError());
+    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(stream));      // the caller's host arrays
+  });
+}
+
+int bpmpc_controller_joint_outputs(bpmpc_controller* c, int batch, double* host_torque, double* host_kp, double* host_kd, double** dev_torque,
+                                   double** dev_kp, double** dev_kd) {
+  if (!c) { set_last_error("null controller handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(BPMPC_ERR_DEVICE, [&] {
+    if (dev_torque) *dev_torque = c->d_torque;
+    if (dev_kp) *dev_kp = c->d_kp;
+    if (dev_kd) *dev_kd = c->d_kd;
+    if (!host_torque && !host_kp && !host_kd) return;
+    if (batch < 1 || batch > c->max_batch) throw std::length_error("bpmpc_controller_joint_outputs: batch exceeds the WBC's max_batch");
+    HIP_CHECK(hipSetDevice(c->device));
+    const size_t bytes = (size_t)batch * c->nj * sizeof(double);
+    if (host_torque) HIP_CHECK(hipMemcpyAsync(host_torque, c->d_torque, bytes, hipMemcpyDeviceToHost, c->s->stream));
+    if (host_kp) HIP_CHECK(hipMemcpyAsync(host_kp, c->d_kp, bytes, hipMemcpyDeviceToHost, c->s->stream));
+    if (host_kd) HIP_CHECK(hipMemcpyAsync(host_kd, c->d_kd, bytes, hipMemcpyDeviceToHost, c->s->stream));
+    HIP_CHECK(hipStreamSynchronize(c->s->stream));
   });
 }
 

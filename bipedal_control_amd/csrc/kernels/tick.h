@@ -240,17 +240,41 @@ __device__ __forceinline__ void tick_observe_policy(const DeviceModel& md, TickL
   if (g == 0) a.mode[b] = a.g_mode[(size_t)grid * N + j];
 }
 
-// joint commands of BipedalController.cpp:237-252: posDes = x*[12:], velDes = u*[12:], torque = the joint-torque block of the WBC solution
+// joint commands of BipedalController.cpp:237-252: posDes = x*[12:], velDes = u*[12:], torque = the joint-torque block of the WBC solution;
+// with the robot's joint gains (the kp / kd of HybridJointHandle::setCommand, :250-254) the torque the hardware layer forms from that five-tuple
+// (bipedal_gazebo/src/BipedalHWSim.cpp:174-175): kp (posDes - q) + kd (velDes - v) + tau, q / v the joint entries of the measured rbd
+struct TickCommandArgs {
+  int batch;
+  const double *x_opt, *u_opt, *sol, *rbd;      // [batch][NX], [batch][NU], [batch][n], [batch][2 (6 + NJ)]
+  const double *kp, *kd;                        // [batch][NJ]
+  double *cmd, *joint_torque;                   // [batch][3][NJ], [batch][NJ]
+};
+
 template <int NJ>
-__device__ __forceinline__ void tick_commands(int batch, const double* x_opt, const double* u_opt, const double* sol, double* cmd) {
-  constexpr int NX = 12 + NJ, NU = 12 + NJ, NSOL = 6 + NJ + 12 + NJ;
+__device__ __forceinline__ void tick_commands(const TickCommandArgs& a) {
+  constexpr int NX = 12 + NJ, NU = 12 + NJ, NV = 6 + NJ, NSOL = 6 + NJ + 12 + NJ;
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= batch * NJ) return;
+  if (idx >= a.batch * NJ) return;
   const int b = idx / NJ, j = idx % NJ;
-  double* c = cmd + (size_t)b * 3 * NJ;
-  c[j] = x_opt[(size_t)b * NX + 12 + j];
-  c[NJ + j] = u_opt[(size_t)b * NU + 12 + j];
-  c[2 * NJ + j] = sol[(size_t)b * NSOL + NSOL - NJ + j];
+  double* c = a.cmd + (size_t)b * 3 * NJ;
+  const double pos = a.x_opt[(size_t)b * NX + 12 + j], vel = a.u_opt[(size_t)b * NU + 12 + j], tau = a.sol[(size_t)b * NSOL + NSOL - NJ + j];
+  c[j] = pos;
+  c[NJ + j] = vel;
+  c[2 * NJ + j] = tau;
+  const double* rb = a.rbd + (size_t)b * 2 * NV;
+  a.joint_torque[idx] = a.kp[idx] * (pos - rb[6 + j]) + a.kd[idx] * (vel - rb[NV + 6 + j]) + tau;
+}
+
+// bpmpc_controller_set_joint_gains: the gains of the robots of `mask` (NULL: every robot below `batch`) become rows b (n_rows == batch) or rows 0
+// (n_rows == 1) of kp_in / kd_in.  One thread per entry.
+__device__ __forceinline__ void set_joint_gains(int batch, int nj, const int* mask, const double* kp_in, const double* kd_in, int n_rows, double* kp, double* kd) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= batch * nj) return;
+  const int b = idx / nj, j = idx % nj;
+  if (mask && !mask[b]) return;
+  const int src = (n_rows == 1 ? 0 : b) * nj + j;
+  kp[idx] = kp_in[src];
+  kd[idx] = kd_in[src];
 }
 
 // The observation of a restart (BipedalController::starting, :126-127: the observation is zeroed, then set from the estimator): for every robot

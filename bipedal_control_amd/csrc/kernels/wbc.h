@@ -32,12 +32,18 @@
 
 namespace bpmpc {
 
+// The controller parameters of one robot, in the layout of a parameter row (include/bpmpc.h, BPMPC_WBC_PARAM_*): k_wbc copies robot b's row of
+// the handle's table over one of these in LDS, once per launch.
+//   setBasePDGains / setSwingLegPDGains (WbcBase.h:55-69), WeightedWbc::setWeights (WeightedWbc.h:48-52), loadTasksSetting for the rest
+constexpr int kWbcParamStride = 32;
 struct WbcSettings {
+  double base_kp[6], base_kd[6], swing_kp, swing_kd, w_swing, w_base, w_force, friction, contact_tolerance;
   double torque_limits[kMaxJoints / 2];
-  double friction, swing_kp, swing_kd, base_kp[6], base_kd[6], contact_tolerance, w_swing, w_base, w_force;
-  int max_working_set_changes;         // qpOASES nWSR of the reference (20)
+  double reserved[7];
 };
+static_assert(sizeof(WbcSettings) == kWbcParamStride * sizeof(double) && kMaxJoints / 2 == 6, "WbcSettings is a parameter row");
 
+constexpr int kWbcMaxWorkingSetChanges = 20;     // int nWsr = 20, WeightedWbc.cpp:57: a constant of the handle, not a row entry
 constexpr double kWbcGravity = 9.81;
 constexpr double kWbcFeasTol = 1e-8;   // relative: equality rows that cannot all hold (as the oracle)
 constexpr double kWbcActiveTol = 1e-9;
@@ -265,11 +271,14 @@ struct WbcLds {
   double z[NZ], mu[NI];
   int colperm[NY], work[NI], nwork, rank, status, iters;
   double y[NY];
+  WbcSettings st;                        // this robot's parameter row
 };
 
 // ---------------------------------------------------------------------------------------------------------------- the controller
 struct WbcArgs {
   int batch, nx;
+  int max_working_set_changes;                      // qpOASES nWSR of the reference (20)
+  const double* params;                             // [max_batch][kWbcParamStride]: a WbcSettings per robot
   const double *state_des, *input_des, *rbd_meas;   // [B][nx], [B][nx], [B][2 nv]
   const int* mode;                                  // [B]
   double* sol;                                      // [B][n]: in = last solution, out = new one (or unchanged on failure)
@@ -279,11 +288,14 @@ struct WbcArgs {
 constexpr int kWbcDebugStride = 1024;
 
 template <int NJ>
-__device__ void wbc_robot(const DeviceModel& md, const WbcSettings& st, WbcLds<NJ>& w, const WbcArgs& a, int b, int l) {
+__device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a, int b, int l) {
   using W = WbcLds<NJ>;
   constexpr int NV = W::NV, NX = W::NX, NY = W::NY, NE = W::NE, NI = W::NI;
   const int n = NV + 12 + NJ;
   WbcRbd<NJ>& r = w.rbd;
+  const WbcSettings& st = w.st;
+  static_assert(kWbcParamStride <= kWave, "one lane per entry of the parameter row");
+  if (l < kWbcParamStride) reinterpret_cast<double*>(&w.st)[l] = a.params[(size_t)b * kWbcParamStride + l];     // read after the next lds_wave_sync
   // ======================================================= desired state (WbcBase::updateDesired, computeBaseKinematicsFromCentroidalModel)
   for (int i = l; i < NX; i += kWave) { w.xd[i] = a.state_des[(size_t)b * NX + i]; w.ud[i] = a.input_des[(size_t)b * NX + i]; }
   if (l < kNumContacts) {
@@ -650,7 +662,7 @@ __device__ void wbc_robot(const DeviceModel& md, const WbcSettings& st, WbcLds<N
     const double gworst = wave_max(worst);
     const int add = wave_min_int(worst == gworst ? wi : 0x7fffffff);
     if (gworst > kWbcActiveTol) {
-      if (iters > st.max_working_set_changes) { status = 1; break; }
+      if (iters > a.max_working_set_changes) { status = 1; break; }
       if (l == 0) { w.work[w.nwork] = add; w.nwork = na + 1; }
       lds_wave_sync();
       continue;
@@ -659,7 +671,7 @@ __device__ void wbc_robot(const DeviceModel& md, const WbcSettings& st, WbcLds<N
     int drop = -1; double mneg = -kWbcActiveTol;
     for (int k = 0; k < na; ++k) if (w.mu[k] < mneg) { mneg = w.mu[k]; drop = k; }
     if (drop >= 0) {
-      if (iters > st.max_working_set_changes) { status = 1; break; }
+      if (iters > a.max_working_set_changes) { status = 1; break; }
       lds_wave_sync();
       if (l == 0) { for (int k = drop; k + 1 < na; ++k) w.work[k] = w.work[k + 1]; w.nwork = na - 1; }
       lds_wave_sync();

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "../../include/bpmpc.h"
 #include "device_model.h"
 #include "robot_model.h"
@@ -12,7 +14,7 @@ struct bpmpc_wbc {
   bpmpc::RobotModel rm;
   bpmpc::DeviceModel dm;
   bpmpc::DeviceModel* d_model = nullptr;
-  bpmpc::WbcSettings st{};
+  bpmpc::WbcSettings defaults{};        // what loadTasksSetting reads from task.info: every parameter row after create / bpmpc_wbc_reset_params
   int device = 0, max_batch = 0, nv = 0, n = 0;
   hipStream_t stream = nullptr;
   double *d_x = nullptr, *d_u = nullptr, *d_rbd = nullptr, *d_sol = nullptr, *d_debug = nullptr;
@@ -20,8 +22,18 @@ struct bpmpc_wbc {
   hipEvent_t ev_foreign = nullptr;      // k_wbc enqueued on another handle's stream (controller tick): this handle's stream waits for it
   hipEvent_t ev_own = nullptr;          // ... and the other way round: a restart only enqueued on this handle's stream, waited for by the next foreign launch
   bool own_pending = false;
-  int* d_mask = nullptr;                // [max_batch] device copy of a host restart mask
+  int* d_mask = nullptr;                // [max_batch] device copy of a host mask (restart, set_params)
+  double* d_params = nullptr;           // [max_batch][kWbcParamStride] the robots' parameter rows (kernels/wbc.h WbcSettings), read by k_wbc
+  double* d_rows = nullptr;             // [max_batch + 1][kWbcParamStride] device copy of host rows; the last row holds `defaults`
 };
+
+static_assert(bpmpc::kWbcParamStride == BPMPC_WBC_PARAM_STRIDE && offsetof(bpmpc::WbcSettings, base_kd) == 8 * BPMPC_WBC_PARAM_BASE_KD &&
+                  offsetof(bpmpc::WbcSettings, swing_kp) == 8 * BPMPC_WBC_PARAM_SWING_KP && offsetof(bpmpc::WbcSettings, w_swing) == 8 * BPMPC_WBC_PARAM_WEIGHT_SWING_LEG &&
+                  offsetof(bpmpc::WbcSettings, friction) == 8 * BPMPC_WBC_PARAM_FRICTION &&
+                  offsetof(bpmpc::WbcSettings, contact_tolerance) == 8 * BPMPC_WBC_PARAM_CONTACT_TOLERANCE &&
+                  offsetof(bpmpc::WbcSettings, torque_limits) == 8 * BPMPC_WBC_PARAM_TORQUE_LIMITS &&
+                  offsetof(bpmpc::WbcSettings, reserved) == 8 * BPMPC_WBC_PARAM_RESERVED,
+              "WbcSettings follows the row layout of include/bpmpc.h");
 
 namespace bpmpc {
 // k_wbc on device inputs, enqueued on `stream`; later work on the WBC handle's own stream waits for it.

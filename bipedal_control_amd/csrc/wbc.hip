@@ -2,8 +2,11 @@
 //   WeightedWbc construction + loadTasksSetting     bipedal_controllers/src/BipedalController.cpp:97-100, bipedal_wbc/src/WbcBase.cpp:405-447,
 //                                                   bipedal_wbc/src/WeightedWbc.cpp:100-116
 //   WeightedWbc::update                             bipedal_controllers/src/BipedalController.cpp:229
+//   setBasePDGains / setSwingLegPDGains / setWeights bipedal_controllers/src/BipedalController.cpp:407-419 (dynamicReconfigCallback), per robot: the
+//                                                   parameter rows of the handle (bpmpc_wbc_get_params / set_params / reset_params)
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -17,11 +20,21 @@
 namespace bpmpc {
 
 template <int NJ>
-__global__ __launch_bounds__(kWave) void k_wbc(const DeviceModel* model, WbcSettings st, WbcArgs a) {
+__global__ __launch_bounds__(kWave) void k_wbc(const DeviceModel* model, WbcArgs a) {
   __shared__ WbcLds<NJ> w;
   const int b = blockIdx.x;
   if (b >= a.batch) return;
-  wbc_robot<NJ>(*model, st, w, a, b, threadIdx.x);
+  wbc_robot<NJ>(*model, w, a, b, threadIdx.x);
+}
+
+// bpmpc_wbc_set_params: the parameter rows of the robots of `mask` (NULL: every robot below `batch`) become rows[b] (n_rows == batch) or
+// rows[0] (n_rows == 1); the reserved entries are written as 0.  One thread per entry.
+__global__ __launch_bounds__(256) void k_wbc_set_params(int batch, const int* mask, const double* rows, int n_rows, double* params) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= batch * kWbcParamStride) return;
+  const int b = i / kWbcParamStride, e = i % kWbcParamStride;
+  if (mask && !mask[b]) return;
+  params[i] = e < BPMPC_WBC_PARAM_RESERVED ? rows[(size_t)(n_rows == 1 ? 0 : b) * kWbcParamStride + e] : 0.0;
 }
 
 // WeightedWbc::clearLastQpSol for the robots of `mask` (bpmpc_wbc_restart): their last solution and status become 0
@@ -58,14 +71,32 @@ WbcSettings load_wbc_settings(const std::string& task_info, int nj) {
   need("weight.swingLeg", &s.w_swing);
   need("weight.baseAccel", &s.w_base);
   need("weight.contactForce", &s.w_force);
-  s.max_working_set_changes = 20;      // int nWsr = 20, WeightedWbc.cpp:57
   return s;
 }
 
 // k_wbc of the handle's robot on `stream`
 void launch_wbc(const bpmpc_wbc* w, const WbcArgs& a, hipStream_t stream) {
-  KL_NJ(w->rm.nj, hipLaunchKernelGGL(k_wbc<NJ>, dim3(a.batch), dim3(kWave), 0, stream, w->d_model, w->st, a));
+  KL_NJ(w->rm.nj, hipLaunchKernelGGL(k_wbc<NJ>, dim3(a.batch), dim3(kWave), 0, stream, w->d_model, a));
   HIP_CHECK(hipGetLastError());
+}
+
+// k_wbc_set_params on device rows and a device mask (NULL: everyone), on the handle's own stream
+void set_params_on_device(bpmpc_wbc* w, int batch, const int* mask, const double* rows, int n_rows) {
+  hipLaunchKernelGGL(k_wbc_set_params, dim3((batch * kWbcParamStride + 255) / 256), dim3(256), 0, w->stream, batch, mask, rows, n_rows, w->d_params);
+  HIP_CHECK(hipGetLastError());
+}
+
+// A host row before it is accepted: every used entry finite; gains, weights, friction and torque limits not negative
+void check_param_row(const double* row, int r, int nj) {
+  static const char* const kNames[] = {"base kp", "base kd", "swing kp", "swing kd", "weight swing leg", "weight base acceleration", "weight contact force",
+                                       "friction coefficient", "no-contact-motion tolerance", "torque limit"};
+  for (int e = 0; e < BPMPC_WBC_PARAM_TORQUE_LIMITS + nj / 2; ++e) {
+    const int kind = e < 6 ? 0 : e < 12 ? 1 : e < BPMPC_WBC_PARAM_TORQUE_LIMITS ? e - 10 : 9;
+    const bool negative_ok = e == BPMPC_WBC_PARAM_CONTACT_TOLERANCE;
+    if (!std::isfinite(row[e]) || (!negative_ok && row[e] < 0.0))
+      throw std::invalid_argument("bpmpc_wbc_set_params: row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + kNames[kind] + ") is " +
+                                  (std::isfinite(row[e]) ? "negative" : "not finite"));
+  }
 }
 }  // namespace
 
@@ -77,7 +108,7 @@ void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const doubl
   if (w->own_pending) HIP_CHECK(hipStreamWaitEvent(stream, w->ev_own, 0));
   WbcArgs a{};
   a.batch = batch; a.nx = w->rm.nx; a.state_des = state_des; a.input_des = input_des; a.rbd_meas = rbd_meas; a.mode = mode;
-  a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr;
+  a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr; a.params = w->d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
   launch_wbc(w, a, stream);
   if (!w->ev_foreign) HIP_CHECK(hipEventCreateWithFlags(&w->ev_foreign, hipEventDisableTiming));
   HIP_CHECK(hipEventRecord(w->ev_foreign, stream));
@@ -115,7 +146,7 @@ int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int d
     w->rm = model_of(model);
     if (w->rm.nj != 10 && w->rm.nj != 12) { set_last_error("only 10- and 12-joint bipeds are instantiated"); return BPMPC_ERR_UNSUPPORTED; }
     w->dm = make_device_model(w->rm);
-    w->st = load_wbc_settings(task_info_path, w->rm.nj);
+    w->defaults = load_wbc_settings(task_info_path, w->rm.nj);
     w->device = device; w->max_batch = max_batch; w->nv = 6 + w->rm.nj; w->n = w->nv + 12 + w->rm.nj;
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
@@ -131,6 +162,11 @@ int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int d
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_status), B * sizeof(int)));
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_mask), B * sizeof(int)));
     HIP_CHECK(hipMemset(w->d_sol, 0, B * w->n * sizeof(double)));      // lastQpSol_ starts at zero (WeightedWbc.h)
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_params), B * sizeof(WbcSettings)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_rows), (B + 1) * sizeof(WbcSettings)));
+    HIP_CHECK(hipMemcpy(w->d_rows + B * kWbcParamStride, &w->defaults, sizeof(WbcSettings), hipMemcpyHostToDevice));
+    set_params_on_device(w.get(), max_batch, nullptr, w->d_rows + B * kWbcParamStride, 1);      // every row starts as the task.info values
+    HIP_CHECK(hipStreamSynchronize(w->stream));
     return BPMPC_OK;
   });
   if (rc != BPMPC_OK) { bpmpc_wbc_destroy(w.release()); return rc; }
@@ -144,7 +180,7 @@ void bpmpc_wbc_destroy(bpmpc_wbc* w) {
   if (w->ev_foreign) (void)hipEventDestroy(w->ev_foreign);
   if (w->ev_own) (void)hipEventDestroy(w->ev_own);
   for (void* p : {(void*)w->d_model, (void*)w->d_x, (void*)w->d_u, (void*)w->d_rbd, (void*)w->d_sol, (void*)w->d_debug, (void*)w->d_mode, (void*)w->d_status,
-                  (void*)w->d_mask})
+                  (void*)w->d_mask, (void*)w->d_params, (void*)w->d_rows})
     if (p) (void)hipFree(p);
   delete w;
 }
@@ -172,6 +208,7 @@ int bpmpc_wbc_update(bpmpc_wbc* w, int batch, const double* state_desired, const
     WbcArgs a{};
     a.batch = batch; a.nx = w->rm.nx; a.state_des = w->d_x; a.input_des = w->d_u; a.rbd_meas = w->d_rbd; a.mode = w->d_mode;
     a.sol = w->d_sol; a.status = w->d_status; a.debug = debug ? w->d_debug : nullptr;
+    a.params = w->d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
     launch_wbc(w, a, w->stream);
     HIP_CHECK(hipMemcpyAsync(solution, w->d_sol, B * w->n * sizeof(double), hipMemcpyDeviceToHost, w->stream));
     if (status) HIP_CHECK(hipMemcpyAsync(status, w->d_status, B * sizeof(int), hipMemcpyDeviceToHost, w->stream));
@@ -207,6 +244,50 @@ int bpmpc_wbc_restart(bpmpc_wbc* w, int batch, const int* mask, int inputs_on_de
       HIP_CHECK(hipEventRecord(w->ev_own, w->stream));
       w->own_pending = true;
     }
+  });
+}
+
+int bpmpc_wbc_get_params(const bpmpc_wbc* w, int robot, double* row) {
+  if (!w || !row) { set_last_error("bpmpc_wbc_get_params: null handle or row"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(BPMPC_ERR_IO, [&] {
+    if (robot >= w->max_batch) throw std::length_error("bpmpc_wbc_get_params: robot exceeds max_batch");
+    HIP_CHECK(hipSetDevice(w->device));
+    const double* src = robot < 0 ? w->d_rows + (size_t)w->max_batch * kWbcParamStride : w->d_params + (size_t)robot * kWbcParamStride;
+    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(WbcSettings), hipMemcpyDeviceToHost, w->stream));
+    HIP_CHECK(hipStreamSynchronize(w->stream));
+  });
+}
+
+int bpmpc_wbc_set_params(bpmpc_wbc* w, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
+  if (!w || !rows) { set_last_error("bpmpc_wbc_set_params: null handle or rows"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(BPMPC_ERR_IO, [&] {
+    if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_set_params: batch exceeds max_batch");
+    if (n_rows != 1 && n_rows != batch) throw std::invalid_argument("bpmpc_wbc_set_params: n_rows must be 1 or batch");
+    HIP_CHECK(hipSetDevice(w->device));
+    if (!inputs_on_device) {
+      for (int r = 0; r < n_rows; ++r)
+        if (n_rows == 1 || !mask || mask[r]) check_param_row(rows + (size_t)r * kWbcParamStride, r, w->rm.nj);
+      HIP_CHECK(hipMemcpyAsync(w->d_rows, rows, (size_t)n_rows * sizeof(WbcSettings), hipMemcpyHostToDevice, w->stream));
+      if (mask) HIP_CHECK(hipMemcpyAsync(w->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, w->stream));
+      set_params_on_device(w, batch, mask ? w->d_mask : nullptr, w->d_rows, n_rows);
+      HIP_CHECK(hipStreamSynchronize(w->stream));
+      w->own_pending = false;
+    } else {                            // only enqueued, as bpmpc_wbc_restart: the next launch on another stream (a controller tick) waits for it
+      set_params_on_device(w, batch, mask, rows, n_rows);
+      if (!w->ev_own) HIP_CHECK(hipEventCreateWithFlags(&w->ev_own, hipEventDisableTiming));
+      HIP_CHECK(hipEventRecord(w->ev_own, w->stream));
+      w->own_pending = true;
+    }
+  });
+}
+
+int bpmpc_wbc_reset_params(bpmpc_wbc* w) {
+  if (!w) { set_last_error("null wbc handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(BPMPC_ERR_IO, [&] {
+    HIP_CHECK(hipSetDevice(w->device));
+    set_params_on_device(w, w->max_batch, nullptr, w->d_rows + (size_t)w->max_batch * kWbcParamStride, 1);
+    HIP_CHECK(hipStreamSynchronize(w->stream));
+    w->own_pending = false;
   });
 }
 

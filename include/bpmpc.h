@@ -373,7 +373,8 @@ int bpmpc_wbc_reset(bpmpc_wbc* wbc);
  *                           solutions as bpmpc_wbc_update (the fallback of WeightedWbc.cpp:68-81 is the same whichever entry point ran)
  *   safety        SafetyChecker::check (SafetyChecker.h:39-52): safe = 0 when |x_obs[10]| > pi/3 or |x_obs[11]| > pi/3 (the limit passes)
  *   commands      :237-252  joint_cmd[b] = [posDes = x*[12:], velDes = u*[12:], torque = last nj entries of the WBC solution] ([3][nj];
- *                           the joint gains kp / kd stay the caller's)
+ *                           the joint gains kp / kd of the five-tuple are per-robot data of the controller, see "Run-time parameters" below,
+ *                           and so is the torque the hardware layer forms from the five-tuple)
  * Everything runs on the solver's stream (three launches: k_tick_observe_policy, k_wbc, k_tick_commands).  The observations also close the
  * loop: bpmpc_solver_setup_commands(x0 = NULL) starts from the states of the last rollout OR the last tick, whichever ran last on the solver.
  * ------------------------------------------------------------------------------------------------------------- */
@@ -443,6 +444,64 @@ int bpmpc_wbc_restart(bpmpc_wbc* wbc, int batch, const int* mask, int inputs_on_
 int bpmpc_gait_batch_restart(bpmpc_gait_batch* gaits, int batch, const int* mask, int inputs_on_device);
 /* rbd[batch*2*(6+nj)]: the measured rigid-body states the restarted robots start from (layout of bpmpc_controller_tick). */
 int bpmpc_controller_restart(bpmpc_controller* controller, int batch, const int* mask, const double* rbd, int inputs_on_device);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Run-time parameters: BipedalController::dynamicReconfigCallback (bipedal_controllers/src/BipedalController.cpp:407-478), the reference's only
+ * run-time tuning interface, for every robot of a batch separately.  It sets the base-task PD gains (WbcBase::setBasePDGains, WbcBase.h:66-69),
+ * the swing-leg PD gains (setSwingLegPDGains, WbcBase.h:55-58), the three task weights (WeightedWbc::setWeights, WeightedWbc.h:48-52) and the
+ * joint-level kp / kd that update() hands to HybridJointHandle::setCommand (:250-254).
+ *   WBC         every robot of a WBC handle has a parameter row of BPMPC_WBC_PARAM_STRIDE doubles on the device; k_wbc reads robot b's row:
+ *                 [0..5]   base kp: position x, y, z, orientation x, y, z (the order of baseAccelPDTask.baseKp)      setBasePDGains
+ *                 [6..11]  base kd, same order                                                                     setBasePDGains
+ *                 [12,13]  swing-leg kp, kd                                                                        setSwingLegPDGains
+ *                 [14..16] weights: swing leg, base acceleration, contact force                                    setWeights
+ *                 [17]     friction coefficient of the WBC's pyramid             loadTasksSetting only: per robot is this engine's extension
+ *                 [18]     noContactMotionTask.tolerance                         likewise
+ *                 [19..24] torque limits per leg joint; nj / 2 entries are used  likewise
+ *                 [25..31] reserved, written as 0
+ *               Every row starts as what loadTasksSetting reads from task.info (the reference's dynamic_reconfigure server additionally calls the
+ *               callback once at start-up with the defaults of its .cfg, which then override task.info from the first tick; this engine
+ *               keeps task.info until the caller sets a row - the Python mirror offers those defaults as a preset).  The working-set budget (nWSR 20)
+ *               stays a constant of the handle.
+ *               bpmpc_wbc_get_params: row[32] = the task.info values (robot < 0) or the robot's current row; synchronises.
+ *               bpmpc_wbc_set_params: the rows of the robots with mask[b] != 0 (mask NULL: every robot below `batch`) are replaced by rows[b]
+ *               (n_rows == batch) or by rows[0] (n_rows == 1); robots outside the mask and at or beyond `batch` keep theirs.  Host arrays are
+ *               validated - every used entry finite; gains, weights, friction and limits not negative (the tolerance may have any sign) - and a
+ *               bad value returns BPMPC_ERR_INVALID_ARGUMENT, names the entry in bpmpc_last_error() and changes nothing; the call synchronises.
+ *               inputs_on_device != 0: mask and rows are device pointers (e.g. a [batch, 32] tensor), nothing is validated and the call only
+ *               enqueues on the WBC handle's stream, ordered like bpmpc_wbc_restart: a later controller tick on another stream waits for it.
+ *               bpmpc_wbc_reset_params: every row back to the task.info values.
+ *               batch > max_batch: BPMPC_ERR_CAPACITY.  A restart keeps the parameters, as starting() does: bpmpc_wbc_reset, bpmpc_wbc_restart and
+ *               bpmpc_controller_restart do not touch the rows.
+ *   controller  joint gains kp[nj], kd[nj] per robot (0 after create; restarts and bpmpc_controller_reset keep them), set by
+ *               bpmpc_controller_set_joint_gains (kp, kd: [n_rows][nj]; mask, n_rows, host / device as bpmpc_wbc_set_params; host values must be
+ *               finite and not negative; on the solver's stream).  k_tick_commands additionally forms the torque with which the reference's
+ *               hardware layer consumes the five-tuple (bipedal_gazebo/src/BipedalHWSim.cpp:174-175),
+ *                 joint_torque[b][j] = kp_j (posDes_j - q_j) + kd_j (velDes_j - v_j) + tau_j     (q, v: the joint entries of the tick's rbd)
+ *               which with zero gains is the WBC torque bit for bit.  bpmpc_controller_joint_outputs: every argument nullable; host_*
+ *               [batch*nj] receive the last tick's joint_torque and the current gains and make the call synchronise; dev_* receive the handle's
+ *               buffers (leading dimension the WBC's max_batch, like bpmpc_controller_device_outputs).
+ * Not reproduced: per-robot MPC cost weights, the SafetyChecker limits, InitialJointController.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_WBC_PARAM_STRIDE 32
+#define BPMPC_WBC_PARAM_BASE_KP 0
+#define BPMPC_WBC_PARAM_BASE_KD 6
+#define BPMPC_WBC_PARAM_SWING_KP 12
+#define BPMPC_WBC_PARAM_SWING_KD 13
+#define BPMPC_WBC_PARAM_WEIGHT_SWING_LEG 14
+#define BPMPC_WBC_PARAM_WEIGHT_BASE_ACCEL 15
+#define BPMPC_WBC_PARAM_WEIGHT_CONTACT_FORCE 16
+#define BPMPC_WBC_PARAM_FRICTION 17
+#define BPMPC_WBC_PARAM_CONTACT_TOLERANCE 18
+#define BPMPC_WBC_PARAM_TORQUE_LIMITS 19
+#define BPMPC_WBC_PARAM_RESERVED 25
+int bpmpc_wbc_get_params(const bpmpc_wbc* wbc, int robot, double* row);
+int bpmpc_wbc_set_params(bpmpc_wbc* wbc, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_wbc_reset_params(bpmpc_wbc* wbc);
+int bpmpc_controller_set_joint_gains(bpmpc_controller* controller, int batch, const int* mask, const double* kp, const double* kd, int n_rows,
+                                     int inputs_on_device);
+int bpmpc_controller_joint_outputs(bpmpc_controller* controller, int batch, double* host_torque, double* host_kp, double* host_kd,
+                                   double** dev_torque, double** dev_kp, double** dev_kd);
 
 #ifdef __cplusplus
 }
