@@ -761,6 +761,166 @@ class WeightedWbc:
         _check(load_library().bpmpc_wbc_reset_params(self._h))
 
 
+class KalmanParams:
+    """A parameter row of the Kalman state estimator (include/bpmpc.h "State estimation", BPMPC_EST_PARAM_STRIDE) with named fields: the seven
+    settings of KalmanFilterEstimate (LinearKalmanFilter.h:45-51), whose defaults are the values without arguments."""
+
+    STRIDE = 8
+    FIELDS = ("footRadius", "imuProcessNoisePosition", "imuProcessNoiseVelocity", "footProcessNoisePosition", "footSensorNoisePosition",
+              "footSensorNoiseVelocity", "footHeightSensorNoise")
+    DEFAULTS = (0.02, 0.02, 0.02, 0.002, 0.005, 0.1, 0.01)
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name, default in zip(self.FIELDS, self.DEFAULTS):
+            setattr(self, name, float(fields.get(name, default)))
+
+    @classmethod
+    def fromRow(cls, row):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
+
+    def toRow(self):
+        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0])
+
+
+class _SensorInputs(C.Structure):
+    NAMES = ("joint_pos", "joint_vel", "quat", "angular_vel_local", "linear_accel_local", "contact", "mode", "feet_heights", "odom_pos", "odom_quat",
+             "odom_lin_vel", "odom_ang_vel")
+    _fields_ = [(n, _ip if n in ("contact", "mode") else _dp) for n in NAMES]
+
+
+class _EstimatorOutputs(C.Structure):
+    _fields_ = [("rbd", _dp), ("x_hat", _dp), ("cov", _dp), ("xy_reset", _ip)]
+
+
+ESTIMATOR_KINDS = {"from_topic": 0, "kalman": 1}
+
+
+def _sensor_args(kind, nj, max_batch, joint_pos, joint_vel, quat=None, angular_vel_local=None, linear_accel_local=None, contact=None, mode=None,
+                 feet_heights=None, odom=None):
+    """Marshals the sensors of one update (bpmpc_estimator_update): checks what the kind needs - the Kalman filter its IMU arrays and exactly one
+    of contact / mode, the from-topic estimator odom = (position [B, 3], quaternion x y z w [B, 4], linear velocity [B, 3], angular velocity
+    [B, 3]) - and the shapes against the batch B = rows of joint_pos.  Returns (B, _SensorInputs, on_device, keep-alive); through _restart_args, so
+    device and host inputs are never mixed."""
+    if kind not in ESTIMATOR_KINDS:
+        raise ValueError("kind must be one of %s" % sorted(ESTIMATOR_KINDS))
+    shape = _shape(joint_pos)
+    if len(shape) not in (1, 2) or shape[-1] != nj:
+        raise ValueError("joint_pos must have the shape [%d] or [B, %d], got %s" % (nj, nj, list(shape)))
+    B = 1 if len(shape) == 1 else shape[0]
+    if B < 1 or B > max_batch:
+        raise ValueError("%d robots for an estimator of max_batch %d" % (B, max_batch))
+    if kind == "kalman":
+        if quat is None or angular_vel_local is None or linear_accel_local is None:
+            raise ValueError("the Kalman filter needs quat, angular_vel_local and linear_accel_local")
+        if contact is None and mode is None:
+            raise ValueError("no contact source: give contact or mode")
+        if contact is not None and mode is not None:
+            raise ValueError("two contact sources: give contact or mode, not both")
+        if odom is not None:
+            raise ValueError("odom belongs to the from-topic estimator")
+        odom = (None,) * 4
+    else:
+        if odom is None or len(odom) != 4 or any(o is None for o in odom):
+            raise ValueError("the from-topic estimator needs odom = (position, quaternion, linear velocity, angular velocity)")
+        contact = mode = feet_heights = None
+    specs = [(joint_pos, C.c_double, B * nj), (joint_vel, C.c_double, B * nj), (quat, C.c_double, B * 4), (angular_vel_local, C.c_double, B * 3),
+             (linear_accel_local, C.c_double, B * 3), (contact, C.c_int, B * 4), (mode, C.c_int, B), (feet_heights, C.c_double, B * 4),
+             (odom[0], C.c_double, B * 3), (odom[1], C.c_double, B * 4), (odom[2], C.c_double, B * 3), (odom[3], C.c_double, B * 3)]
+    ptrs, dev, keep = _restart_args(*specs)
+    return B, _SensorInputs(*ptrs), dev, keep
+
+
+class BatchedStateEstimate:
+    """BipedalController::updateStateEstimation (bipedal_controllers/src/BipedalController.cpp:360-405) for a batch of robots on one MI355X
+    (bpmpc_estimator): IMU, joint encoders and contact flags -> the rbd of BatchedController.tick.  kind "from_topic" is FromTopicStateEstimate, the
+    estimator the reference constructs; kind "kalman" is KalmanFilterEstimate, which the reference declares (LinearKalmanFilter.h) and does not
+    implement (its source file is empty): the filter is the one specified in include/bpmpc.h, per robot, its state kept on the handle.  taskFile
+    (None: the defaults of LinearKalmanFilter.h:45-51) is read for the keys kalmanFilter.<name>."""
+
+    def __init__(self, interface, kind="kalman", taskFile=None, max_batch=1, device=0):
+        if kind not in ESTIMATOR_KINDS:
+            raise ValueError("kind must be one of %s" % sorted(ESTIMATOR_KINDS))
+        self.interface, self.kind, self.max_batch = interface, kind, int(max_batch)
+        self.nj = interface.actuatedDofNum
+        self.generalizedCoordinatesNum = 6 + self.nj
+        self._h = C.c_void_p()
+        _check(load_library().bpmpc_estimator_create(interface.handle, None if taskFile is None else str(taskFile).encode(), ESTIMATOR_KINDS[kind],
+                                                     int(device), self.max_batch, C.byref(self._h)))
+        self.batch = self.max_batch
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.bpmpc_estimator_destroy(self._h)
+            self._h = None
+
+    def update(self, joint_pos, joint_vel, quat=None, angular_vel_local=None, linear_accel_local=None, contact=None, mode=None, feet_heights=None,
+               odom=None, period=0.0025, fetch=True):
+        """One update for B = len(joint_pos) robots.  numpy arrays, or float64 / int32 device tensors (then the call only enqueues on the
+        estimator's stream).  contact [B, 4] or mode [B] (e.g. planned_mode of the last tick) - exactly one for the Kalman kind.  fetch=True: returns
+        rbd [B, 2 (6 + nj)] (synchronises); False: returns None, see device_outputs and BatchedController.tick_estimated."""
+        B, inputs, dev, keep = _sensor_args(self.kind, self.nj, self.max_batch, joint_pos, joint_vel, quat, angular_vel_local, linear_accel_local,
+                                            contact, mode, feet_heights, odom)
+        rbd = np.zeros((B, 2 * self.generalizedCoordinatesNum)) if fetch else None
+        _check(load_library().bpmpc_estimator_update(self._h, B, C.byref(inputs), dev, C.c_double(period), _d(rbd)))
+        del keep
+        self.batch = B
+        return rbd
+
+    def reset(self, mask=None):
+        """x_hat = 0, P = 100 I for the robots with mask[b] != 0 (None: every robot); the others do not change by one bit."""
+        B = self.max_batch if mask is None else _count(mask)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, B))
+        _check(load_library().bpmpc_estimator_reset(self._h, B, mp, dev))
+        del keep
+
+    def getState(self, batch=None):
+        """(x_hat [B, 18], P [B, 18, 18]) of the first B robots (None: the batch of the last update); synchronises."""
+        B = int(batch or self.batch)
+        x, P = np.zeros((B, 18)), np.zeros((B, 18, 18))
+        _check(load_library().bpmpc_estimator_get_state(self._h, B, _d(x), _d(P)))
+        return x, P
+
+    def setState(self, x_hat, cov=None, mask=None):
+        """x_hat [B, 18] and, unless None, P [B, 18, 18] of the robots with mask[b] != 0 (None: every one of the B)."""
+        shape = _shape(x_hat)
+        if len(shape) != 2 or shape[1] != 18:
+            raise ValueError("x_hat must have the shape [B, 18], got %s" % list(shape))
+        B = shape[0]
+        (mp, xp, cp), dev, keep = _restart_args((mask, C.c_int, B), (x_hat, C.c_double, B * 18), (cov, C.c_double, B * 18 * 18))
+        _check(load_library().bpmpc_estimator_set_state(self._h, B, mp, xp, cp, dev))
+        del keep
+
+    def getParams(self, robot=-1):
+        """The parameter row [8] of `robot` (KalmanParams.fromRow names its entries), or with robot < 0 the values every row starts from."""
+        row = np.zeros(KalmanParams.STRIDE)
+        _check(load_library().bpmpc_estimator_get_params(self._h, int(robot), _d(row)))
+        return row
+
+    def setParams(self, rows, mask=None):
+        """rows [8], [1, 8] or [B, 8]; mask as WeightedWbc.setParams.  numpy rows are validated (finite, not negative, the three sensor noises
+        positive) and the call synchronises; device tensors are only enqueued, ordered before the next update."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], KalmanParams.STRIDE, self.max_batch)
+        _check(load_library().bpmpc_estimator_set_params(self._h, B, mp, rp, n_rows, dev))
+        del keep
+
+    def resetParams(self):
+        _check(load_library().bpmpc_estimator_reset_params(self._h))
+
+    def device_outputs(self):
+        """rbd, x_hat, cov, xy_reset of the last update where they live: a dict of DeviceArray over the batch of the last update."""
+        o = _EstimatorOutputs()
+        _check(load_library().bpmpc_estimator_device_outputs(self._h, C.byref(o)))
+        B = self.batch
+        shapes = {"rbd": (B, 2 * self.generalizedCoordinatesNum), "x_hat": (B, 18), "cov": (B, 18, 18), "xy_reset": (B,)}
+        return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k == "xy_reset" else "<f8") for k, shp in shapes.items()}
+
+
 class _TickOutputs(C.Structure):
     _fields_ = [("x_obs", _dp), ("x_opt", _dp), ("u_opt", _dp), ("joint_cmd", _dp), ("wbc_solution", _dp), ("planned_mode", _ip), ("wbc_status", _ip),
                 ("safe", _ip)]
@@ -804,34 +964,62 @@ class BatchedController:
         return {"x_obs": (B, self.nx), "x_opt": (B, self.nx), "u_opt": (B, self.nu), "joint_cmd": (B, 3, self.nj),
                 "wbc_solution": (B, self.wbc.numDecisionVars), "planned_mode": (B,), "wbc_status": (B,), "safe": (B,)}
 
+    def _device_f64(self, a, count):
+        """pointer of a float64 device tensor of `count` entries (a tick input), None for anything that is not a device tensor"""
+        if not (hasattr(a, "data_ptr") and getattr(a, "is_cuda", False)):
+            return None
+        if str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.numel() != count:
+            raise ValueError("device inputs must be contiguous float64 tensors of the batch's size")
+        return C.cast(C.c_void_p(a.data_ptr()), _dp)
+
+    def _run_tick(self, fetch, call):
+        """The part tick and tick_estimated share: host output arrays (fetch), the call - call(host_out pointer or None) -, the joint outputs."""
+        B = self.mpc.batch
+        out, ptrs = None, None
+        if fetch:
+            out = {k: np.zeros(shp, np.int32 if k in ("planned_mode", "wbc_status", "safe") else np.float64) for k, shp in self._shapes(B).items()}
+            ptrs = _TickOutputs(*[(_i if out[k].dtype == np.int32 else _d)(out[k]) for k in self.NAMES])
+        _check(call(C.byref(ptrs) if fetch else None))
+        if fetch:
+            for k in self.JOINT_NAMES:             # every key of device_outputs has its host copy
+                out[k] = np.zeros((B, self.nj))
+            _check(load_library().bpmpc_controller_joint_outputs(self._h, B, *[_d(out[k]) for k in self.JOINT_NAMES], None, None, None))
+        return out
+
     def tick(self, t, rbd, period=0.0025, fetch=True):
         """One tick for the solver's batch.  t: [batch] (or a scalar), rbd: [batch, 2 (6 + nj)].  fetch=True: returns a dict of numpy arrays
         (x_obs, x_opt, u_opt, joint_cmd [batch, 3, nj] = position, velocity, torque, wbc_solution, planned_mode, wbc_status, safe); False: only
         enqueues (see device_outputs).  joint_torque [batch, nj] = kp (posDes - q) + kd (velDes - v) + torque with the robots' joint gains
         (setJointGains; the WBC torque while they are zero) and the gains themselves, joint_kp / joint_kd [batch, nj], come with them."""
         B = self.mpc.batch
-        on_device = hasattr(rbd, "data_ptr") and getattr(rbd, "is_cuda", False)
+        rp = self._device_f64(rbd, B * 2 * self.wbc.generalizedCoordinatesNum)
+        on_device = rp is not None
         if on_device:
-            if not (hasattr(t, "data_ptr") and t.is_cuda):
+            tp, keep = self._device_f64(t, B), None
+            if tp is None:
                 raise ValueError("t and rbd must both be device tensors or both host arrays")
-            for a, n in ((t, B), (rbd, B * 2 * self.wbc.generalizedCoordinatesNum)):
-                if str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.numel() != n:
-                    raise ValueError("device inputs must be contiguous float64 tensors of the batch's size")
-            tp, rp, keep = C.cast(C.c_void_p(t.data_ptr()), _dp), C.cast(C.c_void_p(rbd.data_ptr()), _dp), None
         else:
             tt = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
             rr = _f64(rbd).reshape(B, 2 * self.wbc.generalizedCoordinatesNum)
             tp, rp, keep = _d(tt), _d(rr), (tt, rr)
-        out, ptrs = None, None
-        if fetch:
-            out = {k: np.zeros(shp, np.int32 if k in ("planned_mode", "wbc_status", "safe") else np.float64) for k, shp in self._shapes(B).items()}
-            ptrs = _TickOutputs(*[(_i if out[k].dtype == np.int32 else _d)(out[k]) for k in self.NAMES])
-        _check(load_library().bpmpc_controller_tick(self._h, B, tp, rp, int(on_device), C.c_double(period), C.byref(ptrs) if fetch else None))
+        out = self._run_tick(fetch, lambda host_out: load_library().bpmpc_controller_tick(self._h, B, tp, rp, int(on_device), C.c_double(period), host_out))
         del keep
-        if fetch:
-            for k in self.JOINT_NAMES:             # every key of device_outputs has its host copy
-                out[k] = np.zeros((B, self.nj))
-            _check(load_library().bpmpc_controller_joint_outputs(self._h, B, *[_d(out[k]) for k in self.JOINT_NAMES], None, None, None))
+        return out
+
+    def tick_estimated(self, t, estimator, period=0.0025, fetch=True):
+        """tick on the rbd that `estimator` (BatchedStateEstimate) holds on the device after its last update (bpmpc_controller_tick_estimated):
+        the solver's stream waits for an update that was only enqueued, so estimator.update(..., fetch=False) followed by this call needs no
+        synchronisation.  t: [batch] numpy (or a scalar) or a float64 device tensor; the batch must be that of the estimator's last update.
+        Returns what tick returns."""
+        B = self.mpc.batch
+        tp = self._device_f64(t, B)
+        on_device, keep = tp is not None, t
+        if not on_device:
+            keep = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
+            tp = _d(keep)
+        out = self._run_tick(fetch, lambda host_out: load_library().bpmpc_controller_tick_estimated(self._h, estimator._h, B, tp, int(on_device),
+                                                                                                     C.c_double(period), host_out))
+        del keep
         return out
 
     def setJointGains(self, kp, kd, mask=None):

@@ -1,5 +1,6 @@
 // Host-only part of the C ABI (include/bpmpc.h): model ingest, the reference-manager pre-pass and the error model (capi_internal.h).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
@@ -7,6 +8,8 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "estimator.h"
+#include "info_tree.h"
 #include "reference_gen.h"
 
 struct bpmpc_model { bpmpc::RobotModel rm; };
@@ -26,6 +29,32 @@ int translate(const std::exception& e, int fallback) {
   if (dynamic_cast<const std::invalid_argument*>(&e)) return BPMPC_ERR_INVALID_ARGUMENT;
   if (dynamic_cast<const std::length_error*>(&e)) return BPMPC_ERR_CAPACITY;
   return fallback;
+}
+
+namespace {
+const char* const kEstParamNames[] = {"footRadius", "imuProcessNoisePosition", "imuProcessNoiseVelocity", "footProcessNoisePosition",
+                                      "footSensorNoisePosition", "footSensorNoiseVelocity", "footHeightSensorNoise"};
+}
+
+void estimator_check_param_row(const char* who, const double* row, int r) {
+  for (int e = 0; e < kEstParamStride - 1; ++e) {
+    const bool positive = e >= 4;
+    if (!std::isfinite(row[e]) || row[e] < 0.0 || (positive && row[e] == 0.0))
+      throw std::invalid_argument(std::string(who) + ": row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + kEstParamNames[e] + ") is " +
+                                  (!std::isfinite(row[e]) ? "not finite" : row[e] < 0.0 ? "negative" : "zero"));
+  }
+}
+
+EstSettings estimator_load_settings(const char* task_info_path) {
+  EstSettings s{0.02, 0.02, 0.02, 0.002, 0.005, 0.1, 0.01, 0.0};      // LinearKalmanFilter.h:45-51
+  if (task_info_path) {
+    // [OCS2-upstream] loadData::loadPtreeValue keeps the member's initial value when the key is absent
+    const auto t = read_info_file(task_info_path);
+    double* v = &s.foot_radius;
+    for (int e = 0; e < kEstParamStride - 1; ++e) (void)t->get(std::string("kalmanFilter.") + kEstParamNames[e], v + e);
+    estimator_check_param_row("kalmanFilter settings", v, 0);
+  }
+  return s;
 }
 }  // namespace bpmpc
 
@@ -130,6 +159,23 @@ int bpmpc_model_joint_name(const bpmpc_model* m, int j, char* out, int capacity)
   if ((int)s.size() + 1 > capacity) return fail(BPMPC_ERR_CAPACITY, "name buffer too small");
   std::memcpy(out, s.c_str(), s.size() + 1);
   return (int)s.size();
+}
+
+int bpmpc_estimator_load_params(const char* task_info_path, double* row) {
+  if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_estimator_load_params: null row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    const EstSettings s = estimator_load_settings(task_info_path);
+    std::copy(&s.foot_radius, &s.foot_radius + kEstParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_estimator_check_params(const double* rows, int n_rows) {
+  if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_estimator_check_params: null rows");
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) estimator_check_param_row("bpmpc_estimator_check_params", rows + (size_t)r * kEstParamStride, r);
+    return (int)BPMPC_OK;
+  });
 }
 
 int bpmpc_gait_create(const bpmpc_model* m, bpmpc_gait** out) {

@@ -14,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "estimator.h"
 #include "solver.h"
 #include "wbc.h"
 #include "kernels/tick.h"
@@ -44,6 +45,48 @@ void free_all(bpmpc_controller* c) {
   for (void* p : {(void*)c->d_yaw, (void*)c->d_t, (void*)c->d_rbd, (void*)c->d_xobs, (void*)c->d_xopt, (void*)c->d_uopt, (void*)c->d_cmd, (void*)c->d_mode,
                   (void*)c->d_safe, (void*)c->d_mask, (void*)c->d_kp, (void*)c->d_kd, (void*)c->d_torque, (void*)c->d_kp_in, (void*)c->d_kd_in})
     if (p) (void)hipFree(p);
+}
+
+// the refusals of a tick: a completed run of an SQP solver since the last setup, the batch of that setup, the WBC's capacity
+void check_tick(const bpmpc_controller* c, int batch, const char* who) {
+  check_policy(c->s);
+  if (batch != c->s->batch) throw std::invalid_argument(std::string(who) + ": batch differs from the batch of the solver's last setup");
+  if (batch > c->max_batch) throw std::length_error(std::string(who) + ": batch exceeds the WBC's max_batch");
+}
+
+// the three launches of a tick on the solver's stream, from device inputs
+void enqueue_tick(bpmpc_controller* c, int batch, const double* dt, const double* drbd) {
+  bpmpc_solver* s = c->s;
+  TickArgs a = policy_args(s, batch);
+  a.t = dt; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs; a.x_loop = s->tick_x; a.safe = c->d_safe;
+  a.x_opt = c->d_xopt; a.u_opt = c->d_uopt; a.mode = c->d_mode;
+  kl::tick_observe_policy(c->nj, batch, s->stream, s->d_model, a);
+  HIP_CHECK(hipGetLastError());
+  s->loop_from_tick = true;          // the next setup_commands(x0 = NULL) starts from tick_x (until the next rollout)
+  wbc_launch_on(c->w, batch, c->d_xopt, c->d_uopt, drbd, c->d_mode, s->stream);
+  TickCommandArgs ca{};
+  ca.batch = batch; ca.x_opt = c->d_xopt; ca.u_opt = c->d_uopt; ca.sol = c->w->d_sol; ca.rbd = drbd; ca.kp = c->d_kp; ca.kd = c->d_kd;
+  ca.cmd = c->d_cmd; ca.joint_torque = c->d_torque;
+  kl::tick_commands(c->nj, s->stream, ca);
+  HIP_CHECK(hipGetLastError());
+}
+
+// the host copies of a tick's outputs (host_out NULL: nothing is copied or synchronised)
+void fetch_tick(bpmpc_controller* c, int batch, const bpmpc_tick_outputs* host_out) {
+  if (!host_out) return;
+  bpmpc_solver* s = c->s;
+  const size_t B = batch;
+  const bpmpc_tick_outputs& o = *host_out;
+  auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream)); };
+  down(o.x_obs, c->d_xobs, B * c->nx * sizeof(double));
+  down(o.x_opt, c->d_xopt, B * c->nx * sizeof(double));
+  down(o.u_opt, c->d_uopt, B * c->nx * sizeof(double));
+  down(o.joint_cmd, c->d_cmd, B * 3 * c->nj * sizeof(double));
+  down(o.wbc_solution, c->w->d_sol, B * c->n * sizeof(double));
+  down(o.planned_mode, c->d_mode, B * sizeof(int));
+  down(o.wbc_status, c->w->d_status, B * sizeof(int));
+  down(o.safe, c->d_safe, B * sizeof(int));
+  HIP_CHECK(hipStreamSynchronize(s->stream));
 }
 
 }  // namespace
@@ -136,9 +179,7 @@ int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const
   if (!c || !t || !rbd) { set_last_error("bpmpc_controller_tick: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
   return guarded(BPMPC_ERR_DEVICE, [&] {
     bpmpc_solver* s = c->s;
-    check_policy(s);
-    if (batch != s->batch) throw std::invalid_argument("bpmpc_controller_tick: batch differs from the batch of the solver's last setup");
-    if (batch > c->max_batch) throw std::length_error("bpmpc_controller_tick: batch exceeds the WBC's max_batch");
+    check_tick(c, batch, "bpmpc_controller_tick");
     HIP_CHECK(hipSetDevice(c->device));
     const size_t B = batch;
     const double *dt = t, *drbd = rbd;
@@ -147,31 +188,32 @@ int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const
       HIP_CHECK(hipMemcpyAsync(c->d_rbd, rbd, B * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, s->stream));
       dt = c->d_t; drbd = c->d_rbd;
     }
-    TickArgs a = policy_args(s, batch);
-    a.t = dt; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs; a.x_loop = s->tick_x; a.safe = c->d_safe;
-    a.x_opt = c->d_xopt; a.u_opt = c->d_uopt; a.mode = c->d_mode;
-    kl::tick_observe_policy(c->nj, batch, s->stream, s->d_model, a);
-    HIP_CHECK(hipGetLastError());
-    s->loop_from_tick = true;          // the next setup_commands(x0 = NULL) starts from tick_x (until the next rollout)
-    wbc_launch_on(c->w, batch, c->d_xopt, c->d_uopt, drbd, c->d_mode, s->stream);
-    TickCommandArgs ca{};
-    ca.batch = batch; ca.x_opt = c->d_xopt; ca.u_opt = c->d_uopt; ca.sol = c->w->d_sol; ca.rbd = drbd; ca.kp = c->d_kp; ca.kd = c->d_kd;
-    ca.cmd = c->d_cmd; ca.joint_torque = c->d_torque;
-    kl::tick_commands(c->nj, s->stream, ca);
-    HIP_CHECK(hipGetLastError());
-    if (host_out) {
-      const bpmpc_tick_outputs& o = *host_out;
-      auto down = [&](void* dst, const void* src, size_t bytes) { if (dst) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream)); };
-      down(o.x_obs, c->d_xobs, B * c->nx * sizeof(double));
-      down(o.x_opt, c->d_xopt, B * c->nx * sizeof(double));
-      down(o.u_opt, c->d_uopt, B * c->nx * sizeof(double));
-      down(o.joint_cmd, c->d_cmd, B * 3 * c->nj * sizeof(double));
-      down(o.wbc_solution, c->w->d_sol, B * c->n * sizeof(double));
-      down(o.planned_mode, c->d_mode, B * sizeof(int));
-      down(o.wbc_status, c->w->d_status, B * sizeof(int));
-      down(o.safe, c->d_safe, B * sizeof(int));
-      HIP_CHECK(hipStreamSynchronize(s->stream));
+    enqueue_tick(c, batch, dt, drbd);
+    fetch_tick(c, batch, host_out);
+  });
+}
+
+// bpmpc_controller_tick on the rbd the estimator holds on the device: the solver's stream waits for an update that was only enqueued, and the
+// estimator's stream for this tick before its next update overwrites rbd
+int bpmpc_controller_tick_estimated(bpmpc_controller* c, bpmpc_estimator* e, int batch, const double* t, int inputs_on_device, double period,
+                                    const bpmpc_tick_outputs* host_out) {
+  (void)period;      // as bpmpc_controller_tick: the WBC takes it and does not use it; the filter's dt is the period of bpmpc_estimator_update
+  if (!c || !e || !t) { set_last_error("bpmpc_controller_tick_estimated: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(BPMPC_ERR_DEVICE, [&] {
+    bpmpc_solver* s = c->s;
+    if (e->nj != c->nj) throw std::invalid_argument("bpmpc_controller_tick_estimated: the estimator and the controller are built for different robots");
+    if (e->device != c->device) throw std::invalid_argument("bpmpc_controller_tick_estimated: the estimator and the controller live on different devices");
+    check_tick(c, batch, "bpmpc_controller_tick_estimated");
+    HIP_CHECK(hipSetDevice(c->device));
+    estimator_before_foreign_read(e, batch, s->stream);      // refuses a batch without estimates before anything is enqueued
+    const double* dt = t;
+    if (!inputs_on_device) {
+      HIP_CHECK(hipMemcpyAsync(c->d_t, t, (size_t)batch * sizeof(double), hipMemcpyHostToDevice, s->stream));
+      dt = c->d_t;
     }
+    enqueue_tick(c, batch, dt, e->d_rbd);
+    estimator_after_foreign_read(e, s->stream);
+    fetch_tick(c, batch, host_out);
   });
 }
 

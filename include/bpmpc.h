@@ -503,6 +503,92 @@ int bpmpc_controller_set_joint_gains(bpmpc_controller* controller, int batch, co
 int bpmpc_controller_joint_outputs(bpmpc_controller* controller, int batch, double* host_torque, double* host_kp, double* host_kd,
                                    double** dev_torque, double** dev_kp, double** dev_kd);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * State estimation = BipedalController::updateStateEstimation (bipedal_controllers/src/BipedalController.cpp:188, :360-405) for a BATCH of robots:
+ * what a simulator or a robot delivers - IMU quaternion, body-frame angular velocity and linear acceleration, joint encoders, contact flags -
+ * becomes the rbd of bpmpc_controller_tick, [zyx, position, joints, angular velocity (world), linear velocity, joint velocities], on the device.
+ *   front end, both kinds (bipedal_estimation/src/StateEstimateBase.cpp:34-63, StateEstimateBase.h:70-79): the joints go into their slots unchanged;
+ *     zyx = quatToZyx(quat) with its one-sided clamp asin(min(-2 (x z - w y), .99999)); angular velocity (world) = E(zyx) thetadot, thetadot the
+ *     ZYX Euler rates of the local angular velocity (R(zyx) w_local = E(zyx) thetadot).  zyxOffset_ is zero in the reference and is not reproduced.
+ *   BPMPC_ESTIMATOR_FROM_TOPIC (FromTopicEstimate.cpp:28-47, the estimator the reference constructs, :354-358): zyx = quatToZyx(odom_quat), angular
+ *     velocity = odom_ang_vel as given, position = odom_pos, linear velocity = odom_lin_vel; the IMU pointers may be NULL.
+ *   BPMPC_ESTIMATOR_KALMAN: KalmanFilterEstimate.  The reference DECLARES it (LinearKalmanFilter.h: seven noise settings, a_, b_, c_, q_, p_, r_,
+ *     xHat_, ps_, vs_) and does not implement it: src/LinearKalmanFilter.cpp is an empty file.  What runs here is the linear Kalman filter of the
+ *     project that header cites (qiayuanl/legged_control), recalled and unpinned; this comment is its specification.
+ *     Sizes: 4 contact points, state n = 18: x_hat = [p (3), v (3), foot positions (12)], observations m = 28.  After create / reset x_hat = 0, P = 100 I.
+ *     C (28 x 18), contact i: rows 3i..3i+2 = [I3 at columns 0..2, -I3 at columns 6+3i..], rows 12+3i.. = [I3 at columns 3..5], row 24+i = a single 1
+ *     at column 6+3i+2.  One update with dt = period:
+ *       1. A = I with A[0:3,3:6] = dt I; B (18 x 3): rows 0..2 = dt^2/2 I, rows 3..5 = dt I
+ *       2. Q diagonal: dt/20 imuProcessNoisePosition (0..2), dt 9.81/20 imuProcessNoiseVelocity (3..5), dt footProcessNoisePosition (6..17); the foot
+ *          block of a contact whose flag is 0 is multiplied by 100
+ *       3. R diagonal: footSensorNoisePosition (0..11), footSensorNoiseVelocity (12..23), footHeightSensorNoise (24..27); the velocity block and the
+ *          height entry of a contact whose flag is 0 are multiplied by 100, the position block never
+ *       4. kinematics with the base at the origin, q = [0, zyx, joints], v = [0, thetadot, joint_vel]: contact positions p_i and velocities v_i;
+ *          ps_i = -p_i with footRadius added to its z, vs_i = -v_i, y = [ps, vs, feet_heights]
+ *       5. accel = R(zyx) linear_accel_local + (0, 0, -9.81); x- = A x_hat + B accel; P- = A P A' + Q
+ *       6. S = C P- C' + R; x_hat = x- + P- C' S^-1 (y - C x-); P = (I - P- C' S^-1 C) P-; P = (P + P') / 2
+ *       7. if det P[0:2,0:2] > 1e-6: P[0:2,2:] = 0, P[2:,0:2] = 0, P[0:2,0:2] /= 10, reported as xy_reset[b] = 1 (else 0)
+ *       8. rbd position = x_hat[0:3], linear velocity = x_hat[3:6]
+ *     S is symmetric positive definite (R > 0); k_estimate solves with a Gauss-Jordan elimination without pivoting.
+ *     Not reproduced: the odometry / tf publishing and updateFromTopic of the cited filter; getMode() (stanceLeg2ModeNumber).
+ *   contact flags (Kalman kind): exactly one of `contact` ([batch*4], non-zero = closed) and `mode` ([batch], mode number 0..3 expanded by
+ *     modeNumber2StanceLeg, MotionPhaseDefinition.h:57-76; e.g. the planned_mode device output of the last tick, which is what the reference passes
+ *     today, :377) is non-NULL, otherwise BPMPC_ERR_INVALID_ARGUMENT.  Host modes outside 0..3 are refused (BPMPC_ERR_INVALID_ARGUMENT); device
+ *     modes cannot be looked at without a synchronisation and are not: a device value outside 0..3 counts as mode 0, all four contacts open.
+ *   settings: a parameter row of BPMPC_EST_PARAM_STRIDE doubles per robot, [footRadius, imuProcessNoisePosition, imuProcessNoiseVelocity,
+ *     footProcessNoisePosition, footSensorNoisePosition, footSensorNoiseVelocity, footHeightSensorNoise, reserved 0].  Every row starts as the keys
+ *     kalmanFilter.<name> of task_info_path; an absent key keeps the default of LinearKalmanFilter.h:45-51 (0.02, 0.02, 0.02, 0.002, 0.005, 0.1,
+ *     0.01: loadPtreeValue semantics), a NULL path gives the defaults.  bpmpc_estimator_get_params / set_params / reset_params have the shapes, masks,
+ *     n_rows and host / device semantics of bpmpc_wbc_get_params / set_params / reset_params; host rows are validated - every entry finite and not
+ *     negative, the three sensor noises strictly positive - and a bad entry is named in bpmpc_last_error() and changes nothing.
+ *   streams: the handle has its own stream.  inputs_on_device != 0: every non-NULL member of bpmpc_sensor_inputs (masks, rows, states likewise) is
+ *     a device pointer and the call only enqueues; host arrays are copied first.  bpmpc_estimator_update with host_rbd receives rbd[batch*2*(6+nj)]
+ *     and synchronises; with NULL it is only enqueued.  bpmpc_controller_tick_estimated is bpmpc_controller_tick with rbd = the estimator's device
+ *     buffer (t: host or device by inputs_on_device): the solver's stream first waits for the estimator's pending update and the estimator's stream
+ *     then waits for the tick, so a caller with device inputs never synchronises by hand.  Its outputs are the bits of bpmpc_estimator_update
+ *     followed by bpmpc_controller_tick(rbd = dev_out.rbd, inputs_on_device = 1).  Its batch must be the batch of the estimator's last update
+ *     (else BPMPC_ERR_INVALID_ARGUMENT, also before the first update: the other rows of rbd hold no estimate), besides what bpmpc_controller_tick
+ *     asks of it; its period is accepted and not used, as that of bpmpc_controller_tick (the filter's dt is the period of the update).
+ *   state: bpmpc_estimator_reset puts the robots of mask (NULL: every robot below batch) back to x_hat = 0, P = 100 I; bpmpc_estimator_set_state
+ *     writes x_hat[batch*18] and, unless NULL, cov[batch*18*18] of the robots of mask (NULL: all; host values must be finite);
+ *     bpmpc_estimator_get_state copies them to the host (either pointer nullable; synchronises).  Robots outside a mask do not change by one
+ *     bit.  bpmpc_controller_restart does not touch the estimator.  bpmpc_estimator_device_outputs: rbd, x_hat, cov, xy_reset where they live
+ *     (leading dimension max_batch).
+ * Null handles and required pointers: BPMPC_ERR_INVALID_ARGUMENT ("null" in bpmpc_last_error()); batch > max_batch: BPMPC_ERR_CAPACITY.
+ * ------------------------------------------------------------------------------------------------------------- */
+enum { BPMPC_ESTIMATOR_FROM_TOPIC = 0, BPMPC_ESTIMATOR_KALMAN = 1 };
+#define BPMPC_EST_PARAM_STRIDE 8
+typedef struct bpmpc_estimator bpmpc_estimator;
+typedef struct {
+  const double *joint_pos, *joint_vel;                  /* [batch*nj] */
+  const double *quat;                                   /* [batch*4] x y z w (the order of imuSensorHandle_.getOrientation(), :379-381) */
+  const double *angular_vel_local, *linear_accel_local; /* [batch*3] IMU frame = base frame */
+  const int *contact;                                   /* [batch*4] nullable: contact flags of the four contact points */
+  const int *mode;                                      /* [batch] nullable: mode number 0..3 */
+  const double *feet_heights;                           /* [batch*4] nullable: 0 (flat ground) */
+  const double *odom_pos, *odom_quat, *odom_lin_vel, *odom_ang_vel;   /* FROM_TOPIC only: [batch*3], [batch*4] x y z w, [batch*3], [batch*3] */
+} bpmpc_sensor_inputs;
+typedef struct { double *rbd, *x_hat, *cov; int *xy_reset; } bpmpc_estimator_outputs;
+int bpmpc_estimator_create(const bpmpc_model* model, const char* task_info_path, int kind, int device, int max_batch, bpmpc_estimator** out);
+void bpmpc_estimator_destroy(bpmpc_estimator* estimator);
+int bpmpc_estimator_update(bpmpc_estimator* estimator, int batch, const bpmpc_sensor_inputs* inputs, int inputs_on_device, double period,
+                           double* host_rbd);
+int bpmpc_estimator_device_outputs(bpmpc_estimator* estimator, bpmpc_estimator_outputs* dev_out);
+int bpmpc_estimator_reset(bpmpc_estimator* estimator, int batch, const int* mask, int inputs_on_device);
+int bpmpc_estimator_get_state(bpmpc_estimator* estimator, int batch, double* x_hat, double* cov);
+int bpmpc_estimator_set_state(bpmpc_estimator* estimator, int batch, const int* mask, const double* x_hat, const double* cov, int inputs_on_device);
+int bpmpc_estimator_get_params(const bpmpc_estimator* estimator, int robot, double* row);
+int bpmpc_estimator_set_params(bpmpc_estimator* estimator, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_estimator_reset_params(bpmpc_estimator* estimator);
+/* Two helpers beside the handle, host only: they are the settings ingest of bpmpc_estimator_create and the row validation of
+ * bpmpc_estimator_set_params as functions of their own, so that a configuration can be checked - and both are tested - on a machine without a
+ * device, where no handle can be created.  load_params: row[8] = what every row of a handle created with this task_info_path (nullable) starts
+ * as.  check_params: rows[n_rows*8] as set_params validates host rows; BPMPC_ERR_INVALID_ARGUMENT names the entry. */
+int bpmpc_estimator_load_params(const char* task_info_path, double* row);
+int bpmpc_estimator_check_params(const double* rows, int n_rows);
+int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimator* estimator, int batch, const double* t, int inputs_on_device,
+                                    double period, const bpmpc_tick_outputs* host_out);
+
 #ifdef __cplusplus
 }
 #endif
