@@ -25,6 +25,7 @@ struct bpmpc_controller {
   bpmpc_solver* s = nullptr;
   bpmpc_wbc* w = nullptr;
   int device = 0, max_batch = 0, nj = 0, nx = 0, nv = 0, n = 0;
+  DeviceBuffers mem;      // every d_* below
   double *d_yaw = nullptr, *d_t = nullptr, *d_rbd = nullptr, *d_xobs = nullptr, *d_xopt = nullptr, *d_uopt = nullptr, *d_cmd = nullptr;
   int *d_mode = nullptr, *d_safe = nullptr, *d_mask = nullptr;
   double *d_kp = nullptr, *d_kd = nullptr, *d_torque = nullptr;      // [max_batch][nj]: joint gains (0 after create), the last tick's joint_torque
@@ -39,12 +40,6 @@ TickArgs policy_args(const bpmpc_solver* s, int batch) {
   a.batch = batch; a.N = s->settings.max_nodes; a.feedback = s->feedback();
   a.p_grid = bf.p_grid; a.g_nodes = bf.g_nodes; a.g_kind = bf.g_kind; a.g_mode = bf.g_mode; a.g_time = bf.g_time; a.x = bf.x; a.u = bf.u; a.K = bf.K;
   return a;
-}
-
-void free_all(bpmpc_controller* c) {
-  for (void* p : {(void*)c->d_yaw, (void*)c->d_t, (void*)c->d_rbd, (void*)c->d_xobs, (void*)c->d_xopt, (void*)c->d_uopt, (void*)c->d_cmd, (void*)c->d_mode,
-                  (void*)c->d_safe, (void*)c->d_mask, (void*)c->d_kp, (void*)c->d_kd, (void*)c->d_torque, (void*)c->d_kp_in, (void*)c->d_kd_in})
-    if (p) (void)hipFree(p);
 }
 
 // the refusals of a tick: a completed run of an SQP solver since the last setup, the batch of that setup, the WBC's capacity
@@ -132,25 +127,17 @@ int bpmpc_controller_create(bpmpc_solver* s, bpmpc_wbc* w, bpmpc_controller** ou
     if (s->settings.device != w->device) throw std::invalid_argument("bpmpc_controller_create: the solver and the WBC live on different devices");
     c->s = s; c->w = w; c->device = w->device; c->max_batch = w->max_batch; c->nj = w->rm.nj; c->nx = s->nx; c->nv = w->nv; c->n = w->n;
     HIP_CHECK(hipSetDevice(c->device));
-    const size_t B = c->max_batch;
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_yaw), B * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_t), B * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_rbd), B * 2 * c->nv * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_xobs), B * c->nx * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_xopt), B * c->nx * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_uopt), B * c->nx * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_cmd), B * 3 * c->nj * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_mode), B * sizeof(int)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_safe), B * sizeof(int)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c->d_mask), B * sizeof(int)));
-    for (double** p : {&c->d_kp, &c->d_kd, &c->d_torque, &c->d_kp_in, &c->d_kd_in}) HIP_CHECK(hipMalloc(reinterpret_cast<void**>(p), B * c->nj * sizeof(double)));
-    HIP_CHECK(hipMemset(c->d_kp, 0, B * c->nj * sizeof(double)));
-    HIP_CHECK(hipMemset(c->d_kd, 0, B * c->nj * sizeof(double)));
-    HIP_CHECK(hipMemset(c->d_torque, 0, B * c->nj * sizeof(double)));
-    HIP_CHECK(hipMemset(c->d_yaw, 0, B * sizeof(double)));       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
+    const size_t B = c->max_batch, nj = c->nj;
+    DeviceBuffers& m = c->mem;
+    c->d_yaw = m.alloc<double>(B, true);       // yawLast of BipedalController::starting: the first observation's yaw unwraps from 0
+    c->d_t = m.alloc<double>(B); c->d_rbd = m.alloc<double>(B * 2 * c->nv);
+    c->d_xobs = m.alloc<double>(B * c->nx); c->d_xopt = m.alloc<double>(B * c->nx); c->d_uopt = m.alloc<double>(B * c->nx); c->d_cmd = m.alloc<double>(B * 3 * nj);
+    c->d_mode = m.alloc<int>(B); c->d_safe = m.alloc<int>(B); c->d_mask = m.alloc<int>(B);
+    c->d_kp = m.alloc<double>(B * nj, true); c->d_kd = m.alloc<double>(B * nj, true); c->d_torque = m.alloc<double>(B * nj, true);
+    c->d_kp_in = m.alloc<double>(B * nj); c->d_kd_in = m.alloc<double>(B * nj);
     HIP_CHECK(hipDeviceSynchronize());
   });
-  if (rc != BPMPC_OK) { free_all(c.get()); return rc; }
+  if (rc != BPMPC_OK) { c->mem.release(); return rc; }
   *out = c.release();
   return BPMPC_OK;
 }
@@ -159,14 +146,12 @@ void bpmpc_controller_destroy(bpmpc_controller* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();           // a tick may still be in flight on the solver's stream
-  free_all(c);
+  c->mem.release();
   delete c;
 }
 
 int bpmpc_controller_reset(bpmpc_controller* c) {
-  if (!c) { set_last_error("null controller handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_DEVICE, [&] {
-    HIP_CHECK(hipSetDevice(c->device));
+  return guarded(c, BPMPC_ERR_DEVICE, "null controller handle", [&] {
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipMemset(c->d_yaw, 0, (size_t)c->max_batch * sizeof(double)));
     HIP_CHECK(hipDeviceSynchronize());
@@ -176,19 +161,11 @@ int bpmpc_controller_reset(bpmpc_controller* c) {
 int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const double* rbd, int inputs_on_device, double period,
                           const bpmpc_tick_outputs* host_out) {
   (void)period;      // WeightedWbc::update takes it and does not use it (WbcBase.cpp:242-243), as bpmpc_wbc_update
-  if (!c || !t || !rbd) { set_last_error("bpmpc_controller_tick: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_DEVICE, [&] {
-    bpmpc_solver* s = c->s;
+  return guarded(c, BPMPC_ERR_DEVICE, "bpmpc_controller_tick: null argument", t && rbd, [&] {
+    hipStream_t st = c->s->stream;
     check_tick(c, batch, "bpmpc_controller_tick");
-    HIP_CHECK(hipSetDevice(c->device));
-    const size_t B = batch;
-    const double *dt = t, *drbd = rbd;
-    if (!inputs_on_device) {
-      HIP_CHECK(hipMemcpyAsync(c->d_t, t, B * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      HIP_CHECK(hipMemcpyAsync(c->d_rbd, rbd, B * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      dt = c->d_t; drbd = c->d_rbd;
-    }
-    enqueue_tick(c, batch, dt, drbd);
+    const double* dt = staged(t, c->d_t, batch, inputs_on_device, st);
+    enqueue_tick(c, batch, dt, staged(rbd, c->d_rbd, (size_t)batch * 2 * c->nv, inputs_on_device, st));
     fetch_tick(c, batch, host_out);
   });
 }
@@ -198,21 +175,14 @@ int bpmpc_controller_tick(bpmpc_controller* c, int batch, const double* t, const
 int bpmpc_controller_tick_estimated(bpmpc_controller* c, bpmpc_estimator* e, int batch, const double* t, int inputs_on_device, double period,
                                     const bpmpc_tick_outputs* host_out) {
   (void)period;      // as bpmpc_controller_tick: the WBC takes it and does not use it; the filter's dt is the period of bpmpc_estimator_update
-  if (!c || !e || !t) { set_last_error("bpmpc_controller_tick_estimated: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_DEVICE, [&] {
-    bpmpc_solver* s = c->s;
+  return guarded(c, BPMPC_ERR_DEVICE, "bpmpc_controller_tick_estimated: null argument", e && t, [&] {
+    hipStream_t st = c->s->stream;
     if (e->nj != c->nj) throw std::invalid_argument("bpmpc_controller_tick_estimated: the estimator and the controller are built for different robots");
     if (e->device != c->device) throw std::invalid_argument("bpmpc_controller_tick_estimated: the estimator and the controller live on different devices");
     check_tick(c, batch, "bpmpc_controller_tick_estimated");
-    HIP_CHECK(hipSetDevice(c->device));
-    estimator_before_foreign_read(e, batch, s->stream);      // refuses a batch without estimates before anything is enqueued
-    const double* dt = t;
-    if (!inputs_on_device) {
-      HIP_CHECK(hipMemcpyAsync(c->d_t, t, (size_t)batch * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      dt = c->d_t;
-    }
-    enqueue_tick(c, batch, dt, e->d_rbd);
-    estimator_after_foreign_read(e, s->stream);
+    estimator_before_foreign_read(e, batch, st);      // refuses a batch without estimates before anything is enqueued
+    enqueue_tick(c, batch, staged(t, c->d_t, batch, inputs_on_device, st), e->d_rbd);
+    estimator_after_foreign_read(e, st);
     fetch_tick(c, batch, host_out);
   });
 }
@@ -220,21 +190,13 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* c, bpmpc_estimator* e, int
 // BipedalController::starting for the robots of `mask`: the observation unwrapped against yawLast = 0 (:126-127), MPC_BASE::reset from it (:147-148),
 // clearLastQpSol (:179).  The refusals of bpmpc_solver_restart (DDP, batch of the last setup) and the tick's (the WBC's max_batch) come first.
 int bpmpc_controller_restart(bpmpc_controller* c, int batch, const int* mask, const double* rbd, int inputs_on_device) {
-  if (!c || !mask || !rbd) { set_last_error("bpmpc_controller_restart: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_DEVICE, [&] {
+  return guarded(c, BPMPC_ERR_DEVICE, "bpmpc_controller_restart: null argument", mask && rbd, [&] {
     bpmpc_solver* s = c->s;
     check_restart(s, batch);
     if (batch > c->max_batch) throw std::length_error("bpmpc_controller_restart: batch exceeds the WBC's max_batch");
-    HIP_CHECK(hipSetDevice(c->device));
-    const int* dmask = mask;
-    const double* drbd = rbd;
-    if (!inputs_on_device) {
-      HIP_CHECK(hipMemcpyAsync(c->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
-      HIP_CHECK(hipMemcpyAsync(c->d_rbd, rbd, (size_t)batch * 2 * c->nv * sizeof(double), hipMemcpyHostToDevice, s->stream));
-      dmask = c->d_mask; drbd = c->d_rbd;
-    }
+    const int* dmask = staged(mask, c->d_mask, batch, inputs_on_device, s->stream);
     RestartArgs a{};
-    a.batch = batch; a.mask = dmask; a.rbd = drbd; a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs;
+    a.batch = batch; a.mask = dmask; a.rbd = staged(rbd, c->d_rbd, (size_t)batch * 2 * c->nv, inputs_on_device, s->stream); a.yaw_last = c->d_yaw; a.x_obs = c->d_xobs;
     kl::restart_observe(c->nj, batch, s->stream, s->d_model, a);
     HIP_CHECK(hipGetLastError());
     restart(s, batch, dmask, c->d_xobs, true);
@@ -245,45 +207,29 @@ int bpmpc_controller_restart(bpmpc_controller* c, int batch, const int* mask, co
 
 // The joint-level kp / kd of dynamicReconfigCallback (:423-472) for the robots of `mask`, on the solver's stream
 int bpmpc_controller_set_joint_gains(bpmpc_controller* c, int batch, const int* mask, const double* kp, const double* kd, int n_rows, int inputs_on_device) {
-  if (!c || !kp || !kd) { set_last_error("bpmpc_controller_set_joint_gains: null handle or gains"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_DEVICE, [&] {
+  return guarded(c, BPMPC_ERR_DEVICE, "bpmpc_controller_set_joint_gains: null handle or gains", kp && kd, [&] {
     if (batch < 1 || batch > c->max_batch) throw std::length_error("bpmpc_controller_set_joint_gains: batch exceeds the WBC's max_batch");
-    if (n_rows != 1 && n_rows != batch) throw std::invalid_argument("bpmpc_controller_set_joint_gains: n_rows must be 1 or batch");
-    HIP_CHECK(hipSetDevice(c->device));
-    hipStream_t stream = c->s->stream;
-    const int* dmask = mask;
-    const double *dkp = kp, *dkd = kd;
-    if (!inputs_on_device) {
-      for (int r = 0; r < n_rows; ++r) {
-        if (n_rows != 1 && mask && !mask[r]) continue;
-        for (int j = 0; j < c->nj; ++j)
-          for (const double* g : {kp, kd})
-            if (!std::isfinite(g[r * c->nj + j]) || g[r * c->nj + j] < 0.0)
-              throw std::invalid_argument("bpmpc_controller_set_joint_gains: row " + std::to_string(r) + ", joint " + std::to_string(j) + ": " + (g == kp ? "kp" : "kd") +
-                                          " must be finite and not negative");
-      }
-      const size_t bytes = (size_t)n_rows * c->nj * sizeof(double);
-      HIP_CHECK(hipMemcpyAsync(c->d_kp_in, kp, bytes, hipMemcpyHostToDevice, stream));
-      HIP_CHECK(hipMemcpyAsync(c->d_kd_in, kd, bytes, hipMemcpyHostToDevice, stream));
-      if (mask) HIP_CHECK(hipMemcpyAsync(c->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, stream));
-      dmask = mask ? c->d_mask : nullptr; dkp = c->d_kp_in; dkd = c->d_kd_in;
-    }
-    kl::set_joint_gains(c->nj, batch, stream, dmask, dkp, dkd, n_rows, c->d_kp, c->d_kd);
-    HIP_CHECK(hipGetLastError());
-    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(stream));      // the caller's host arrays
+    auto check_row = [&](int r) {
+      for (int j = 0; j < c->nj; ++j)
+        for (const double* g : {kp, kd})
+          if (!std::isfinite(g[r * c->nj + j]) || g[r * c->nj + j] < 0.0)
+            throw std::invalid_argument("bpmpc_controller_set_joint_gains: row " + std::to_string(r) + ", joint " + std::to_string(j) + ": " + (g == kp ? "kp" : "kd") +
+                                        " must be finite and not negative");
+    };
+    set_rows("bpmpc_controller_set_joint_gains", c->s->stream, batch, c->nj, c->nj, mask, c->d_mask, n_rows, inputs_on_device, check_row, {kp, c->d_kp_in, c->d_kp},
+             {kd, c->d_kd_in, c->d_kd});
+    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(c->s->stream));      // the caller's host arrays
   });
 }
 
 int bpmpc_controller_joint_outputs(bpmpc_controller* c, int batch, double* host_torque, double* host_kp, double* host_kd, double** dev_torque,
                                    double** dev_kp, double** dev_kd) {
-  if (!c) { set_last_error("null controller handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_DEVICE, [&] {
+  return guarded(c, BPMPC_ERR_DEVICE, "null controller handle", [&] {
     if (dev_torque) *dev_torque = c->d_torque;
     if (dev_kp) *dev_kp = c->d_kp;
     if (dev_kd) *dev_kd = c->d_kd;
     if (!host_torque && !host_kp && !host_kd) return;
     if (batch < 1 || batch > c->max_batch) throw std::length_error("bpmpc_controller_joint_outputs: batch exceeds the WBC's max_batch");
-    HIP_CHECK(hipSetDevice(c->device));
     const size_t bytes = (size_t)batch * c->nj * sizeof(double);
     if (host_torque) HIP_CHECK(hipMemcpyAsync(host_torque, c->d_torque, bytes, hipMemcpyDeviceToHost, c->s->stream));
     if (host_kp) HIP_CHECK(hipMemcpyAsync(host_kp, c->d_kp, bytes, hipMemcpyDeviceToHost, c->s->stream));

@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/bpmpc.h"
-#include "device_model.h"
+#include "device_handle.h"
 #include "robot_model.h"
 #include "kernels/estimator.h"
 
@@ -15,10 +15,8 @@ struct bpmpc_estimator {
   bpmpc::EstSettings defaults{};        // LinearKalmanFilter.h:45-51 overridden by the kalmanFilter block of task.info: every row after create / reset_params
   int kind = 0, device = 0, max_batch = 0, nj = 0, nv = 0;
   int last_batch = 0;                   // batch of the last update: the rows of d_rbd that hold an estimate (0 before the first update)
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_foreign = nullptr;      // a controller tick on another stream reads d_rbd: this handle's stream waits for it (as bpmpc_wbc)
-  hipEvent_t ev_own = nullptr;          // an update that was only enqueued on this handle's stream, waited for by the next such tick
-  bool own_pending = false;
+  bpmpc::DeviceBuffers mem;             // every d_* below
+  bpmpc::StreamHandshake hs;            // the handle's stream; foreign launches: a controller tick on the solver's stream that reads d_rbd
   double *d_rbd = nullptr, *d_xhat = nullptr, *d_cov = nullptr;      // [max_batch][2 nv], [max_batch][18], [max_batch][18][18]
   int* d_xy_reset = nullptr;                                        // [max_batch]
   double* d_params = nullptr;           // [max_batch][kEstParamStride]

@@ -38,7 +38,7 @@ struct bpmpc_gait_batch {
   int* restart_dev = nullptr;
   int restart_epoch = 0, restart_base = 0;
   bool restart_on_device = false;
-  std::vector<void*> allocations;
+  DeviceBuffers mem;
 };
 
 namespace {
@@ -260,18 +260,18 @@ int bpmpc_gait_batch_create(bpmpc_solver* s, const bpmpc_gait_template* gaits, i
     const GaitLibrary lib = gait_library(s->rm, gaits, n_gaits);
     const int B = s->settings.max_batch;
     g->solver = s; g->max_batch = B; g->n_gaits = n_gaits;
-    auto alloc = [&](size_t bytes) { void* p = nullptr; HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); g->allocations.push_back(p); return p; };
-    double* lib_d = static_cast<double*>(alloc(lib.d.size() * sizeof(double)));
-    int* lib_i = static_cast<int*>(alloc(lib.i.size() * sizeof(int)));
+    DeviceBuffers& m = g->mem;
+    double* lib_d = m.alloc<double>(lib.d.size());
+    int* lib_i = m.alloc<int>(lib.i.size());
     for (int k = 0; k < 2; ++k) {
-      g->ev[k] = static_cast<double*>(alloc((size_t)B * kRefMaxEvents * sizeof(double)));
-      g->ms[k] = static_cast<int*>(alloc((size_t)B * (kRefMaxEvents + 1) * sizeof(int)));
-      g->meta[k] = static_cast<int*>(alloc((size_t)B * kGaitMeta * sizeof(int)));
+      g->ev[k] = m.alloc<double>((size_t)B * kRefMaxEvents);
+      g->ms[k] = m.alloc<int>((size_t)B * (kRefMaxEvents + 1));
+      g->meta[k] = m.alloc<int>((size_t)B * kGaitMeta);
     }
-    g->grp_i = static_cast<int*>(alloc(3 * (size_t)B * sizeof(int)));
-    g->grp_d = static_cast<double*>(alloc(3 * (size_t)B * sizeof(double)));
-    g->cmd_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
-    g->restart_dev = static_cast<int*>(alloc((size_t)B * sizeof(int)));
+    g->grp_i = m.alloc<int>(3 * (size_t)B);
+    g->grp_d = m.alloc<double>(3 * (size_t)B);
+    g->cmd_dev = m.alloc<int>((size_t)B);
+    g->restart_dev = m.alloc<int>((size_t)B);
     HIP_CHECK(hipMemsetAsync(g->restart_dev, 0, (size_t)B * sizeof(int), s->stream));
     HIP_CHECK(hipMemcpyAsync(lib_d, lib.d.data(), lib.d.size() * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_CHECK(hipMemcpyAsync(lib_i, lib.i.data(), lib.i.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
@@ -288,7 +288,7 @@ int bpmpc_gait_batch_create(bpmpc_solver* s, const bpmpc_gait_template* gaits, i
 void bpmpc_gait_batch_destroy(bpmpc_gait_batch* g) {
   if (!g) return;
   if (g->solver && g->solver->stream) (void)hipStreamSynchronize(g->solver->stream);
-  for (void* p : g->allocations) (void)hipFree(p);
+  g->mem.release();
   delete g;
 }
 int bpmpc_gait_batch_reset(bpmpc_gait_batch* g) {

@@ -1,5 +1,5 @@
 // Controller tick kernels (kernels/tick.h): observation + policy evaluation in one launch, the joint commands behind k_wbc; the observation of
-// a controller restart; the masked write of the joint gains.
+// a controller restart.
 #include <hip/hip_runtime.h>
 
 #include "kernel_launchers.h"
@@ -16,10 +16,6 @@ __global__ __launch_bounds__(kWave) void k_tick_observe_policy(const DeviceModel
 template <int NJ>
 __global__ __launch_bounds__(256) void k_tick_commands(TickCommandArgs a) {
   tick_commands<NJ>(a);
-}
-
-__global__ __launch_bounds__(256) void k_set_joint_gains(int batch, int nj, const int* mask, const double* kp_in, const double* kd_in, int n_rows, double* kp, double* kd) {
-  set_joint_gains(batch, nj, mask, kp_in, kd_in, n_rows, kp, kd);
 }
 
 template <int NJ>
@@ -44,10 +40,6 @@ void tick_commands(int nj, hipStream_t st, const TickCommandArgs& a) {
   const int grid = (a.batch * nj + 255) / 256;
   if (nj == 10) hipLaunchKernelGGL(k_tick_commands<10>, dim3(grid), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(k_tick_commands<12>, dim3(grid), dim3(256), 0, st, a);
-}
-
-void set_joint_gains(int nj, int batch, hipStream_t st, const int* mask, const double* kp_in, const double* kd_in, int n_rows, double* kp, double* kd) {
-  hipLaunchKernelGGL(k_set_joint_gains, dim3((batch * nj + 255) / 256), dim3(256), 0, st, batch, nj, mask, kp_in, kd_in, n_rows, kp, kd);
 }
 
 void restart_observe(int nj, int batch, hipStream_t st, const DeviceModel* model, const RestartArgs& a) {

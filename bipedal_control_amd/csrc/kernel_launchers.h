@@ -68,7 +68,6 @@ void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, doubl
 // ---- k_tick.hip: the controller tick (observation + policy evaluation in one launch; the joint commands behind k_wbc), the restart's observation
 void tick_observe_policy(int nj, int batch, hipStream_t st, const DeviceModel* model, const TickArgs& a);
 void tick_commands(int nj, hipStream_t st, const TickCommandArgs& a);
-void set_joint_gains(int nj, int batch, hipStream_t st, const int* mask, const double* kp_in, const double* kd_in, int n_rows, double* kp, double* kd);
 void restart_observe(int nj, int batch, hipStream_t st, const DeviceModel* model, const RestartArgs& a);
 
 }  // namespace kl

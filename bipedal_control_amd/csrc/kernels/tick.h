@@ -265,18 +265,6 @@ __device__ __forceinline__ void tick_commands(const TickCommandArgs& a) {
   a.joint_torque[idx] = a.kp[idx] * (pos - rb[6 + j]) + a.kd[idx] * (vel - rb[NV + 6 + j]) + tau;
 }
 
-// bpmpc_controller_set_joint_gains: the gains of the robots of `mask` (NULL: every robot below `batch`) become rows b (n_rows == batch) or rows 0
-// (n_rows == 1) of kp_in / kd_in.  One thread per entry.
-__device__ __forceinline__ void set_joint_gains(int batch, int nj, const int* mask, const double* kp_in, const double* kd_in, int n_rows, double* kp, double* kd) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= batch * nj) return;
-  const int b = idx / nj, j = idx % nj;
-  if (mask && !mask[b]) return;
-  const int src = (n_rows == 1 ? 0 : b) * nj + j;
-  kp[idx] = kp_in[src];
-  kd[idx] = kd_in[src];
-}
-
 // The observation of a restart (BipedalController::starting, :126-127: the observation is zeroed, then set from the estimator): for every robot
 // with mask[b] != 0 x_obs[b] and yaw_last[b] from rbd[b], the yaw unwrapped against 0 (wrapped to (-pi, pi]); other robots are not written.
 // The tick's mapping and device functions; a wavefront without a restarted robot leaves at once.

@@ -12,8 +12,7 @@
 #include <vector>
 
 #include "../../include/bpmpc.h"
-#include "capi_internal.h"
-#include "device_model.h"
+#include "device_handle.h"
 #include "kernel_launchers.h"
 #include "launch.h"
 #include "kernels/reference_device.h"

@@ -572,12 +572,8 @@ void check_policy(const bpmpc_solver* s) {
 void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device) {
   check_restart(s, batch);
   const size_t NX = s->nx;
-  if (!on_device) {
-    HIP_CHECK(hipMemcpyAsync(s->restart_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s->stream));
-    if (x_new) HIP_CHECK(hipMemcpyAsync(s->restart_x, x_new, (size_t)batch * NX * sizeof(double), hipMemcpyHostToDevice, s->stream));
-    mask = s->restart_mask;
-    if (x_new) x_new = s->restart_x;
-  }
+  mask = staged(mask, s->restart_mask, batch, on_device, s->stream);
+  x_new = staged(x_new, s->restart_x, batch * NX, on_device, s->stream);
   // the start that setup(x0 = NULL) reads (copy_loop_x0); neither a tick nor a rollout can replace it before that setup (both are refused)
   double* loop_x = s->loop_from_tick ? s->tick_x : s->buf.roll_x;
   hipLaunchKernelGGL(k_restart_mark, dim3((unsigned)((batch * NX + 255) / 256)), dim3(256), 0, s->stream, batch, (int)NX, mask, s->restart_flag, x_new, loop_x);

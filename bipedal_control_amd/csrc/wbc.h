@@ -6,7 +6,7 @@
 #include <cstddef>
 
 #include "../../include/bpmpc.h"
-#include "device_model.h"
+#include "device_handle.h"
 #include "robot_model.h"
 #include "kernels/wbc.h"
 
@@ -16,12 +16,10 @@ struct bpmpc_wbc {
   bpmpc::DeviceModel* d_model = nullptr;
   bpmpc::WbcSettings defaults{};        // what loadTasksSetting reads from task.info: every parameter row after create / bpmpc_wbc_reset_params
   int device = 0, max_batch = 0, nv = 0, n = 0;
-  hipStream_t stream = nullptr;
+  bpmpc::DeviceBuffers mem;             // every d_* below
+  bpmpc::StreamHandshake hs;            // the handle's stream; foreign launches: k_wbc and k_wbc_restart of a controller tick / restart on the solver's stream
   double *d_x = nullptr, *d_u = nullptr, *d_rbd = nullptr, *d_sol = nullptr, *d_debug = nullptr;
   int *d_mode = nullptr, *d_status = nullptr;
-  hipEvent_t ev_foreign = nullptr;      // k_wbc enqueued on another handle's stream (controller tick): this handle's stream waits for it
-  hipEvent_t ev_own = nullptr;          // ... and the other way round: a restart only enqueued on this handle's stream, waited for by the next foreign launch
-  bool own_pending = false;
   int* d_mask = nullptr;                // [max_batch] device copy of a host mask (restart, set_params)
   double* d_params = nullptr;           // [max_batch][kWbcParamStride] the robots' parameter rows (kernels/wbc.h WbcSettings), read by k_wbc
   double* d_rows = nullptr;             // [max_batch + 1][kWbcParamStride] device copy of host rows; the last row holds `defaults`

@@ -27,16 +27,6 @@ __global__ __launch_bounds__(kWave) void k_wbc(const DeviceModel* model, WbcArgs
   wbc_robot<NJ>(*model, w, a, b, threadIdx.x);
 }
 
-// bpmpc_wbc_set_params: the parameter rows of the robots of `mask` (NULL: every robot below `batch`) become rows[b] (n_rows == batch) or
-// rows[0] (n_rows == 1); the reserved entries are written as 0.  One thread per entry.
-__global__ __launch_bounds__(256) void k_wbc_set_params(int batch, const int* mask, const double* rows, int n_rows, double* params) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= batch * kWbcParamStride) return;
-  const int b = i / kWbcParamStride, e = i % kWbcParamStride;
-  if (mask && !mask[b]) return;
-  params[i] = e < BPMPC_WBC_PARAM_RESERVED ? rows[(size_t)(n_rows == 1 ? 0 : b) * kWbcParamStride + e] : 0.0;
-}
-
 // WeightedWbc::clearLastQpSol for the robots of `mask` (bpmpc_wbc_restart): their last solution and status become 0
 __global__ __launch_bounds__(256) void k_wbc_restart(int batch, int n, const int* mask, double* sol, int* status) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -80,10 +70,10 @@ void launch_wbc(const bpmpc_wbc* w, const WbcArgs& a, hipStream_t stream) {
   HIP_CHECK(hipGetLastError());
 }
 
-// k_wbc_set_params on device rows and a device mask (NULL: everyone), on the handle's own stream
-void set_params_on_device(bpmpc_wbc* w, int batch, const int* mask, const double* rows, int n_rows) {
-  hipLaunchKernelGGL(k_wbc_set_params, dim3((batch * kWbcParamStride + 255) / 256), dim3(256), 0, w->stream, batch, mask, rows, n_rows, w->d_params);
-  HIP_CHECK(hipGetLastError());
+// every parameter row becomes the task.info values (the last row of d_rows), on the handle's own stream
+void write_default_params(bpmpc_wbc* w) {
+  write_rows(w->hs.stream, w->max_batch, kWbcParamStride, BPMPC_WBC_PARAM_RESERVED, nullptr, 1, {w->d_rows + (size_t)w->max_batch * kWbcParamStride, nullptr, w->d_params});
+  w->hs.synchronise_own();
 }
 
 // A host row before it is accepted: every used entry finite; gains, weights, friction and torque limits not negative
@@ -105,28 +95,21 @@ namespace bpmpc {
 // The launch of bpmpc_wbc_update without its transfers: device inputs, the handle's last solutions and statuses, on the caller's stream.
 void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const double* input_des, const double* rbd_meas, const int* mode, hipStream_t stream) {
   if (batch < 1 || batch > w->max_batch) throw std::length_error("controller tick: batch exceeds the WBC's max_batch");
-  if (w->own_pending) HIP_CHECK(hipStreamWaitEvent(stream, w->ev_own, 0));
+  w->hs.before_foreign(stream);
   WbcArgs a{};
   a.batch = batch; a.nx = w->rm.nx; a.state_des = state_des; a.input_des = input_des; a.rbd_meas = rbd_meas; a.mode = mode;
   a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr; a.params = w->d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
   launch_wbc(w, a, stream);
-  if (!w->ev_foreign) HIP_CHECK(hipEventCreateWithFlags(&w->ev_foreign, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(w->ev_foreign, stream));
-  HIP_CHECK(hipStreamWaitEvent(w->stream, w->ev_foreign, 0));
+  w->hs.after_foreign(stream);
 }
 
 // k_wbc_restart on a device mask, enqueued on `stream` under the rule of wbc_launch_on (the handle's own stream: no events)
 void wbc_restart_on(bpmpc_wbc* w, int batch, const int* mask, hipStream_t stream) {
   if (batch < 1 || batch > w->max_batch) throw std::length_error("restart: batch exceeds the WBC's max_batch");
-  const bool foreign = stream != w->stream;
-  if (foreign && w->own_pending) HIP_CHECK(hipStreamWaitEvent(stream, w->ev_own, 0));
+  w->hs.before_foreign(stream);
   hipLaunchKernelGGL(k_wbc_restart, dim3((batch * w->n + 255) / 256), dim3(256), 0, stream, batch, w->n, mask, w->d_sol, w->d_status);
   HIP_CHECK(hipGetLastError());
-  if (foreign) {
-    if (!w->ev_foreign) HIP_CHECK(hipEventCreateWithFlags(&w->ev_foreign, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(w->ev_foreign, stream));
-    HIP_CHECK(hipStreamWaitEvent(w->stream, w->ev_foreign, 0));
-  }
+  w->hs.after_foreign(stream);
 }
 
 }  // namespace bpmpc
@@ -136,37 +119,20 @@ extern "C" {
 int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int device, int max_batch, bpmpc_wbc** out) {
   if (!model || !task_info_path || !out || max_batch < 1) { set_last_error("bpmpc_wbc_create: bad argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
   *out = nullptr;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1 || device < 0 || device >= count) {
-    set_last_error("bpmpc_wbc_create: no usable HIP device (this engine has no CPU path)");
-    return BPMPC_ERR_NO_DEVICE;
-  }
   std::unique_ptr<bpmpc_wbc> w(new bpmpc_wbc);
   const int rc = guarded(BPMPC_ERR_IO, [&]() -> int {
-    w->rm = model_of(model);
-    if (w->rm.nj != 10 && w->rm.nj != 12) { set_last_error("only 10- and 12-joint bipeds are instantiated"); return BPMPC_ERR_UNSUPPORTED; }
-    w->dm = make_device_model(w->rm);
+    if (const int refused = open_side_handle("bpmpc_wbc_create", w.get(), model, device, max_batch)) return refused;
     w->defaults = load_wbc_settings(task_info_path, w->rm.nj);
-    w->device = device; w->max_batch = max_batch; w->nv = 6 + w->rm.nj; w->n = w->nv + 12 + w->rm.nj;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_model), sizeof(DeviceModel)));
-    HIP_CHECK(hipMemcpy(w->d_model, &w->dm, sizeof(DeviceModel), hipMemcpyHostToDevice));
+    w->nv = 6 + w->rm.nj; w->n = w->nv + 12 + w->rm.nj;
     const size_t B = max_batch;
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_x), B * w->rm.nx * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_u), B * w->rm.nu * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_rbd), B * 2 * w->nv * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_sol), B * w->n * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_debug), B * kWbcDebugStride * sizeof(double)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_mode), B * sizeof(int)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_status), B * sizeof(int)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_mask), B * sizeof(int)));
-    HIP_CHECK(hipMemset(w->d_sol, 0, B * w->n * sizeof(double)));      // lastQpSol_ starts at zero (WeightedWbc.h)
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_params), B * sizeof(WbcSettings)));
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&w->d_rows), (B + 1) * sizeof(WbcSettings)));
+    DeviceBuffers& m = w->mem;
+    w->d_x = m.alloc<double>(B * w->rm.nx); w->d_u = m.alloc<double>(B * w->rm.nu); w->d_rbd = m.alloc<double>(B * 2 * w->nv);
+    w->d_sol = m.alloc<double>(B * w->n, true);      // lastQpSol_ starts at zero (WeightedWbc.h)
+    w->d_debug = m.alloc<double>(B * kWbcDebugStride);
+    w->d_mode = m.alloc<int>(B); w->d_status = m.alloc<int>(B); w->d_mask = m.alloc<int>(B);
+    w->d_params = m.alloc<double>(B * kWbcParamStride); w->d_rows = m.alloc<double>((B + 1) * kWbcParamStride);
     HIP_CHECK(hipMemcpy(w->d_rows + B * kWbcParamStride, &w->defaults, sizeof(WbcSettings), hipMemcpyHostToDevice));
-    set_params_on_device(w.get(), max_batch, nullptr, w->d_rows + B * kWbcParamStride, 1);      // every row starts as the task.info values
-    HIP_CHECK(hipStreamSynchronize(w->stream));
+    write_default_params(w.get());
     return BPMPC_OK;
   });
   if (rc != BPMPC_OK) { bpmpc_wbc_destroy(w.release()); return rc; }
@@ -174,16 +140,7 @@ int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int d
   return BPMPC_OK;
 }
 
-void bpmpc_wbc_destroy(bpmpc_wbc* w) {
-  if (!w) return;
-  if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
-  if (w->ev_foreign) (void)hipEventDestroy(w->ev_foreign);
-  if (w->ev_own) (void)hipEventDestroy(w->ev_own);
-  for (void* p : {(void*)w->d_model, (void*)w->d_x, (void*)w->d_u, (void*)w->d_rbd, (void*)w->d_sol, (void*)w->d_debug, (void*)w->d_mode, (void*)w->d_status,
-                  (void*)w->d_mask, (void*)w->d_params, (void*)w->d_rows})
-    if (p) (void)hipFree(p);
-  delete w;
-}
+void bpmpc_wbc_destroy(bpmpc_wbc* w) { close_side_handle(w); }
 
 int bpmpc_wbc_dims(const bpmpc_wbc* w, int* n_decision, int* nv) {
   if (!w) { set_last_error("null wbc handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
@@ -195,100 +152,63 @@ int bpmpc_wbc_dims(const bpmpc_wbc* w, int* n_decision, int* nv) {
 int bpmpc_wbc_update(bpmpc_wbc* w, int batch, const double* state_desired, const double* input_desired, const double* rbd_state_measured,
                      const int* mode, double period, double* solution, int* status, double* debug) {
   (void)period;      // the joint-acceleration feed-forward that used it is commented out in the reference (WbcBase.cpp:242-243)
-  if (!w || !state_desired || !input_desired || !rbd_state_measured || !mode || !solution) { set_last_error("bpmpc_wbc_update: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_IO, [&] {
+  return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_update: null argument", state_desired && input_desired && rbd_state_measured && mode && solution, [&] {
     if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_update: batch exceeds max_batch");
     for (int b = 0; b < batch; ++b) if (mode[b] < 0 || mode[b] > 3) throw std::invalid_argument("bpmpc_wbc_update: mode must be 0..3");
-    HIP_CHECK(hipSetDevice(w->device));
     const size_t B = batch;
-    HIP_CHECK(hipMemcpyAsync(w->d_x, state_desired, B * w->rm.nx * sizeof(double), hipMemcpyHostToDevice, w->stream));
-    HIP_CHECK(hipMemcpyAsync(w->d_u, input_desired, B * w->rm.nu * sizeof(double), hipMemcpyHostToDevice, w->stream));
-    HIP_CHECK(hipMemcpyAsync(w->d_rbd, rbd_state_measured, B * 2 * w->nv * sizeof(double), hipMemcpyHostToDevice, w->stream));
-    HIP_CHECK(hipMemcpyAsync(w->d_mode, mode, B * sizeof(int), hipMemcpyHostToDevice, w->stream));
+    HIP_CHECK(hipMemcpyAsync(w->d_x, state_desired, B * w->rm.nx * sizeof(double), hipMemcpyHostToDevice, w->hs.stream));
+    HIP_CHECK(hipMemcpyAsync(w->d_u, input_desired, B * w->rm.nu * sizeof(double), hipMemcpyHostToDevice, w->hs.stream));
+    HIP_CHECK(hipMemcpyAsync(w->d_rbd, rbd_state_measured, B * 2 * w->nv * sizeof(double), hipMemcpyHostToDevice, w->hs.stream));
+    HIP_CHECK(hipMemcpyAsync(w->d_mode, mode, B * sizeof(int), hipMemcpyHostToDevice, w->hs.stream));
     WbcArgs a{};
     a.batch = batch; a.nx = w->rm.nx; a.state_des = w->d_x; a.input_des = w->d_u; a.rbd_meas = w->d_rbd; a.mode = w->d_mode;
     a.sol = w->d_sol; a.status = w->d_status; a.debug = debug ? w->d_debug : nullptr;
     a.params = w->d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
-    launch_wbc(w, a, w->stream);
-    HIP_CHECK(hipMemcpyAsync(solution, w->d_sol, B * w->n * sizeof(double), hipMemcpyDeviceToHost, w->stream));
-    if (status) HIP_CHECK(hipMemcpyAsync(status, w->d_status, B * sizeof(int), hipMemcpyDeviceToHost, w->stream));
-    if (debug) HIP_CHECK(hipMemcpyAsync(debug, w->d_debug, B * kWbcDebugStride * sizeof(double), hipMemcpyDeviceToHost, w->stream));
-    HIP_CHECK(hipStreamSynchronize(w->stream));
-    w->own_pending = false;
+    launch_wbc(w, a, w->hs.stream);
+    HIP_CHECK(hipMemcpyAsync(solution, w->d_sol, B * w->n * sizeof(double), hipMemcpyDeviceToHost, w->hs.stream));
+    if (status) HIP_CHECK(hipMemcpyAsync(status, w->d_status, B * sizeof(int), hipMemcpyDeviceToHost, w->hs.stream));
+    if (debug) HIP_CHECK(hipMemcpyAsync(debug, w->d_debug, B * kWbcDebugStride * sizeof(double), hipMemcpyDeviceToHost, w->hs.stream));
+    w->hs.synchronise_own();
   });
 }
 
 int bpmpc_wbc_reset(bpmpc_wbc* w) {
-  if (!w) { set_last_error("null wbc handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_IO, [&] {
-    HIP_CHECK(hipSetDevice(w->device));
-    HIP_CHECK(hipMemsetAsync(w->d_sol, 0, (size_t)w->max_batch * w->n * sizeof(double), w->stream));
-    HIP_CHECK(hipStreamSynchronize(w->stream));
-    w->own_pending = false;
+  return guarded(w, BPMPC_ERR_IO, "null wbc handle", [&] {
+    HIP_CHECK(hipMemsetAsync(w->d_sol, 0, (size_t)w->max_batch * w->n * sizeof(double), w->hs.stream));
+    w->hs.synchronise_own();
   });
 }
 
 int bpmpc_wbc_restart(bpmpc_wbc* w, int batch, const int* mask, int inputs_on_device) {
-  if (!w || !mask) { set_last_error("bpmpc_wbc_restart: null handle or mask"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_IO, [&] {
+  return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_restart: null handle or mask", mask != nullptr, [&] {
     if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_restart: batch exceeds max_batch");
-    HIP_CHECK(hipSetDevice(w->device));
-    if (!inputs_on_device) {
-      HIP_CHECK(hipMemcpyAsync(w->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, w->stream));
-      wbc_restart_on(w, batch, w->d_mask, w->stream);
-      HIP_CHECK(hipStreamSynchronize(w->stream));
-      w->own_pending = false;
-    } else {                            // only enqueued: the next launch on another stream (a controller tick) waits for it
-      wbc_restart_on(w, batch, mask, w->stream);
-      if (!w->ev_own) HIP_CHECK(hipEventCreateWithFlags(&w->ev_own, hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(w->ev_own, w->stream));
-      w->own_pending = true;
-    }
+    wbc_restart_on(w, batch, staged(mask, w->d_mask, batch, inputs_on_device, w->hs.stream), w->hs.stream);
+    if (!inputs_on_device) w->hs.synchronise_own();
+    else w->hs.enqueued_own();      // only enqueued: the next launch on another stream (a controller tick) waits for it
   });
 }
 
 int bpmpc_wbc_get_params(const bpmpc_wbc* w, int robot, double* row) {
-  if (!w || !row) { set_last_error("bpmpc_wbc_get_params: null handle or row"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_IO, [&] {
+  return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_get_params: null handle or row", row != nullptr, [&] {
     if (robot >= w->max_batch) throw std::length_error("bpmpc_wbc_get_params: robot exceeds max_batch");
-    HIP_CHECK(hipSetDevice(w->device));
     const double* src = robot < 0 ? w->d_rows + (size_t)w->max_batch * kWbcParamStride : w->d_params + (size_t)robot * kWbcParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(WbcSettings), hipMemcpyDeviceToHost, w->stream));
-    HIP_CHECK(hipStreamSynchronize(w->stream));
+    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(WbcSettings), hipMemcpyDeviceToHost, w->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(w->hs.stream));
   });
 }
 
 int bpmpc_wbc_set_params(bpmpc_wbc* w, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
-  if (!w || !rows) { set_last_error("bpmpc_wbc_set_params: null handle or rows"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_IO, [&] {
+  return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_set_params: null handle or rows", rows != nullptr, [&] {
     if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_set_params: batch exceeds max_batch");
-    if (n_rows != 1 && n_rows != batch) throw std::invalid_argument("bpmpc_wbc_set_params: n_rows must be 1 or batch");
-    HIP_CHECK(hipSetDevice(w->device));
-    if (!inputs_on_device) {
-      for (int r = 0; r < n_rows; ++r)
-        if (n_rows == 1 || !mask || mask[r]) check_param_row(rows + (size_t)r * kWbcParamStride, r, w->rm.nj);
-      HIP_CHECK(hipMemcpyAsync(w->d_rows, rows, (size_t)n_rows * sizeof(WbcSettings), hipMemcpyHostToDevice, w->stream));
-      if (mask) HIP_CHECK(hipMemcpyAsync(w->d_mask, mask, (size_t)batch * sizeof(int), hipMemcpyHostToDevice, w->stream));
-      set_params_on_device(w, batch, mask ? w->d_mask : nullptr, w->d_rows, n_rows);
-      HIP_CHECK(hipStreamSynchronize(w->stream));
-      w->own_pending = false;
-    } else {                            // only enqueued, as bpmpc_wbc_restart: the next launch on another stream (a controller tick) waits for it
-      set_params_on_device(w, batch, mask, rows, n_rows);
-      if (!w->ev_own) HIP_CHECK(hipEventCreateWithFlags(&w->ev_own, hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(w->ev_own, w->stream));
-      w->own_pending = true;
-    }
+    set_rows("bpmpc_wbc_set_params", w->hs.stream, batch, kWbcParamStride, BPMPC_WBC_PARAM_RESERVED, mask, w->d_mask, n_rows, inputs_on_device,
+             [&](int r) { check_param_row(rows + (size_t)r * kWbcParamStride, r, w->rm.nj); }, {rows, w->d_rows, w->d_params});
+    if (!inputs_on_device) w->hs.synchronise_own();
+    else w->hs.enqueued_own();      // only enqueued, as bpmpc_wbc_restart
   });
 }
 
 int bpmpc_wbc_reset_params(bpmpc_wbc* w) {
-  if (!w) { set_last_error("null wbc handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  return guarded(BPMPC_ERR_IO, [&] {
-    HIP_CHECK(hipSetDevice(w->device));
-    set_params_on_device(w, w->max_batch, nullptr, w->d_rows + (size_t)w->max_batch * kWbcParamStride, 1);
-    HIP_CHECK(hipStreamSynchronize(w->stream));
-    w->own_pending = false;
-  });
+  return guarded(w, BPMPC_ERR_IO, "null wbc handle", [&] { write_default_params(w); });
 }
 
 }  // extern "C"
