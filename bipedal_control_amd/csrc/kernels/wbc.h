@@ -22,8 +22,10 @@
 // equalities they amount to (J a + Jdot v = tolerance, see oracle/wbc_py.py on this reference quirk).  What is left - 6 + 3 n_stance
 // equalities on y = [vdot, F_stance] - is eliminated by an LU with complete pivoting (rank deficient: two points per rigid foot),
 // the reduced problem (<= 12 unknowns, torque limits and friction pyramids as inequalities) by a primal active-set iteration on
-// small dense KKT systems, capped like the reference's nWSR = 20.  Inconsistent equalities or an exhausted iteration budget leave
-// the previous solution in place (WeightedWbc.cpp:68-81) and report status 1.
+// small dense KKT systems, capped like the reference's nWSR = 20 (20 working-set changes, 21 KKT solves).  Status 1 means "not solved": the
+// equalities are inconsistent, or this add / drop iteration needed more than 20 changes or put rows into its working set whose KKT matrix is
+// singular.  It does not mean that the QP is infeasible (the stalled QPs examined were feasible).  The previous solution then stays in place
+// (WeightedWbc.cpp:68-81).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -555,6 +557,10 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
   // the scale of the comparison is the original right-hand side; the eliminated one is what is at hand (same order of magnitude)
   bad = wave_max(bad); scale = wave_max(scale);
   int status = bad > 10.0 * kWbcFeasTol * scale ? 1 : 0;
+  // for the debug block only: why the iteration ended (0 solved, 1 equalities inconsistent, 2 singular KKT system, 3 change budget exhausted,
+  // 4 nk > NK), the smallest pivot any KKT elimination accepted and the one that was rejected
+  int reason = status;
+  double minpiv = HUGE_VAL, rejpiv = 0.0;
   // back substitution: U11 Y = [rhs | U12], one right-hand side per lane
   const int nz = ny - rank;
   {
@@ -609,7 +615,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
   while (!done) {
     ++iters;
     const int na = w.nwork, nk = nz + na;
-    if (nk > W::NK) { status = 1; break; }
+    if (nk > W::NK) { status = 1; reason = 4; break; }
     // K = [Hz Dw'; Dw 0 | -gz; fw]
     for (int idx = l; idx < nk * (nk + 1); idx += kWave) {
       const int i = idx / (nk + 1), j = idx % (nk + 1);
@@ -626,7 +632,8 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
       for (int i = k + l; i < nk; i += kWave) { const double v = fabs(w.K[i][k]); if (v > best) { best = v; where = i; } }
       const double gmax = wave_max(best);
       const int pi = wave_min_int(best == gmax ? where : 0x7fffffff);
-      if (!(gmax > 1e-14)) { singular = true; break; }
+      if (!(gmax > 1e-14)) { singular = true; rejpiv = gmax; break; }
+      minpiv = fmin(minpiv, gmax);
       lds_wave_sync();
       if (pi != k) for (int c = l; c <= nk; c += kWave) { const double t = w.K[k][c]; w.K[k][c] = w.K[pi][c]; w.K[pi][c] = t; }
       lds_wave_sync();
@@ -637,7 +644,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
       }
       lds_wave_sync();
     }
-    if (singular) { status = 1; break; }
+    if (singular) { status = 1; reason = 2; break; }
     if (l == 0) {
       double sol[W::NK];
       for (int i = nk - 1; i >= 0; --i) {
@@ -662,7 +669,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
     const double gworst = wave_max(worst);
     const int add = wave_min_int(worst == gworst ? wi : 0x7fffffff);
     if (gworst > kWbcActiveTol) {
-      if (iters > a.max_working_set_changes) { status = 1; break; }
+      if (iters > a.max_working_set_changes) { status = 1; reason = 3; break; }
       if (l == 0) { w.work[w.nwork] = add; w.nwork = na + 1; }
       lds_wave_sync();
       continue;
@@ -671,7 +678,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
     int drop = -1; double mneg = -kWbcActiveTol;
     for (int k = 0; k < na; ++k) if (w.mu[k] < mneg) { mneg = w.mu[k]; drop = k; }
     if (drop >= 0) {
-      if (iters > a.max_working_set_changes) { status = 1; break; }
+      if (iters > a.max_working_set_changes) { status = 1; reason = 3; break; }
       lds_wave_sync();
       if (l == 0) { for (int k = drop; k + 1 < na; ++k) w.work[k] = w.work[k + 1]; w.nwork = na - 1; }
       lds_wave_sync();
@@ -704,6 +711,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
     if (l < 12) dbg[NV * NV + NV + 12 * NV + l] = w.djv[l];
     if (l < 6) dbg[NV * NV + NV + 12 * NV + 12 + l] = w.base_b[l];
     if (l == 0) { dbg[NV * NV + NV + 12 * NV + 18] = (double)rank; dbg[NV * NV + NV + 12 * NV + 19] = (double)iters; dbg[NV * NV + NV + 12 * NV + 20] = (double)w.nwork; }
+    if (l == 0) { dbg[NV * NV + NV + 12 * NV + 21] = (double)reason; dbg[NV * NV + NV + 12 * NV + 22] = minpiv < HUGE_VAL ? minpiv : 0.0; dbg[NV * NV + NV + 12 * NV + 23] = rejpiv; }
     if (l < w.nwork) dbg[NV * NV + NV + 12 * NV + 24 + l] = (double)w.work[l];
   }
 }

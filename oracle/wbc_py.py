@@ -334,16 +334,26 @@ def formulate(m, st, x_des, u_des, rbd, mode):
 
 
 class Infeasible(Exception):
+    """The equations of a working set are inconsistent.  With the empty working set these are the QP's equalities and the QP has no feasible
+    point.  With inequality rows in the working set (WorkingSetInconsistent) it only says that the add / drop rule put rows together that cannot
+    all be tight: the QP itself may be - and in every case examined was - feasible."""
+
+
+class WorkingSetInconsistent(Infeasible):
     pass
 
 
 FEAS_TOL = 1e-8      # relative to max(1, |rhs|): equality rows (explicit ones and opposite pairs) that cannot all hold
 
 
-def solve_qp(H, g, Aeq, beq, D, f, max_iter=400, tol=1e-9):
+def solve_qp(H, g, Aeq, beq, D, f, max_iter=400, tol=1e-9, trace=None):
     """min 1/2 x'Hx + g'x  s.t. Aeq x = beq, D x <= f  by a primal-dual active-set iteration on dense KKT systems (null-space form, rank
     deficient working sets allowed).  H may be singular as long as it is positive definite on the null space of the working set.
-    Returns x, multipliers of [Aeq; D] (zero for inactive rows), the working set, iterations."""
+    Returns x, multipliers of [Aeq; D] (zero for inactive rows), the working set, iterations.
+    trace (optional list, changes no result): one dict per iteration is appended - decision ("add", "drop", "done", "inconsistent"), index
+    (the row added / the position dropped), work (the working set the iteration solved with), residual (relative residual of the working-set
+    equations), viol / viol_second (largest and second largest violation of the rows outside the working set, -inf if none), mu / mu_second
+    (smallest and second smallest multiplier of the working set, +inf if none).  Rows are counted without the opposite pairs (see below)."""
     n = len(g)
     # a pair of opposite one-sided rows with opposite bounds (d x <= f and -d x <= -f) is the equality d x = f: taken out of the
     # inequality set up front (the reference's no-contact-motion task is made of such pairs; kept as inequalities they are linearly
@@ -357,7 +367,7 @@ def solve_qp(H, g, Aeq, beq, D, f, max_iter=400, tol=1e-9):
     firsts = sorted(i for i in pair_of if i < pair_of[i])
     if firsts:
         keep = [i for i in range(len(D)) if i not in pair_of]
-        x, mult, work, iters = solve_qp(H, g, np.vstack([Aeq, D[firsts]]), np.concatenate([beq, f[firsts]]), D[keep], f[keep], max_iter, tol)
+        x, mult, work, iters = solve_qp(H, g, np.vstack([Aeq, D[firsts]]), np.concatenate([beq, f[firsts]]), D[keep], f[keep], max_iter, tol, trace)
         full = np.zeros(n_eq0 + len(D))
         full[:n_eq0] = mult[:n_eq0]
         for k, i in enumerate(firsts):       # multiplier of the equality split by sign between the two one-sided rows
@@ -374,7 +384,12 @@ def solve_qp(H, g, Aeq, beq, D, f, max_iter=400, tol=1e-9):
         r = int((s > 1e-11 * max(1.0, s[0] if len(s) else 1.0)).sum())
         xp = Vt[:r].T @ ((U[:, :r].T @ d) / s[:r])
         if len(C) and np.abs(C @ xp - d).max() > FEAS_TOL * max(1.0, np.abs(d).max()):
-            raise Infeasible("working-set equations are inconsistent")
+            if trace is not None:
+                trace.append(dict(decision="inconsistent", index=-1, work=list(work), residual=float(np.abs(C @ xp - d).max() / max(1.0, np.abs(d).max())),
+                                  viol=-np.inf, viol_second=-np.inf, mu=np.inf, mu_second=np.inf))
+            if work:
+                raise WorkingSetInconsistent("the rows of the working set cannot all be tight: not solved by this iteration (the QP may be feasible)")
+            raise Infeasible("the equalities are inconsistent")
         Z = Vt[r:].T
         if Z.shape[1]:
             Hz = Z.T @ H @ Z
@@ -386,11 +401,21 @@ def solve_qp(H, g, Aeq, beq, D, f, max_iter=400, tol=1e-9):
         viol = D @ x - f
         viol[work] = -np.inf
         worst = int(np.argmax(viol)) if len(viol) else -1
+        mu = lam[len(Aeq):]
+        if trace is not None:
+            vs, ms = np.sort(viol)[::-1], np.sort(mu)
+            trace.append(dict(decision="done", index=-1, work=list(work),
+                              residual=float(np.abs(C @ xp - d).max() / max(1.0, np.abs(d).max())) if len(C) else 0.0,
+                              viol=float(vs[0]) if len(vs) else -np.inf, viol_second=float(vs[1]) if len(vs) > 1 else -np.inf,
+                              mu=float(ms[0]) if len(ms) else np.inf, mu_second=float(ms[1]) if len(ms) > 1 else np.inf))
         if worst >= 0 and viol[worst] > tol:
+            if trace is not None:
+                trace[-1].update(decision="add", index=worst)
             work.append(worst)
             continue
-        mu = lam[len(Aeq):]
         if len(mu) and mu.min() < -tol:
+            if trace is not None:
+                trace[-1].update(decision="drop", index=int(np.argmin(mu)))
             work.pop(int(np.argmin(mu)))
             continue
         mult = np.zeros(len(Aeq) + len(D))
@@ -403,9 +428,12 @@ def solve_qp(H, g, Aeq, beq, D, f, max_iter=400, tol=1e-9):
 
 def update(m, st, x_des, u_des, rbd, mode, last=None):
     """WeightedWbc::update (WeightedWbc.cpp:20-84): returns the decision vector and a dict with the QP and its KKT data.
-    A QP that is not solved returns `last` (lastQpSol_, WeightedWbc.cpp:68-81); here "not solved" = infeasible constraints - e.g. the
-    no-contact-motion equalities of the two points of a foot that rotates (their required accelerations are then incompatible with a
-    rigid body).  qpOASES' other failure (more than nWSR = 20 working-set recalculations) has no counterpart in this exact method."""
+    A QP that is not solved returns `last` (lastQpSol_, WeightedWbc.cpp:68-81) with status 1.  "Not solved" does not mean infeasible.  It means
+    that the equalities are inconsistent - e.g. the no-contact-motion equalities of the two points of a foot that rotates (their required
+    accelerations are then incompatible with a rigid body) - or that the add / drop iteration of solve_qp put rows into its working set that cannot
+    all be tight (WorkingSetInconsistent; those QPs were feasible wherever a phase-1 LP was run on them), or that it cycled (RuntimeError, not
+    caught here).  The device adds the budget of the reference (nWSR = 20 working-set changes, 21 KKT solves): a QP for which solve_qp returns
+    more than 21 iterations is solved here and reported as status 1 there (tests/wbc_stress_cases.py labels the cases)."""
     p = formulate(m, st, x_des, u_des, rbd, mode)
     H = p["Aw"].T @ p["Aw"]
     g = -p["Aw"].T @ p["bw"]
