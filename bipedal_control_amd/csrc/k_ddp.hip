@@ -270,12 +270,22 @@ __global__ __launch_bounds__(kWave) void k_ddp_nominal(Launch L, DdpBuffers d) {
 }
 
 // receding-horizon warm start of the next run: the previous solution is a FeedforwardController on the roll-out's own time points, one time
-// trajectory per problem (k_warm_shift reads tp_* per grid: problem b becomes its own "grid"), no pre-event entries
-__global__ void k_ddp_keep_times(DdpBuffers d, int batch, int N, double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid) {
+// trajectory per problem (k_warm_shift reads tp_* per grid: problem b becomes its own "grid"), no pre-event entries.  A failed problem (statuses 2
+// and 3) keeps its nominal trajectories ON THE GRID it was set up on: it gets a row of its own as well, a copy of that grid's times, kinds and
+// node count.  The copy is read from g_* / p_grid (the grid tables of the previous setup, which the next one has not yet replaced), not from the
+// tp_* rows preserve_previous filled: row p_grid[b] of tp_* belongs to problem p_grid[b], whose block of this launch rewrites it.
+__global__ void k_ddp_keep_times(DdpBuffers d, int batch, int N, const double* g_time, const int* g_kind, const int* g_nodes, const int* p_grid,
+                                 double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid) {
   const int b = blockIdx.x;
   if (b >= batch) return;
   const int n = d.n_points[b];
-  if (n <= 0) return;      // a failed problem keeps its nominal trajectories ON THE GRID: the copies preserve_previous made of the grid tables stay
+  if (n <= 0) {
+    const int grid = p_grid[b];
+    for (int i = threadIdx.x; i < N + 1; i += blockDim.x) tp_time[(size_t)b * (N + 1) + i] = g_time[(size_t)grid * (N + 1) + i];
+    for (int i = threadIdx.x; i < N; i += blockDim.x) tp_kind[(size_t)b * N + i] = g_kind[(size_t)grid * N + i];
+    if (threadIdx.x == 0) { tp_nodes[b] = g_nodes[grid]; tp_grid[b] = b; }
+    return;
+  }
   for (int i = threadIdx.x; i < N + 1; i += blockDim.x) tp_time[(size_t)b * (N + 1) + i] = i < n ? d.sol_t[(size_t)b * d.cap + i] : 0.0;
   for (int i = threadIdx.x; i < N; i += blockDim.x) tp_kind[(size_t)b * N + i] = 0;
   if (threadIdx.x == 0) { tp_nodes[b] = n - 1; tp_grid[b] = b; }
@@ -294,8 +304,9 @@ void ddp_select(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuf
   KL_NJ(nj, hipLaunchKernelGGL(k_ddp_select<NJ>, dim3(batch), dim3(kWave), 0, st, L, d, armijo));
 }
 void ddp_nominal(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d) { KL_NJ(nj, hipLaunchKernelGGL(k_ddp_nominal<NJ>, dim3(batch * (L.N + 1)), dim3(kWave), 0, st, L, d)); }
-void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid) {
-  hipLaunchKernelGGL(k_ddp_keep_times, dim3(batch), dim3(kWave), 0, st, d, batch, N, tp_time, tp_kind, tp_nodes, tp_grid);
+void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, const double* g_time, const int* g_kind, const int* g_nodes, const int* p_grid,
+                    double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid) {
+  hipLaunchKernelGGL(k_ddp_keep_times, dim3(batch), dim3(kWave), 0, st, d, batch, N, g_time, g_kind, g_nodes, p_grid, tp_time, tp_kind, tp_nodes, tp_grid);
 }
 void ddp_finish(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d) { KL_NJ(nj, hipLaunchKernelGGL(k_ddp_finish<NJ>, dim3(batch), dim3(kWave), 0, st, L, d)); }
 

@@ -63,7 +63,8 @@ void ddp_cost(int nj, int batch, bool fast, hipStream_t st, const Launch& L, con
 void ddp_select(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d, double armijo);
 void ddp_nominal(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d);
 void ddp_finish(int nj, int batch, hipStream_t st, const Launch& L, const DdpBuffers& d);
-void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid);
+void ddp_keep_times(int batch, int N, hipStream_t st, const DdpBuffers& d, const double* g_time, const int* g_kind, const int* g_nodes, const int* p_grid,
+                    double* tp_time, int* tp_kind, int* tp_nodes, int* tp_grid);
 
 // ---- k_tick.hip: the controller tick (observation + policy evaluation in one launch; the joint commands behind k_wbc), the restart's observation
 void tick_observe_policy(int nj, int batch, hipStream_t st, const DeviceModel* model, const TickArgs& a);

@@ -225,6 +225,15 @@ void bpmpc_solver::ddp_nominal_rollout() {
 
 namespace {
 
+// step lengths of the DDP line search: maxStepLength, x contractionRate, .. >= minStepLength.  The table of the line search (DdpBuffers::alpha_v) holds
+// kMaxDdpSteps entries, the baseline and kMaxDdpSteps - 1 lengths; the count stops one past `limit` (minStepLength may be tiny).
+constexpr double kDdpContractionRate = 0.5;              // [OCS2-upstream] line_search::Settings default (not in task.info)
+int ddp_step_lengths(const DdpConfig& d, int limit) {
+  int n = 0;
+  for (double al = d.ls_max_step_length; al >= d.ls_min_step_length && al > 0.0 && n <= limit; al *= kDdpContractionRate) ++n;
+  return n;
+}
+
 void allocate(bpmpc_solver* s) {
   const size_t B = s->settings.max_batch, N = s->settings.max_nodes, NX = s->nx, NU = s->nu, S = B * N;
   Buffers& b = s->buf;
@@ -294,10 +303,10 @@ void allocate(bpmpc_solver* s) {
   if (s->is_ddp()) {
     DdpBuffers& d = s->ddp;
     d.cap = (int)N + 1;
-    {   // step lengths of the line search: the baseline, then maxStepLength, x contractionRate, .. >= minStepLength (task.info:147-155: eight roll-outs)
-      constexpr double kContractionRate = 0.5;                                  // [OCS2-upstream] line_search::Settings default (not in task.info)
+    {   // step lengths of the line search: the baseline, then maxStepLength, x contractionRate, .. >= minStepLength (task.info:147-155: eight roll-outs);
+      // bpmpc_solver_create has refused a sequence that does not fit the table
       d.nv = 0; d.alpha_v[d.nv++] = 0.0;
-      for (double al = s->rm.ddp.ls_max_step_length; al >= s->rm.ddp.ls_min_step_length && d.nv < kMaxDdpSteps; al *= kContractionRate) d.alpha_v[d.nv++] = al;
+      for (double al = s->rm.ddp.ls_max_step_length; al >= s->rm.ddp.ls_min_step_length && d.nv < kMaxDdpSteps; al *= kDdpContractionRate) d.alpha_v[d.nv++] = al;
     }
     const size_t P = B * (size_t)d.cap, V = (size_t)d.nv;
     d.lff = s->alloc<double>("ddp_lff", S * NU);
@@ -360,7 +369,7 @@ void preserve_previous(bpmpc_solver* s, int batch, bool warm_arrays) {
     launch_copy_table(s, t);
   }
   if (s->is_ddp()) {      // the previous DDP solution lives on the time points of its roll-out, not on the grid it was computed on
-    kl::ddp_keep_times(batch, (int)N, s->stream, s->ddp, bp.tp_time, bp.tp_kind, bp.tp_nodes, bp.tp_grid);
+    kl::ddp_keep_times(batch, (int)N, s->stream, s->ddp, bp.g_time, bp.g_kind, bp.g_nodes, bp.p_grid, bp.tp_time, bp.tp_kind, bp.tp_nodes, bp.tp_grid);
     HIP_CHECK(hipGetLastError());
   }
 }
@@ -866,6 +875,10 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
       if (d.ls_hessian_correction_strategy != 0) { set_last_error("DDP: only lineSearch.hessianCorrectionStrategy DIAGONAL_SHIFT is implemented"); return BPMPC_ERR_UNSUPPORTED; }
       if (d.max_num_iterations != 1 || settings->sqp_iterations > 1) { set_last_error("DDP: one ILQR iteration per run (ddp.maxNumIterations 1): later iterations live on the roll-out's adaptive time grid"); return BPMPC_ERR_UNSUPPORTED; }
       if (!(d.ls_min_step_length > 0.0) || !(d.ls_max_step_length >= d.ls_min_step_length)) { set_last_error("DDP: lineSearch.minStepLength / maxStepLength"); return BPMPC_ERR_INVALID_ARGUMENT; }
+      if (ddp_step_lengths(d, kMaxDdpSteps - 1) > kMaxDdpSteps - 1) {      // (the engine would try fewer step lengths than the configuration asks for and report status 1)
+        set_last_error("DDP: lineSearch.minStepLength / maxStepLength ask for more than " + std::to_string(kMaxDdpSteps - 1) + " step lengths (contraction rate 0.5), the line search table holds no more");
+        return BPMPC_ERR_UNSUPPORTED;
+      }
       if (d.use_feedback_policy && settings->feedback_policy != 2) { set_last_error("DDP: ddp.useFeedbackPolicy true is not implemented (the gains live on the nominal grid, the solution on the roll-out's time points)"); return BPMPC_ERR_UNSUPPORTED; }
       if (settings->feedback_policy == 1) { set_last_error("DDP: feedback_policy 1 (LinearController) is not implemented for the DDP solution"); return BPMPC_ERR_UNSUPPORTED; }
       // round 6: the backward pass runs on the fast kernels (reference_kernels = 1 keeps the lane-emulated bodies: cross-check); the ILQR form of the

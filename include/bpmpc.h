@@ -148,7 +148,8 @@ typedef struct {
   int solver;           /* BPMPC_SOLVER_SQP (0, default): SqpMpc, the solver of BipedalController.cpp:303-306 / BipedalRobotSqpMpcNode.cpp:70.
                            BPMPC_SOLVER_DDP (1): GaussNewtonDDP_MPC of ocs2_bipedal_robot_ros/src/BipedalRobotDdpMpcNode.cpp:70-71 with the ddp block of
                            task.info:115-156 - ONE ILQR iteration per run (ddp.algorithm ILQR, maxNumIterations 1, strategy LINE_SEARCH, hessian
-                           correction DIAGONAL_SHIFT; anything else: BPMPC_ERR_UNSUPPORTED): Euler-discretised LQ model on the time grid of the
+                           correction DIAGONAL_SHIFT, at most 15 step lengths maxStepLength, / 2, .. >= minStepLength; anything else: BPMPC_ERR_UNSUPPORTED):
+                           Euler-discretised LQ model on the time grid of the
                            nominal trajectories, equality-constrained Riccati recursion, line search over TimeTriggeredRollout roll-outs of the
                            policy (rollout block of task.info).  The solution is the accepted roll-out ON ITS OWN TIME POINTS: bpmpc_solver_fetch
                            returns them in out_t, stats.n_nodes = points - 1 (at most max_nodes), stats.step_size = the accepted step length,

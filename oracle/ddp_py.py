@@ -124,17 +124,20 @@ def step_lengths(ddp):
     return out
 
 
-def nominal_rollout(om, nodes, x_measured, x_shifted, u_shifted, event_times, rollout):
+def nominal_rollout(om, nodes, x_measured, x_shifted, u_shifted, event_times, rollout, info=None):
     """Nominal trajectories of a warm MPC tick.  [OCS2-upstream, recalled] GaussNewtonDDP::rolloutInitialTrajectory: the controller of the previous run
     (ddp.useFeedbackPolicy false: a FeedforwardController, here the input trajectory already shifted onto the new grid - warm_start_from_previous with
     feedback=False -, the initializer's input beyond its end) is rolled out from the measured state with TimeTriggeredRollout; the state trajectory of
     that roll-out is the nominal one.  The backward pass of this engine works on the shooting grid: node k takes LinearInterpolation(t_k) of the
-    roll-out (the first node the measured state).  Follows csrc/k_ddp.hip k_ddp_nominal / solver.hip ddp_nominal_rollout.  Returns x_nom [N + 1, nx]."""
+    roll-out (the first node the measured state).  Follows csrc/k_ddp.hip k_ddp_nominal / solver.hip ddp_nominal_rollout.  Returns x_nom [N + 1, nx];
+    info (a dict, optional) receives `record`, the number of time points of the roll-out (the engine's record holds max_nodes + 1)."""
     N = int(nodes["N"])
     tp = np.asarray(nodes["times"], float)
     tpa, _, uff, KK = rp.primal_solution_arrays(nodes, x_shifted, u_shifted, np.zeros((N, om.nu, om.nx)))
     ctrl = lambda t, x: rp.linear_controller_input(tpa, uff, KK, t, x)      # K = 0: the interpolated input trajectory
     ro = rp.time_triggered_rollout(lambda x, u: om.flow_map(x, u), ctrl, float(tp[0]), x_measured, float(tp[-1]), list(event_times), rollout)
+    if info is not None:
+        info["record"] = len(ro["times"])
     x_nom = np.array(x_shifted, float)
     for k in range(N + 1):
         i, al = rp.time_segment(ro["times"], float(tp[k]))
@@ -143,19 +146,34 @@ def nominal_rollout(om, nodes, x_measured, x_shifted, u_shifted, event_times, ro
     return x_nom
 
 
-def ilqr_iteration(om, model, nodes, x_measured, x_nom, u_nom, event_times, mode_sequence, target_times, target_states, ddp, rollout):
-    """One GaussNewtonDDP / ILQR iteration.  Returns dict(alpha, times, states, inputs, K, lff, merit0, merits, update_is)."""
+def ilqr_iteration(om, model, nodes, x_measured, x_nom, u_nom, event_times, mode_sequence, target_times, target_states, ddp, rollout, record_cap=None):
+    """One GaussNewtonDDP / ILQR iteration.  Returns dict(alpha, times, states, inputs, K, lff, merit0, merits, update_is, records, status).
+    records: the number of time points of every roll-out, the baseline first, then the step lengths in descending order (None: the integrator
+    found no step size).  record_cap = None is upstream: no limit on a record, an integrator failure raises.  With record_cap (the engine:
+    max_nodes + 1 time points, csrc/kernels/rollout.h) a roll-out that fails or has more time points than that takes no part in the search
+    (its merit is nan); without a baseline there is no search: status 3, alpha 0, times / states / inputs None - the nominal trajectories stay
+    (k_ddp_select / k_ddp_finish).  status otherwise as the engine reports it: 0 a step was accepted, 1 none (the baseline is the solution)."""
     N = int(nodes["N"])
     lq = euler_lq(om, nodes, x_nom, u_nom)
     K, lff, S0, s0 = backward_pass(lq, nodes, float(ddp["hessianCorrectionMultiple"]))
     update_is = float(sum(nodes["dt"][k] * lff[k] @ lff[k] for k in range(N) if nodes["kind"][k] == 0))
     tp = np.asarray(nodes["times"], float)
     flow = lambda x, u: om.flow_map(x, u)
+    records = []
 
     def closed_loop(alpha):
         tpa, _, uff, KK = rp.primal_solution_arrays(nodes, x_nom, u_nom + alpha * lff, K)
         ctrl = lambda t, x: rp.linear_controller_input(tpa, uff, KK, t, x)
-        ro = rp.time_triggered_rollout(flow, ctrl, float(tp[0]), x_measured, float(tp[-1]), list(event_times), rollout)
+        try:
+            ro = rp.time_triggered_rollout(flow, ctrl, float(tp[0]), x_measured, float(tp[-1]), list(event_times), rollout)
+        except RuntimeError:
+            if record_cap is None:
+                raise
+            records.append(None)
+            return None, float("nan")
+        records.append(len(ro["times"]))
+        if record_cap is not None and len(ro["times"]) > record_cap:
+            return None, float("nan")
         return ro, trajectory_cost(om, model, ro["times"], ro["states"], ro["inputs"], event_times, mode_sequence, target_times, target_states)
 
     base, merit0 = closed_loop(0.0)        # the baseline of the search: the roll-out under the new gains with NO feedforward increment (step length 0)
@@ -163,7 +181,10 @@ def ilqr_iteration(om, model, nodes, x_measured, x_nom, u_nom, event_times, mode
     for alpha in step_lengths(ddp):
         ro, merit = closed_loop(alpha)
         merits.append(merit)
-        if best is None and merit < merit0 - ARMIJO_COEFFICIENT * alpha * update_is:
+        if base is not None and ro is not None and best is None and merit < merit0 - ARMIJO_COEFFICIENT * alpha * update_is:
             best = (alpha, ro)
+    out = dict(K=K, lff=lff, merit0=merit0, merits=merits, update_is=update_is, records=records)
+    if base is None:
+        return dict(out, alpha=0.0, times=None, states=None, inputs=None, status=3)
     alpha, ro = best if best is not None else (0.0, base)
-    return dict(alpha=alpha, times=ro["times"], states=ro["states"], inputs=ro["inputs"], K=K, lff=lff, merit0=merit0, merits=merits, update_is=update_is)
+    return dict(out, alpha=alpha, times=ro["times"], states=ro["states"], inputs=ro["inputs"], status=0 if best is not None else 1)
