@@ -872,6 +872,16 @@ class BatchedStateEstimate:
         self.batch = B
         return rbd
 
+    def update_from_plant(self, plant, period=0.0025, fetch=True):
+        """update on the device outputs of `plant` (BatchedPlant) after its last step (bpmpc_estimator_update_from_plant): the estimator's stream
+        waits for a step that was only enqueued and the plant's stream for this update, so plant.step_controlled, this call with fetch=False and
+        BatchedController.tick_estimated need no synchronisation between them.  Returns what update returns."""
+        B = plant.batch
+        rbd = np.zeros((B, 2 * self.generalizedCoordinatesNum)) if fetch else None
+        _check(load_library().bpmpc_estimator_update_from_plant(self._h, plant._h, B, C.c_double(period), _d(rbd)))
+        self.batch = B
+        return rbd
+
     def reset(self, mask=None):
         """x_hat = 0, P = 100 I for the robots with mask[b] != 0 (None: every robot); the others do not change by one bit."""
         B = self.max_batch if mask is None else _count(mask)
@@ -1067,6 +1077,131 @@ class BatchedController:
         for k, p in zip(self.JOINT_NAMES, ptrs):
             views[k] = DeviceArray(C.cast(p, C.c_void_p).value, (B, self.nj), "<f8")
         return views
+
+
+class PlantParams:
+    """A parameter row of the plant (include/bpmpc.h "Plant", BPMPC_PLANT_PARAM_STRIDE) with named fields: contact stiffness kn [N/m], normal damping
+    cn [N s/m], the penetration d0 [m] at which the normal damping is fully on, friction coefficient mu, the velocity v_eps [m/s] that regularises
+    the Coulomb law, and the normal force contact_threshold [N] above which a contact point reports contact.  The defaults are the values without
+    arguments."""
+
+    STRIDE = 8
+    FIELDS = ("kn", "cn", "d0", "mu", "v_eps", "contact_threshold")
+    DEFAULTS = (5e4, 5e2, 1e-3, 0.7, 0.01, 1.0)
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name, default in zip(self.FIELDS, self.DEFAULTS):
+            setattr(self, name, float(fields.get(name, default)))
+
+    @classmethod
+    def fromRow(cls, row):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
+
+    def toRow(self):
+        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0, 0.0])
+
+
+class _JointCommand(C.Structure):
+    NAMES = ("pos_des", "vel_des", "tau_ff", "kp", "kd", "base_force", "feet_heights")
+    _fields_ = [(n, _dp) for n in NAMES]
+
+
+class _PlantOutputs(C.Structure):
+    _fields_ = [("sensors", _SensorInputs), ("rbd", _dp), ("contact_force", _dp)]
+
+
+class BatchedPlant:
+    """A rigid-body simulation of a batch of robots on one MI355X (bpmpc_plant; include/bpmpc.h "Plant" is its specification): joint commands ->
+    the sensors BatchedStateEstimate.update takes and the ground-truth rbd.  This engine's own model - penalty contacts with implicit damping, a
+    joint PD with an implicit kd term, semi-implicit Euler - and not an imitation of the simulators the reference runs against.  taskFile (None:
+    the interface's) is read for the keys plant.<name> and for the WBC's torque limits."""
+
+    def __init__(self, interface, max_batch=1, taskFile=None, device=0):
+        self.interface, self.max_batch = interface, int(max_batch)
+        self.nj = interface.actuatedDofNum
+        self.generalizedCoordinatesNum = 6 + self.nj
+        self._h = C.c_void_p()
+        _check(load_library().bpmpc_plant_create(interface.handle, str(taskFile or interface.taskFile).encode(), int(device), self.max_batch, C.byref(self._h)))
+        self.batch = 0
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:
+            _LIB.bpmpc_plant_destroy(self._h)
+            self._h = None
+
+    def set_state(self, rbd, mask=None):
+        """q, v of the robots with mask[b] != 0 (None: every one of the B) from rbd [B, 2 (6 + nj)] in the layout of BatchedController.tick; the
+        others do not change by one bit.  numpy arrays (validated, synchronises) or float64 / int32 device tensors (only enqueued)."""
+        shape = _shape(rbd)
+        if len(shape) != 2 or shape[1] != 2 * self.generalizedCoordinatesNum:
+            raise ValueError("rbd must have the shape [B, %d], got %s" % (2 * self.generalizedCoordinatesNum, list(shape)))
+        B = shape[0]
+        (mp, rp), dev, keep = _restart_args((mask, C.c_int, B), (rbd, C.c_double, B * shape[1]))
+        _check(load_library().bpmpc_plant_set_state(self._h, B, mp, rp, dev))
+        del keep
+        self.batch = B
+
+    def get_state(self, batch=None):
+        """The ground-truth rbd [B, 2 (6 + nj)] of the first B robots (None: the batch of the last set_state); synchronises."""
+        B = int(batch or self.batch)
+        rbd = np.zeros((B, 2 * self.generalizedCoordinatesNum))
+        _check(load_library().bpmpc_plant_get_state(self._h, B, _d(rbd)))
+        return rbd
+
+    def step(self, pos_des, vel_des, tau_ff, kp, kd, base_force=None, feet_heights=None, period=0.002, substeps=4):
+        """One control step of `period` in `substeps` substeps for the batch of the last set_state.  pos_des, vel_des, tau_ff, kp, kd: [B, nj];
+        base_force [B, 3] (world-frame force on the base origin) and feet_heights [B, 4] (ground height under each contact point) may be None.
+        numpy arrays (synchronises) or float64 device tensors (only enqueued; see outputs)."""
+        B, nj = self.batch, self.nj
+        ptrs, dev, keep = _restart_args(*[(a, C.c_double, B * nj) for a in (pos_des, vel_des, tau_ff, kp, kd)], (base_force, C.c_double, B * 3),
+                                        (feet_heights, C.c_double, B * 4))
+        cmd = _JointCommand(*ptrs)
+        _check(load_library().bpmpc_plant_step(self._h, B, C.byref(cmd), dev, C.c_double(period), int(substeps)))
+        del keep
+
+    def step_controlled(self, controller, base_force=None, feet_heights=None, period=0.002, substeps=4):
+        """One control step on the last tick of `controller` (BatchedController): posDes / velDes / torque of its joint_cmd and its joint gains, read
+        on the device; the two handles' streams are ordered by events, nothing is synchronised unless base_force / feet_heights are host arrays."""
+        B = self.batch
+        (fp, gp), dev, keep = _restart_args((base_force, C.c_double, B * 3), (feet_heights, C.c_double, B * 4))
+        _check(load_library().bpmpc_plant_step_controlled(self._h, controller._h, B, C.c_double(period), int(substeps), fp, gp, dev))
+        del keep
+
+    def outputs(self):
+        """The outputs of the last step where they live: a dict of DeviceArray (`.torch()` wraps one without a copy) over the batch of the last
+        set_state - the sensors of BatchedStateEstimate.update by name (joint_pos, joint_vel, quat, angular_vel_local, linear_accel_local, contact,
+        feet_heights, odom_pos, odom_quat, odom_lin_vel, odom_ang_vel), rbd and contact_force [B, 4, 3]."""
+        o = _PlantOutputs()
+        _check(load_library().bpmpc_plant_device_outputs(self._h, C.byref(o)))
+        B, nj = self.batch or self.max_batch, self.nj
+        shapes = {"joint_pos": (B, nj), "joint_vel": (B, nj), "quat": (B, 4), "angular_vel_local": (B, 3), "linear_accel_local": (B, 3), "contact": (B, 4),
+                  "feet_heights": (B, 4), "odom_pos": (B, 3), "odom_quat": (B, 4), "odom_lin_vel": (B, 3), "odom_ang_vel": (B, 3)}
+        views = {k: DeviceArray(C.cast(getattr(o.sensors, k), C.c_void_p).value, shp, "<i4" if k == "contact" else "<f8") for k, shp in shapes.items()}
+        views["rbd"] = DeviceArray(C.cast(o.rbd, C.c_void_p).value, (B, 2 * self.generalizedCoordinatesNum), "<f8")
+        views["contact_force"] = DeviceArray(C.cast(o.contact_force, C.c_void_p).value, (B, 4, 3), "<f8")
+        return views
+
+    def getParams(self, robot=-1):
+        """The parameter row [8] of `robot` (PlantParams.fromRow names its entries), or with robot < 0 the values every row starts from."""
+        row = np.zeros(PlantParams.STRIDE)
+        _check(load_library().bpmpc_plant_get_params(self._h, int(robot), _d(row)))
+        return row
+
+    def setParams(self, rows, mask=None):
+        """rows [8], [1, 8] or [B, 8]; mask as WeightedWbc.setParams.  numpy rows are validated (finite; kn, d0, v_eps positive; the others not
+        negative) and the call synchronises; device tensors are only enqueued, ordered before the next step."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], PlantParams.STRIDE, self.max_batch)
+        _check(load_library().bpmpc_plant_set_params(self._h, B, mp, rp, n_rows, dev))
+        del keep
+
+    def resetParams(self):
+        _check(load_library().bpmpc_plant_reset_params(self._h))
 
 
 class BatchedDdpMpc(BatchedSqpMpc):

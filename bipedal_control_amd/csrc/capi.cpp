@@ -10,6 +10,7 @@
 #include "capi_internal.h"
 #include "estimator.h"
 #include "info_tree.h"
+#include "plant.h"
 #include "reference_gen.h"
 
 struct bpmpc_model { bpmpc::RobotModel rm; };
@@ -53,6 +54,31 @@ EstSettings estimator_load_settings(const char* task_info_path) {
     double* v = &s.foot_radius;
     for (int e = 0; e < kEstParamStride - 1; ++e) (void)t->get(std::string("kalmanFilter.") + kEstParamNames[e], v + e);
     estimator_check_param_row("kalmanFilter settings", v, 0);
+  }
+  return s;
+}
+
+namespace {
+const char* const kPlantParamNames[] = {"kn", "cn", "d0", "mu", "v_eps", "contact_threshold"};
+constexpr int kPlantParamUsed = 6;
+}
+
+void plant_check_param_row(const char* who, const double* row, int r) {
+  for (int e = 0; e < kPlantParamUsed; ++e) {
+    const bool positive = e == 0 || e == 2 || e == 4;
+    if (!std::isfinite(row[e]) || row[e] < 0.0 || (positive && row[e] == 0.0))
+      throw std::invalid_argument(std::string(who) + ": row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + kPlantParamNames[e] + ") is " +
+                                  (!std::isfinite(row[e]) ? "not finite" : row[e] < 0.0 ? "negative" : "zero"));
+  }
+}
+
+PlantSettings plant_load_settings(const char* task_info_path) {
+  PlantSettings s{5e4, 5e2, 1e-3, 0.7, 0.01, 1.0, {0.0, 0.0}};      // include/bpmpc.h "Plant"
+  if (task_info_path) {
+    const auto t = read_info_file(task_info_path);
+    double* v = &s.kn;
+    for (int e = 0; e < kPlantParamUsed; ++e) (void)t->get(std::string("plant.") + kPlantParamNames[e], v + e);
+    plant_check_param_row("plant settings", v, 0);
   }
   return s;
 }
@@ -174,6 +200,23 @@ int bpmpc_estimator_check_params(const double* rows, int n_rows) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_estimator_check_params: null rows");
   return guarded(BPMPC_ERR_IO, [&] {
     for (int r = 0; r < n_rows; ++r) estimator_check_param_row("bpmpc_estimator_check_params", rows + (size_t)r * kEstParamStride, r);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_load_params(const char* task_info_path, double* row) {
+  if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_params: null row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    const PlantSettings s = plant_load_settings(task_info_path);
+    std::copy(&s.kn, &s.kn + kPlantParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_check_params(const double* rows, int n_rows) {
+  if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_params: null rows");
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) plant_check_param_row("bpmpc_plant_check_params", rows + (size_t)r * kPlantParamStride, r);
     return (int)BPMPC_OK;
   });
 }

@@ -15,6 +15,7 @@
 #include <string>
 
 #include "estimator.h"
+#include "plant.h"
 #include "solver.h"
 #include "wbc.h"
 #include "kernels/tick.h"
@@ -30,6 +31,7 @@ struct bpmpc_controller {
   int *d_mode = nullptr, *d_safe = nullptr, *d_mask = nullptr;
   double *d_kp = nullptr, *d_kd = nullptr, *d_torque = nullptr;      // [max_batch][nj]: joint gains (0 after create), the last tick's joint_torque
   double *d_kp_in = nullptr, *d_kd_in = nullptr;                     // device copies of host gain rows
+  int last_tick_batch = 0;                                           // rows of d_cmd that hold the commands of a tick (0: no tick yet)
 };
 
 namespace {
@@ -64,6 +66,7 @@ void enqueue_tick(bpmpc_controller* c, int batch, const double* dt, const double
   ca.cmd = c->d_cmd; ca.joint_torque = c->d_torque;
   kl::tick_commands(c->nj, s->stream, ca);
   HIP_CHECK(hipGetLastError());
+  c->last_tick_batch = batch;
 }
 
 // the host copies of a tick's outputs (host_out NULL: nothing is copied or synchronised)
@@ -85,6 +88,12 @@ void fetch_tick(bpmpc_controller* c, int batch, const bpmpc_tick_outputs* host_o
 }
 
 }  // namespace
+
+namespace bpmpc {
+ControllerCommands controller_commands(const bpmpc_controller* c) {
+  return {c->s->stream, c->d_cmd, c->d_kp, c->d_kd, c->nj, c->device, c->max_batch, c->last_tick_batch};
+}
+}  // namespace bpmpc
 
 extern "C" {
 

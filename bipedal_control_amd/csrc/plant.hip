@@ -1,0 +1,271 @@
+// Host side of the batched rigid-body plant (kernels/plant.h): settings ingest, device buffers, the C ABI (include/bpmpc.h "Plant").  The plant
+// stands where the reference has MuJoCo or Gazebo (bipedal_mujoco, bipedal_gazebo/src/BipedalHWSim.cpp) and imitates neither: the model is the one
+// specified in include/bpmpc.h.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "capi_internal.h"
+#include "estimator.h"
+#include "info_tree.h"
+#include "kernel_launchers.h"
+#include "plant.h"
+
+namespace bpmpc {
+
+template <int NJ>
+__global__ __launch_bounds__(kWave) void k_plant_step(const DeviceModel* model, PlantArgs a) {
+  __shared__ PlantLds<NJ> w;
+  const int b = blockIdx.x;
+  if (b >= a.batch) return;
+  plant_robot<NJ>(*model, w, a, b, threadIdx.x);
+}
+
+// bpmpc_plant_set_state for the robots of `mask` (NULL: every robot below `batch`): q, v from rbd_in[b] (the Euler rates from the world angular
+// velocity as WbcBase::updateMeasured forms them) and the robot's row of the rbd output.  One thread per entry of [q | v].
+__global__ __launch_bounds__(256) void k_plant_set_state(int batch, int nv, const int* mask, const double* rbd_in, double* state, double* rbd_out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= batch * 2 * nv) return;
+  const int b = i / (2 * nv), e = i % (2 * nv);
+  if (mask && !mask[b]) return;
+  const double* rb = rbd_in + (size_t)b * 2 * nv;
+  rbd_out[i] = rb[e];
+  double val;
+  if (e < 3) val = rb[3 + e];
+  else if (e < 6) val = rb[e - 3];
+  else if (e < nv) val = rb[e];
+  else if (e < nv + 3) val = rb[e + 3];
+  else if (e < nv + 6) {
+    const double cy = cos(rb[0]), sy = sin(rb[0]), cp = cos(rb[1]), sp = sin(rb[1]);
+    const double wx = rb[nv], wy = rb[nv + 1], wz = rb[nv + 2];
+    const double rr = (cy * wx + sy * wy) / cp;          // roll rate
+    const double pr = -sy * wx + cy * wy;                // pitch rate
+    val = e == nv + 3 ? wz + sp * rr : (e == nv + 4 ? pr : rr);
+  } else val = rb[e];
+  state[i] = val;
+}
+
+}  // namespace bpmpc
+
+using namespace bpmpc;
+
+namespace {
+
+// every parameter row becomes the defaults (the last row of d_rows)
+void write_default_params(bpmpc_plant* p) {
+  write_rows(p->hs.stream, p->max_batch, kPlantParamStride, kPlantParamStride - 2, nullptr, 1, {p->d_rows + (size_t)p->max_batch * kPlantParamStride, nullptr, p->d_params});
+}
+
+void check_batch(const bpmpc_plant* p, int batch, const char* who) {
+  if (batch < 1) throw std::invalid_argument(std::string(who) + ": batch must be positive");
+  if (batch > p->max_batch) throw std::length_error(std::string(who) + ": batch exceeds max_batch");
+}
+
+// the refusals of a step behind its null checks
+void check_step(const bpmpc_plant* p, int batch, double period, int substeps, const char* who) {
+  if (substeps < 1) throw std::invalid_argument(std::string(who) + ": substeps must be at least 1");
+  if (!std::isfinite(period) || period <= 0.0) throw std::invalid_argument(std::string(who) + ": period must be finite and positive");
+  check_batch(p, batch, who);
+  if (batch != p->last_batch)
+    throw std::invalid_argument(std::string(who) + ": batch " + std::to_string(batch) + " differs from the batch of the last set_state (" + std::to_string(p->last_batch) +
+                                "): the other robots have no state");
+}
+
+PlantArgs step_args(const bpmpc_plant* p, int batch, double period, int substeps) {
+  PlantArgs a{};
+  a.batch = batch; a.substeps = substeps; a.h = period / substeps; a.params = p->d_params; a.state = p->d_state;
+  for (int i = 0; i < kMaxJoints / 2; ++i) a.torque_limits[i] = p->torque_limits[i];
+  a.out = p->d_out; a.max_batch = p->max_batch;
+  return a;
+}
+
+void launch_step(bpmpc_plant* p, const PlantArgs& a) {
+  KL_NJ(p->nj, hipLaunchKernelGGL(k_plant_step<NJ>, dim3(a.batch), dim3(kWave), 0, p->hs.stream, p->d_model, a));
+  HIP_CHECK(hipGetLastError());
+}
+
+void record(hipEvent_t* ev, hipStream_t on) {
+  if (!*ev) HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+  HIP_CHECK(hipEventRecord(*ev, on));
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int device, int max_batch, bpmpc_plant** out) {
+  if (!model || !out) { set_last_error("bpmpc_plant_create: null model or output"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  *out = nullptr;
+  if (max_batch < 1) { set_last_error("bpmpc_plant_create: max_batch must be positive"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  std::unique_ptr<bpmpc_plant> p(new bpmpc_plant);
+  const int rc = guarded(BPMPC_ERR_IO, [&]() -> int {
+    if (const int refused = open_side_handle("bpmpc_plant_create", p.get(), model, device, max_batch)) return refused;
+    p->defaults = plant_load_settings(task_info_path);
+    p->nj = p->rm.nj; p->nv = 6 + p->rm.nj;
+    if (task_info_path) {
+      const auto t = read_info_file(task_info_path);
+      const std::vector<double> lim = load_matrix(*t, "torqueLimitsTask", p->nj / 2, 1);
+      for (int i = 0; i < p->nj / 2; ++i) p->torque_limits[i] = lim[i];
+    }
+    const size_t B = max_batch, nj = p->nj, nv = p->nv;
+    DeviceBuffers& m = p->mem;
+    p->d_state = m.alloc<double>(B * 2 * nv, true);
+    p->d_params = m.alloc<double>(B * kPlantParamStride); p->d_rows = m.alloc<double>((B + 1) * kPlantParamStride); p->d_mask = m.alloc<int>(B);
+    p->d_rbd_in = m.alloc<double>(B * 2 * nv);
+    p->d_pd = m.alloc<double>(B * nj); p->d_vd = m.alloc<double>(B * nj); p->d_tf = m.alloc<double>(B * nj); p->d_kp = m.alloc<double>(B * nj); p->d_kd = m.alloc<double>(B * nj);
+    p->d_force = m.alloc<double>(B * 3); p->d_ground = m.alloc<double>(B * 4);
+    p->d_out = m.alloc<double>(B * plant_out_offset(kPlantOutEnd, p->nj), true);
+    auto section = [&](int sec) { return p->d_out + B * plant_out_offset(sec, p->nj); };
+    bpmpc_sensor_inputs& s = p->out.sensors;
+    s.joint_pos = section(kPlantJointPos); s.joint_vel = section(kPlantJointVel); s.quat = section(kPlantQuat);
+    s.angular_vel_local = section(kPlantAngLocal); s.linear_accel_local = section(kPlantAccLocal);
+    s.contact = reinterpret_cast<int*>(section(kPlantContact)); s.mode = nullptr;
+    s.feet_heights = section(kPlantFeetHeights); s.odom_pos = section(kPlantOdomPos); s.odom_quat = section(kPlantOdomQuat);
+    s.odom_lin_vel = section(kPlantOdomLin); s.odom_ang_vel = section(kPlantOdomAng);
+    p->out.rbd = section(kPlantRbd); p->out.contact_force = section(kPlantContactForce);
+    HIP_CHECK(hipMemcpy(p->d_rows + B * kPlantParamStride, &p->defaults, sizeof(PlantSettings), hipMemcpyHostToDevice));
+    write_default_params(p.get());
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    return BPMPC_OK;
+  });
+  if (rc != BPMPC_OK) { bpmpc_plant_destroy(p.release()); return rc; }
+  *out = p.release();
+  return BPMPC_OK;
+}
+
+void bpmpc_plant_destroy(bpmpc_plant* p) {
+  if (!p) return;
+  if (p->hs.stream) { (void)hipSetDevice(p->device); (void)hipStreamSynchronize(p->hs.stream); }
+  if (p->ev_tick) (void)hipEventDestroy(p->ev_tick);
+  if (p->ev_step) (void)hipEventDestroy(p->ev_step);
+  close_side_handle(p);
+}
+
+int bpmpc_plant_set_state(bpmpc_plant* p, int batch, const int* mask, const double* rbd, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_state: null handle or rbd", rbd != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_state");
+    const size_t B = batch, E = 2 * p->nv;
+    if (!inputs_on_device)
+      for (size_t i = 0; i < B * E; ++i)
+        if (!mask || mask[i / E]) if (!std::isfinite(rbd[i])) throw std::invalid_argument("bpmpc_plant_set_state: rbd of robot " + std::to_string(i / E) + " is not finite");
+    hipStream_t st = p->hs.stream;
+    const int* dmask = staged(mask, p->d_mask, B, inputs_on_device, st);
+    const double* drbd = staged(rbd, p->d_rbd_in, B * E, inputs_on_device, st);
+    hipLaunchKernelGGL(k_plant_set_state, dim3((batch * (int)E + 255) / 256), dim3(256), 0, st, batch, p->nv, dmask, drbd, p->d_state, p->out.rbd);
+    HIP_CHECK(hipGetLastError());
+    p->last_batch = batch;
+    if (!inputs_on_device) p->hs.synchronise_own();
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_get_state(bpmpc_plant* p, int batch, double* host_rbd) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_state: null handle or rbd", host_rbd != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_get_state");
+    HIP_CHECK(hipMemcpyAsync(host_rbd, p->out.rbd, (size_t)batch * 2 * p->nv * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    p->hs.synchronise_own();
+  });
+}
+
+int bpmpc_plant_step(bpmpc_plant* p, int batch, const bpmpc_joint_command* c, int inputs_on_device, double period, int substeps) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_step: null handle or command", c && c->pos_des && c->vel_des && c->tau_ff && c->kp && c->kd, [&] {
+    check_step(p, batch, period, substeps, "bpmpc_plant_step");
+    const size_t B = batch, nj = p->nj;
+    hipStream_t st = p->hs.stream;
+    PlantArgs a = step_args(p, batch, period, substeps);
+    a.cmd_stride = p->nj;
+    a.pos_des = staged(c->pos_des, p->d_pd, B * nj, inputs_on_device, st);
+    a.vel_des = staged(c->vel_des, p->d_vd, B * nj, inputs_on_device, st);
+    a.tau_ff = staged(c->tau_ff, p->d_tf, B * nj, inputs_on_device, st);
+    a.kp = staged(c->kp, p->d_kp, B * nj, inputs_on_device, st);
+    a.kd = staged(c->kd, p->d_kd, B * nj, inputs_on_device, st);
+    a.base_force = staged(c->base_force, p->d_force, B * 3, inputs_on_device, st);
+    a.ground = staged(c->feet_heights, p->d_ground, B * 4, inputs_on_device, st);
+    launch_step(p, a);
+    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_device_outputs(bpmpc_plant* p, bpmpc_plant_outputs* o) {
+  if (!p || !o) { set_last_error("bpmpc_plant_device_outputs: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  *o = p->out;
+  return BPMPC_OK;
+}
+
+// One step on the commands of the controller's last tick, read where the tick wrote them: the plant's stream waits for the tick on the solver's
+// stream, and the solver's stream waits for the step before the next tick overwrites joint_cmd
+int bpmpc_plant_step_controlled(bpmpc_plant* p, bpmpc_controller* controller, int batch, double period, int substeps, const double* base_force,
+                                const double* feet_heights, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_step_controlled: null plant or controller", controller != nullptr, [&] {
+    const ControllerCommands cc = controller_commands(controller);
+    if (cc.nj != p->nj) throw std::invalid_argument("bpmpc_plant_step_controlled: the plant and the controller are built for different robots");
+    if (cc.device != p->device) throw std::invalid_argument("bpmpc_plant_step_controlled: the plant and the controller live on different devices");
+    check_step(p, batch, period, substeps, "bpmpc_plant_step_controlled");
+    if (cc.last_tick_batch == 0) throw std::invalid_argument("bpmpc_plant_step_controlled: the controller has not ticked yet: there are no joint commands");
+    if (batch != cc.last_tick_batch)
+      throw std::invalid_argument("bpmpc_plant_step_controlled: batch " + std::to_string(batch) + " differs from the batch of the controller's last tick (" +
+                                  std::to_string(cc.last_tick_batch) + ")");
+    const size_t B = batch;
+    hipStream_t st = p->hs.stream;
+    PlantArgs a = step_args(p, batch, period, substeps);
+    a.cmd_stride = 3 * p->nj;
+    a.pos_des = cc.joint_cmd; a.vel_des = cc.joint_cmd + p->nj; a.tau_ff = cc.joint_cmd + 2 * p->nj;
+    a.kp = cc.kp; a.kd = cc.kd;
+    a.base_force = staged(base_force, p->d_force, B * 3, inputs_on_device, st);
+    a.ground = staged(feet_heights, p->d_ground, B * 4, inputs_on_device, st);
+    record(&p->ev_tick, cc.stream);
+    HIP_CHECK(hipStreamWaitEvent(st, p->ev_tick, 0));
+    launch_step(p, a);
+    record(&p->ev_step, st);
+    HIP_CHECK(hipStreamWaitEvent(cc.stream, p->ev_step, 0));
+    if (!inputs_on_device && (base_force || feet_heights)) p->hs.synchronise_own();      // the caller's host arrays
+    else p->hs.enqueued_own();
+  });
+}
+
+// bpmpc_estimator_update on the plant's device outputs: the estimator's stream waits for a step that was only enqueued, and the plant's stream for
+// this update before its next step overwrites the outputs
+int bpmpc_estimator_update_from_plant(bpmpc_estimator* e, bpmpc_plant* p, int batch, double period, double* host_rbd) {
+  if (!e) { set_last_error("bpmpc_estimator_update_from_plant: null estimator"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_estimator_update_from_plant: null plant", [&]() -> int {
+    if (e->nj != p->nj) throw std::invalid_argument("bpmpc_estimator_update_from_plant: the estimator and the plant are built for different robots");
+    if (e->device != p->device) throw std::invalid_argument("bpmpc_estimator_update_from_plant: the estimator and the plant live on different devices");
+    if (batch != p->last_batch) throw std::invalid_argument("bpmpc_estimator_update_from_plant: batch differs from the batch of the plant's last set_state");
+    p->hs.before_foreign(e->hs.stream);
+    const int rc = bpmpc_estimator_update(e, batch, &p->out.sensors, 1, period, host_rbd);
+    p->hs.after_foreign(e->hs.stream);
+    return rc;
+  });
+}
+
+int bpmpc_plant_get_params(const bpmpc_plant* p, int robot, double* row) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_params: null handle or row", row != nullptr, [&] {
+    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_params: robot exceeds max_batch");
+    const double* src = robot < 0 ? p->d_rows + (size_t)p->max_batch * kPlantParamStride : p->d_params + (size_t)robot * kPlantParamStride;
+    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(PlantSettings), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_set_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_params: null handle or rows", rows != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_params");
+    set_rows("bpmpc_plant_set_params", p->hs.stream, batch, kPlantParamStride, kPlantParamStride - 2, mask, p->d_mask, n_rows, inputs_on_device,
+             [&](int r) { plant_check_param_row("bpmpc_plant_set_params", rows + (size_t)r * kPlantParamStride, r); }, {rows, p->d_rows, p->d_params});
+    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // device rows are only enqueued on the handle's stream: the next step runs behind them
+  });
+}
+
+int bpmpc_plant_reset_params(bpmpc_plant* p) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_params: null handle", [&] {
+    write_default_params(p);
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+}  // extern "C"

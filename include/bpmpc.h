@@ -593,6 +593,84 @@ int bpmpc_estimator_check_params(const double* rows, int n_rows);
 int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimator* estimator, int batch, const double* t, int inputs_on_device,
                                     double period, const bpmpc_tick_outputs* host_out);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Plant = a rigid-body simulation of a BATCH of robots on the device: joint commands in, the sensors of bpmpc_sensor_inputs out, so that the
+ * loop sensors -> bpmpc_estimator_update -> bpmpc_controller_tick_estimated -> joint commands closes without leaving the device.  The reference
+ * closes its loop with MuJoCo or Gazebo (bipedal_mujoco, bipedal_gazebo/src/BipedalHWSim.cpp).  This plant imitates neither: it is this engine's own
+ * model, this comment is its specification, and it is nowhere pinned against the reference's simulators.  It has no joint limits, no
+ * self-collision and no tangential contact spring.
+ *   state per robot: q[6+nj] = [position, zyx, joints], v[6+nj] = dq/dt (Euler rates, not angular velocity: the coordinates of the WBC), so
+ *     integrating q is a plain sum.  One control step of length `period` is `substeps` equal substeps of h = period / substeps.  One substep:
+ *       1. rigid-body pass at (q, v) with gravity: M, nle (as the WBC's), the four contact points p_i, the stacked contact Jacobian J (12 x nv),
+ *          the point velocities c_i = J_i v
+ *       2. contact point i with ground height g_i (feet_heights, NULL: 0) and penetration d_i = g_i - p_i,z: open unless d_i > 0.  Closed:
+ *          spring force f_i = (0, 0, kn d_i); normal damping cn_i = cn min(1, d_i / d0); start-of-step normal force
+ *          n_i = max(0, kn d_i - cn_i c_i,z); tangential damping ct_i = mu n_i / sqrt(c_i,x^2 + c_i,y^2 + v_eps^2) (a regularised Coulomb law);
+ *          D_i = diag(ct_i, ct_i, cn_i).  Open: f_i = 0, D_i = 0, n_i = 0.
+ *       3. joint torque tau_j = kp_j (posDes_j - q_j) + tau_ff,j, clamped to +- the torque limit of its leg joint when that limit is > 0; the
+ *          kd term kd_j (velDes_j - v+_j) is implicit and not clamped
+ *       4. v+ solves (M + h J'DJ + h diag(0_6, kd)) v+ = M v + h (S'(tau + kd velDes) - nle + J'f + w_ext); S selects the joints, w_ext is the
+ *          external force base_force (world frame, NULL: 0) on the base origin, acting on coordinates 0..2.  The matrix is symmetric positive
+ *          definite; k_plant_step factors it by a Cholesky factorisation without pivoting.
+ *       5. q+ = q + h v+
+ *     All damping is linearly implicit, the contact spring is explicit.
+ *   outputs, written after the last substep from (q+, v+), in the layouts of bpmpc_sensor_inputs: joint_pos, joint_vel; quat (x y z w) of R(zyx);
+ *     angular_vel_local = R' E(zyx) thetadot; linear_accel_local = R' (a + (0, 0, 9.81)) with a = (v+ - v)[0:3] / h of the last substep (what step 5
+ *     of the Kalman filter inverts); contact[4] = (n_i > contact_threshold), n_i of the last substep; feet_heights = the ground heights given (0);
+ *     mode = NULL (the plant reports contact flags); the ground truth for BPMPC_ESTIMATOR_FROM_TOPIC, odom_pos, odom_quat, odom_lin_vel and
+ *     odom_ang_vel = E(zyx) thetadot (world); rbd[2*(6+nj)], the ground truth in the layout of bpmpc_controller_tick; contact_force[12], the force
+ *     the ground applied to each point over the last substep, f_i - D_i J_i v+ (0 for an open point).  bpmpc_plant_device_outputs: these buffers where
+ *     they live, leading dimension max_batch; &outputs.sensors is an argument of bpmpc_estimator_update (inputs_on_device = 1) as it stands.
+ *   state: bpmpc_plant_set_state sets q, v of the robots of mask (NULL: every robot below batch) from rbd[batch*2*(6+nj)] (thetadot = E^-1 angular
+ *     velocity) and their rows of the rbd output; the other outputs keep the values of the last step.  Robots outside the mask do not change by one
+ *     bit.  Host values must be finite.  bpmpc_plant_get_state: host copy of the rbd output (synchronises).  A step needs a state for every robot of
+ *     its batch: its batch must be that of the last set_state.
+ *   bpmpc_plant_step: one control step.  The command holds pos_des, vel_des, tau_ff, kp, kd ([batch*nj] each), base_force ([batch*3], nullable) and
+ *     feet_heights ([batch*4], nullable).  inputs_on_device != 0: device pointers, the call only enqueues on the plant's stream; host arrays are
+ *     copied first and the call synchronises.  BPMPC_ERR_INVALID_ARGUMENT: substeps < 1, period not finite or <= 0, a null handle or required
+ *     pointer, a batch other than that of the last set_state; batch > max_batch: BPMPC_ERR_CAPACITY.
+ *   bpmpc_plant_step_controlled: one step on the controller's last tick, gathered on the device: posDes / velDes / tau from the tick's joint_cmd,
+ *     kp / kd from the controller's joint gains (bpmpc_controller_joint_outputs).  The plant's stream waits for the tick and the solver's stream
+ *     waits for the step, so no caller synchronises by hand.  base_force / feet_heights: host or device by inputs_on_device.  Before the first tick,
+ *     or with a batch other than the last tick's: BPMPC_ERR_INVALID_ARGUMENT.
+ *   bpmpc_estimator_update_from_plant: bpmpc_estimator_update(inputs = the plant's device outputs, inputs_on_device = 1) with the estimator's stream
+ *     waiting for a step that was only enqueued and the plant's stream waiting for the update before the next step overwrites the outputs.  The loop
+ *     step_controlled -> update_from_plant -> bpmpc_controller_tick_estimated -> every k ticks setup_commands(x0 = NULL) + run synchronises nowhere.
+ *     A caller who passes the output pointers to bpmpc_estimator_update itself orders the two streams itself (bpmpc_plant_get_state synchronises).
+ *   settings: a parameter row of BPMPC_PLANT_PARAM_STRIDE doubles per robot, [kn, cn, d0, mu, v_eps, contact_threshold, reserved 0, reserved 0].
+ *     Every row starts as the keys plant.<name> of task_info_path; an absent key or a NULL path gives the defaults 5e4 N/m, 5e2 N s/m, 1e-3 m,
+ *     0.7, 0.01 m/s, 1 N.  bpmpc_plant_get_params / set_params / reset_params have the shapes, masks, n_rows and host / device semantics of
+ *     bpmpc_estimator_get_params / set_params / reset_params; host rows are validated - every entry finite, kn, d0 and v_eps positive, the others not
+ *     negative - and a bad entry is named in bpmpc_last_error() and changes nothing.  bpmpc_plant_load_params / check_params: the settings ingest
+ *     and the row validation as host-only functions, as the estimator's.  The torque limits are the WBC's key torqueLimitsTask of task_info_path,
+ *     per handle (a NULL path: no limits).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_PLANT_PARAM_STRIDE 8
+typedef struct bpmpc_plant bpmpc_plant;
+typedef struct {
+  const double *pos_des, *vel_des, *tau_ff, *kp, *kd;   /* [batch*nj] */
+  const double *base_force;                             /* [batch*3] nullable: world-frame force on the base origin */
+  const double *feet_heights;                           /* [batch*4] nullable: ground height under each contact point */
+} bpmpc_joint_command;
+typedef struct {
+  bpmpc_sensor_inputs sensors;
+  double *rbd, *contact_force;                          /* [batch*2*(6+nj)], [batch*12] */
+} bpmpc_plant_outputs;
+int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int device, int max_batch, bpmpc_plant** out);
+void bpmpc_plant_destroy(bpmpc_plant* plant);
+int bpmpc_plant_set_state(bpmpc_plant* plant, int batch, const int* mask, const double* rbd, int inputs_on_device);
+int bpmpc_plant_get_state(bpmpc_plant* plant, int batch, double* host_rbd);
+int bpmpc_plant_step(bpmpc_plant* plant, int batch, const bpmpc_joint_command* command, int inputs_on_device, double period, int substeps);
+int bpmpc_plant_device_outputs(bpmpc_plant* plant, bpmpc_plant_outputs* dev_out);
+int bpmpc_plant_step_controlled(bpmpc_plant* plant, bpmpc_controller* controller, int batch, double period, int substeps, const double* base_force,
+                                const double* feet_heights, int inputs_on_device);
+int bpmpc_estimator_update_from_plant(bpmpc_estimator* estimator, bpmpc_plant* plant, int batch, double period, double* host_rbd);
+int bpmpc_plant_get_params(const bpmpc_plant* plant, int robot, double* row);
+int bpmpc_plant_set_params(bpmpc_plant* plant, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_plant_reset_params(bpmpc_plant* plant);
+int bpmpc_plant_load_params(const char* task_info_path, double* row);
+int bpmpc_plant_check_params(const double* rows, int n_rows);
+
 #ifdef __cplusplus
 }
 #endif
