@@ -1203,6 +1203,37 @@ class BatchedPlant:
     def resetParams(self):
         _check(load_library().bpmpc_plant_reset_params(self._h))
 
+    def setStiction(self, kt, mask=None):
+        """The tangential contact stiffness kt [N/m] of the robots with mask[b] != 0 (None: every one): one value for all of them, or [B] values.
+        kt = 0 is the plant without stick-slip contacts.  A robot whose kt changes loses its anchors.  numpy values are validated (finite, not
+        negative) and the call synchronises; float64 / int32 device tensors are only enqueued, ordered before the next step."""
+        if hasattr(kt, "data_ptr"):
+            rows = kt.reshape(1) if kt.numel() == 1 else kt.reshape(-1, 1)
+        else:
+            kt = np.asarray(kt, float).reshape(-1)
+            rows = kt if kt.size == 1 else kt.reshape(-1, 1)
+        B, n_rows, (mp, kp), dev, keep = _rows_args(mask, [rows], 1, self.max_batch)
+        _check(load_library().bpmpc_plant_set_stiction(self._h, B, mp, kp, n_rows, dev))
+        del keep
+
+    def getStiction(self, robot=-1):
+        """kt of `robot`, or with robot < 0 the value every robot starts from (the key plant.kt of the task file; absent: 0)."""
+        kt = C.c_double()
+        _check(load_library().bpmpc_plant_get_stiction(self._h, int(robot), C.byref(kt)))
+        return kt.value
+
+    def resetStiction(self):
+        """Every robot's kt back to the handle's start value; every anchor cleared."""
+        _check(load_library().bpmpc_plant_reset_stiction(self._h))
+
+    def anchors(self):
+        """(anchor [B, 4, 2], anchored [B, 4]) of the batch of the last set_state (before it: max_batch): the world xy each contact point's tangential
+        spring is anchored at, and whether it is; synchronises."""
+        B = self.batch or self.max_batch
+        anchor, anchored = np.zeros((B, 4, 2)), np.zeros((B, 4), np.int32)
+        _check(load_library().bpmpc_plant_get_anchors(self._h, B, _d(anchor), _i(anchored)))
+        return anchor, anchored
+
 
 class BatchedDdpMpc(BatchedSqpMpc):
     """A batch of GaussNewtonDDP_MPC instances (ocs2_bipedal_robot_ros/src/BipedalRobotDdpMpcNode.cpp:70-71; ddp block of task.info): the same

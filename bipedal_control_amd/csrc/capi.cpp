@@ -82,6 +82,16 @@ PlantSettings plant_load_settings(const char* task_info_path) {
   }
   return s;
 }
+
+double plant_load_stiction(const char* task_info_path) {
+  double kt = 0.0;
+  if (task_info_path) {
+    const auto t = read_info_file(task_info_path);
+    (void)t->get("plant.kt", &kt);
+    if (!std::isfinite(kt) || kt < 0.0) throw std::invalid_argument(std::string("plant settings: kt is ") + (!std::isfinite(kt) ? "not finite" : "negative"));
+  }
+  return kt;
+}
 }  // namespace bpmpc
 
 using namespace bpmpc;
@@ -209,6 +219,14 @@ int bpmpc_plant_load_params(const char* task_info_path, double* row) {
   return guarded(BPMPC_ERR_IO, [&] {
     const PlantSettings s = plant_load_settings(task_info_path);
     std::copy(&s.kn, &s.kn + kPlantParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_load_stiction(const char* task_info_path, double* kt) {
+  if (!kt) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_stiction: null kt");
+  return guarded(BPMPC_ERR_IO, [&] {
+    *kt = plant_load_stiction(task_info_path);
     return (int)BPMPC_OK;
   });
 }

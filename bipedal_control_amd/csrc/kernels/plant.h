@@ -12,8 +12,18 @@
 //   solve             Cholesky without pivoting in LDS, lane per row, the forward substitution folded into the factorisation; back substitution
 //   integrate         v+ = the solution, q+ = q + h v+
 // The sensors are formed from (q+, v+) of the last substep.  The arithmetic of one robot depends on nothing but that robot's data.
+//
+// Stick-slip contacts (STICK; k_plant_stick_step): a robot with kt > 0 carries an anchor and a flag per contact point.  They are loaded once per
+// launch, live in LDS beside q and v over the substeps and meet HBM at entry and exit only.  Lanes 0..3 own the law: anchor a fresh contact, clamp
+// the spring at the Coulomb cap (slip), give the damper the friction the spring has not used, make the sticking spring linearly implicit.  kt is
+// wave-uniform; a robot with kt = 0 takes the branch that is the plant without stiction, operation for operation, and touches no anchor.  The
+// handle launches the instantiation without STICK until stiction is first set on it.  The two instantiations are compiled in translation units of
+// their own (plant.hip, plant_stick.hip): each then has one call site of the rigid-body pass, and the compiler inlines and contracts k_plant_step
+// as it did before the plant had stiction - the same bits at the same speed.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../device_model.h"
 #include "wbc.h"   // wbc_rbd_pass, wbc_on_chain, wbc_contact_jac_col, w_*, lds_wave_sync, kWave
@@ -62,6 +72,13 @@ struct PlantArgs {
   int max_batch;
 };
 
+// Stick-slip contacts: what the STICK instantiation takes beside PlantArgs
+struct PlantStickArgs {
+  const double* kt;                                 // [max_batch] tangential stiffness; 0: none
+  double* anchor;                                   // [max_batch][4][2] world xy of the anchors; read and updated for a robot with kt > 0
+  int* anchored;                                    // [max_batch][4]
+};
+
 template <int NJ>
 struct PlantLds {
   static constexpr int NV = 6 + NJ;
@@ -78,8 +95,19 @@ struct PlantLds {
   double h;
 };
 
+// Stick-slip contacts in LDS, behind the members above: the robot's kt; for kt > 0 the tangential spring forces, the anchors and the flags over
+// the substeps
 template <int NJ>
-__device__ void plant_robot(const DeviceModel& md, PlantLds<NJ>& w, const PlantArgs& a, int b, int l) {
+struct PlantStickLds : PlantLds<NJ> {
+  double ft[kNumContacts][2], anchor[kNumContacts][2];
+  int anchored[kNumContacts];
+  double kt;
+  double* anchor_row;                    // this robot's anchors and flags in HBM: parked here over the substeps as state and out are
+  int* anchored_row;
+};
+
+template <int NJ, bool STICK>
+__device__ void plant_robot(const DeviceModel& md, std::conditional_t<STICK, PlantStickLds<NJ>, PlantLds<NJ>>& w, const PlantArgs& a, const PlantStickArgs& sa, int b, int l) {
   constexpr int NV = 6 + NJ, NC = kNumContacts;
   WbcRbd<NJ>& r = w.rbd;
   if (l < kPlantParamStride) {      // these lanes all park the same pointers: one predicate for the prologue
@@ -100,6 +128,14 @@ __device__ void plant_robot(const DeviceModel& md, PlantLds<NJ>& w, const PlantA
   }
   if (l < 3 && a.base_force) wext = a.base_force[(size_t)b * 3 + l];
   if (l < NC && a.ground) ground = a.ground[(size_t)b * NC + l];
+  if constexpr (STICK) {
+    const double kt = sa.kt[b];
+    if (l == 0) { w.kt = kt; w.anchor_row = sa.anchor + (size_t)b * NC * 2; w.anchored_row = sa.anchored + (size_t)b * NC; }
+    if (l < NC && kt > 0.0) {
+      w.anchor[l][0] = sa.anchor[((size_t)b * NC + l) * 2]; w.anchor[l][1] = sa.anchor[((size_t)b * NC + l) * 2 + 1];
+      w.anchored[l] = sa.anchored[(size_t)b * NC + l];
+    }
+  }
   double acc = 0.0;      // lanes 0..2: (v+ - v) / h of the last substep
 
 #pragma unroll 1
@@ -137,6 +173,33 @@ __device__ void plant_robot(const DeviceModel& md, PlantLds<NJ>& w, const PlantA
         n = fmax(0.0, kn * d - cni * r.cv[l][2]);
         ct = mu * n / sqrt(r.cv[l][0] * r.cv[l][0] + r.cv[l][1] * r.cv[l][1] + veps * veps);
       }
+      if constexpr (STICK) {
+        const double kt = w.kt;
+        if (kt > 0.0) {
+          double fx = 0.0, fy = 0.0;
+          int anchored = 0;
+          if (closed) {
+            const double px = r.cp[l][0], py = r.cp[l][1];
+            double ax = px, ay = py;      // a point that closes anchors where it is
+            if (w.anchored[l]) { ax = w.anchor[l][0]; ay = w.anchor[l][1]; }
+            double sx = ax - px, sy = ay - py;
+            const double phi = kt * sqrt(sx * sx + sy * sy), cap = mu * n;
+            double room = cap - phi, imp = w.h * kt;
+            if (phi > cap) {      // slip: the anchor follows at the cap, the damper has nothing left and the spring is explicit
+              const double scale = cap / phi;
+              ax = cap > 0.0 ? px + sx * scale : px; ay = cap > 0.0 ? py + sy * scale : py;
+              sx = ax - px; sy = ay - py;
+              room = 0.0; imp = 0.0;
+            }
+            fx = kt * sx; fy = kt * sy;
+            ct = room / sqrt(r.cv[l][0] * r.cv[l][0] + r.cv[l][1] * r.cv[l][1] + veps * veps) + imp;
+            w.anchor[l][0] = ax; w.anchor[l][1] = ay;
+            anchored = 1;
+          }
+          w.anchored[l] = anchored;
+          w.ft[l][0] = fx; w.ft[l][1] = fy;
+        }
+      }
       w.closed[l] = closed ? 1 : 0;
       w.fz[l] = f; w.nrm[l] = n;
       w.D[3 * l] = ct; w.D[3 * l + 1] = ct; w.D[3 * l + 2] = cni;
@@ -151,6 +214,13 @@ __device__ void plant_robot(const DeviceModel& md, PlantLds<NJ>& w, const PlantA
       for (int g = 0; g < NV; ++g) mv += w.A[l][g] * r.v[g];
       double gen = -nle;
       for (int i = 0; i < NC; ++i) gen += w.J[3 * i + 2][l] * w.fz[i];
+      if constexpr (STICK) {
+        if (w.kt > 0.0) {
+          double tang = 0.0;
+          for (int i = 0; i < NC; ++i) tang += w.J[3 * i][l] * w.ft[i][0] + w.J[3 * i + 1][l] * w.ft[i][1];
+          gen += tang;
+        }
+      }
       // base lanes carry kp = kd = tf = 0 and the other lanes wext = 0: no branch on the lane's kind
       const double tau = fmin(lim, fmax(-lim, kp * (pd - r.q[l]) + tf));
       gen += wext + tau + kd * vd;
@@ -210,9 +280,20 @@ __device__ void plant_robot(const DeviceModel& md, PlantLds<NJ>& w, const PlantA
     if (w.closed[i]) {
       double jv = 0.0;
       for (int g = 0; g < NV; ++g) jv += w.J[l][g] * r.v[g];
-      f = (l % 3 == 2 ? w.fz[i] : 0.0) - w.D[l] * jv;
+      double spring = l % 3 == 2 ? w.fz[i] : 0.0;
+      if constexpr (STICK) {
+        if (l % 3 != 2 && w.kt > 0.0) spring = w.ft[i][l % 3];
+      }
+      f = spring - w.D[l] * jv;
     }
     out(kPlantContactForce)[(size_t)b * 3 * NC + l] = f;
+  }
+  if constexpr (STICK) {
+    if (l < NC && w.kt > 0.0) {
+      double* const anchor_row = w.anchor_row;
+      anchor_row[2 * l] = w.anchor[l][0]; anchor_row[2 * l + 1] = w.anchor[l][1];
+      w.anchored_row[l] = w.anchored[l];
+    }
   }
   if (l < NC) {
     reinterpret_cast<int*>(out(kPlantContact))[(size_t)b * NC + l] = w.nrm[l] > w.par[5] ? 1 : 0;

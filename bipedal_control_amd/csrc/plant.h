@@ -25,6 +25,13 @@ struct bpmpc_plant {
   int* d_mask = nullptr;                // [max_batch] device copy of a host mask
   // device copies of host inputs
   double *d_rbd_in = nullptr, *d_pd = nullptr, *d_vd = nullptr, *d_tf = nullptr, *d_kp = nullptr, *d_kd = nullptr, *d_force = nullptr, *d_ground = nullptr;
+  // stick-slip contacts (include/bpmpc.h "Plant"): per-robot tangential stiffness, anchors and flags
+  double kt_start = 0.0;                // the key plant.kt of task.info (absent: 0): every robot's kt after create / reset_stiction
+  bool stick = false;                   // steps launch k_plant_stick_step: kt_start > 0, or stiction has been set since create / reset_stiction
+  double* d_kt = nullptr;               // [max_batch]
+  double* d_kt_in = nullptr;            // [max_batch] device copy of host values
+  double* d_anchor = nullptr;           // [max_batch][4][2]
+  int* d_anchored = nullptr;            // [max_batch][4]
   double* d_out = nullptr;              // the output block of k_plant_step (kernels/plant.h PlantOut)
   bpmpc_plant_outputs out{};            // its sections (leading dimension max_batch)
 };
@@ -36,6 +43,11 @@ namespace bpmpc {
 PlantSettings plant_load_settings(const char* task_info_path);
 // A host row before it is accepted: every entry finite, kn, d0 and v_eps positive, the others not negative; throws std::invalid_argument naming the entry
 void plant_check_param_row(const char* who, const double* row, int r);
+// The key plant.kt of task.info (absent, or a NULL path: 0); throws std::invalid_argument naming kt when it is negative or not finite
+double plant_load_stiction(const char* task_info_path);
+
+// plant_stick.hip: one launch of k_plant_stick_step<nj> for a.batch robots on `stream`
+void launch_plant_stick_step(int nj, hipStream_t stream, const DeviceModel* model, const PlantArgs& a, const PlantStickArgs& sa);
 
 // What bpmpc_plant_step_controlled reads of a controller (controller.cpp): the last tick's joint_cmd ([batch][3][nj]) and the joint gains where they
 // live, the stream they are written on, the batch of the last tick (0: none yet)

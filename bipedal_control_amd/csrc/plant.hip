@@ -22,16 +22,30 @@ __global__ __launch_bounds__(kWave) void k_plant_step(const DeviceModel* model, 
   __shared__ PlantLds<NJ> w;
   const int b = blockIdx.x;
   if (b >= a.batch) return;
-  plant_robot<NJ>(*model, w, a, b, threadIdx.x);
+  plant_robot<NJ, false>(*model, w, a, PlantStickArgs{}, b, threadIdx.x);
+}
+
+// bpmpc_plant_set_stiction for the robots of `mask` (NULL: every robot below `batch`): kt[b] = src[b] (n_rows == batch) or src[0]; a robot whose
+// kt changes loses its anchors.  One thread per robot.
+__global__ __launch_bounds__(256) void k_plant_set_stiction(int batch, const int* mask, const double* src, int n_rows, double* kt, double* anchor, int* anchored) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= batch || (mask && !mask[b])) return;
+  const double val = src[n_rows == 1 ? 0 : b];
+  if (val == kt[b]) return;
+  kt[b] = val;
+  for (int i = 0; i < kNumContacts; ++i) { anchored[b * kNumContacts + i] = 0; anchor[(b * kNumContacts + i) * 2] = 0.0; anchor[(b * kNumContacts + i) * 2 + 1] = 0.0; }
 }
 
 // bpmpc_plant_set_state for the robots of `mask` (NULL: every robot below `batch`): q, v from rbd_in[b] (the Euler rates from the world angular
-// velocity as WbcBase::updateMeasured forms them) and the robot's row of the rbd output.  One thread per entry of [q | v].
-__global__ __launch_bounds__(256) void k_plant_set_state(int batch, int nv, const int* mask, const double* rbd_in, double* state, double* rbd_out) {
+// velocity as WbcBase::updateMeasured forms them) and the robot's row of the rbd output; the robot's anchors are cleared.  One thread per entry of
+// [q | v].
+__global__ __launch_bounds__(256) void k_plant_set_state(int batch, int nv, const int* mask, const double* rbd_in, double* state, double* rbd_out, double* anchor,
+                                                         int* anchored) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= batch * 2 * nv) return;
   const int b = i / (2 * nv), e = i % (2 * nv);
   if (mask && !mask[b]) return;
+  if (e < kNumContacts) { anchored[b * kNumContacts + e] = 0; anchor[(b * kNumContacts + e) * 2] = 0.0; anchor[(b * kNumContacts + e) * 2 + 1] = 0.0; }
   const double* rb = rbd_in + (size_t)b * 2 * nv;
   rbd_out[i] = rb[e];
   double val;
@@ -60,6 +74,17 @@ void write_default_params(bpmpc_plant* p) {
   write_rows(p->hs.stream, p->max_batch, kPlantParamStride, kPlantParamStride - 2, nullptr, 1, {p->d_rows + (size_t)p->max_batch * kPlantParamStride, nullptr, p->d_params});
 }
 
+// every robot's kt becomes the handle's start value and every anchor is cleared
+void write_default_stiction(bpmpc_plant* p) {
+  const size_t B = p->max_batch;
+  std::vector<double> kt(B, p->kt_start);
+  HIP_CHECK(hipMemcpyAsync(p->d_kt, kt.data(), B * sizeof(double), hipMemcpyHostToDevice, p->hs.stream));
+  HIP_CHECK(hipMemsetAsync(p->d_anchor, 0, B * kNumContacts * 2 * sizeof(double), p->hs.stream));
+  HIP_CHECK(hipMemsetAsync(p->d_anchored, 0, B * kNumContacts * sizeof(int), p->hs.stream));
+  HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // kt lives on this frame
+  p->stick = p->kt_start > 0.0;
+}
+
 void check_batch(const bpmpc_plant* p, int batch, const char* who) {
   if (batch < 1) throw std::invalid_argument(std::string(who) + ": batch must be positive");
   if (batch > p->max_batch) throw std::length_error(std::string(who) + ": batch exceeds max_batch");
@@ -84,7 +109,11 @@ PlantArgs step_args(const bpmpc_plant* p, int batch, double period, int substeps
 }
 
 void launch_step(bpmpc_plant* p, const PlantArgs& a) {
-  KL_NJ(p->nj, hipLaunchKernelGGL(k_plant_step<NJ>, dim3(a.batch), dim3(kWave), 0, p->hs.stream, p->d_model, a));
+  if (p->stick) {
+    const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
+    launch_plant_stick_step(p->nj, p->hs.stream, p->d_model, a, sa);
+  }
+  else KL_NJ(p->nj, hipLaunchKernelGGL(k_plant_step<NJ>, dim3(a.batch), dim3(kWave), 0, p->hs.stream, p->d_model, a));
   HIP_CHECK(hipGetLastError());
 }
 
@@ -105,6 +134,7 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
   const int rc = guarded(BPMPC_ERR_IO, [&]() -> int {
     if (const int refused = open_side_handle("bpmpc_plant_create", p.get(), model, device, max_batch)) return refused;
     p->defaults = plant_load_settings(task_info_path);
+    p->kt_start = plant_load_stiction(task_info_path);
     p->nj = p->rm.nj; p->nv = 6 + p->rm.nj;
     if (task_info_path) {
       const auto t = read_info_file(task_info_path);
@@ -118,6 +148,8 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
     p->d_rbd_in = m.alloc<double>(B * 2 * nv);
     p->d_pd = m.alloc<double>(B * nj); p->d_vd = m.alloc<double>(B * nj); p->d_tf = m.alloc<double>(B * nj); p->d_kp = m.alloc<double>(B * nj); p->d_kd = m.alloc<double>(B * nj);
     p->d_force = m.alloc<double>(B * 3); p->d_ground = m.alloc<double>(B * 4);
+    p->d_kt = m.alloc<double>(B); p->d_kt_in = m.alloc<double>(B);
+    p->d_anchor = m.alloc<double>(B * kNumContacts * 2); p->d_anchored = m.alloc<int>(B * kNumContacts);
     p->d_out = m.alloc<double>(B * plant_out_offset(kPlantOutEnd, p->nj), true);
     auto section = [&](int sec) { return p->d_out + B * plant_out_offset(sec, p->nj); };
     bpmpc_sensor_inputs& s = p->out.sensors;
@@ -129,6 +161,7 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
     p->out.rbd = section(kPlantRbd); p->out.contact_force = section(kPlantContactForce);
     HIP_CHECK(hipMemcpy(p->d_rows + B * kPlantParamStride, &p->defaults, sizeof(PlantSettings), hipMemcpyHostToDevice));
     write_default_params(p.get());
+    write_default_stiction(p.get());
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
     return BPMPC_OK;
   });
@@ -155,7 +188,8 @@ int bpmpc_plant_set_state(bpmpc_plant* p, int batch, const int* mask, const doub
     hipStream_t st = p->hs.stream;
     const int* dmask = staged(mask, p->d_mask, B, inputs_on_device, st);
     const double* drbd = staged(rbd, p->d_rbd_in, B * E, inputs_on_device, st);
-    hipLaunchKernelGGL(k_plant_set_state, dim3((batch * (int)E + 255) / 256), dim3(256), 0, st, batch, p->nv, dmask, drbd, p->d_state, p->out.rbd);
+    hipLaunchKernelGGL(k_plant_set_state, dim3((batch * (int)E + 255) / 256), dim3(256), 0, st, batch, p->nv, dmask, drbd, p->d_state, p->out.rbd,
+                       p->d_anchor, p->d_anchored);
     HIP_CHECK(hipGetLastError());
     p->last_batch = batch;
     if (!inputs_on_device) p->hs.synchronise_own();
@@ -265,6 +299,47 @@ int bpmpc_plant_reset_params(bpmpc_plant* p) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_params: null handle", [&] {
     write_default_params(p);
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_set_stiction(bpmpc_plant* p, int batch, const int* mask, const double* kt, int n_rows, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_stiction: null handle or kt", kt != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_stiction");
+    if (n_rows != 1 && n_rows != batch) throw std::invalid_argument("bpmpc_plant_set_stiction: n_rows must be 1 or batch");
+    if (!inputs_on_device)
+      for (int r = 0; r < n_rows; ++r)
+        if ((n_rows == 1 || !mask || mask[r]) && (!std::isfinite(kt[r]) || kt[r] < 0.0))
+          throw std::invalid_argument("bpmpc_plant_set_stiction: entry " + std::to_string(r) + " (kt) is " + (!std::isfinite(kt[r]) ? "not finite" : "negative"));
+    hipStream_t st = p->hs.stream;
+    const int* dmask = staged(mask, p->d_mask, (size_t)batch, inputs_on_device, st);
+    const double* dkt = staged(kt, p->d_kt_in, (size_t)n_rows, inputs_on_device, st);
+    hipLaunchKernelGGL(k_plant_set_stiction, dim3((batch + 255) / 256), dim3(256), 0, st, batch, dmask, dkt, n_rows, p->d_kt, p->d_anchor, p->d_anchored);
+    HIP_CHECK(hipGetLastError());
+    p->stick = true;
+    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_get_stiction(const bpmpc_plant* p, int robot, double* kt) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_stiction: null handle or kt", kt != nullptr, [&] {
+    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_stiction: robot exceeds max_batch");
+    if (robot < 0) { *kt = p->kt_start; return; }
+    HIP_CHECK(hipMemcpyAsync(kt, p->d_kt + robot, sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_reset_stiction(bpmpc_plant* p) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_stiction: null handle", [&] { write_default_stiction(p); });
+}
+
+int bpmpc_plant_get_anchors(bpmpc_plant* p, int batch, double* host_anchor, int* host_anchored) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_anchors: null handle, anchor or anchored", host_anchor && host_anchored, [&] {
+    check_batch(p, batch, "bpmpc_plant_get_anchors");
+    HIP_CHECK(hipMemcpyAsync(host_anchor, p->d_anchor, (size_t)batch * kNumContacts * 2 * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipMemcpyAsync(host_anchored, p->d_anchored, (size_t)batch * kNumContacts * sizeof(int), hipMemcpyDeviceToHost, p->hs.stream));
+    p->hs.synchronise_own();
   });
 }
 

@@ -598,7 +598,9 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  * loop sensors -> bpmpc_estimator_update -> bpmpc_controller_tick_estimated -> joint commands closes without leaving the device.  The reference
  * closes its loop with MuJoCo or Gazebo (bipedal_mujoco, bipedal_gazebo/src/BipedalHWSim.cpp).  This plant imitates neither: it is this engine's own
  * model, this comment is its specification, and it is nowhere pinned against the reference's simulators.  It has no joint limits, no
- * self-collision and no tangential contact spring.
+ * self-collision and no torsional friction about the contact normal.  Its contacts stick and slip (a tangential anchor spring with a Coulomb cap)
+ * for the robots whose tangential stiffness kt is set above 0; with kt = 0, the default, friction is the regularised Coulomb damper alone, under
+ * which a loaded foot creeps.
  *   state per robot: q[6+nj] = [position, zyx, joints], v[6+nj] = dq/dt (Euler rates, not angular velocity: the coordinates of the WBC), so
  *     integrating q is a plain sum.  One control step of length `period` is `substeps` equal substeps of h = period / substeps.  One substep:
  *       1. rigid-body pass at (q, v) with gravity: M, nle (as the WBC's), the four contact points p_i, the stacked contact Jacobian J (12 x nv),
@@ -607,13 +609,24 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *          spring force f_i = (0, 0, kn d_i); normal damping cn_i = cn min(1, d_i / d0); start-of-step normal force
  *          n_i = max(0, kn d_i - cn_i c_i,z); tangential damping ct_i = mu n_i / sqrt(c_i,x^2 + c_i,y^2 + v_eps^2) (a regularised Coulomb law);
  *          D_i = diag(ct_i, ct_i, cn_i).  Open: f_i = 0, D_i = 0, n_i = 0.
+ *          Stick-slip, for a robot with kt > 0 (a robot with kt = 0 runs the arithmetic above and nothing else; its flags stay 0).  Each point
+ *          carries an anchor a_i (world x, y) and a flag anchored_i; p is the point's xy at the start-of-substep q.  Closed point:
+ *            a. not anchored: a_i = p, anchored_i = 1
+ *            b. s = a_i - p, phi = kt |s|, cap = mu n_i
+ *            c. phi > cap: the point slips: a_i = p + s (cap / phi) (a_i = p when cap = 0), s = a_i - p again, stick = 0; otherwise stick = 1
+ *            d. the spring force gains its tangential part: f_i = (kt s_x, kt s_y, kn d_i)
+ *            e. the Coulomb damper gets the friction the spring has not used: ct_i = (cap - kt |s|) / sqrt(c_i,x^2 + c_i,y^2 + v_eps^2) when
+ *               sticking, exactly 0 when slipping
+ *            f. the spring is linearly implicit while sticking: D_i = diag(ct_i + stick h kt, ct_i + stick h kt, cn_i)
+ *          Open point: anchored_i = 0.  At the start-of-step linearisation the tangential force never exceeds mu n_i.  Anchors are evaluated at
+ *          the start of each substep only; after a step they hold what its last substep left.
  *       3. joint torque tau_j = kp_j (posDes_j - q_j) + tau_ff,j, clamped to +- the torque limit of its leg joint when that limit is > 0; the
  *          kd term kd_j (velDes_j - v+_j) is implicit and not clamped
  *       4. v+ solves (M + h J'DJ + h diag(0_6, kd)) v+ = M v + h (S'(tau + kd velDes) - nle + J'f + w_ext); S selects the joints, w_ext is the
  *          external force base_force (world frame, NULL: 0) on the base origin, acting on coordinates 0..2.  The matrix is symmetric positive
  *          definite; k_plant_step factors it by a Cholesky factorisation without pivoting.
  *       5. q+ = q + h v+
- *     All damping is linearly implicit, the contact spring is explicit.
+ *     All damping is linearly implicit, the normal contact spring is explicit, the tangential spring is linearly implicit while it sticks.
  *   outputs, written after the last substep from (q+, v+), in the layouts of bpmpc_sensor_inputs: joint_pos, joint_vel; quat (x y z w) of R(zyx);
  *     angular_vel_local = R' E(zyx) thetadot; linear_accel_local = R' (a + (0, 0, 9.81)) with a = (v+ - v)[0:3] / h of the last substep (what step 5
  *     of the Kalman filter inverts); contact[4] = (n_i > contact_threshold), n_i of the last substep; feet_heights = the ground heights given (0);
@@ -623,7 +636,7 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *     they live, leading dimension max_batch; &outputs.sensors is an argument of bpmpc_estimator_update (inputs_on_device = 1) as it stands.
  *   state: bpmpc_plant_set_state sets q, v of the robots of mask (NULL: every robot below batch) from rbd[batch*2*(6+nj)] (thetadot = E^-1 angular
  *     velocity) and their rows of the rbd output; the other outputs keep the values of the last step.  Robots outside the mask do not change by one
- *     bit.  Host values must be finite.  bpmpc_plant_get_state: host copy of the rbd output (synchronises).  A step needs a state for every robot of
+ *     bit.  The anchors of the robots of mask are cleared, and of no other robot.  Host values must be finite.  bpmpc_plant_get_state: host copy of the rbd output (synchronises).  A step needs a state for every robot of
  *     its batch: its batch must be that of the last set_state.
  *   bpmpc_plant_step: one control step.  The command holds pos_des, vel_des, tau_ff, kp, kd ([batch*nj] each), base_force ([batch*3], nullable) and
  *     feet_heights ([batch*4], nullable).  inputs_on_device != 0: device pointers, the call only enqueues on the plant's stream; host arrays are
@@ -644,6 +657,15 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *     negative - and a bad entry is named in bpmpc_last_error() and changes nothing.  bpmpc_plant_load_params / check_params: the settings ingest
  *     and the row validation as host-only functions, as the estimator's.  The torque limits are the WBC's key torqueLimitsTask of task_info_path,
  *     per handle (a NULL path: no limits).
+ *   stiction: kt >= 0 [N/m] per robot, beside the parameter row (whose layout and reserved entries it leaves alone).  Every robot starts with the key
+ *     plant.kt of task_info_path; an absent key or a NULL path gives 0.  bpmpc_plant_set_stiction(kt[n_rows], n_rows = 1 or batch): masks and host /
+ *     device semantics of bpmpc_plant_set_params; host values must be finite and not negative, else BPMPC_ERR_INVALID_ARGUMENT names the entry in
+ *     bpmpc_last_error() and nothing changes.  A robot whose kt changes loses its anchors.  bpmpc_plant_get_stiction: kt of `robot`, or with
+ *     robot < 0 the start value.  bpmpc_plant_reset_stiction: every robot back to the start value, every anchor cleared.
+ *     bpmpc_plant_load_stiction: the ingest as a host-only function.  bpmpc_plant_get_anchors: host copies of the anchors [batch*4*2] and the
+ *     flags [batch*4] (synchronises).  A handle on which stiction was never set - start value 0, no set_stiction since create or
+ *     reset_stiction - launches the kernel without stick-slip contacts, k_plant_step; any other launches k_plant_stick_step, in which a robot with
+ *     kt = 0 computes the same bits.
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_PLANT_PARAM_STRIDE 8
 typedef struct bpmpc_plant bpmpc_plant;
@@ -670,6 +692,11 @@ int bpmpc_plant_set_params(bpmpc_plant* plant, int batch, const int* mask, const
 int bpmpc_plant_reset_params(bpmpc_plant* plant);
 int bpmpc_plant_load_params(const char* task_info_path, double* row);
 int bpmpc_plant_check_params(const double* rows, int n_rows);
+int bpmpc_plant_set_stiction(bpmpc_plant* plant, int batch, const int* mask, const double* kt, int n_rows, int inputs_on_device);
+int bpmpc_plant_get_stiction(const bpmpc_plant* plant, int robot, double* kt);
+int bpmpc_plant_reset_stiction(bpmpc_plant* plant);
+int bpmpc_plant_load_stiction(const char* task_info_path, double* kt);
+int bpmpc_plant_get_anchors(bpmpc_plant* plant, int batch, double* host_anchor, int* host_anchored);
 
 #ifdef __cplusplus
 }

@@ -11,12 +11,16 @@ Per shape: a solved batch (setup_commands + run), one tick for the joint command
 each timed with a host clock around the call and the synchronise that ends it; the medians and minima are reported.  A number here is a call time
 as a caller sees it (launch, kernel, synchronise), not a kernel time.  The state is set back before every timed step, so every step advances the
 same standing robots.  One JSON line per shape on stdout; --out appends them to a file (profiles/plant_probe.jsonl is where the published one
-belongs).
-usage (GPU box, repository root): python tools/plant_probe.py [--shapes h1:1,h1:256,h1:4096] [--ticks 200] [--substeps 4] [--out FILE]
+belongs).  --kt K gives every robot the tangential stiffness K (BatchedPlant.setStiction; "kn": the robot's kn) before the rounds; without it the
+handle never hears of stiction.  --commit names the commit the library was built from in every line.  Beside the median and the minimum a line
+holds the 5th and 95th percentile of the 200 as the spread.  Every shape runs in a child process of its own under a time limit (--limit seconds);
+the first shape that fails or runs out of time ends the probe.
+usage (GPU box, repository root): python tools/plant_probe.py [--shapes h1:1,h1:256,h1:4096] [--ticks 200] [--substeps 4] [--kt K] [--commit ID] [--out FILE]
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -29,7 +33,7 @@ from tools.controller_tick_probe import _setup      # noqa: E402
 SHAPES = "h1:1,h1:256,h1:4096"
 
 
-def measure(robot, B, ticks, warmup, substeps, period):
+def measure(robot, B, ticks, warmup, substeps, period, kt=None):
     import numpy as np
     import torch
     import bipedal_control_amd as bp
@@ -39,6 +43,9 @@ def measure(robot, B, ticks, warmup, substeps, period):
     ctrl.setJointGains(np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KP), np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KD))
     rbd[:, 5] -= 0.0025                                    # the soles a little in the ground: every contact closed
     plant = bp.BatchedPlant(mpc.interface, max_batch=B)
+    if kt is not None:
+        plant.batch = B
+        plant.setStiction(plant.getParams()[0] if kt == "kn" else float(kt))
     dev = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda")      # noqa: E731
     t_dev, r_dev = torch.full((B,), 0.0025, dtype=torch.float64, device="cuda"), dev(rbd)
     torch.cuda.synchronize()
@@ -74,9 +81,13 @@ def measure(robot, B, ticks, warmup, substeps, period):
     state = plant.get_state()
     line = dict(robot=robot, batch=B, ticks=ticks, substeps=substeps, period=period, state_finite=bool(np.isfinite(state).all()),
                 contacts_closed=int(plant.outputs()["contact"].torch().sum().item()))
+    if kt is not None:
+        line["kt"] = float(plant.getStiction(0))
+        line["anchored"] = int(plant.anchors()[1].sum())
     for name, _ in variants:
         line[name + "_host_ms_median"] = float(np.median(times[name]))
         line[name + "_host_ms_min"] = float(np.min(times[name]))
+        line[name + "_host_ms_p05"], line[name + "_host_ms_p95"] = (float(x) for x in np.percentile(times[name], [5, 95]))
     return line
 
 
@@ -87,20 +98,37 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--substeps", type=int, default=4)
     ap.add_argument("--period", type=float, default=0.002)
+    ap.add_argument("--kt", help="tangential stiffness of every robot [N/m], or kn")
+    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
+    ap.add_argument("--limit", type=int, default=240, help="time limit of one shape's child process [s]")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.child:      # one shape, in this process
+        robot, B = a.child.split(":")
+        line = measure(robot, int(B), a.ticks, a.warmup, a.substeps, a.period, a.kt)
+        if a.commit:
+            line["commit"] = a.commit
+        print(json.dumps(line), flush=True)
+        return 0
     lines = []
     for shape in a.shapes.split(","):
-        robot, B = shape.split(":")
-        line = measure(robot, int(B), a.ticks, a.warmup, a.substeps, a.period)
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-    if a.out:
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", shape, "--ticks", str(a.ticks), "--warmup", str(a.warmup),
+               "--substeps", str(a.substeps), "--period", repr(a.period)] + (["--kt", a.kt] if a.kt else []) + (["--commit", a.commit] if a.commit else [])
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
+            print("plant_probe: shape %s ended with status %d; stopping" % (shape, r.returncode), file=sys.stderr)
+            break
+        text = r.stdout.strip().splitlines()[-1]
+        print(text, flush=True)
+        lines.append(text)
+    if a.out and lines:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+            for text in lines:
+                f.write(text + "\n")
+    return 0 if len(lines) == len(a.shapes.split(",")) else 1
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

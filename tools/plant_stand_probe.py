@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Do the robots stand in the plant under the whole controller?  The loop of INTEGRATION.md "Plant" - bpmpc_plant_step_controlled ->
+bpmpc_estimator_update_from_plant -> bpmpc_controller_tick_estimated, the MPC re-armed every 10 ticks - for H1, batch 8, 2 s of simulated time
+(1000 ticks of 2 ms, 4 substeps), once with kt = 0 (the regularised Coulomb damper alone) and once with kt = kn (stick-slip contacts).
+
+Per run and robot: the first tick with safe == 0 (null: none), the lowest base height, the base height at the end, and the largest drift of a
+contact point in the ground plane from where it stood after the first tick (over the ticks the point was in contact).  A run ends at the first
+tick after which a robot's state is not finite (ticks_run, state_finite; that robot's final height is null).  A probe, not a test: nothing asserts
+its outcome.  Each run is a child process of its own under a time limit (--limit seconds); a run that fails or runs out of time
+ends the probe.  One JSON line per run on stdout; --out appends them to a file (profiles/plant_stand_probe.jsonl is where the published one
+belongs).
+usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--commit ID] [--out FILE]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
+
+
+def run(kt, B, seconds):
+    import numpy as np
+    import torch
+    import bipedal_control_amd as bp
+    from bipedal_control_amd import scenarios as sc
+    from oracle import wbc_py as wp
+    from tests import oracle_bridge as ob
+    from tests.test_plant_reference import standing_state
+    itf = sc.interface("h1")
+    horizon = NI * sc.DT
+    mpc = bp.BatchedSqpMpc(itf, max_batch=B, max_nodes=sc.max_nodes_for(NI, horizon), return_gains=True)
+    wbc = bp.WeightedWbc(itf, max_batch=B)
+    ctrl = bp.BatchedController(mpc, wbc)
+    est = bp.BatchedStateEstimate(itf, kind="from_topic", max_batch=B)
+    plant = bp.BatchedPlant(itf, max_batch=B)
+    gaits = [bp.loadModeSequenceTemplate(sc.ROBOTS["h1"]["gait"], "stance")]
+    m = ob.model("h1")
+    nj = m["nj"]
+    q, v, _ = standing_state(m, depth=0.0025)
+    rng = np.random.default_rng(5)
+    rbd0 = np.array([wp.rbd_from(m, q + 0.002 * rng.standard_normal(len(q)) * np.r_[np.zeros(6), np.ones(len(q) - 6)], v) for _ in range(B)])
+    x0 = np.tile(itf.getInitialState(), (B, 1))
+    x0[:, 6:] = np.c_[rbd0[:, 3:6], rbd0[:, 0:3], rbd0[:, 6:6 + nj]]
+    ctrl.setJointGains(np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KP), np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KD))
+    kn = plant.getParams()[0]
+    if kt != "0":      # kt = 0: a handle that never hears of stiction
+        plant.setStiction(kn if kt == "kn" else float(kt))
+    plant.set_state(rbd0)
+
+    def arm(t, first):
+        mpc.setup_commands(t, x0 if first else None, gaits, -1, 0.0, np.zeros(4), horizon=horizon, from_previous=not first)
+        mpc.enqueue()
+
+    def points(rbd):
+        out = []
+        for b in range(B):
+            qb, _ = wp.measured_state(m, rbd[b])
+            R, o, _ = wp.fk(m, qb)
+            out.append(np.array(wp.contact_points(m, R, o))[:, :2])
+        return np.array(out)
+
+    def num(a):
+        """a list of floats; null for a value that is not finite"""
+        return [float(x) if np.isfinite(x) else None for x in a]
+
+    ticks = int(round(seconds / PERIOD))
+    arm(0.0, True)
+    torch.cuda.synchronize()
+    ctrl.tick(torch.zeros(B, dtype=torch.float64, device="cuda"), plant.outputs()["rbd"].torch(), period=PERIOD, fetch=False)
+    first_unsafe = [None] * B
+    lowest = np.full(B, np.inf)
+    drift = np.zeros(B)
+    start, finite = None, True
+    for k in range(ticks):
+        plant.step_controlled(ctrl, period=PERIOD, substeps=SUBSTEPS)
+        est.update_from_plant(plant, period=PERIOD, fetch=False)
+        t = torch.full((B,), PERIOD * (k + 1), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()      # t is filled on torch's stream, which the handles' streams do not wait for
+        ctrl.tick_estimated(t, est, period=PERIOD, fetch=False)
+        if k % REARM == REARM - 1:
+            arm(PERIOD * (k + 1), False)
+        torch.cuda.synchronize()
+        rbd = plant.get_state()
+        safe = ctrl.device_outputs()["safe"].torch().cpu().numpy()
+        contact = plant.outputs()["contact"].torch().cpu().numpy()
+        if not np.all(np.isfinite(rbd)):
+            finite = False
+            break
+        p = points(rbd)
+        start = p if start is None else start
+        lowest = np.minimum(lowest, rbd[:, 5])
+        moved = np.linalg.norm(p - start, axis=2) * (contact != 0)
+        drift = np.maximum(drift, moved.max(axis=1))
+        for b in range(B):
+            if first_unsafe[b] is None and safe[b] == 0:
+                first_unsafe[b] = k
+    anchored = plant.anchors()[1]
+    return dict(robot="h1", batch=B, seconds=seconds, ticks_run=k + 1, period=PERIOD, substeps=SUBSTEPS, rearm_every=REARM, kt=float(plant.getStiction(0)),
+                state_finite=finite, first_unsafe_tick=first_unsafe, lowest_base_height=num(lowest), final_base_height=num(rbd[:, 5]),
+                start_base_height=num(rbd0[:, 5]), largest_foot_drift=num(drift), anchored_at_end=[int(x) for x in anchored.sum(axis=1)])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--kts", default="0,kn")
+    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
+    ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    if a.child is not None:
+        line = run(a.child, a.batch, a.seconds)
+        if a.commit:
+            line["commit"] = a.commit
+        print(json.dumps(line), flush=True)
+        return 0
+    lines = []
+    kts = a.kts.split(",")
+    for kt in kts:
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch)]
+        r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
+            print("plant_stand_probe: kt = %s ended with status %d; stopping" % (kt, r.returncode), file=sys.stderr)
+            break
+        text = r.stdout.strip().splitlines()[-1]
+        print(text, flush=True)
+        lines.append(text)
+    if a.out and lines:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for text in lines:
+                f.write(text + "\n")
+    return 0 if len(lines) == len(kts) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
