@@ -17,10 +17,12 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import abi
+from .abi import (Stats, _dp, _EstimatorOutputs, _GaitTemplate, _ip, _JointCommand, _PlantOutputs, _Schedule, _SensorInputs, _Settings,  # noqa: F401
+                  _Target, _TickOutputs)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
-_dp = C.POINTER(C.c_double)
-_ip = C.POINTER(C.c_int)
 
 ModeSchedule = namedtuple("ModeSchedule", ["eventTimes", "modeSequence"])
 ModeSequenceTemplate = namedtuple("ModeSequenceTemplate", ["switchingTimes", "modeSequence"])
@@ -35,31 +37,6 @@ class BpmpcError(RuntimeError):
         self.status = status
 
 
-class _Settings(C.Structure):
-    _fields_ = [("device", C.c_int), ("max_batch", C.c_int), ("max_nodes", C.c_int), ("sqp_iterations", C.c_int), ("dt", C.c_double),
-                ("return_gains", C.c_int), ("profile", C.c_int), ("stream", C.c_void_p), ("reference_kernels", C.c_int),
-                ("pipeline_chunks", C.c_int), ("materialize_lq", C.c_int), ("reg_prim", C.c_double), ("solver", C.c_int), ("feedback_policy", C.c_int)]
-
-
-class _Schedule(C.Structure):
-    _fields_ = [("n_events", C.c_int), ("event_times", _dp), ("modes", _ip)]
-
-
-class _GaitTemplate(C.Structure):
-    _fields_ = [("n_modes", C.c_int), ("switching_times", _dp), ("modes", _ip)]
-
-
-class _Target(C.Structure):
-    _fields_ = [("n_points", C.c_int), ("times", _dp), ("states", _dp)]
-
-
-class Stats(C.Structure):
-    _fields_ = [("n_nodes", C.c_int), ("iterations", C.c_int), ("status", C.c_int), ("reserved", C.c_int),
-                ("merit_before", C.c_double), ("dynamics_sse_before", C.c_double), ("equality_sse_before", C.c_double),
-                ("merit_after", C.c_double), ("dynamics_sse_after", C.c_double), ("equality_sse_after", C.c_double),
-                ("step_size", C.c_double), ("armijo_descent", C.c_double), ("dx_norm", C.c_double), ("du_norm", C.c_double)]
-
-
 def library_path():
     return os.path.join(_HERE, "libbpmpc.so")
 
@@ -71,10 +48,9 @@ def load_library():
         path = library_path()
         if not os.path.exists(path):
             raise BpmpcError(-4, "libbpmpc.so is missing - build it with `python -m bipedal_control_amd.build` (hipcc, gfx950)")
-        lib = C.CDLL(path)
-        lib.bpmpc_last_error.restype = C.c_char_p
-        lib.bpmpc_version.restype = C.c_char_p
-        _LIB = lib
+        if not os.path.exists(abi.HEADER):
+            raise BpmpcError(-4, "include/bpmpc.h is missing - the signatures of libbpmpc.so are bound from it")
+        _LIB = abi.bind(C.CDLL(path))
     return _LIB
 
 
@@ -82,6 +58,24 @@ def _check(rc):
     if rc < 0:
         raise BpmpcError(rc, load_library().bpmpc_last_error().decode())
     return rc
+
+
+class _Handle:
+    """Owner of one opaque handle of the C ABI: `_h`, destroyed by the function a subclass names in _DESTROY."""
+
+    _DESTROY = None
+
+    def __init__(self):
+        self._h = C.c_void_p()
+
+    def _call(self, name, *args):
+        """lib.<name>(handle, *args), a negative status raised as BpmpcError"""
+        return _check(getattr(load_library(), name)(self._h, *args))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _LIB is not None:       # (_LIB is None again while the interpreter shuts down)
+            getattr(_LIB, self._DESTROY)(self._h)
+            self._h = None
 
 
 def _d(a):
@@ -152,6 +146,26 @@ def _rows_args(mask, arrays, width, max_batch):
     return batch, n_rows, ptrs, dev, keep
 
 
+def _param_methods(prefix, stride, get_doc, set_doc, reset_doc=None):
+    """getParams / setParams / resetParams of a handle class with max_batch, over <prefix>_get_params / _set_params / _reset_params and parameter
+    rows of `stride` doubles; the docstrings are the class's own."""
+    def getParams(self, robot=-1):
+        row = np.zeros(stride)
+        self._call(prefix + "_get_params", int(robot), _d(row))
+        return row
+
+    def setParams(self, rows, mask=None):
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], stride, self.max_batch)
+        self._call(prefix + "_set_params", B, mp, rp, n_rows, dev)
+        del keep
+
+    def resetParams(self):
+        self._call(prefix + "_reset_params")
+
+    getParams.__doc__, setParams.__doc__, resetParams.__doc__ = get_doc, set_doc, reset_doc
+    return getParams, setParams, resetParams
+
+
 class WbcParams:
     """A parameter row of the WBC (include/bpmpc.h "Run-time parameters", BPMPC_WBC_PARAM_*) with named fields, so that no caller writes index
     arithmetic: baseKp / baseKd [6] (position x, y, z, orientation x, y, z: WbcBase::setBasePDGains), swingKp / swingKd (setSwingLegPDGains),
@@ -213,26 +227,22 @@ class WbcParams:
                    weightSwingLeg=100.0, weightBaseAccel=1.0, weightContactForce=0.1, **rest)
 
 
-class BipedalRobotInterface:
+class BipedalRobotInterface(_Handle):
     """Problem definition: model constants + settings (BipedalRobotInterface.cpp:67-204)."""
+
+    _DESTROY = "bpmpc_model_destroy"
 
     def __init__(self, taskFile, urdfFile, referenceFile, useHardFrictionConeConstraint=False):
         """Fourth argument as in the reference (BipedalRobotInterface.h:66-69): friction cones as inequality constraints, which the SQP
         solver penalises with sqp.inequalityConstraintMu / Delta (include/bpmpc.h bpmpc_model_create_ex)."""
-        lib = load_library()
-        self._h = C.c_void_p()
+        super().__init__()
         self.useHardFrictionConeConstraint = bool(useHardFrictionConeConstraint)
-        _check(lib.bpmpc_model_create_ex(str(urdfFile).encode(), str(taskFile).encode(), str(referenceFile).encode(),
-                                         1 if useHardFrictionConeConstraint else 0, C.byref(self._h)))
+        _check(load_library().bpmpc_model_create_ex(str(urdfFile).encode(), str(taskFile).encode(), str(referenceFile).encode(),
+                                                    1 if useHardFrictionConeConstraint else 0, C.byref(self._h)))
         nx, nu, nc, nj = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        _check(lib.bpmpc_model_dims(self._h, C.byref(nx), C.byref(nu), C.byref(nc), C.byref(nj)))
+        self._call("bpmpc_model_dims", C.byref(nx), C.byref(nu), C.byref(nc), C.byref(nj))
         self.stateDim, self.inputDim, self.numThreeDofContacts, self.actuatedDofNum = nx.value, nu.value, nc.value, nj.value
         self.taskFile, self.urdfFile, self.referenceFile = str(taskFile), str(urdfFile), str(referenceFile)
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_model_destroy(self._h)
-            self._h = None
 
     @property
     def handle(self):
@@ -240,7 +250,7 @@ class BipedalRobotInterface:
 
     def get(self, name, capacity=4096):
         out = np.zeros(capacity)
-        n = _check(load_library().bpmpc_model_get(self._h, name.encode(), _d(out), capacity))
+        n = self._call("bpmpc_model_get", name.encode(), _d(out), capacity)
         return out[:n].copy()
 
     def getInitialState(self):
@@ -250,7 +260,7 @@ class BipedalRobotInterface:
         buf = C.create_string_buffer(256)
         names = []
         for j in range(self.actuatedDofNum):
-            _check(load_library().bpmpc_model_joint_name(self._h, j, buf, 256))
+            self._call("bpmpc_model_joint_name", j, buf, 256)
             names.append(buf.value.decode())
         return names
 
@@ -318,13 +328,13 @@ class BipedalRobotInterface:
             timeToTarget = self.mpcSettings()["timeHorizon"]
         cmd, x = _f64(cmdVel), _f64(state)
         times, states = np.zeros(2), np.zeros((2, self.stateDim))
-        _check(load_library().bpmpc_cmd_vel_to_targets(self._h, _d(cmd), C.c_double(time), _d(x), C.c_double(timeToTarget), _d(times), _d(states)))
+        self._call("bpmpc_cmd_vel_to_targets", _d(cmd), time, _d(x), timeToTarget, _d(times), _d(states))
         return TargetTrajectories(times, states)
 
     def goalToTargetTrajectories(self, goal, time, state):
         g, x = _f64(goal), _f64(state)
         times, states = np.zeros(2), np.zeros((2, self.stateDim))
-        _check(load_library().bpmpc_goal_to_targets(self._h, _d(g), C.c_double(time), _d(x), _d(times), _d(states)))
+        self._call("bpmpc_goal_to_targets", _d(g), time, _d(x), _d(times), _d(states))
         return TargetTrajectories(times, states)
 
 
@@ -334,33 +344,32 @@ def loadModeSequenceTemplate(filename, topicName):
     return ModeSequenceTemplate(times[:n.value + 1].copy(), modes[:n.value].copy())
 
 
-class GaitSchedule:
+class GaitSchedule(_Handle):
     """GaitSchedule(initModeSchedule, defaultModeSequenceTemplate, phaseTransitionStanceTime) as loaded by
     BipedalRobotInterface::loadGaitSchedule (BipedalRobotInterface.cpp:209-234)."""
 
-    def __init__(self, interface):
-        self._h = C.c_void_p()
-        _check(load_library().bpmpc_gait_create(interface.handle, C.byref(self._h)))
+    _DESTROY = "bpmpc_gait_destroy"
 
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_gait_destroy(self._h)
-            self._h = None
+    def __init__(self, interface):
+        super().__init__()
+        _check(load_library().bpmpc_gait_create(interface.handle, C.byref(self._h)))
 
     def insertModeSequenceTemplate(self, modeSequenceTemplate, startTime, finalTime):
         t, m = _f64(modeSequenceTemplate.switchingTimes), np.ascontiguousarray(modeSequenceTemplate.modeSequence, np.int32)
-        _check(load_library().bpmpc_gait_insert_template(self._h, _d(t), _i(m), len(m), C.c_double(startTime), C.c_double(finalTime)))
+        self._call("bpmpc_gait_insert_template", _d(t), _i(m), len(m), startTime, finalTime)
 
     def getModeSchedule(self, lowerBoundTime, upperBoundTime, capacity=4096):
         ev, ms, n = np.zeros(capacity), np.zeros(capacity, np.int32), C.c_int()
-        _check(load_library().bpmpc_gait_mode_schedule(self._h, C.c_double(lowerBoundTime), C.c_double(upperBoundTime), _d(ev), _i(ms), capacity, C.byref(n)))
+        self._call("bpmpc_gait_mode_schedule", lowerBoundTime, upperBoundTime, _d(ev), _i(ms), capacity, C.byref(n))
         return ModeSchedule(ev[:n.value].copy(), ms[:n.value + 1].copy())
 
 
-class BatchedGaitSchedule:
+class BatchedGaitSchedule(_Handle):
     """One GaitSchedule per robot of a BatchedSqpMpc, kept on the device (bpmpc_gait_batch): gait commands with the semantics of
     GaitReceiver (GaitReceiver.cpp:49-59) take effect in the solver's setup_gaits.  `gaits` is the template library (a list of
     ModeSequenceTemplate); robots refer to a template by its index."""
+
+    _DESTROY = "bpmpc_gait_batch_destroy"
 
     def __init__(self, mpc, gaits):
         self.mpc, self.gaits, self.max_batch = mpc, list(gaits), mpc.max_batch
@@ -369,13 +378,8 @@ class BatchedGaitSchedule:
             sw, mo = _f64(g.switchingTimes), np.ascontiguousarray(g.modeSequence, np.int32)
             keep += [sw, mo]
             tm[i] = _GaitTemplate(len(mo), _d(sw), _i(mo))
-        self._h = C.c_void_p()
+        super().__init__()
         _check(load_library().bpmpc_gait_batch_create(mpc._h, tm, len(self.gaits), C.byref(self._h)))
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_gait_batch_destroy(self._h)
-            self._h = None
 
     def _robots(self, *arrays):
         shape = np.broadcast(*[np.asarray(a) for a in arrays]).shape
@@ -387,7 +391,7 @@ class BatchedGaitSchedule:
         shape = self._robots(gait, startTime, finalTime)
         g = np.ascontiguousarray(np.broadcast_to(np.asarray(gait, np.int32), shape))
         st, fi = _f64(np.broadcast_to(np.asarray(startTime, float), shape)), _f64(np.broadcast_to(np.asarray(finalTime, float), shape))
-        _check(load_library().bpmpc_gait_batch_insert(self._h, len(g), _i(g), _d(st), _d(fi)))
+        self._call("bpmpc_gait_batch_insert", len(g), _i(g), _d(st), _d(fi))
 
     def command(self, gait):
         """GaitReceiver::mpcModeSequenceCallback for robots 0 .. len(gait) - 1: gait[b] >= 0 becomes robot b's pending template (the latest
@@ -398,14 +402,14 @@ class BatchedGaitSchedule:
             shape = tuple(iface["shape"])
             if iface["typestr"] != "<i4" or len(shape) != 1 or iface.get("strides") not in (None, (4,)):
                 raise ValueError("device gait commands must be a contiguous one-dimensional int32 array")
-            _check(load_library().bpmpc_gait_batch_command(self._h, int(shape[0]), C.cast(C.c_void_p(iface["data"][0]), _ip), 1))
+            self._call("bpmpc_gait_batch_command", int(shape[0]), C.cast(C.c_void_p(iface["data"][0]), _ip), 1)
             return
         g = np.ascontiguousarray(np.broadcast_to(np.asarray(gait, np.int32), self._robots(gait)))
-        _check(load_library().bpmpc_gait_batch_command(self._h, len(g), _i(g), 0))
+        self._call("bpmpc_gait_batch_command", len(g), _i(g), 0)
 
     def reset(self):
         """Every robot back to GaitSchedule(initialModeSchedule, defaultModeSequenceTemplate); nothing pending."""
-        _check(load_library().bpmpc_gait_batch_reset(self._h))
+        self._call("bpmpc_gait_batch_reset")
 
     def restart(self, mask):
         """Robots with mask[b] != 0 (robots 0 .. len(mask) - 1) back to their state after create / reset, their pending insert and command dropped
@@ -413,13 +417,13 @@ class BatchedGaitSchedule:
         tensor (its read-back waits for that setup)."""
         n = _count(mask)
         (mp,), dev, keep = _restart_args((mask, C.c_int, n))
-        _check(load_library().bpmpc_gait_batch_restart(self._h, n, mp, dev))
+        self._call("bpmpc_gait_batch_restart", n, mp, dev)
         del keep
 
     def modeSchedule(self, robot, capacity=1024):
         """Robot's schedule after the last setup (does not mutate anything, unlike the reference's getModeSchedule)."""
         ev, ms, n = np.zeros(capacity), np.zeros(capacity, np.int32), C.c_int()
-        _check(load_library().bpmpc_gait_batch_mode_schedule(self._h, int(robot), _d(ev), _i(ms), capacity, C.byref(n)))
+        self._call("bpmpc_gait_batch_mode_schedule", int(robot), _d(ev), _i(ms), capacity, C.byref(n))
         return ModeSchedule(ev[:n.value].copy(), ms[:n.value + 1].copy())
 
 
@@ -434,14 +438,16 @@ def swing_reference(interface, modeSchedule, times):
 def time_discretization_with_events(initTime, finalTime, dt, eventTimes, capacity=8192):
     ev = _f64(eventTimes)
     t, e, n = np.zeros(capacity), np.zeros(capacity, np.int32), C.c_int()
-    _check(load_library().bpmpc_time_grid(C.c_double(initTime), C.c_double(finalTime), C.c_double(dt), _d(ev), len(ev), _d(t), _i(e), capacity, C.byref(n)))
+    _check(load_library().bpmpc_time_grid(initTime, finalTime, dt, _d(ev), len(ev), _d(t), _i(e), capacity, C.byref(n)))
     return t[:n.value].copy(), e[:n.value].copy()
 
 
-class BatchedSqpMpc:
+class BatchedSqpMpc(_Handle):
     # (the DDP variant is the same handle with solver="ddp": BatchedDdpMpc below)
     """A batch of independent SqpMpc instances on one MI355X.  `run` plays the role of MPC_BASE::run(t, x) /
     MPC_MRT_Interface::advanceMpc() (BipedalController.cpp:339) for every problem of the batch at once."""
+
+    _DESTROY = "bpmpc_solver_destroy"
 
     def __init__(self, interface, max_batch, max_nodes, sqp_iterations=0, dt=0.0, return_gains=False, profile=False, device=0, stream=None,
                  reference_kernels=False, pipeline_chunks=0, materialize_lq=False, reg_prim=0.0, solver="sqp", feedback_policy=None):
@@ -461,15 +467,10 @@ class BatchedSqpMpc:
                        C.c_void_p(int(stream)) if stream is not None else None, int(bool(reference_kernels)), int(pipeline_chunks), int(bool(materialize_lq)), float(reg_prim),
                        {"sqp": 0, "ddp": 1}[solver], 0 if feedback_policy is None else (1 if feedback_policy else 2))
         self.solver = solver
-        self._h = C.c_void_p()
+        super().__init__()
         _check(lib.bpmpc_solver_create(interface.handle, C.byref(st), C.byref(self._h)))
         self._keep = None
         self.batch = 0
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_solver_destroy(self._h)
-            self._h = None
 
     # ---- argument marshalling
     def _marshal(self, t0, x0, modeSchedules, targetTrajectories, warm_x, warm_u):
@@ -510,7 +511,7 @@ class BatchedSqpMpc:
         if horizon is None:
             horizon = self.interface.mpcSettings()["timeHorizon"]
         B, t0, x0, sched, ns, tg, wx, wu, keep = self._marshal(t0, x0, modeSchedules, targetTrajectories, warm_x, warm_u)
-        _check(load_library().bpmpc_solver_setup(self._h, B, C.c_double(horizon), _d(t0), _d(x0), sched, ns, tg, _d(wx), _d(wu)))
+        self._call("bpmpc_solver_setup", B, horizon, _d(t0), _d(x0), sched, ns, tg, _d(wx), _d(wu))
         self.batch = B
         return self.layout()
 
@@ -520,7 +521,7 @@ class BatchedSqpMpc:
         if horizon is None:
             horizon = self.interface.mpcSettings()["timeHorizon"]
         B, t0, x0, sched, ns, tg, _, _, keep = self._marshal(t0, x0, modeSchedules, targetTrajectories, None, None)
-        _check(load_library().bpmpc_solver_setup_from_previous(self._h, B, C.c_double(horizon), _d(t0), _d(x0), sched, ns, tg))
+        self._call("bpmpc_solver_setup_from_previous", B, horizon, _d(t0), _d(x0), sched, ns, tg)
         self.batch = B
         return self.layout()
 
@@ -544,8 +545,8 @@ class BatchedSqpMpc:
             sw, mo = _f64(g.switchingTimes), np.ascontiguousarray(g.modeSequence, np.int32)
             keep += [sw, mo]
             tm[i] = _GaitTemplate(len(mo), _d(sw), _i(mo))
-        _check(load_library().bpmpc_solver_setup_commands(self._h, B, C.c_double(horizon), _d(t0), _d(x0), tm, len(gaits), _i(gop), _d(gst), _d(cmd),
-                                                          int(bool(goal)), C.c_double(time_to_target), int(bool(from_previous))))
+        self._call("bpmpc_solver_setup_commands", B, horizon, _d(t0), _d(x0), tm, len(gaits), _i(gop), _d(gst), _d(cmd), int(bool(goal)), time_to_target,
+                   int(bool(from_previous)))
         self.batch = B
         return self.layout()
 
@@ -561,8 +562,7 @@ class BatchedSqpMpc:
             B = x0.shape[0]
         t0 = _f64(np.broadcast_to(np.asarray(t0, float), (B,)))
         cmd = _f64(np.broadcast_to(np.asarray(cmd_vel, float), (B, 4)))
-        _check(load_library().bpmpc_solver_setup_gaits(self._h, gait_schedules._h, B, C.c_double(horizon), _d(t0), _d(x0), _d(cmd), int(bool(goal)),
-                                                       C.c_double(time_to_target), int(bool(from_previous))))
+        self._call("bpmpc_solver_setup_gaits", gait_schedules._h, B, horizon, _d(t0), _d(x0), _d(cmd), int(bool(goal)), time_to_target, int(bool(from_previous)))
         self.batch = B
         return self.layout()
 
@@ -573,10 +573,10 @@ class BatchedSqpMpc:
         ts = None if t_start is None else _f64(np.broadcast_to(np.asarray(t_start, float), (B,)))
         xs = None if x_start is None else _f64(x_start).reshape(B, self.nx)
         if not fetch:
-            _check(load_library().bpmpc_solver_rollout(self._h, _d(ts), _d(xs), C.c_double(duration), None, None, None))
+            self._call("bpmpc_solver_rollout", _d(ts), _d(xs), duration, None, None, None)
             return None
         x_end, u_end, steps = np.zeros((B, self.nx)), np.zeros((B, self.nu)), np.zeros((B, 2), np.int32)
-        _check(load_library().bpmpc_solver_rollout(self._h, _d(ts), _d(xs), C.c_double(duration), _d(x_end), _d(u_end), _i(steps)))
+        self._call("bpmpc_solver_rollout", _d(ts), _d(xs), duration, _d(x_end), _d(u_end), _i(steps))
         return x_end, u_end, steps
 
     def advance(self, t0, x0, modeSchedules, targetTrajectories, horizon=None, gains=False):
@@ -587,20 +587,20 @@ class BatchedSqpMpc:
 
     def layout(self):
         b, n, g, nx, nu = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int()
-        _check(load_library().bpmpc_solver_layout(self._h, C.byref(b), C.byref(n), C.byref(g), C.byref(nx), C.byref(nu)))
+        self._call("bpmpc_solver_layout", C.byref(b), C.byref(n), C.byref(g), C.byref(nx), C.byref(nu))
         return dict(batch=b.value, n_nodes_max=n.value, n_grids=g.value, nx=nx.value, nu=nu.value)
 
     def reset(self):
-        _check(load_library().bpmpc_solver_reset(self._h))
+        self._call("bpmpc_solver_reset")
 
     def enqueue(self):
-        _check(load_library().bpmpc_solver_run(self._h))
+        self._call("bpmpc_solver_run")
 
     def synchronize(self):
-        _check(load_library().bpmpc_solver_sync(self._h))
+        self._call("bpmpc_solver_sync")
 
     def stage(self, name):
-        _check(load_library().bpmpc_solver_stage(self._h, name.encode()))
+        self._call("bpmpc_solver_stage", name.encode())
 
     def fetch(self, gains=False):
         B, N = self.batch, self.max_nodes
@@ -609,7 +609,7 @@ class BatchedSqpMpc:
         u = np.zeros((B, N, self.nu))
         K = np.zeros((B, N, self.nu, self.nx)) if gains else None
         stats = (Stats * B)()
-        _check(load_library().bpmpc_solver_fetch(self._h, _d(t), _d(x), _d(u), _d(K), stats))
+        self._call("bpmpc_solver_fetch", _d(t), _d(x), _d(u), _d(K), stats)
         return t, x, u, K, list(stats)
 
     def run(self, t0, x0, modeSchedules, targetTrajectories, horizon=None, warm_x=None, warm_u=None, gains=False):
@@ -630,35 +630,33 @@ class BatchedSqpMpc:
         u = np.zeros((B, N, self.nu))
         K = np.zeros((B, N, self.nu, self.nx)) if gains else None
         stats = (Stats * B)()
-        _check(load_library().bpmpc_solve_batch(self._h, B, C.c_double(horizon), _d(t0), _d(x0), sched, ns, tg, _d(wx), _d(wu), _d(t), _d(x),
-                                                _d(u), _d(K), stats))
+        self._call("bpmpc_solve_batch", B, horizon, _d(t0), _d(x0), sched, ns, tg, _d(wx), _d(wu), _d(t), _d(x), _d(u), _d(K), stats)
         self.batch = B
         return t, x, u, K, list(stats)
 
     def read(self, name):
         """Named device buffer as a flat float64 array (tests / debugging)."""
-        lib = load_library()
-        cap = _check(lib.bpmpc_solver_read(self._h, name.encode(), None, C.c_long(0)))
+        cap = self._call("bpmpc_solver_read", name.encode(), None, 0)
         out = np.zeros(cap)
-        n = _check(lib.bpmpc_solver_read(self._h, name.encode(), _d(out), C.c_long(cap)))
+        n = self._call("bpmpc_solver_read", name.encode(), _d(out), cap)
         return out[:n]
 
     def set_materialize(self, materialize_lq):
         """True: the lineariser writes the complete per-node LQ model (parity stages, roofline pass); False: the fused solve mode."""
-        _check(load_library().bpmpc_solver_set_materialize(self._h, int(bool(materialize_lq))))
+        self._call("bpmpc_solver_set_materialize", int(bool(materialize_lq)))
 
     def set_profile(self, level):
         """0 off, 1 every kernel class, 2 the linearisation kernel only."""
-        _check(load_library().bpmpc_solver_set_profile(self._h, int(level)))
+        self._call("bpmpc_solver_set_profile", int(level))
 
     def kernel_time(self, kernel, reset=True):
         ms, n = C.c_double(), C.c_int()
-        _check(load_library().bpmpc_solver_kernel_time(self._h, kernel.encode(), int(reset), C.byref(ms), C.byref(n)))
+        self._call("bpmpc_solver_kernel_time", kernel.encode(), int(reset), C.byref(ms), C.byref(n))
         return ms.value, n.value
 
     def device_trajectories(self):
         xp, up = _dp(), _dp()
-        _check(load_library().bpmpc_solver_device_trajectories(self._h, C.byref(xp), C.byref(up)))
+        self._call("bpmpc_solver_device_trajectories", C.byref(xp), C.byref(up))
         return C.cast(xp, C.c_void_p).value, C.cast(up, C.c_void_p).value
 
     def constraint_values(self):
@@ -669,12 +667,12 @@ class BatchedSqpMpc:
         v = np.zeros((B, self.max_nodes, 16))
         rows = np.zeros((B, self.max_nodes), np.int32)
         modes = np.zeros((B, self.max_nodes), np.int32)
-        _check(load_library().bpmpc_solver_constraint_values(self._h, _d(v), _i(rows), _i(modes)))
+        self._call("bpmpc_solver_constraint_values", _d(v), _i(rows), _i(modes))
         return v, rows, modes
 
     def export_trajectories(self, x_dst_ptr, u_dst_ptr):
         """Async D2D copy of the iterate into device buffers given by raw pointers (e.g. torch tensors' data_ptr())."""
-        _check(load_library().bpmpc_solver_export_trajectories(self._h, C.c_void_p(x_dst_ptr), C.c_void_p(u_dst_ptr)))
+        self._call("bpmpc_solver_export_trajectories", C.cast(x_dst_ptr, _dp), C.cast(u_dst_ptr, _dp))
 
     def restart(self, mask, x=None):
         """MPC_BASE::reset for the problems with mask[b] != 0 (bpmpc_solver_restart): the next setup gives them the initializer's guess instead of the
@@ -683,7 +681,7 @@ class BatchedSqpMpc:
         the batch of the last setup."""
         B = _count(mask)
         (mp, xp), dev, keep = _restart_args((mask, C.c_int, B), (x, C.c_double, B * self.nx))
-        _check(load_library().bpmpc_solver_restart(self._h, B, mp, xp, dev))
+        self._call("bpmpc_solver_restart", B, mp, xp, dev)
         del keep
 
     def evaluatePolicy(self, t, x):
@@ -693,30 +691,26 @@ class BatchedSqpMpc:
         t = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
         x = _f64(x).reshape(B, self.nx)
         x_opt, u_opt, mode = np.zeros((B, self.nx)), np.zeros((B, self.nu)), np.zeros(B, np.int32)
-        _check(load_library().bpmpc_solver_evaluate_policy(self._h, B, _d(t), _d(x), _d(x_opt), _d(u_opt), _i(mode)))
+        self._call("bpmpc_solver_evaluate_policy", B, _d(t), _d(x), _d(x_opt), _d(u_opt), _i(mode))
         return x_opt, u_opt, mode
 
 
-class WeightedWbc:
+class WeightedWbc(_Handle):
     """A batch of WeightedWbc instances on one MI355X (bipedal_wbc/include/bipedal_wbc/WeightedWbc.h; construction + loadTasksSetting as
     in bipedal_controllers/src/BipedalController.cpp:97-100).  `update` mirrors WeightedWbc::update(stateDesired, inputDesired,
     rbdStateMeasured, mode, period) (BipedalController.cpp:229) with a leading batch dimension; it returns (x, status) where
     x[b] = [generalised accelerations, contact forces, joint torques] and status[b] = 1 when that robot's QP was not solved and its
     previous solution was returned instead (lastQpSol_)."""
 
-    def __init__(self, interface, taskFile=None, max_batch=1, device=0):
-        lib = load_library()
-        self.interface = interface
-        self._h = C.c_void_p()
-        _check(lib.bpmpc_wbc_create(interface.handle, str(taskFile or interface.taskFile).encode(), int(device), int(max_batch), C.byref(self._h)))
-        n, nv = C.c_int(), C.c_int()
-        _check(lib.bpmpc_wbc_dims(self._h, C.byref(n), C.byref(nv)))
-        self.numDecisionVars, self.generalizedCoordinatesNum, self.max_batch = n.value, nv.value, int(max_batch)
+    _DESTROY = "bpmpc_wbc_destroy"
 
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_wbc_destroy(self._h)
-            self._h = None
+    def __init__(self, interface, taskFile=None, max_batch=1, device=0):
+        self.interface = interface
+        super().__init__()
+        _check(load_library().bpmpc_wbc_create(interface.handle, str(taskFile or interface.taskFile).encode(), int(device), int(max_batch), C.byref(self._h)))
+        n, nv = C.c_int(), C.c_int()
+        self._call("bpmpc_wbc_dims", C.byref(n), C.byref(nv))
+        self.numDecisionVars, self.generalizedCoordinatesNum, self.max_batch = n.value, nv.value, int(max_batch)
 
     def update(self, stateDesired, inputDesired, rbdStateMeasured, mode, period=0.002, debug=False):
         x = _f64(stateDesired).reshape(-1, self.interface.stateDim)
@@ -727,38 +721,28 @@ class WeightedWbc:
         sol = np.zeros((B, self.numDecisionVars))
         status = np.zeros(B, np.int32)
         dbg = np.zeros((B, 1024)) if debug else None
-        _check(load_library().bpmpc_wbc_update(self._h, B, _d(x), _d(u), _d(rbd), _i(md), C.c_double(period), _d(sol), _i(status), _d(dbg)))
+        self._call("bpmpc_wbc_update", B, _d(x), _d(u), _d(rbd), _i(md), period, _d(sol), _i(status), _d(dbg))
         return (sol, status, dbg) if debug else (sol, status)
 
     def reset(self):
-        _check(load_library().bpmpc_wbc_reset(self._h))
+        self._call("bpmpc_wbc_reset")
 
     def restart(self, mask):
         """clearLastQpSol for the robots with mask[b] != 0 (robots 0 .. len(mask) - 1; bpmpc_wbc_restart): their last solution and status become 0."""
         n = _count(mask)
         (mp,), dev, keep = _restart_args((mask, C.c_int, n))
-        _check(load_library().bpmpc_wbc_restart(self._h, n, mp, dev))
+        self._call("bpmpc_wbc_restart", n, mp, dev)
         del keep
 
-    def getParams(self, robot=-1):
+    getParams, setParams, resetParams = _param_methods(
+        "bpmpc_wbc", WbcParams.STRIDE,
         """The parameter row [32] of `robot` (WbcParams.fromRow names its entries), or with robot < 0 the values loadTasksSetting read from
-        task.info, which every row holds until it is set (bpmpc_wbc_get_params; synchronises)."""
-        row = np.zeros(WbcParams.STRIDE)
-        _check(load_library().bpmpc_wbc_get_params(self._h, int(robot), _d(row)))
-        return row
-
-    def setParams(self, rows, mask=None):
+        task.info, which every row holds until it is set (bpmpc_wbc_get_params; synchronises).""",
         """dynamicReconfigCallback's setBasePDGains / setSwingLegPDGains / setWeights (BipedalController.cpp:407-478) per robot, and this engine's
         per-robot friction, contact tolerance and torque limits (bpmpc_wbc_set_params).  rows: [32] or [1, 32] (one row for every robot written)
         or [B, 32]; mask (None: every robot; else [B], non-zero = write).  numpy arrays are validated and the call synchronises; float64 / int32
-        device tensors are only enqueued on the WBC's stream (a later controller tick waits for it)."""
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], WbcParams.STRIDE, self.max_batch)
-        _check(load_library().bpmpc_wbc_set_params(self._h, B, mp, rp, n_rows, dev))
-        del keep
-
-    def resetParams(self):
-        """Every row back to the task.info values (bpmpc_wbc_reset_params)."""
-        _check(load_library().bpmpc_wbc_reset_params(self._h))
+        device tensors are only enqueued on the WBC's stream (a later controller tick waits for it).""",
+        """Every row back to the task.info values (bpmpc_wbc_reset_params).""")
 
 
 class KalmanParams:
@@ -786,16 +770,6 @@ class KalmanParams:
 
     def toRow(self):
         return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0])
-
-
-class _SensorInputs(C.Structure):
-    NAMES = ("joint_pos", "joint_vel", "quat", "angular_vel_local", "linear_accel_local", "contact", "mode", "feet_heights", "odom_pos", "odom_quat",
-             "odom_lin_vel", "odom_ang_vel")
-    _fields_ = [(n, _ip if n in ("contact", "mode") else _dp) for n in NAMES]
-
-
-class _EstimatorOutputs(C.Structure):
-    _fields_ = [("rbd", _dp), ("x_hat", _dp), ("cov", _dp), ("xy_reset", _ip)]
 
 
 ESTIMATOR_KINDS = {"from_topic": 0, "kalman": 1}
@@ -836,12 +810,14 @@ def _sensor_args(kind, nj, max_batch, joint_pos, joint_vel, quat=None, angular_v
     return B, _SensorInputs(*ptrs), dev, keep
 
 
-class BatchedStateEstimate:
+class BatchedStateEstimate(_Handle):
     """BipedalController::updateStateEstimation (bipedal_controllers/src/BipedalController.cpp:360-405) for a batch of robots on one MI355X
     (bpmpc_estimator): IMU, joint encoders and contact flags -> the rbd of BatchedController.tick.  kind "from_topic" is FromTopicStateEstimate, the
     estimator the reference constructs; kind "kalman" is KalmanFilterEstimate, which the reference declares (LinearKalmanFilter.h) and does not
     implement (its source file is empty): the filter is the one specified in include/bpmpc.h, per robot, its state kept on the handle.  taskFile
     (None: the defaults of LinearKalmanFilter.h:45-51) is read for the keys kalmanFilter.<name>."""
+
+    _DESTROY = "bpmpc_estimator_destroy"
 
     def __init__(self, interface, kind="kalman", taskFile=None, max_batch=1, device=0):
         if kind not in ESTIMATOR_KINDS:
@@ -849,15 +825,10 @@ class BatchedStateEstimate:
         self.interface, self.kind, self.max_batch = interface, kind, int(max_batch)
         self.nj = interface.actuatedDofNum
         self.generalizedCoordinatesNum = 6 + self.nj
-        self._h = C.c_void_p()
+        super().__init__()
         _check(load_library().bpmpc_estimator_create(interface.handle, None if taskFile is None else str(taskFile).encode(), ESTIMATOR_KINDS[kind],
                                                      int(device), self.max_batch, C.byref(self._h)))
         self.batch = self.max_batch
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_estimator_destroy(self._h)
-            self._h = None
 
     def update(self, joint_pos, joint_vel, quat=None, angular_vel_local=None, linear_accel_local=None, contact=None, mode=None, feet_heights=None,
                odom=None, period=0.0025, fetch=True):
@@ -867,7 +838,7 @@ class BatchedStateEstimate:
         B, inputs, dev, keep = _sensor_args(self.kind, self.nj, self.max_batch, joint_pos, joint_vel, quat, angular_vel_local, linear_accel_local,
                                             contact, mode, feet_heights, odom)
         rbd = np.zeros((B, 2 * self.generalizedCoordinatesNum)) if fetch else None
-        _check(load_library().bpmpc_estimator_update(self._h, B, C.byref(inputs), dev, C.c_double(period), _d(rbd)))
+        self._call("bpmpc_estimator_update", B, C.byref(inputs), dev, period, _d(rbd))
         del keep
         self.batch = B
         return rbd
@@ -878,7 +849,7 @@ class BatchedStateEstimate:
         BatchedController.tick_estimated need no synchronisation between them.  Returns what update returns."""
         B = plant.batch
         rbd = np.zeros((B, 2 * self.generalizedCoordinatesNum)) if fetch else None
-        _check(load_library().bpmpc_estimator_update_from_plant(self._h, plant._h, B, C.c_double(period), _d(rbd)))
+        self._call("bpmpc_estimator_update_from_plant", plant._h, B, period, _d(rbd))
         self.batch = B
         return rbd
 
@@ -886,14 +857,14 @@ class BatchedStateEstimate:
         """x_hat = 0, P = 100 I for the robots with mask[b] != 0 (None: every robot); the others do not change by one bit."""
         B = self.max_batch if mask is None else _count(mask)
         (mp,), dev, keep = _restart_args((mask, C.c_int, B))
-        _check(load_library().bpmpc_estimator_reset(self._h, B, mp, dev))
+        self._call("bpmpc_estimator_reset", B, mp, dev)
         del keep
 
     def getState(self, batch=None):
         """(x_hat [B, 18], P [B, 18, 18]) of the first B robots (None: the batch of the last update); synchronises."""
         B = int(batch or self.batch)
         x, P = np.zeros((B, 18)), np.zeros((B, 18, 18))
-        _check(load_library().bpmpc_estimator_get_state(self._h, B, _d(x), _d(P)))
+        self._call("bpmpc_estimator_get_state", B, _d(x), _d(P))
         return x, P
 
     def setState(self, x_hat, cov=None, mask=None):
@@ -903,37 +874,22 @@ class BatchedStateEstimate:
             raise ValueError("x_hat must have the shape [B, 18], got %s" % list(shape))
         B = shape[0]
         (mp, xp, cp), dev, keep = _restart_args((mask, C.c_int, B), (x_hat, C.c_double, B * 18), (cov, C.c_double, B * 18 * 18))
-        _check(load_library().bpmpc_estimator_set_state(self._h, B, mp, xp, cp, dev))
+        self._call("bpmpc_estimator_set_state", B, mp, xp, cp, dev)
         del keep
 
-    def getParams(self, robot=-1):
-        """The parameter row [8] of `robot` (KalmanParams.fromRow names its entries), or with robot < 0 the values every row starts from."""
-        row = np.zeros(KalmanParams.STRIDE)
-        _check(load_library().bpmpc_estimator_get_params(self._h, int(robot), _d(row)))
-        return row
-
-    def setParams(self, rows, mask=None):
+    getParams, setParams, resetParams = _param_methods(
+        "bpmpc_estimator", KalmanParams.STRIDE,
+        """The parameter row [8] of `robot` (KalmanParams.fromRow names its entries), or with robot < 0 the values every row starts from.""",
         """rows [8], [1, 8] or [B, 8]; mask as WeightedWbc.setParams.  numpy rows are validated (finite, not negative, the three sensor noises
-        positive) and the call synchronises; device tensors are only enqueued, ordered before the next update."""
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], KalmanParams.STRIDE, self.max_batch)
-        _check(load_library().bpmpc_estimator_set_params(self._h, B, mp, rp, n_rows, dev))
-        del keep
-
-    def resetParams(self):
-        _check(load_library().bpmpc_estimator_reset_params(self._h))
+        positive) and the call synchronises; device tensors are only enqueued, ordered before the next update.""")
 
     def device_outputs(self):
         """rbd, x_hat, cov, xy_reset of the last update where they live: a dict of DeviceArray over the batch of the last update."""
         o = _EstimatorOutputs()
-        _check(load_library().bpmpc_estimator_device_outputs(self._h, C.byref(o)))
+        self._call("bpmpc_estimator_device_outputs", C.byref(o))
         B = self.batch
         shapes = {"rbd": (B, 2 * self.generalizedCoordinatesNum), "x_hat": (B, 18), "cov": (B, 18, 18), "xy_reset": (B,)}
         return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k == "xy_reset" else "<f8") for k, shp in shapes.items()}
-
-
-class _TickOutputs(C.Structure):
-    _fields_ = [("x_obs", _dp), ("x_opt", _dp), ("u_opt", _dp), ("joint_cmd", _dp), ("wbc_solution", _dp), ("planned_mode", _ip), ("wbc_status", _ip),
-                ("safe", _ip)]
 
 
 class DeviceArray:
@@ -949,26 +905,23 @@ class DeviceArray:
         return torch.as_tensor(self, device="cuda")
 
 
-class BatchedController:
+class BatchedController(_Handle):
     """BipedalController::update (bipedal_controllers/src/BipedalController.cpp:186-262) for the batch of a BatchedSqpMpc and a WeightedWbc
     (bpmpc_controller_tick): measured rigid-body state -> observation (centroidal state, yaw unwrap), evaluatePolicy of the last run, the WBC,
     SafetyChecker, joint commands - three kernels on the solver's stream.  `tick` takes numpy arrays (host) or device tensors (e.g. torch
     tensors of a GPU simulator; order their producer against the solver's stream, e.g. by creating the solver on a torch stream)."""
+
+    _DESTROY = "bpmpc_controller_destroy"
 
     NAMES = ("x_obs", "x_opt", "u_opt", "joint_cmd", "wbc_solution", "planned_mode", "wbc_status", "safe")
     JOINT_NAMES = ("joint_torque", "joint_kp", "joint_kd")      # bpmpc_controller_joint_outputs
 
     def __init__(self, mpc, wbc):
         self.mpc, self.wbc = mpc, wbc
-        self._h = C.c_void_p()
+        super().__init__()
         _check(load_library().bpmpc_controller_create(mpc._h, wbc._h, C.byref(self._h)))
         self.nx, self.nu, self.nj = mpc.nx, mpc.nu, mpc.interface.actuatedDofNum
         self.max_batch = wbc.max_batch
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_controller_destroy(self._h)
-            self._h = None
 
     def _shapes(self, B):
         return {"x_obs": (B, self.nx), "x_opt": (B, self.nx), "u_opt": (B, self.nu), "joint_cmd": (B, 3, self.nj),
@@ -982,18 +935,19 @@ class BatchedController:
             raise ValueError("device inputs must be contiguous float64 tensors of the batch's size")
         return C.cast(C.c_void_p(a.data_ptr()), _dp)
 
-    def _run_tick(self, fetch, call):
-        """The part tick and tick_estimated share: host output arrays (fetch), the call - call(host_out pointer or None) -, the joint outputs."""
+    def _run_tick(self, fetch, name, *args):
+        """The part tick and tick_estimated share: host output arrays (fetch), the call - lib.<name>(handle, *args, host_out pointer or None) -,
+        the joint outputs."""
         B = self.mpc.batch
         out, ptrs = None, None
         if fetch:
             out = {k: np.zeros(shp, np.int32 if k in ("planned_mode", "wbc_status", "safe") else np.float64) for k, shp in self._shapes(B).items()}
             ptrs = _TickOutputs(*[(_i if out[k].dtype == np.int32 else _d)(out[k]) for k in self.NAMES])
-        _check(call(C.byref(ptrs) if fetch else None))
+        self._call(name, *args, C.byref(ptrs) if fetch else None)
         if fetch:
             for k in self.JOINT_NAMES:             # every key of device_outputs has its host copy
                 out[k] = np.zeros((B, self.nj))
-            _check(load_library().bpmpc_controller_joint_outputs(self._h, B, *[_d(out[k]) for k in self.JOINT_NAMES], None, None, None))
+            self._call("bpmpc_controller_joint_outputs", B, *[_d(out[k]) for k in self.JOINT_NAMES], None, None, None)
         return out
 
     def tick(self, t, rbd, period=0.0025, fetch=True):
@@ -1012,7 +966,7 @@ class BatchedController:
             tt = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
             rr = _f64(rbd).reshape(B, 2 * self.wbc.generalizedCoordinatesNum)
             tp, rp, keep = _d(tt), _d(rr), (tt, rr)
-        out = self._run_tick(fetch, lambda host_out: load_library().bpmpc_controller_tick(self._h, B, tp, rp, int(on_device), C.c_double(period), host_out))
+        out = self._run_tick(fetch, "bpmpc_controller_tick", B, tp, rp, int(on_device), period)
         del keep
         return out
 
@@ -1027,8 +981,7 @@ class BatchedController:
         if not on_device:
             keep = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
             tp = _d(keep)
-        out = self._run_tick(fetch, lambda host_out: load_library().bpmpc_controller_tick_estimated(self._h, estimator._h, B, tp, int(on_device),
-                                                                                                     C.c_double(period), host_out))
+        out = self._run_tick(fetch, "bpmpc_controller_tick_estimated", estimator._h, B, tp, int(on_device), period)
         del keep
         return out
 
@@ -1037,7 +990,7 @@ class BatchedController:
         dynamicReconfigCallback :423-472) per robot (bpmpc_controller_set_joint_gains): kp, kd [nj], [1, nj] or [B, nj]; mask as
         WeightedWbc.setParams.  On the solver's stream; all gains are 0 after create and survive restarts and reset."""
         B, n_rows, (mp, pp, dp), dev, keep = _rows_args(mask, [kp, kd], self.nj, self.max_batch)
-        _check(load_library().bpmpc_controller_set_joint_gains(self._h, B, mp, pp, dp, n_rows, dev))
+        self._call("bpmpc_controller_set_joint_gains", B, mp, pp, dp, n_rows, dev)
         del keep
 
     def setLegMotorGains(self, kp_leg, kd_leg, mask=None):
@@ -1054,7 +1007,7 @@ class BatchedController:
 
     def reset(self):
         """yaw_last = 0 for every robot (BipedalController::starting)."""
-        _check(load_library().bpmpc_controller_reset(self._h))
+        self._call("bpmpc_controller_reset")
 
     def restart(self, mask, rbd):
         """BipedalController::starting for the robots with mask[b] != 0 (bpmpc_controller_restart): their observation from rbd [batch, 2 (6 + nj)]
@@ -1062,18 +1015,18 @@ class BatchedController:
         a float64 device tensor (e.g. (safe == 0).int() of device_outputs: then the call only enqueues); len(mask) must be the solver's batch."""
         B = _count(mask)
         (mp, rp), dev, keep = _restart_args((mask, C.c_int, B), (rbd, C.c_double, B * 2 * self.wbc.generalizedCoordinatesNum))
-        _check(load_library().bpmpc_controller_restart(self._h, B, mp, rp, dev))
+        self._call("bpmpc_controller_restart", B, mp, rp, dev)
         del keep
 
     def device_outputs(self):
         """The results of the last tick where they live: a dict of DeviceArray (zero-copy; `.torch()` wraps one as a tensor) over the solver's batch."""
         o = _TickOutputs()
-        _check(load_library().bpmpc_controller_device_outputs(self._h, C.byref(o)))
+        self._call("bpmpc_controller_device_outputs", C.byref(o))
         B = self.mpc.batch
         views = {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k in ("planned_mode", "wbc_status", "safe") else "<f8")
                  for k, shp in self._shapes(B).items()}
         ptrs = [_dp() for _ in self.JOINT_NAMES]
-        _check(load_library().bpmpc_controller_joint_outputs(self._h, B, None, None, None, *[C.byref(p) for p in ptrs]))
+        self._call("bpmpc_controller_joint_outputs", B, None, None, None, *[C.byref(p) for p in ptrs])
         for k, p in zip(self.JOINT_NAMES, ptrs):
             views[k] = DeviceArray(C.cast(p, C.c_void_p).value, (B, self.nj), "<f8")
         return views
@@ -1107,33 +1060,21 @@ class PlantParams:
         return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0, 0.0])
 
 
-class _JointCommand(C.Structure):
-    NAMES = ("pos_des", "vel_des", "tau_ff", "kp", "kd", "base_force", "feet_heights")
-    _fields_ = [(n, _dp) for n in NAMES]
-
-
-class _PlantOutputs(C.Structure):
-    _fields_ = [("sensors", _SensorInputs), ("rbd", _dp), ("contact_force", _dp)]
-
-
-class BatchedPlant:
+class BatchedPlant(_Handle):
     """A rigid-body simulation of a batch of robots on one MI355X (bpmpc_plant; include/bpmpc.h "Plant" is its specification): joint commands ->
     the sensors BatchedStateEstimate.update takes and the ground-truth rbd.  This engine's own model - penalty contacts with implicit damping, a
     joint PD with an implicit kd term, semi-implicit Euler - and not an imitation of the simulators the reference runs against.  taskFile (None:
     the interface's) is read for the keys plant.<name> and for the WBC's torque limits."""
 
+    _DESTROY = "bpmpc_plant_destroy"
+
     def __init__(self, interface, max_batch=1, taskFile=None, device=0):
         self.interface, self.max_batch = interface, int(max_batch)
         self.nj = interface.actuatedDofNum
         self.generalizedCoordinatesNum = 6 + self.nj
-        self._h = C.c_void_p()
+        super().__init__()
         _check(load_library().bpmpc_plant_create(interface.handle, str(taskFile or interface.taskFile).encode(), int(device), self.max_batch, C.byref(self._h)))
         self.batch = 0
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _LIB is not None:
-            _LIB.bpmpc_plant_destroy(self._h)
-            self._h = None
 
     def set_state(self, rbd, mask=None):
         """q, v of the robots with mask[b] != 0 (None: every one of the B) from rbd [B, 2 (6 + nj)] in the layout of BatchedController.tick; the
@@ -1143,7 +1084,7 @@ class BatchedPlant:
             raise ValueError("rbd must have the shape [B, %d], got %s" % (2 * self.generalizedCoordinatesNum, list(shape)))
         B = shape[0]
         (mp, rp), dev, keep = _restart_args((mask, C.c_int, B), (rbd, C.c_double, B * shape[1]))
-        _check(load_library().bpmpc_plant_set_state(self._h, B, mp, rp, dev))
+        self._call("bpmpc_plant_set_state", B, mp, rp, dev)
         del keep
         self.batch = B
 
@@ -1151,7 +1092,7 @@ class BatchedPlant:
         """The ground-truth rbd [B, 2 (6 + nj)] of the first B robots (None: the batch of the last set_state); synchronises."""
         B = int(batch or self.batch)
         rbd = np.zeros((B, 2 * self.generalizedCoordinatesNum))
-        _check(load_library().bpmpc_plant_get_state(self._h, B, _d(rbd)))
+        self._call("bpmpc_plant_get_state", B, _d(rbd))
         return rbd
 
     def step(self, pos_des, vel_des, tau_ff, kp, kd, base_force=None, feet_heights=None, period=0.002, substeps=4):
@@ -1162,7 +1103,7 @@ class BatchedPlant:
         ptrs, dev, keep = _restart_args(*[(a, C.c_double, B * nj) for a in (pos_des, vel_des, tau_ff, kp, kd)], (base_force, C.c_double, B * 3),
                                         (feet_heights, C.c_double, B * 4))
         cmd = _JointCommand(*ptrs)
-        _check(load_library().bpmpc_plant_step(self._h, B, C.byref(cmd), dev, C.c_double(period), int(substeps)))
+        self._call("bpmpc_plant_step", B, C.byref(cmd), dev, period, int(substeps))
         del keep
 
     def step_controlled(self, controller, base_force=None, feet_heights=None, period=0.002, substeps=4):
@@ -1170,7 +1111,7 @@ class BatchedPlant:
         on the device; the two handles' streams are ordered by events, nothing is synchronised unless base_force / feet_heights are host arrays."""
         B = self.batch
         (fp, gp), dev, keep = _restart_args((base_force, C.c_double, B * 3), (feet_heights, C.c_double, B * 4))
-        _check(load_library().bpmpc_plant_step_controlled(self._h, controller._h, B, C.c_double(period), int(substeps), fp, gp, dev))
+        self._call("bpmpc_plant_step_controlled", controller._h, B, period, int(substeps), fp, gp, dev)
         del keep
 
     def outputs(self):
@@ -1178,7 +1119,7 @@ class BatchedPlant:
         set_state - the sensors of BatchedStateEstimate.update by name (joint_pos, joint_vel, quat, angular_vel_local, linear_accel_local, contact,
         feet_heights, odom_pos, odom_quat, odom_lin_vel, odom_ang_vel), rbd and contact_force [B, 4, 3]."""
         o = _PlantOutputs()
-        _check(load_library().bpmpc_plant_device_outputs(self._h, C.byref(o)))
+        self._call("bpmpc_plant_device_outputs", C.byref(o))
         B, nj = self.batch or self.max_batch, self.nj
         shapes = {"joint_pos": (B, nj), "joint_vel": (B, nj), "quat": (B, 4), "angular_vel_local": (B, 3), "linear_accel_local": (B, 3), "contact": (B, 4),
                   "feet_heights": (B, 4), "odom_pos": (B, 3), "odom_quat": (B, 4), "odom_lin_vel": (B, 3), "odom_ang_vel": (B, 3)}
@@ -1187,21 +1128,11 @@ class BatchedPlant:
         views["contact_force"] = DeviceArray(C.cast(o.contact_force, C.c_void_p).value, (B, 4, 3), "<f8")
         return views
 
-    def getParams(self, robot=-1):
-        """The parameter row [8] of `robot` (PlantParams.fromRow names its entries), or with robot < 0 the values every row starts from."""
-        row = np.zeros(PlantParams.STRIDE)
-        _check(load_library().bpmpc_plant_get_params(self._h, int(robot), _d(row)))
-        return row
-
-    def setParams(self, rows, mask=None):
+    getParams, setParams, resetParams = _param_methods(
+        "bpmpc_plant", PlantParams.STRIDE,
+        """The parameter row [8] of `robot` (PlantParams.fromRow names its entries), or with robot < 0 the values every row starts from.""",
         """rows [8], [1, 8] or [B, 8]; mask as WeightedWbc.setParams.  numpy rows are validated (finite; kn, d0, v_eps positive; the others not
-        negative) and the call synchronises; device tensors are only enqueued, ordered before the next step."""
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], PlantParams.STRIDE, self.max_batch)
-        _check(load_library().bpmpc_plant_set_params(self._h, B, mp, rp, n_rows, dev))
-        del keep
-
-    def resetParams(self):
-        _check(load_library().bpmpc_plant_reset_params(self._h))
+        negative) and the call synchronises; device tensors are only enqueued, ordered before the next step.""")
 
     def setStiction(self, kt, mask=None):
         """The tangential contact stiffness kt [N/m] of the robots with mask[b] != 0 (None: every one): one value for all of them, or [B] values.
@@ -1213,25 +1144,25 @@ class BatchedPlant:
             kt = np.asarray(kt, float).reshape(-1)
             rows = kt if kt.size == 1 else kt.reshape(-1, 1)
         B, n_rows, (mp, kp), dev, keep = _rows_args(mask, [rows], 1, self.max_batch)
-        _check(load_library().bpmpc_plant_set_stiction(self._h, B, mp, kp, n_rows, dev))
+        self._call("bpmpc_plant_set_stiction", B, mp, kp, n_rows, dev)
         del keep
 
     def getStiction(self, robot=-1):
         """kt of `robot`, or with robot < 0 the value every robot starts from (the key plant.kt of the task file; absent: 0)."""
         kt = C.c_double()
-        _check(load_library().bpmpc_plant_get_stiction(self._h, int(robot), C.byref(kt)))
+        self._call("bpmpc_plant_get_stiction", int(robot), C.byref(kt))
         return kt.value
 
     def resetStiction(self):
         """Every robot's kt back to the handle's start value; every anchor cleared."""
-        _check(load_library().bpmpc_plant_reset_stiction(self._h))
+        self._call("bpmpc_plant_reset_stiction")
 
     def anchors(self):
         """(anchor [B, 4, 2], anchored [B, 4]) of the batch of the last set_state (before it: max_batch): the world xy each contact point's tangential
         spring is anchored at, and whether it is; synchronises."""
         B = self.batch or self.max_batch
         anchor, anchored = np.zeros((B, 4, 2)), np.zeros((B, 4), np.int32)
-        _check(load_library().bpmpc_plant_get_anchors(self._h, B, _d(anchor), _i(anchored)))
+        self._call("bpmpc_plant_get_anchors", B, _d(anchor), _i(anchored))
         return anchor, anchored
 
 

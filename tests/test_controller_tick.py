@@ -36,7 +36,7 @@ def test_null_handles_and_arguments_are_refused():
     assert lib.bpmpc_controller_create(None, None, C.byref(out)) == -1 and not out.value
     assert lib.bpmpc_controller_create(None, None, None) == -1
     assert lib.bpmpc_controller_reset(None) == -1
-    assert lib.bpmpc_controller_tick(None, 1, d, d, 0, C.c_double(0.0025), None) == -1
+    assert lib.bpmpc_controller_tick(None, 1, d, d, 0, 0.0025, None) == -1
     assert lib.bpmpc_controller_device_outputs(None, None) == -1
     assert lib.bpmpc_solver_evaluate_policy(None, 1, d, d, d, d, i) == -1
     assert b"null" in lib.bpmpc_last_error()

@@ -11,6 +11,8 @@ import shutil
 import numpy as np
 import pytest
 
+from bipedal_control_amd import load_library
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ["bpmpc_estimator_create", "bpmpc_estimator_update", "bpmpc_estimator_device_outputs", "bpmpc_estimator_reset", "bpmpc_estimator_get_state",
              "bpmpc_estimator_set_state", "bpmpc_estimator_get_params", "bpmpc_estimator_set_params", "bpmpc_estimator_reset_params",
@@ -19,17 +21,10 @@ INVALID, NO_DEVICE = -1, -4
 DEFAULTS = [0.02, 0.02, 0.02, 0.002, 0.005, 0.1, 0.01, 0.0]
 
 
-def _lib():
-    import bipedal_control_amd as bp
-    lib = bp.load_library()
-    lib.bpmpc_last_error.restype = C.c_char_p
-    return lib
-
-
 def test_functions_are_declared_and_exported():
     raw = open(os.path.join(ROOT, "include", "bpmpc.h")).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    lib = _lib()
+    lib = load_library()
     for name in FUNCTIONS:
         assert re.search(r"\bint\s+%s\s*\(" % name, text), name + " is not declared"
         assert hasattr(lib, name), "libbpmpc.so does not export " + name
@@ -47,20 +42,20 @@ def test_functions_are_declared_and_exported():
 
 def test_null_handles_are_refused():
     from bipedal_control_amd.api import _EstimatorOutputs, _SensorInputs
-    lib = _lib()
+    lib = load_library()
     d = (C.c_double * 1024)()
     m = (C.c_int * 4)(1, 0, 1, 0)
     inputs, outs = _SensorInputs(), _EstimatorOutputs()
     null = lambda rc: rc == INVALID and b"null" in lib.bpmpc_last_error()      # noqa: E731
     h = C.c_void_p()
     assert null(lib.bpmpc_estimator_create(None, None, 1, 0, 4, C.byref(h))) and not h
-    assert null(lib.bpmpc_estimator_update(None, 4, C.byref(inputs), 0, C.c_double(0.0025), d))
+    assert null(lib.bpmpc_estimator_update(None, 4, C.byref(inputs), 0, 0.0025, d))
     assert b"bpmpc_estimator_update" in lib.bpmpc_last_error()
     assert null(lib.bpmpc_estimator_device_outputs(None, C.byref(outs)))
     assert null(lib.bpmpc_estimator_get_state(None, 4, d, d))
     assert null(lib.bpmpc_estimator_get_params(None, 0, d))
     assert null(lib.bpmpc_estimator_reset_params(None))
-    assert null(lib.bpmpc_controller_tick_estimated(None, None, 4, d, 0, C.c_double(0.0025), None))
+    assert null(lib.bpmpc_controller_tick_estimated(None, None, 4, d, 0, 0.0025, None))
     for on_device in (0, 1):
         for mask in (m, None):
             assert null(lib.bpmpc_estimator_reset(None, 4, mask, on_device))
@@ -157,7 +152,7 @@ def _model(lib, robot, task=None):
 
 def test_create_refuses_bad_arguments():
     """Without a GPU the create call ends with BPMPC_ERR_NO_DEVICE behind its argument checks."""
-    lib = _lib()
+    lib = load_library()
     model = _model(lib, "h1")
     h = C.c_void_p()
     try:
@@ -176,7 +171,7 @@ def test_kalman_block_of_task_info_is_ingested(tmp_path):
     """The shipped files have no kalmanFilter block (every key absent: the header's defaults, as with a NULL path); a copy with the block appended
     gives its values and keeps the defaults of the keys it leaves out; a bad value is refused and named."""
     from bipedal_control_amd import KalmanParams, scenarios as sc
-    lib = _lib()
+    lib = load_library()
     row = (C.c_double * 8)()
     assert lib.bpmpc_estimator_load_params(None, row) == 0 and list(row) == DEFAULTS
     for robot in sc.ROBOTS:
@@ -199,7 +194,7 @@ def test_kalman_block_of_task_info_is_ingested(tmp_path):
 
 
 def test_bad_parameter_rows_are_named():
-    lib = _lib()
+    lib = load_library()
     good = np.tile(np.array(DEFAULTS), (3, 1))
     rows = lambda a: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(C.c_double))      # noqa: E731
     assert lib.bpmpc_estimator_check_params(rows(good), 3) == 0

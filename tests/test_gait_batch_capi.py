@@ -35,7 +35,7 @@ def test_null_and_out_of_range_arguments_are_refused():
     assert lib.bpmpc_gait_batch_create(None, None, 0, C.byref(out)) == INVALID and not out.value
     assert lib.bpmpc_gait_batch_create(None, None, 0, None) == INVALID
     d, i = (C.c_double * 4)(), (C.c_int * 4)()
-    assert lib.bpmpc_solver_setup_gaits(None, None, 1, C.c_double(1.0), d, d, d, 0, C.c_double(0.0), 0) == INVALID
+    assert lib.bpmpc_solver_setup_gaits(None, None, 1, 1.0, d, d, d, 0, 0.0, 0) == INVALID
     assert lib.bpmpc_gait_batch_reset(None) == INVALID
     assert lib.bpmpc_gait_batch_insert(None, 1, i, d, d) == INVALID
     assert lib.bpmpc_gait_batch_command(None, 1, i, 0) == INVALID

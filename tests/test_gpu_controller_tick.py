@@ -329,7 +329,7 @@ def test_refusals():
     lib = bp.load_library()
     d = np.zeros(4 * 2 * 16)
     dp = d.ctypes.data_as(C.POINTER(C.c_double))
-    assert lib.bpmpc_controller_tick(ctrl._h, 1, dp, dp, 0, C.c_double(0.0025), None) == -1
-    assert lib.bpmpc_controller_tick(ctrl._h, 3, dp, dp, 0, C.c_double(0.0025), None) == -1
+    assert lib.bpmpc_controller_tick(ctrl._h, 1, dp, dp, 0, 0.0025, None) == -1
+    assert lib.bpmpc_controller_tick(ctrl._h, 3, dp, dp, 0, 0.0025, None) == -1
     ip = np.zeros(4, np.int32).ctypes.data_as(C.POINTER(C.c_int))
     assert lib.bpmpc_solver_evaluate_policy(mpc._h, 3, dp, dp, dp, dp, ip) == -1

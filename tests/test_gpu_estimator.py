@@ -423,7 +423,7 @@ def test_refusals_on_a_live_handle():
     arrs = dict(jp=z(5, 10), jv=z(5, 10), q=q, w=z(5, 3), a=z(5, 3), mode=np.full(5, 3, np.int32), contact=np.ones((5, 4), np.int32))
     base = dict(joint_pos=_d(arrs["jp"]), joint_vel=_d(arrs["jv"]), quat=_d(arrs["q"]), angular_vel_local=_d(arrs["w"]), linear_accel_local=_d(arrs["a"]))
     rbd = z(5, 32)
-    call = lambda batch, **kw: lib.bpmpc_estimator_update(est._h, batch, C.byref(_SensorInputs(**dict(base, **kw))), 0, C.c_double(DT), _d(rbd))      # noqa: E731
+    call = lambda batch, **kw: lib.bpmpc_estimator_update(est._h, batch, C.byref(_SensorInputs(**dict(base, **kw))), 0, DT, _d(rbd))      # noqa: E731
     assert call(4) == -1 and b"no contact source" in lib.bpmpc_last_error()
     assert call(4, mode=_i(arrs["mode"]), contact=_i(arrs["contact"])) == -1 and b"two contact sources" in lib.bpmpc_last_error()
     assert call(5, mode=_i(arrs["mode"])) == -6                                       # BPMPC_ERR_CAPACITY

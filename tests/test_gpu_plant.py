@@ -385,7 +385,7 @@ def test_refusals():
     lib = bp.load_library()
     from bipedal_control_amd.api import _JointCommand, _d
     partial = _JointCommand(pos_des=_d(np.ascontiguousarray(args[0])))
-    assert lib.bpmpc_plant_step(plant._h, 4, C.byref(partial), 0, C.c_double(0.002), 4) == INVALID and b"null" in lib.bpmpc_last_error()
+    assert lib.bpmpc_plant_step(plant._h, 4, C.byref(partial), 0, 0.002, 4) == INVALID and b"null" in lib.bpmpc_last_error()
     assert np.array_equal(plant.get_state(), before)                             # no refusal touched the state
     # step_controlled before any tick
     lp = _Loop()

@@ -10,6 +10,8 @@ import shutil
 import numpy as np
 import pytest
 
+from bipedal_control_amd import load_library
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ["bpmpc_plant_create", "bpmpc_plant_set_state", "bpmpc_plant_get_state", "bpmpc_plant_step", "bpmpc_plant_device_outputs",
              "bpmpc_plant_step_controlled", "bpmpc_plant_get_params", "bpmpc_plant_set_params", "bpmpc_plant_reset_params", "bpmpc_plant_load_params",
@@ -18,17 +20,10 @@ INVALID, NO_DEVICE = -1, -4
 DEFAULTS = [5e4, 5e2, 1e-3, 0.7, 0.01, 1.0, 0.0, 0.0]
 
 
-def _lib():
-    import bipedal_control_amd as bp
-    lib = bp.load_library()
-    lib.bpmpc_last_error.restype = C.c_char_p
-    return lib
-
-
 def test_functions_are_declared_and_exported():
     raw = open(os.path.join(ROOT, "include", "bpmpc.h")).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    lib = _lib()
+    lib = load_library()
     for name in FUNCTIONS:
         assert re.search(r"\bint\s+%s\s*\(" % name, text), name + " is not declared"
         assert hasattr(lib, name), "libbpmpc.so does not export " + name
@@ -44,16 +39,16 @@ def test_functions_are_declared_and_exported():
 
 def test_null_handles_are_refused():
     from bipedal_control_amd.api import _JointCommand, _PlantOutputs
-    lib = _lib()
+    lib = load_library()
     d = (C.c_double * 1024)()
     m = (C.c_int * 4)(1, 0, 1, 0)
     cmd, outs = _JointCommand(), _PlantOutputs()
     null = lambda rc: rc == INVALID and b"null" in lib.bpmpc_last_error()      # noqa: E731
     h = C.c_void_p()
     assert null(lib.bpmpc_plant_create(None, None, 0, 4, C.byref(h))) and not h
-    assert null(lib.bpmpc_plant_step(None, 4, C.byref(cmd), 0, C.c_double(0.002), 4)) and b"bpmpc_plant_step" in lib.bpmpc_last_error()
-    assert null(lib.bpmpc_plant_step_controlled(None, None, 4, C.c_double(0.002), 4, None, None, 0))
-    assert null(lib.bpmpc_estimator_update_from_plant(None, None, 4, C.c_double(0.002), d))
+    assert null(lib.bpmpc_plant_step(None, 4, C.byref(cmd), 0, 0.002, 4)) and b"bpmpc_plant_step" in lib.bpmpc_last_error()
+    assert null(lib.bpmpc_plant_step_controlled(None, None, 4, 0.002, 4, None, None, 0))
+    assert null(lib.bpmpc_estimator_update_from_plant(None, None, 4, 0.002, d))
     assert null(lib.bpmpc_plant_device_outputs(None, C.byref(outs)))
     assert null(lib.bpmpc_plant_get_state(None, 4, d))
     assert null(lib.bpmpc_plant_get_params(None, 0, d))
@@ -98,7 +93,7 @@ def test_plant_block_of_task_info_is_ingested(tmp_path):
     """The shipped files have no plant block (every key absent: the defaults, as with a NULL path); a copy with the block appended gives its values and
     keeps the defaults of the keys it leaves out; a bad value is refused and named."""
     from bipedal_control_amd import scenarios as sc
-    lib = _lib()
+    lib = load_library()
     row = (C.c_double * 8)()
     assert lib.bpmpc_plant_load_params(None, row) == 0 and list(row) == DEFAULTS
     row = (C.c_double * 8)(*([7.0] * 8))
@@ -119,7 +114,7 @@ def test_plant_block_of_task_info_is_ingested(tmp_path):
 
 
 def test_bad_parameter_rows_are_named():
-    lib = _lib()
+    lib = load_library()
     good = np.tile(np.array(DEFAULTS), (3, 1))
     rows = lambda a: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(C.c_double))      # noqa: E731
     assert lib.bpmpc_plant_check_params(rows(good), 3) == 0
@@ -139,7 +134,7 @@ def test_bad_parameter_rows_are_named():
 def test_create_refuses_bad_arguments():
     """Without a GPU the create call ends with BPMPC_ERR_NO_DEVICE behind its argument checks, as bpmpc_estimator_create."""
     from bipedal_control_amd import scenarios as sc
-    lib = _lib()
+    lib = load_library()
     r = sc.ROBOTS["h1"]
     model = C.c_void_p()
     assert lib.bpmpc_model_create(r["urdf"].encode(), r["task"].encode(), r["reference"].encode(), C.byref(model)) == 0, lib.bpmpc_last_error()

@@ -10,23 +10,18 @@ import shutil
 import numpy as np
 import pytest
 
+from bipedal_control_amd import load_library
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FUNCTIONS = ["bpmpc_plant_set_stiction", "bpmpc_plant_get_stiction", "bpmpc_plant_reset_stiction", "bpmpc_plant_load_stiction", "bpmpc_plant_get_anchors"]
 INVALID = -1
 DEFAULTS = [5e4, 5e2, 1e-3, 0.7, 0.01, 1.0, 0.0, 0.0]
 
 
-def _lib():
-    import bipedal_control_amd as bp
-    lib = bp.load_library()
-    lib.bpmpc_last_error.restype = C.c_char_p
-    return lib
-
-
 def test_functions_are_declared_and_exported():
     raw = open(os.path.join(ROOT, "include", "bpmpc.h")).read()
     text = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    lib = _lib()
+    lib = load_library()
     for name in FUNCTIONS:
         assert re.search(r"\bint\s+%s\s*\(" % name, text), name + " is not declared"
         assert hasattr(lib, name), "libbpmpc.so does not export " + name
@@ -35,7 +30,7 @@ def test_functions_are_declared_and_exported():
 
 
 def test_null_handles_and_pointers_are_refused_by_name():
-    lib = _lib()
+    lib = load_library()
     d = (C.c_double * 64)()
     i = (C.c_int * 16)()
     m = (C.c_int * 4)(1, 0, 1, 0)
@@ -56,7 +51,7 @@ def test_null_handles_and_pointers_are_refused_by_name():
 
 def test_plant_kt_of_task_info_is_ingested(tmp_path):
     from bipedal_control_amd import scenarios as sc
-    lib = _lib()
+    lib = load_library()
     kt = C.c_double(7.0)
     assert lib.bpmpc_plant_load_stiction(None, C.byref(kt)) == 0 and kt.value == 0.0
     kt = C.c_double(7.0)
@@ -84,7 +79,7 @@ def test_plant_kt_of_task_info_is_ingested(tmp_path):
 
 def test_parameter_row_and_plant_params_are_unchanged():
     from bipedal_control_amd import PlantParams
-    lib = _lib()
+    lib = load_library()
     row = (C.c_double * 8)()
     assert lib.bpmpc_plant_load_params(None, row) == 0 and list(row) == DEFAULTS
     assert PlantParams.STRIDE == 8 and PlantParams.FIELDS == ("kn", "cn", "d0", "mu", "v_eps", "contact_threshold")

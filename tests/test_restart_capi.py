@@ -38,7 +38,6 @@ def test_null_handles_and_masks_are_refused():
         assert lib.bpmpc_controller_restart(None, 4, m, d, on_device) == INVALID
         assert lib.bpmpc_controller_restart(None, 4, None, d, on_device) == INVALID
         assert lib.bpmpc_controller_restart(None, 4, m, None, on_device) == INVALID
-    lib.bpmpc_last_error.restype = C.c_char_p
     assert b"null" in lib.bpmpc_last_error()
 
 

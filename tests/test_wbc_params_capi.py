@@ -34,7 +34,6 @@ def test_functions_are_declared_and_exported():
 def test_null_handles_and_rows_are_refused():
     import bipedal_control_amd as bp
     lib = bp.load_library()
-    lib.bpmpc_last_error.restype = C.c_char_p
     m = (C.c_int * 4)(1, 0, 1, 0)
     d = (C.c_double * 128)()
     assert lib.bpmpc_wbc_get_params(None, 0, d) == INVALID and b"null" in lib.bpmpc_last_error()

@@ -163,9 +163,8 @@ def main():
     parent = None
     if args.parent_lib:
         import ctypes as C
-        parent = C.CDLL(os.path.abspath(args.parent_lib))
-        parent.bpmpc_last_error.restype = C.c_char_p
-        parent.bpmpc_version.restype = C.c_char_p
+        from bipedal_control_amd import abi
+        parent = abi.bind(C.CDLL(os.path.abspath(args.parent_lib)), strict=False)      # the parent exports less than the header declares
         if hasattr(parent, "bpmpc_estimator_update"):
             raise SystemExit("--parent-lib already has bpmpc_estimator_update: not the parent commit's library")
     for shape in args.shapes.split(","):

@@ -108,14 +108,12 @@ def main():
         ap.error("the spread of (a) needs at least three repeats")
     import numpy as np
     import torch
-    from bipedal_control_amd import api
+    from bipedal_control_amd import abi, api
     mine = api.load_library()
     parent = None
     if args.parent_lib:
         with step("load parent library", 60):
-            parent = C.CDLL(os.path.abspath(args.parent_lib))
-            parent.bpmpc_last_error.restype = C.c_char_p
-            parent.bpmpc_version.restype = C.c_char_p
+            parent = abi.bind(C.CDLL(os.path.abspath(args.parent_lib)), strict=False)      # the parent exports less than the header declares
             if hasattr(parent, "bpmpc_wbc_set_params"):
                 raise SystemExit("--parent-lib already has bpmpc_wbc_set_params: not the parent commit's library")
     stream = torch.cuda.Stream()
