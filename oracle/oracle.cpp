@@ -1085,6 +1085,10 @@ int oracle_solve(const oracle_model* om, int N, const int* kind, const double* d
     bool accepted = false;
     double perf[3] = {0, 0, 0};
     int trials = 0;
+    // st[11]: the smallest relative distance of any comparison of this iteration's line search and convergence test from its threshold (a decision
+    // closer than rounding can be taken the other way by an implementation that sums in another order; the parity tests assert this margin)
+    double margin = 1e300;
+    auto note = [&margin](double lhs, double rhs) { margin = std::min(margin, std::fabs(lhs - rhs) / std::max(std::fabs(rhs), 1e-300)); };
     do {
       for (size_t i = 0; i < x.size(); ++i) xn[i] = x[i] + alpha * so.dx[i];
       for (size_t i = 0; i < u.size(); ++i) un[i] = u[i] + alpha * so.du[i];
@@ -1092,15 +1096,21 @@ int oracle_solve(const oracle_model* om, int N, const int* kind, const double* d
       ++trials;
       const double viol = std::sqrt(perf[1] + perf[2]);
       const double descent = alpha * so.armijo;
+      note(viol, g_max);
       if (viol > g_max) {
         accepted = viol < (1.0 - gamma_c) * viol0;
+        note(viol, (1.0 - gamma_c) * viol0);
       } else if (viol < g_min && viol0 < g_min && descent < 0.0) {
         accepted = perf[0] < merit0 + armijo * descent;
+        note(perf[0], merit0 + armijo * descent);
       } else {
         accepted = perf[0] < (merit0 - gamma_c * viol0) || viol < (1.0 - gamma_c) * viol0;
+        note(viol, g_min); note(viol0, g_min);
+        note(perf[0], merit0 - gamma_c * viol0); note(viol, (1.0 - gamma_c) * viol0);
       }
       if (accepted) break;
       alpha *= alpha_decay;
+      note(alpha * dun, delta_tol); note(alpha * dxn, delta_tol); note(alpha, alpha_min);
       // [OCS2-upstream] SqpSolver::takeStep: "detect too small step size during back-tracking to escape early" - once the
       // next trial step would be below deltaTol in both norms the search stops and no step is taken
       if (alpha * dun < delta_tol && alpha * dxn < delta_tol) break;
@@ -1113,6 +1123,8 @@ int oracle_solve(const oracle_model* om, int N, const int* kind, const double* d
     } else {
       st[3] = 0.0; st[4] = merit0; st[5] = so.base[1]; st[6] = so.base[2];
     }
+    if (accepted) { note(std::fabs(st[4] - merit0), cost_tol); note(std::sqrt(st[5] + st[6]), g_min); note(st[8], delta_tol); note(st[9], delta_tol); }
+    st[11] = margin;
     // convergence
     if (it + 1 >= iters) break;
     if (st[3] < alpha_min) break;

@@ -75,7 +75,9 @@ int oracle_lu_projection(int nc, int nx, int nu, const double* C, const double* 
 /* Full solve.  Node arrays have N entries (intervals); x_init (N+1)*nx, u_init N*nu.
  * opts[9] = {sqp_iterations, g_max, g_min, alpha_decay, alpha_min, gamma_c, armijo_factor, delta_tol}
  * Outputs: x_out (N+1)*nx, u_out N*nu, K_out N*nu*nx (nullable), stats[16 * iterations]:
- *   per iteration {merit0, dyn0, eq0, alpha, merit1, dyn1, eq1, armijo_descent, dx_norm, du_norm, n_trials, 0...}. */
+ *   per iteration {merit0, dyn0, eq0, alpha, merit1, dyn1, eq1, armijo_descent, dx_norm, du_norm, n_trials, decision_margin, 0...};
+ *   decision_margin: the smallest relative distance |lhs - rhs| / |rhs| of any comparison of the iteration's line search and convergence test
+ *   from its threshold. */
 int oracle_solve(const oracle_model*, int N, const int* kind, const double* dt, const int* mode, const double* zref, const double* zdref,
                  const double* xref, const double* x0, const double* x_init, const double* u_init, const double* opts, double* x_out,
                  double* u_out, double* K_out, double* stats);

@@ -1,5 +1,10 @@
 """Test-side glue: rebuild a product scenario (bipedal_control_amd.scenarios) with the ORACLE's own ingest and
-reference pre-pass and solve it with the C++ oracle.  Used by the GPU parity tests and by __graft_entry__.smoke()."""
+reference pre-pass and solve it with the C++ oracle.  Used by the GPU parity tests and by __graft_entry__.smoke().
+
+The mode schedule handed to the oracle's pre-pass (oracle_nodes below) is the PRODUCT's: scenarios.gait_schedule tiles the gait template with the
+product's own GaitSchedule (C++), and the oracle starts from its event times and mode sequence.  The oracle's time grid, swing references and target
+interpolation are its own; the tiling is not re-derived here.  It is checked independently on the CPU tier, against the oracle's own pure-Python
+GaitSchedule and a hand-derived answer: tests/test_reference_prepass.py::test_gait_schedule_tiling and ::test_trot_tiling_known_answer."""
 import functools
 import os
 

@@ -277,7 +277,10 @@ def test_solver_reuse_across_gaits_matches_fresh_solver(ctx):
 
 # 300 > number of CUs: the eight-wave sweep in two rounds (the default of the 22-state robots since round 6) or, BPMPC_R8_ROUNDS=1, the four-wave workgroups
 # (two per CU; what nx = 24 runs at that batch)
-@pytest.mark.parametrize("batch,r8_rounds", [(48, None), (300, None), (300, "1"), (600, None)])
+@pytest.mark.parametrize("batch,r8_rounds", [(48, None), (300, None), (300, "1"), (600, None),
+                                              # the boundaries of the eight-wave sweep in rounds (nx = 22: three rounds of 256): the end of the second round, the full third
+                                              # round, and the first batch on a wave per problem
+                                              (512, None), (768, None), (769, None)])
 def test_repeated_solves_are_bit_identical(ctx, batch, r8_rounds, monkeypatch):
     """Races, stale LDS or stale HBM scratch would show up as run-to-run differences; also checks the larger-batch Riccati variants
     against the oracle."""
