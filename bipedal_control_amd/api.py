@@ -1005,6 +1005,12 @@ class BatchedController(_Handle):
             raise ValueError("leg gains need %d values per robot" % (self.nj // 2))
         self.setJointGains(both(kp_leg), both(kd_leg), mask)
 
+    def attachPolicy(self, policy):
+        """Ticks, restarts and joint-gain writes move to the stream of `policy` (a PolicyBuffer of the same solver) and the tick evaluates the
+        policy it adopted last (bpmpc_controller_attach_policy); None detaches: everything is back on the solver's stream and arrays."""
+        self._call("bpmpc_controller_attach_policy", None if policy is None else policy._h)
+        self.policy = policy
+
     def reset(self):
         """yaw_last = 0 for every robot (BipedalController::starting)."""
         self._call("bpmpc_controller_reset")
@@ -1030,6 +1036,43 @@ class BatchedController(_Handle):
         for k, p in zip(self.JOINT_NAMES, ptrs):
             views[k] = DeviceArray(C.cast(p, C.c_void_p).value, (B, self.nj), "<f8")
         return views
+
+
+class PolicyBuffer(_Handle):
+    """MPC_MRT_Interface between the solve and the control tick (bpmpc_policy_*; BipedalController.cpp:191-200, :332-350): two slots of the
+    solution per robot on the device.  `publish` copies the solver's last run into the slot the ticks do not read, on the solver's stream;
+    `update` (updatePolicy) makes it the slot they read, on the buffer's own stream.  A BatchedController with the buffer attached
+    (attachPolicy) ticks on that stream and on the adopted policy, whatever the solver is doing meanwhile."""
+
+    _DESTROY = "bpmpc_policy_destroy"
+
+    def __init__(self, mpc, max_batch):
+        self.mpc, self.max_batch = mpc, int(max_batch)
+        super().__init__()
+        _check(load_library().bpmpc_policy_create(mpc._h, self.max_batch, C.byref(self._h)))
+
+    def publish(self, mask=None, skip_failed=False):
+        """The last run of the solver into the back slot, for the robots with mask[b] != 0 (None: every robot; a numpy array, or an int32 device
+        tensor: then nothing synchronises) and, with skip_failed, only those whose solve status on the device is not 2."""
+        B = self.mpc.batch
+        (mp,), dev, keep = _restart_args((mask, C.c_int, B))
+        self._call("bpmpc_policy_publish", B, mp, dev, int(bool(skip_failed)))
+        del keep
+
+    def update(self, wait=True):
+        """updatePolicy.  wait=True: the buffer's stream waits for the last publish and adopts it, the host does not block; wait=False: adopts it
+        only if it has completed.  Returns whether an adoption was enqueued (False with no publish outstanding)."""
+        adopted = C.c_int(0)
+        self._call("bpmpc_policy_update", int(bool(wait)), C.byref(adopted))
+        return bool(adopted.value)
+
+    def info(self, batch=None):
+        """{"generation", "t0", "status"}: per robot the number of policies adopted, the time of node 0 of the policy the ticks read and the solve
+        status it was published with (synchronises the buffer's stream)."""
+        B = int(batch or self.mpc.batch or self.max_batch)
+        out = {"generation": np.zeros(B, np.int32), "t0": np.zeros(B), "status": np.zeros(B, np.int32)}
+        self._call("bpmpc_policy_info", B, _i(out["generation"]), _d(out["t0"]), _i(out["status"]))
+        return out
 
 
 class PlantParams:

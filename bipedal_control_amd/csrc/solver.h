@@ -104,6 +104,9 @@ struct bpmpc_solver {
   // that the tick, not a rollout, ran last on the handle - bpmpc_solver_setup_commands(x0 = NULL) then starts from tick_x instead of roll_x
   double* tick_x = nullptr;
   bool loop_from_tick = false;
+  // a controller whose ticks run on a policy buffer's stream (policy.h): that stream's handshake.  What this handle's stream does to tick_x - the
+  // read of setup_commands(x0 = NULL), the rows a restart writes - waits for the last such tick, and the next tick waits for it.  NULL: no buffer
+  StreamHandshake* tick_hs = nullptr;
   // per-problem restarts (bpmpc_solver_restart, MPC_BASE::reset per problem): restart_flag[b] != 0 from the restart to the next accepted setup,
   // which keeps k_prepare's guess for those problems instead of the shifted solution.  restart_pending: flags recorded and not consumed yet;
   // restart_wait: tick, evaluate_policy and rollout are refused until the first run after that setup (a fresh handle before its first run)

@@ -451,8 +451,12 @@ ReferenceGenArgs reference_args(bpmpc_solver* s, const GaitLibraryView& lib, int
 
 // x0 == NULL: the start states are already on the device
 void copy_loop_x0(bpmpc_solver* s, int batch, const double* x0) {
-  if (!x0) HIP_CHECK(hipMemcpyAsync(s->buf.p_x0, s->loop_from_tick ? s->tick_x : s->buf.roll_x, (size_t)batch * s->nx * sizeof(double), hipMemcpyDeviceToDevice,
-                                    s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
+  if (x0) return;
+  const bool foreign_tick = s->loop_from_tick && s->tick_hs;      // the ticks that write tick_x run on a policy buffer's stream
+  if (foreign_tick) s->tick_hs->before_foreign(s->stream);
+  HIP_CHECK(hipMemcpyAsync(s->buf.p_x0, s->loop_from_tick ? s->tick_x : s->buf.roll_x, (size_t)batch * s->nx * sizeof(double), hipMemcpyDeviceToDevice,
+                           s->stream));   // closed loop on the device: the end states of the last rollout or the observations of the last tick
+  if (foreign_tick) s->tick_hs->after_foreign(s->stream);
 }
 
 #define EXACT_FP_BODY _Pragma("clang fp contract(off)")   // first statement of a body: no fused multiply-add, as on the host (kernels/reference_device.h)
@@ -585,8 +589,11 @@ void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, b
   x_new = staged(x_new, s->restart_x, batch * NX, on_device, s->stream);
   // the start that setup(x0 = NULL) reads (copy_loop_x0); neither a tick nor a rollout can replace it before that setup (both are refused)
   double* loop_x = s->loop_from_tick ? s->tick_x : s->buf.roll_x;
+  const bool foreign_tick = s->loop_from_tick && s->tick_hs;      // as copy_loop_x0
+  if (foreign_tick) s->tick_hs->before_foreign(s->stream);
   hipLaunchKernelGGL(k_restart_mark, dim3((unsigned)((batch * NX + 255) / 256)), dim3(256), 0, s->stream, batch, (int)NX, mask, s->restart_flag, x_new, loop_x);
   HIP_CHECK(hipGetLastError());
+  if (foreign_tick) s->tick_hs->after_foreign(s->stream);
   s->restart_pending = s->restart_wait = true;
   if (!on_device) HIP_CHECK(hipStreamSynchronize(s->stream));   // the caller's host arrays
 }

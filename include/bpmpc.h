@@ -698,6 +698,63 @@ int bpmpc_plant_reset_stiction(bpmpc_plant* plant);
 int bpmpc_plant_load_stiction(const char* task_info_path, double* kt);
 int bpmpc_plant_get_anchors(bpmpc_plant* plant, int batch, double* host_anchor, int* host_anchored);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Policy buffer = MPC_MRT_Interface between the solve and the control tick for a BATCH of robots, on the device.  In the reference a thread calls
+ * advanceMpc() at mpcDesiredFrequency (bipedal_controllers/src/BipedalController.cpp:332-350) while update() calls updatePolicy() and
+ * evaluatePolicy() at the control rate on whatever policy was finished last (:191-200): a tick never waits for a solve, and a solve that is still
+ * running changes nothing for the ticks that happen meanwhile.  Without a buffer a tick reads the solver's working arrays on the solver's stream:
+ * it queues behind the solve, the policy is gone from bpmpc_solver_setup_commands to the end of bpmpc_solver_run, and a failed solve hands its
+ * iterate to the next tick.
+ *   layout: two slots.  A slot holds per robot, with nothing shared between robots, the grid row the solver keeps per grid (node times, node kinds,
+ *     modes, node count), x[N+1][nx], u[N][nu] and, when the solver's feedback policy is on, K[N][nu][nx]; N is the solver's max_nodes.  Ticks read
+ *     the FRONT slot, publishes write the BACK slot.  Beside the slots, per robot: pending, generation (0 after create), t0 (the time of node 0 of
+ *     the robot's policy) and status (the solve status it was published with).  The handle owns a stream: the buffer's stream.
+ *   bpmpc_policy_create: for an SQP solver; a DDP solver is refused with BPMPC_ERR_UNSUPPORTED (its solution lives on the time points of its own
+ *     roll-out, as for bpmpc_controller_tick).  max_batch above the solver's: BPMPC_ERR_CAPACITY.  The solver must outlive the buffer; detach the
+ *     buffer from every controller before it is destroyed.
+ *   bpmpc_policy_publish: enqueued on the SOLVER's stream, behind the run it publishes; with inputs_on_device != 0 or mask == NULL it never
+ *     synchronises (a host mask is copied first and the call waits for the solver's stream).  Robot b is taken when mask[b] != 0 (NULL: every
+ *     robot) and, with skip_failed != 0, the status of its last run is not 2; the status is read from the statistics on the device, not from the
+ *     host.  A taken robot's live nodes (its grid's node count, plus one for x and the times) are copied from the solver's solution and grid row
+ *     into the back slot, its pending flag is set and t0 and status are noted for the adoption.  A robot that is not taken keeps the policy,
+ *     generation, t0 and status it has; the first publish after an adoption copies its front row into the back slot, so that the adoption can turn
+ *     the slots over for the whole batch with one set of pointers for the tick kernel.  The refusals are those of a tick without a buffer - a
+ *     completed bpmpc_solver_run since the last setup, no restart waiting, the batch of that setup - BPMPC_ERR_CAPACITY above max_batch, and a publish
+ *     whose batch differs from the last publish's must take every robot (mask == NULL, skip_failed == 0).  Before it writes, the solver's stream
+ *     waits for the last adoption: ticks enqueued before that adoption may still be reading what is now the back slot.  A second publish before an
+ *     adoption overwrites the pending data of the robots it takes, and only theirs.
+ *   bpmpc_policy_update = updatePolicy.  With no publish outstanding *adopted = 0 and nothing happens.  wait != 0: the buffer's stream waits for the
+ *     last publish, then the adoption: the slots change roles and every pending robot takes generation + 1, its new t0 and status; nothing blocks on
+ *     the host (simulations and tests: the policy takes effect at a known tick).  wait == 0: the reference's behaviour; if the last publish has
+ *     not completed yet nothing is enqueued and *adopted = 0.  *adopted = 1 says that an adoption was enqueued, also when every robot of the
+ *     publish was skipped.
+ *   bpmpc_policy_info: host copies of generation, t0 and status [batch], each nullable; synchronises the buffer's stream.  They describe the
+ *     policies of the front slot as of the last adoption.
+ *   bpmpc_controller_attach_policy (NULL detaches): while attached, bpmpc_controller_tick, bpmpc_controller_tick_estimated,
+ *     bpmpc_controller_set_joint_gains and the observation and WBC part of bpmpc_controller_restart run on the BUFFER's stream and the tick
+ *     evaluates the front slot; the tick kernels are the same.  Detached, every call does exactly what it does without a buffer, on the solver's
+ *     stream.  The call drains both streams once; afterwards events order them: bpmpc_solver_setup_commands(x0 = NULL) waits for the last tick
+ *     (whose observations it starts from) and the next tick waits for that read, a restart's solver part waits for its observation,
+ *     bpmpc_plant_step_controlled waits for the tick on the buffer's stream.  BPMPC_ERR_INVALID_ARGUMENT when the buffer was created for another
+ *     solver or device.  A buffered tick is refused with BPMPC_ERR_INVALID_ARGUMENT until one publish with mask == NULL and skip_failed == 0 has
+ *     been adopted (the reference's "waiting for the initial policy"), with a batch other than the published one, and after a
+ *     bpmpc_controller_restart until the next adoption.  That adoption's publish must take the restarted robots: the buffer does not check it, it
+ *     is the caller's job (a restarted robot that a masked or skip_failed publish leaves out keeps ticking on the policy of its previous episode).
+ *   the loop, M ticks per MPC period, the policy D ticks old when it takes effect:
+ *       every tick:        bpmpc_plant_step_controlled -> bpmpc_estimator_update_from_plant -> bpmpc_controller_tick_estimated
+ *       tick k, k % M == 0: bpmpc_solver_setup_commands(x0 = NULL); bpmpc_solver_run; bpmpc_policy_publish(skip_failed = 1)
+ *       tick k, k % M == D: bpmpc_policy_update(wait = 1)
+ *     Four streams carry its work: the solver's, the buffer's, the estimator's and the plant's; the handles create six (the solver's producer
+ *     stream and the WBC's own are idle in it), against the four hardware queues a process opens by default.
+ * ------------------------------------------------------------------------------------------------------------- */
+typedef struct bpmpc_policy bpmpc_policy;
+int bpmpc_policy_create(bpmpc_solver* solver, int max_batch, bpmpc_policy** out);
+void bpmpc_policy_destroy(bpmpc_policy* policy);
+int bpmpc_policy_publish(bpmpc_policy* policy, int batch, const int* mask, int inputs_on_device, int skip_failed);
+int bpmpc_policy_update(bpmpc_policy* policy, int wait, int* adopted);
+int bpmpc_policy_info(bpmpc_policy* policy, int batch, int* generation, double* t0, int* status);
+int bpmpc_controller_attach_policy(bpmpc_controller* controller, bpmpc_policy* policy);
+
 #ifdef __cplusplus
 }
 #endif
