@@ -185,13 +185,9 @@ int bpmpc_policy_publish(bpmpc_policy* p, int batch, const int* mask, int inputs
     a.front = p->slot[p->front]; a.back = p->slot[1 - p->front];
     a.pending = p->d_pending; a.status_pend = p->d_status_pend; a.t0_pend = p->d_t0_pend;
     if (p->ev_adopt) HIP_CHECK(hipStreamWaitEvent(st, p->ev_adopt, 0));      // ticks enqueued before the last adoption may still read the back slot
-    if (s->timed("policy_publish")) {             // bpmpc_solver_kernel_time("policy_publish"): the kernel's own duration (tools/policy_buffer_probe.py)
-      hipEvent_t e0, e1;
-      HIP_CHECK(hipEventCreateWithFlags(&e0, bpmpc_solver::kTimingEventFlags));
-      if (hipEventCreateWithFlags(&e1, bpmpc_solver::kTimingEventFlags) != hipSuccess) { (void)hipEventDestroy(e0); throw DeviceError("hipEventCreate failed"); }
-      try { launch_policy_publish(st, s->num_cus, a, e0, e1); } catch (...) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); throw; }
-      s->timers["policy_publish"].pending.emplace_back(e0, e1);
-    } else launch_policy_publish(st, s->num_cus, a);
+    if (KernelTimers::timed(s->settings.profile, "policy_publish"))      // bpmpc_solver_kernel_time("policy_publish"): the kernel's own duration (tools/policy_buffer_probe.py)
+      s->timers.attached("policy_publish", [&](hipEvent_t e0, hipEvent_t e1) { launch_policy_publish(st, s->num_cus, a, e0, e1); });
+    else launch_policy_publish(st, s->num_cus, a);
     record(&p->ev_publish, st);
     p->batch = batch; p->outstanding = true; p->full_outstanding = p->full_outstanding || full;
     if (mask && !inputs_on_device) HIP_CHECK(hipStreamSynchronize(st));      // the caller's host mask

@@ -14,18 +14,10 @@
 #include "../../include/bpmpc.h"
 #include "device_handle.h"
 #include "kernel_launchers.h"
+#include "kernel_timers.h"
 #include "launch.h"
+#include "sweep_plan.h"
 #include "kernels/reference_device.h"
-
-namespace bpmpc {
-
-struct KernelTimer {
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  double total_ms = 0.0;
-  int launches = 0;
-};
-
-}  // namespace bpmpc
 
 using namespace bpmpc;
 
@@ -72,31 +64,15 @@ struct bpmpc_solver {
   int nx = 0, nu = 0;
   int batch = 0, n_grids = 0, n_nodes_max = 0;
   int num_cus = 256;                                        // compute units of the device
+  Switches sw;                                              // the environment switches, read when the solver is created (sweep_plan.h)
   // change of variables reading the packed joint rows of the structured elimination: needs an input weight without force / joint-velocity
   // cross terms (checked when the solver is created; BipedalRobotInterface.cpp:239-271 builds it so).  BPMPC_DENSE_PROJECT=1 switches it off.
   bool structured_project = false;
-  // Riccati sweep by regime: eight waves with fixed roles while every problem has a CU to itself; four-wave workgroups up to two problems per CU;
-  // beyond that one wavefront per problem (riccati_wave.h at one wave per SIMD up to four problems per CU, riccati_wave2.h at two beyond).
-  // BPMPC_RICCATI_WAVE: 0 never a wave per problem; 1 (default) as described; 2 riccati_wave.h at every batch size, 4 riccati_wave2.h at every
-  // batch size (tests); 3 riccati_wave2.h whenever a wave per problem is used
-  int riccati_wave = 1;
-  bool lin_compact = true;                                  // BPMPC_LIN_COMPACT=0: the lineariser keeps the event nodes in line (A/B, tests)
-  bool force_tables = false;                                // BPMPC_LIN_TABLES=1: the table walks also on a robot of two serial legs (tests)
-  bool wt_joint_rows = false;                               // BPMPC_WT_JOINT_ROWS=1: the change of variables always writes the joint rows of Wt (A/B of the byte cut below)
-  // which sweep runs the current batch (see launch_riccati)
-  bool sweep_wave_regime() const { return riccati_wave == 2 || riccati_wave == 4 || ((riccati_wave == 1 || riccati_wave == 3) && batch > 2 * num_cus); }
-  bool sweep_two_per_simd() const { return sweep_wave_regime() && (riccati_wave >= 3 || (riccati_wave == 1 && batch > 4 * num_cus)); }
+  bool serial_legs() const { return dm.serial_legs && !sw.lin_tables; }      // the per-node kernels run their tree walks by DPP
   // the wave-per-problem sweeps (riccati_wave.h, riccati_wave2.h) and the loaders of the eight-wave sweep (riccati_mfma8.h, PackedStageLoader JR) complete the joint rows of Wt = [At | bt | Bt] from Vt ([I | b | 0] + dt Vt): the change of variables then
-  // neither computes nor writes them (3.8 KB per node less each way at the batch sizes where both kernels stream)
-  bool sweep_completes_joint_rows() const { return !wt_joint_rows && structured_project && !settings.reference_kernels; }     // every fast sweep does
-  // The eight-wave sweep holds a CU per problem; a larger batch runs it in ROUNDS (the dispatcher starts a workgroup as a CU becomes free, so the roll-outs
-  // behind the sweeps no longer stream at the same time).  Since its roll-out goes through the ring (round 6) two and three rounds of it beat what those batch
-  // sizes ran before on the 22-state robots - batch 512: 0.5447 against 0.5837 ms on the four-wave workgroups, 768: 0.807 against 0.878 on a wave per problem;
-  // 1024 in four rounds: 1.075 against 0.917, so from there on the wave sweeps - and lose on nx = 24 (G1 / 512: 0.8545 against 0.7682 on the four-wave
-  // workgroups), whose eight-wave stage is 55 % longer (`experiments/LOG.md`).  BPMPC_R8_ROUNDS overrides (1: the regimes of rounds 3 to 5; tests).
-  int r8_rounds = 0;                                        // 0: by the robot, as measured
-  int eight_wave_rounds() const { return r8_rounds > 0 ? r8_rounds : (rm.nj == 10 ? 3 : 1); }
-  bool sweep_eight_waves() const { return riccati_wave != 2 && riccati_wave != 4 && batch <= eight_wave_rounds() * num_cus; }
+  // neither computes nor writes them (3.8 KB per node less each way at the batch sizes where both kernels stream).  The `joint_rows` argument of
+  // the launchers: false where every fast sweep does so
+  bool joint_rows() const { return sw.wt_joint_rows || !structured_project || settings.reference_kernels; }
   bool has_solution = false;                               // a solve has completed on the current setup
   bool has_rollout = false;                                // roll_x holds the end states of a rollout
   bool rollout_unchecked = false;                          // ... whose status flags have not been read back yet
@@ -125,11 +101,11 @@ struct bpmpc_solver {
   std::vector<hipEvent_t> ev_chunk;
   Buffers buf{};
   std::vector<void*> allocations;
-  std::map<std::string, std::pair<void*, size_t>> named;   // name -> (device ptr, element count)  (doubles unless in int_named)
-  std::map<std::string, bool> is_int;
+  struct NamedBuffer { void* ptr; size_t count; bool integer; };      // doubles unless integer
+  std::map<std::string, NamedBuffer> named;                // what bpmpc_solver_read hands out
   std::vector<double> node_times;                          // host copy: [n_grids][N+1]
   std::vector<int> grid_nodes, grid_of_problem;
-  std::map<std::string, KernelTimer> timers;
+  KernelTimers timers;
   int* h_remaining = nullptr;                              // pinned
   LineSearchSettings ls{};
 
@@ -139,12 +115,19 @@ struct bpmpc_solver {
     HIP_CHECK(hipMalloc(&p, count * sizeof(T)));
     HIP_CHECK(hipMemsetAsync(p, 0, count * sizeof(T), stream));
     allocations.push_back(p);
-    if (name) { named[name] = {p, count}; is_int[name] = integer; }
+    if (name) named[name] = {p, count, integer};
     return static_cast<T*>(p);
   }
 
-  Launch launch_params() const {
-    Launch L;
+  // Everything a launch reads of the handle, built ONCE per setup (build_plan, the first thing finish_setup does); the stages launch from it.
+  // pipelined_backward edits a copy (k0, klen, lin_ev_n).  `buf` stays the owner of the pointers: plan.buf is the copy made at that point.
+  // Where the inputs change: buf in preserve_previous only (the swap of the solution buffers); batch, n_grids, n_nodes_max, cold, grid_kind and
+  // grid_nodes in the two setup bodies only (setup of solver.hip; accept_reference_grids for setup_commands and setup_gaits) - all of them before
+  // finish_setup.  Everything else is fixed when the solver is created: d_model, dm, rm, sw, ls, and of settings max_nodes, reg_prim, solver and
+  // feedback_policy (set_materialize and set_profile write fields no launch reads from here).
+  Launch plan{};
+  void build_plan() {
+    Launch& L = plan;
     L.model = d_model;
     L.buf = buf;
     L.batch = batch;
@@ -154,13 +137,13 @@ struct bpmpc_solver {
     // workgroups onto batch x klen node slots and every slot beyond a problem's grid is a lane group that idles
     L.klen = n_nodes_max > 0 ? n_nodes_max : settings.max_nodes;
     L.cold = cold ? 1 : 0;
-    L.serial_legs = (dm.serial_legs && !force_tables) ? 1 : 0;
+    L.serial_legs = serial_legs() ? 1 : 0;
     L.feedback = feedback();
     L.ls = ls;
     L.reg_prim = settings.reg_prim;
     L.lin_ev_n = -1; L.lin_inter = 0;
     for (int i = 0; i < kLinMaxEvents; ++i) L.lin_ev[i] = 0;
-    if (n_grids == 1 && lin_compact && !grid_kind.empty() && (int)grid_nodes.size() == 1) {
+    if (n_grids == 1 && sw.lin_compact && !grid_kind.empty() && (int)grid_nodes.size() == 1) {
       const int n = grid_nodes[0];
       int ne = 0;
       for (int k = 0; k < n; ++k)
@@ -169,56 +152,12 @@ struct bpmpc_solver {
     }
     L.ilqr = is_ddp() ? 1 : 0;                                  // the DDP solver: every kernel of the backward pass works on the Euler-discretised model
     L.ilqr_shift = is_ddp() ? rm.ddp.ls_hessian_correction_multiple : 0.0;
-    return L;
-  }
-
-  // Events that only measure time: no system-scope fence when they complete (hipEventDisableSystemFence: "avoiding the cost of cache writeback and
-  // invalidation, and the performance impact of those actions on the execution of following work") - with the default flags the step that carries
-  // the roofline kernel's events ran 3 % slower than the steps without them (the kernel behind the lineariser found its inputs flushed from L2)
-  static constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
-  // settings.profile: 0 off, 1 every kernel class, 2 the linearisation kernel only (the roofline measurement of bench.py: every
-  // event pair costs one to two microseconds of stream time, ten pairs per solve are 2 % of a step)
-  bool timed(const char* cls) const { return settings.profile == 1 || (settings.profile == 2 && std::strcmp(cls, "linearize") == 0); }
-  void time_begin(const char* cls, hipEvent_t* a, hipEvent_t* b, hipStream_t on = nullptr) {
-    if (!timed(cls)) return;
-    HIP_CHECK(hipEventCreateWithFlags(a, kTimingEventFlags));
-    if (hipEventCreateWithFlags(b, kTimingEventFlags) != hipSuccess) { (void)hipEventDestroy(*a); throw DeviceError("hipEventCreate failed"); }
-    if (hipEventRecord(*a, on ? on : stream) != hipSuccess) { (void)hipEventDestroy(*a); (void)hipEventDestroy(*b); throw DeviceError("hipEventRecord failed"); }
-  }
-  void time_end(const char* cls, hipEvent_t a, hipEvent_t b, hipStream_t on = nullptr) {
-    if (!timed(cls)) return;
-    HIP_CHECK(hipEventRecord(b, on ? on : stream));
-    KernelTimer& t = timers[cls];
-    t.pending.emplace_back(a, b);
-    if (t.pending.size() > 4096) collect_timers();   // a profiled loop that never asks for the times must not grow without bound
   }
   // The lineariser's events are attached to its dispatch (kl::linearize_fast): their elapsed time is the kernel's duration, without the barrier
   // packets and the dispatch latency a pair of hipEventRecord calls brackets as well
   void launch_linearize_fast(hipStream_t on, const Launch& L, int nodes) {
-    if (!timed("linearize")) { kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L); return; }
-    hipEvent_t a, b;
-    HIP_CHECK(hipEventCreateWithFlags(&a, kTimingEventFlags));
-    if (hipEventCreateWithFlags(&b, kTimingEventFlags) != hipSuccess) { (void)hipEventDestroy(a); throw DeviceError("hipEventCreate failed"); }
-    kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L, a, b);
-    KernelTimer& t = timers["linearize"];
-    t.pending.emplace_back(a, b);
-    if (t.pending.size() > 4096) collect_timers();
-  }
-  void collect_timers() {
-    for (auto& kv : timers) {
-      hipError_t first_error = hipSuccess;                 // the events are destroyed whatever happens; the first failure is reported afterwards
-      for (auto& pr : kv.second.pending) {
-        float ms = 0.f;
-        hipError_t e = hipEventSynchronize(pr.second);
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, pr.first, pr.second);
-        if (e == hipSuccess) { kv.second.total_ms += ms; kv.second.launches += 1; }
-        else if (first_error == hipSuccess) first_error = e;
-        (void)hipEventDestroy(pr.first);
-        (void)hipEventDestroy(pr.second);
-      }
-      kv.second.pending.clear();
-      if (first_error != hipSuccess) throw DeviceError(std::string("kernel timers: ") + hipGetErrorString(first_error));
-    }
+    if (!KernelTimers::timed(settings.profile, "linearize")) { kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L); return; }
+    timers.attached("linearize", [&](hipEvent_t a, hipEvent_t b) { kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L, a, b); });
   }
 
   void stage_prepare();

@@ -30,9 +30,9 @@
 #define TIMED_ON(on, cls, ...)                                                      \
   do {                                                                              \
     hipEvent_t ev_a_, ev_b_;                                                        \
-    time_begin(cls, &ev_a_, &ev_b_, on);                                            \
+    timers.begin(settings.profile, on, cls, &ev_a_, &ev_b_);                        \
     __VA_ARGS__;                                                                    \
-    time_end(cls, ev_a_, ev_b_, on);                                                \
+    timers.end(settings.profile, on, cls, ev_a_, ev_b_);                            \
     HIP_CHECK(hipGetLastError());                                                   \
   } while (0)
 #define TIMED(cls, ...) TIMED_ON(stream, cls, __VA_ARGS__)
@@ -53,53 +53,55 @@ RolloutArgs rollout_args(const bpmpc_solver* s) {
   a.max_steps = (int)(s->rm.rollout.max_steps_per_second * std::max(1.0, longest));
   return a;
 }
+// ... of the two roll-outs of the DDP solver: every problem from its measured state over its own horizon [t_0, t_N], recorded on its own time points
+RolloutArgs ddp_rollout_args(const bpmpc_solver* s) {
+  const DdpBuffers& d = s->ddp;
+  RolloutArgs a = rollout_args(s);
+  a.x_start = s->buf.p_x0; a.t_start = nullptr; a.duration = -1.0;
+  a.x_end = d.end_x; a.u_end = d.end_u; a.steps = d.roll_steps; a.status = d.roll_status;
+  a.rec_t = d.rec_t; a.rec_x = d.rec_x; a.rec_u = d.rec_u; a.rec_n = d.rec_n; a.rec_cap = d.cap;
+  return a;
+}
 
 }  // namespace
 
-void bpmpc_solver::stage_prepare() {
-  const Launch L = launch_params();
-  TIMED("prepare", kl::prepare(nj(), batch * settings.max_nodes, stream, L));
-}
+void bpmpc_solver::stage_prepare() { TIMED("prepare", kl::prepare(nj(), batch * settings.max_nodes, stream, plan)); }
 void bpmpc_solver::stage_linearize() {
-  const Launch L = launch_params();
-  if (settings.reference_kernels) TIMED("linearize", kl::linearize_reference(nj(), batch * settings.max_nodes, stream, L));
-  else { launch_linearize_fast(stream, L, batch * L.klen); HIP_CHECK(hipGetLastError()); }
+  if (settings.reference_kernels) TIMED("linearize", kl::linearize_reference(nj(), batch * settings.max_nodes, stream, plan));
+  else { launch_linearize_fast(stream, plan, batch * plan.klen); HIP_CHECK(hipGetLastError()); }
 }
 // constraint elimination + change of variables of `nodes` node slots (the fast kernels)
 void bpmpc_solver::launch_project(hipStream_t on, const Launch& L, int nodes) {
   // packed joint rows of [Px | Pe | Pu] when the input weight allows the change of variables to generate the force rows; Px, Pu, Pe for the
   // general one (which packs the joint rows for the sweeps' loaders itself)
   TIMED_ON(on, "project_lu", kl::project_lu_s(nj(), max_vel_rows, structured_project, nodes, on, L));
-  TIMED_ON(on, "project", kl::project_fast(nj(), structured_project, !sweep_completes_joint_rows(), nodes, on, L));
+  TIMED_ON(on, "project", kl::project_fast(nj(), structured_project, joint_rows(), nodes, on, L));
 }
 void bpmpc_solver::stage_project() {
-  const Launch L = launch_params();
-  if (settings.reference_kernels) TIMED("project", kl::project_reference(nj(), batch * settings.max_nodes, stream, L));
-  else launch_project(stream, L, batch * L.klen);
+  if (settings.reference_kernels) TIMED("project", kl::project_reference(nj(), batch * settings.max_nodes, stream, plan));
+  else launch_project(stream, plan, batch * plan.klen);
 }
+// the sweep of the batch's regime (sweep_plan.h); the roll-out of the wave sweeps is a launch of its own behind the last chunk of the horizon
 void bpmpc_solver::launch_riccati(const Launch& L) {
-  if (sweep_eight_waves()) { TIMED("riccati", kl::riccati_fast8(nj(), !sweep_completes_joint_rows(), batch, stream, L)); return; }
-  // up to two problems per CU the four-wave workgroups finish in one round (0.61 against 0.91 ms at batch 512); beyond that a wave per
-  // problem, four per CU, wins (G1 / 1024: 1.30 against 1.54 ms; 4096: 4.07 against 4.53 ms)
-  if (!sweep_wave_regime()) {
-    TIMED("riccati", kl::riccati_fast(nj(), !sweep_completes_joint_rows(), batch, stream, L));
-    return;
+  const Sweep sweep = choose_sweep(nj(), batch, num_cus, sw);
+  switch (sweep) {
+    case Sweep::EightWave: TIMED("riccati", kl::riccati_fast8(nj(), joint_rows(), batch, stream, L)); break;
+    case Sweep::FourWave: TIMED("riccati", kl::riccati_fast(nj(), joint_rows(), batch, stream, L)); break;
+    case Sweep::WavePerSimd:
+    case Sweep::TwoWavesPerSimd:
+      TIMED("riccati", { kl::riccati_wave(nj(), sweep == Sweep::TwoWavesPerSimd, joint_rows(), batch, stream, L); if (L.k0 == 0) kl::riccati_rollout(nj(), batch, stream, L); });
+      break;
   }
-  // two waves per SIMD (riccati_wave2.h) need eight problems per CU to fill the chip - the dispatcher packs a CU before it opens the next
-  // one, 1024 problems would occupy half of the CUs - and win from the first batch that takes riccati_wave.h a second round: beyond four
-  // problems per CU (batch 1024: 0.98 against 1.27 ms; 4096: 3.75 against 3.22 ms)
-  TIMED("riccati", { kl::riccati_wave(nj(), sweep_two_per_simd(), !sweep_completes_joint_rows(), batch, stream, L); if (L.k0 == 0) kl::riccati_rollout(nj(), batch, stream, L); });
 }
 void bpmpc_solver::stage_riccati() {
-  const Launch L = launch_params();
-  if (settings.reference_kernels) TIMED("riccati", kl::riccati_reference(nj(), batch, stream, L));
-  else launch_riccati(L);
+  if (settings.reference_kernels) TIMED("riccati", kl::riccati_reference(nj(), batch, stream, plan));
+  else launch_riccati(plan);
 }
 void bpmpc_solver::stage_linesearch() {
-  const Launch L = launch_params();
+  const Launch& L = plan;
   if (settings.reference_kernels) HIP_CHECK(hipMemsetAsync(buf.remaining, 0, sizeof(int), stream));   // only the host loop below reads the counter
   hipEvent_t ev_a, ev_b;
-  time_begin("linesearch", &ev_a, &ev_b);
+  timers.begin(settings.profile, stream, "linesearch", &ev_a, &ev_b);
   if (settings.reference_kernels) kl::ls_begin(nj(), batch, stream, L);   // fast path: done inside the Riccati kernel
   // alpha = 1, 1/2, ... >= alpha_min  ([OCS2-upstream] SqpSolver::takeStep do-while)
   int max_trials = 0;
@@ -109,8 +111,7 @@ void bpmpc_solver::stage_linesearch() {
     // of 256, six of 4096) has its ~107 trial nodes evaluated by seven workgroups at once instead of four passes of ONE workgroup in k_ls_tail
     // (95 -> ~35 us for the whole batch); workgroups of finished problems leave after reading two flags.  Later rounds per problem on the
     // device (k_ls_tail).  No read-back inside a solve.  BPMPC_LS_WIDE_ROUNDS (default 2) = rounds that run as launches over all nodes.
-    const int nodes = batch * L.klen;
-    static const int wide_rounds = [] { const char* e = std::getenv("BPMPC_LS_WIDE_ROUNDS"); const int v = e ? std::atoi(e) : 2; return v < 1 ? 1 : v; }();
+    const int nodes = batch * L.klen, wide_rounds = sw.ls_wide_rounds;
     int round = 0;
     bool pending = false;                                  // the last of these rounds is judged by k_ls_tail (the workgroups of the few problems still open)
     for (; round < wide_rounds && round < max_trials; ++round) {
@@ -120,7 +121,7 @@ void bpmpc_solver::stage_linesearch() {
     }
     kl::ls_tail(nj(), batch, stream, L, round, max_trials, pending);
     HIP_CHECK(hipGetLastError());
-    time_end("linesearch", ev_a, ev_b);
+    timers.end(settings.profile, stream, "linesearch", ev_a, ev_b);
     return;
   }
   for (int t = 0; t < max_trials; ++t) {
@@ -132,7 +133,7 @@ void bpmpc_solver::stage_linesearch() {
     HIP_CHECK(hipStreamSynchronize(stream));
     if (*h_remaining <= 0) break;
   }
-  time_end("linesearch", ev_a, ev_b);
+  timers.end(settings.profile, stream, "linesearch", ev_a, ev_b);
 }
 // Linearisation, projection and Riccati sweep of one SQP iteration with the horizon cut into chunks: the producers
 // (linearise, LU, change of variables) of chunk c+1 run on their own stream while the latency-bound Riccati sweep of
@@ -146,7 +147,7 @@ void bpmpc_solver::pipelined_backward() {
     // chunk c covers [lo, hi), latest stages first
     const int hi = n - (int)((long long)n * c / chunks), lo = n - (int)((long long)n * (c + 1) / chunks);
     if (hi <= lo) continue;
-    Launch L = launch_params();
+    Launch L = plan;
     L.k0 = lo;
     L.klen = hi - lo;
     L.lin_ev_n = -1;                 // a chunk of the horizon: node slot = launch index
@@ -186,40 +187,33 @@ void bpmpc_solver::run_iterations() {
 
 // One ILQR iteration of the DDP solver (k_ddp.hip; oracle/ddp_py.py is its restatement, step for step).  Everything is enqueued on the solver's
 // stream, nothing is read back or waited for.  Round 6: the backward pass runs on the kernels of the SQP path - the fast lineariser in its ILQR
-// form, structured elimination, change of variables on the matrix cores, the Riccati sweep of the batch's regime (launch_params() carries the
+// form, structured elimination, change of variables on the matrix cores, the Riccati sweep of the batch's regime (the plan carries the
 // ILQR switch) - and the line search rolls ALL step lengths out in one launch (batch x nv virtual problems), as upstream evaluates them concurrently.
 void bpmpc_solver::run_ddp() {
   stage_linearize();            // Euler-discretised LQ model, DIAGONAL_SHIFT on R
   stage_project();              // constraint elimination
   stage_riccati();              // Riccati recursion from S_N = 0; its linear roll-out gives du = lff + K dx
-  const Launch L = launch_params();
+  const Launch& L = plan;
   kl::ddp_policy(nj(), batch, stream, L, ddp);
   HIP_CHECK(hipGetLastError());
   // line search: the baseline (step length 0: the new gains, no feedforward increment) and maxStepLength, x contractionRate, .. >= minStepLength
   constexpr double kArmijoCoefficient = 1e-4;                                 // [OCS2-upstream] line_search::Settings default (not in task.info)
-  RolloutArgs a = rollout_args(this);
+  RolloutArgs a = ddp_rollout_args(this);
   a.batch = batch * ddp.nv; a.n_problems = batch; a.lff = ddp.lff;
   for (int v = 0; v < ddp.nv; ++v) a.alpha[v] = ddp.alpha_v[v];
-  a.x_start = buf.p_x0;
-  a.t_start = nullptr; a.duration = -1.0;                                      // every problem over its own horizon [t_0, t_N]
   a.feedback = 1;                                                            // the search rolls out the FEEDBACK policy whatever controller is handed out
-  a.x_end = ddp.end_x; a.u_end = ddp.end_u; a.steps = ddp.roll_steps; a.status = ddp.roll_status;
-  a.rec_t = ddp.rec_t; a.rec_x = ddp.rec_x; a.rec_u = ddp.rec_u; a.rec_n = ddp.rec_n; a.rec_cap = ddp.cap;
-  TIMED("ddp_rollout", kl::rollout(rm.nj, dm.serial_legs && !force_tables, batch * ddp.nv, stream, d_model, a));
+  TIMED("ddp_rollout", kl::rollout(rm.nj, serial_legs(), batch * ddp.nv, stream, d_model, a));
   TIMED("ddp_search", { kl::ddp_cost(nj(), batch, !settings.reference_kernels, stream, L, ddp); kl::ddp_select(nj(), batch, stream, L, ddp, kArmijoCoefficient); kl::ddp_finish(nj(), batch, stream, L, ddp); });
 }
 
 // GaussNewtonDDP::rolloutInitialTrajectory of a warm tick (k_ddp.hip k_ddp_nominal): the shifted previous FeedforwardController integrated from the
 // measured state over the new horizon (TimeTriggeredRollout, ODE45), its states interpolated onto the shooting grid as the nominal trajectory.
 void bpmpc_solver::ddp_nominal_rollout() {
-  RolloutArgs a = rollout_args(this);
-  a.batch = batch; a.x_start = buf.p_x0;
-  a.t_start = nullptr; a.duration = -1.0;
+  RolloutArgs a = ddp_rollout_args(this);
+  a.batch = batch;
   a.feedback = 0;                                      // ddp.useFeedbackPolicy false: the previous controller is its input trajectory
-  a.x_end = ddp.end_x; a.u_end = ddp.end_u; a.steps = ddp.roll_steps; a.status = ddp.roll_status;
-  a.rec_t = ddp.rec_t; a.rec_x = ddp.rec_x; a.rec_u = ddp.rec_u; a.rec_n = ddp.rec_n; a.rec_cap = ddp.cap;
-  kl::rollout(rm.nj, dm.serial_legs && !force_tables, batch, stream, d_model, a);
-  kl::ddp_nominal(nj(), batch, stream, launch_params(), ddp);
+  kl::rollout(rm.nj, serial_legs(), batch, stream, d_model, a);
+  kl::ddp_nominal(nj(), batch, stream, plan, ddp);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -232,6 +226,23 @@ int ddp_step_lengths(const DdpConfig& d, int limit) {
   int n = 0;
   for (double al = d.ls_max_step_length; al >= d.ls_min_step_length && al > 0.0 && n <= limit; al *= kDdpContractionRate) ++n;
   return n;
+}
+
+// What the DDP slice implements is what the reference configures (task.info:115-156); every other value of the ddp block is refused, not ignored.
+// BPMPC_OK, or the status of the first refusal with its message set.
+int check_ddp_settings(const DdpConfig& d, const bpmpc_settings& st) {
+  if (d.algorithm != 1) { set_last_error("DDP: only ddp.algorithm ILQR is implemented (SLQ integrates continuous-time Riccati equations)"); return BPMPC_ERR_UNSUPPORTED; }
+  if (d.strategy != 0) { set_last_error("DDP: only ddp.strategy LINE_SEARCH is implemented"); return BPMPC_ERR_UNSUPPORTED; }
+  if (d.ls_hessian_correction_strategy != 0) { set_last_error("DDP: only lineSearch.hessianCorrectionStrategy DIAGONAL_SHIFT is implemented"); return BPMPC_ERR_UNSUPPORTED; }
+  if (d.max_num_iterations != 1 || st.sqp_iterations > 1) { set_last_error("DDP: one ILQR iteration per run (ddp.maxNumIterations 1): later iterations live on the roll-out's adaptive time grid"); return BPMPC_ERR_UNSUPPORTED; }
+  if (!(d.ls_min_step_length > 0.0) || !(d.ls_max_step_length >= d.ls_min_step_length)) { set_last_error("DDP: lineSearch.minStepLength / maxStepLength"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  if (ddp_step_lengths(d, kMaxDdpSteps - 1) > kMaxDdpSteps - 1) {      // (the engine would try fewer step lengths than the configuration asks for and report status 1)
+    set_last_error("DDP: lineSearch.minStepLength / maxStepLength ask for more than " + std::to_string(kMaxDdpSteps - 1) + " step lengths (contraction rate 0.5), the line search table holds no more");
+    return BPMPC_ERR_UNSUPPORTED;
+  }
+  if (d.use_feedback_policy && st.feedback_policy != 2) { set_last_error("DDP: ddp.useFeedbackPolicy true is not implemented (the gains live on the nominal grid, the solution on the roll-out's time points)"); return BPMPC_ERR_UNSUPPORTED; }
+  if (st.feedback_policy == 1) { set_last_error("DDP: feedback_policy 1 (LinearController) is not implemented for the DDP solution"); return BPMPC_ERR_UNSUPPORTED; }
+  return BPMPC_OK;
 }
 
 void allocate(bpmpc_solver* s) {
@@ -359,8 +370,8 @@ void preserve_previous(bpmpc_solver* s, int batch, bool warm_arrays) {
   Buffers& bp = s->buf;
   if (!bp.K) throw std::invalid_argument("setup_from_previous needs the feedback gains (return_gains with reference kernels)");
   std::swap(bp.x, bp.x_prev); std::swap(bp.u, bp.u_prev); std::swap(bp.K, bp.K_prev);
-  s->named["x"].first = bp.x; s->named["u"].first = bp.u; s->named["K"].first = bp.K;
-  s->named["x_prev"].first = bp.x_prev; s->named["u_prev"].first = bp.u_prev; s->named["K_prev"].first = bp.K_prev;
+  s->named["x"].ptr = bp.x; s->named["u"].ptr = bp.u; s->named["K"].ptr = bp.K;
+  s->named["x_prev"].ptr = bp.x_prev; s->named["u_prev"].ptr = bp.u_prev; s->named["K_prev"].ptr = bp.K_prev;
   {   // the grid tables of the previous solve, one launch instead of four copies
     CopyTable t{};
     auto keep = [&](void* dst, const void* src, size_t bytes) { t.dst[t.n] = dst; t.src[t.n] = src; t.words[t.n] = (unsigned)(bytes / 4); ++t.n; };
@@ -378,13 +389,14 @@ void preserve_previous(bpmpc_solver* s, int batch, bool warm_arrays) {
 void finish_setup(bpmpc_solver* s, int batch, const double* warm_x, const double* warm_u, bool from_previous) {
   const int N = s->settings.max_nodes, NX = s->nx, NU = s->nu;
   Buffers& bf = s->buf;
+  s->build_plan();                                  // the buffers have traded places (preserve_previous) and the grids are the new setup's: nothing changes them before the next setup
   if (!s->cold) {
     HIP_CHECK(hipMemcpyAsync(bf.x, warm_x, (size_t)batch * (N + 1) * NX * sizeof(double), hipMemcpyHostToDevice, s->stream));
     HIP_CHECK(hipMemcpyAsync(bf.u, warm_u, (size_t)batch * N * NU * sizeof(double), hipMemcpyHostToDevice, s->stream));
   }
   s->stage_prepare();
   if (from_previous) {
-    const Launch L = s->launch_params();
+    const Launch& L = s->plan;
     kl::warm_shift(s->rm.nj, batch * L.N, s->stream, L, s->restart_pending ? s->restart_flag : nullptr);   // restarted problems keep the cold guess
     HIP_CHECK(hipGetLastError());
     if (s->is_ddp()) s->ddp_nominal_rollout();      // the nominal state trajectory of a DDP tick is the roll-out of the previous controller from the measured state
@@ -782,14 +794,13 @@ void rollout(bpmpc_solver* s, const double* t_start, const double* x_start, doub
   for (int b = 0; b < B; ++b) ts[b] = t_start ? t_start[b] : s->node_times[(size_t)s->grid_of_problem[b] * (N + 1)];
   upload(s, bf.roll_t, ts);
   if (x_start) HIP_CHECK(hipMemcpyAsync(bf.roll_x0, x_start, (size_t)B * NX * sizeof(double), hipMemcpyHostToDevice, s->stream));
-  RolloutArgs a{};
-  a.batch = B; a.N = N; a.p_grid = bf.p_grid; a.g_nodes = bf.g_nodes; a.g_kind = bf.g_kind; a.g_time = bf.g_time;
-  a.x = bf.x; a.u = bf.u; a.K = bf.K; a.t_start = bf.roll_t; a.x_start = x_start ? bf.roll_x0 : bf.p_x0;
-  a.duration = duration; a.abs_tol = s->rm.rollout.abs_tol; a.rel_tol = s->rm.rollout.rel_tol; a.time_step = s->rm.rollout.time_step;
-  a.max_steps = (int)(s->rm.rollout.max_steps_per_second * std::max(1.0, duration));
+  RolloutArgs a = rollout_args(s);
+  a.batch = B; a.t_start = bf.roll_t; a.x_start = x_start ? bf.roll_x0 : bf.p_x0;
+  a.duration = duration;
+  a.max_steps = (int)(s->rm.rollout.max_steps_per_second * std::max(1.0, duration));      // from the duration, not from the longest grid
   a.feedback = s->feedback();
   a.x_end = bf.roll_x; a.u_end = bf.roll_u; a.steps = bf.roll_steps; a.status = bf.roll_status;
-  kl::rollout(s->rm.nj, s->dm.serial_legs && !s->force_tables, B, s->stream, s->d_model, a);
+  kl::rollout(s->rm.nj, s->serial_legs(), B, s->stream, s->d_model, a);
   HIP_CHECK(hipGetLastError());
   s->has_rollout = true;
   s->loop_from_tick = false;
@@ -846,7 +857,7 @@ void fetch(bpmpc_solver* s, double* out_t, double* out_x, double* out_u, double*
       st.step_size = r[9]; st.armijo_descent = r[10]; st.dx_norm = r[11]; st.du_norm = r[12];
     }
   }
-  s->collect_timers();   // the stream is idle here; a closed loop of advance() calls never reaches bpmpc_solver_sync
+  s->timers.collect();   // the stream is idle here; a closed loop of advance() calls never reaches bpmpc_solver_sync
 }
 
 }  // namespace
@@ -875,19 +886,7 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
     if (settings->solver != BPMPC_SOLVER_SQP && settings->solver != BPMPC_SOLVER_DDP) { set_last_error("bpmpc_solver_create: unknown solver"); return BPMPC_ERR_INVALID_ARGUMENT; }
     if (settings->feedback_policy < 0 || settings->feedback_policy > 2) { set_last_error("bpmpc_solver_create: feedback_policy must be 0, 1 or 2"); return BPMPC_ERR_INVALID_ARGUMENT; }
     if (settings->solver == BPMPC_SOLVER_DDP) {
-      // what the slice implements is what the reference configures (task.info:115-156); every other value of the ddp block is refused, not ignored
-      const DdpConfig& d = s->rm.ddp;
-      if (d.algorithm != 1) { set_last_error("DDP: only ddp.algorithm ILQR is implemented (SLQ integrates continuous-time Riccati equations)"); return BPMPC_ERR_UNSUPPORTED; }
-      if (d.strategy != 0) { set_last_error("DDP: only ddp.strategy LINE_SEARCH is implemented"); return BPMPC_ERR_UNSUPPORTED; }
-      if (d.ls_hessian_correction_strategy != 0) { set_last_error("DDP: only lineSearch.hessianCorrectionStrategy DIAGONAL_SHIFT is implemented"); return BPMPC_ERR_UNSUPPORTED; }
-      if (d.max_num_iterations != 1 || settings->sqp_iterations > 1) { set_last_error("DDP: one ILQR iteration per run (ddp.maxNumIterations 1): later iterations live on the roll-out's adaptive time grid"); return BPMPC_ERR_UNSUPPORTED; }
-      if (!(d.ls_min_step_length > 0.0) || !(d.ls_max_step_length >= d.ls_min_step_length)) { set_last_error("DDP: lineSearch.minStepLength / maxStepLength"); return BPMPC_ERR_INVALID_ARGUMENT; }
-      if (ddp_step_lengths(d, kMaxDdpSteps - 1) > kMaxDdpSteps - 1) {      // (the engine would try fewer step lengths than the configuration asks for and report status 1)
-        set_last_error("DDP: lineSearch.minStepLength / maxStepLength ask for more than " + std::to_string(kMaxDdpSteps - 1) + " step lengths (contraction rate 0.5), the line search table holds no more");
-        return BPMPC_ERR_UNSUPPORTED;
-      }
-      if (d.use_feedback_policy && settings->feedback_policy != 2) { set_last_error("DDP: ddp.useFeedbackPolicy true is not implemented (the gains live on the nominal grid, the solution on the roll-out's time points)"); return BPMPC_ERR_UNSUPPORTED; }
-      if (settings->feedback_policy == 1) { set_last_error("DDP: feedback_policy 1 (LinearController) is not implemented for the DDP solution"); return BPMPC_ERR_UNSUPPORTED; }
+      if (const int refused = check_ddp_settings(s->rm.ddp, *settings)) return refused;
       // round 6: the backward pass runs on the fast kernels (reference_kernels = 1 keeps the lane-emulated bodies: cross-check); the ILQR form of the
       // fast lineariser exists for serial-leg robots (every robot of the reference), any other tree runs the reference bodies
       s->settings.return_gains = 1;
@@ -896,19 +895,14 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
     s->nx = s->rm.nx; s->nu = s->rm.nu;
     HIP_CHECK(hipSetDevice(settings->device));
     { hipDeviceProp_t prop; HIP_CHECK(hipGetDeviceProperties(&prop, settings->device)); s->num_cus = prop.multiProcessorCount; }
-    { const char* e = std::getenv("BPMPC_WT_JOINT_ROWS"); s->wt_joint_rows = e && e[0] == '1'; }
-    { const char* e = std::getenv("BPMPC_LIN_TABLES"); s->force_tables = e && e[0] == '1'; }
-    { const char* e = std::getenv("BPMPC_LIN_COMPACT"); s->lin_compact = !(e && e[0] == '0'); }
-    { const char* e = std::getenv("BPMPC_RICCATI_WAVE"); s->riccati_wave = e ? std::atoi(e) : 1; }
-    { const char* e = std::getenv("BPMPC_R8_ROUNDS"); s->r8_rounds = e ? std::atoi(e) : 0; }
+    s->sw = read_switches([](const char* name) -> const char* { return std::getenv(name); });
     {
       bool block_diagonal = true;
       for (int c = 0; c < 12; ++c)
         for (int j = 12; j < s->nu; ++j) block_diagonal = block_diagonal && s->dm.R[c * s->nu + j] == 0.0 && s->dm.R[j * s->nu + c] == 0.0;
-      const char* e = std::getenv("BPMPC_DENSE_PROJECT");
-      s->structured_project = block_diagonal && !(e && e[0] == '1');
+      s->structured_project = block_diagonal && !s->sw.dense_project;
     }
-    if (s->is_ddp() && !(s->dm.serial_legs && !s->force_tables)) s->settings.reference_kernels = 1;
+    if (s->is_ddp() && !s->serial_legs()) s->settings.reference_kernels = 1;
     if (settings->stream) { s->stream = static_cast<hipStream_t>(settings->stream); }
     else { HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)); s->own_stream = true; }
     if (s->settings.pipeline_chunks <= 0) s->settings.pipeline_chunks = 1;
@@ -975,7 +969,7 @@ int bpmpc_solver_run(bpmpc_solver* s) {
 int bpmpc_solver_sync(bpmpc_solver* s) {
   return guarded(s, [&] {
     HIP_CHECK(hipStreamSynchronize(s->stream));
-    s->collect_timers();
+    s->timers.collect();
   });
 }
 int bpmpc_solver_fetch(bpmpc_solver* s, double* out_t, double* out_x, double* out_u, double* out_K, bpmpc_stats* stats) {
@@ -1006,7 +1000,7 @@ int bpmpc_solve_batch(bpmpc_solver* s, int batch, double horizon, const double* 
     setup(s, batch, horizon, t0, x0, schedules, n_schedules, targets, warm_x, warm_u);
     s->run_iterations();
     fetch(s, out_t, out_x, out_u, out_K, stats);
-    s->collect_timers();
+    s->timers.collect();
   });
 }
 int bpmpc_solver_stage(bpmpc_solver* s, const char* stage) {
@@ -1031,8 +1025,8 @@ int bpmpc_solver_read(bpmpc_solver* s, const char* name, double* out, long capac
 #endif
       auto q = s->named.find(name);
       if (q == s->named.end()) throw std::invalid_argument(std::string("unknown buffer ") + name);
-      if (q->second.second > 0x7fffffffu) throw std::length_error("bpmpc_solver_read: buffer exceeds 2^31 elements");
-      return (int)q->second.second;
+      if (q->second.count > 0x7fffffffu) throw std::length_error("bpmpc_solver_read: buffer exceeds 2^31 elements");
+      return (int)q->second.count;
     }
     HIP_CHECK(hipSetDevice(s->settings.device));
 #if defined(BPMPC_EVAL_PROFILE)
@@ -1048,16 +1042,16 @@ int bpmpc_solver_read(bpmpc_solver* s, const char* name, double* out, long capac
 #endif
     auto it = s->named.find(name);
     if (it == s->named.end()) throw std::invalid_argument(std::string("unknown buffer ") + name);
-    const size_t n = it->second.second;
+    const size_t n = it->second.count;
     if ((long)n > capacity) throw std::length_error("bpmpc_solver_read: capacity too small");
     if (n > 0x7fffffffu) throw std::length_error("bpmpc_solver_read: buffer exceeds 2^31 elements");
     HIP_CHECK(hipStreamSynchronize(s->stream));
-    if (s->is_int[name]) {
+    if (it->second.integer) {
       std::vector<int> tmp(n);
-      HIP_CHECK(hipMemcpy(tmp.data(), it->second.first, n * sizeof(int), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(tmp.data(), it->second.ptr, n * sizeof(int), hipMemcpyDeviceToHost));
       for (size_t i = 0; i < n; ++i) out[i] = tmp[i];
     } else {
-      HIP_CHECK(hipMemcpy(out, it->second.first, n * sizeof(double), hipMemcpyDeviceToHost));
+      HIP_CHECK(hipMemcpy(out, it->second.ptr, n * sizeof(double), hipMemcpyDeviceToHost));
     }
     return (int)n;
   });
@@ -1089,7 +1083,7 @@ int bpmpc_solver_constraint_values(bpmpc_solver* s, double* values, int* rows, i
     HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d_eqv), S * kMaxEqRows * sizeof(double)));     // a debugging path (solver observers): allocated per call
     try {
       HIP_CHECK(hipMemsetAsync(d_eqv, 0, S * kMaxEqRows * sizeof(double), s->stream));
-      const Launch L = s->launch_params();
+      const Launch& L = s->plan;
       kl::constraint_values(s->rm.nj, s->batch * L.klen, s->stream, L, d_eqv);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipMemcpyAsync(values, d_eqv, S * kMaxEqRows * sizeof(double), hipMemcpyDeviceToHost, s->stream));
@@ -1118,8 +1112,8 @@ int bpmpc_solver_kernel_time(bpmpc_solver* s, const char* kernel, int reset_afte
   return guarded(s, [&] {
     if (!kernel) throw std::invalid_argument("null kernel class");
     HIP_CHECK(hipStreamSynchronize(s->stream));
-    s->collect_timers();
-    KernelTimer& t = s->timers[kernel];
+    s->timers.collect();
+    KernelTimer& t = s->timers.by_class[kernel];
     if (total_ms) *total_ms = t.total_ms;
     if (launches) *launches = t.launches;
     if (reset_after) { t.total_ms = 0.0; t.launches = 0; }

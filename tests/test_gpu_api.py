@@ -300,3 +300,43 @@ def test_constraint_values_at_the_solution_match_oracle(ctx):
             assert np.abs(v[b, k, :lq["nc"]] - np.asarray(lq["e"])[:lq["nc"]]).max() < 1e-10
             seen.add(int(modes[b, k]))
     assert seen >= {0, 1, 2} and np.all(rows[:, n:] == 0)
+
+
+def test_setups_of_different_shape_on_one_handle_match_a_fresh_handle(ctx):
+    """What a launch reads of the handle is put together once per setup.  A handle that has solved a larger batch on a shorter, event-free grid
+    from a cold start, then takes a setup with another batch, another longest grid, a gait event inside the horizon and the caller's warm-start
+    arrays, then a receding-horizon step - and computes bit for bit what a handle that has only seen the last two does."""
+    bp, sc, ob, itf = ctx
+    N = 48
+
+    def targets(t0, x0, horizon):
+        return [itf.cmdVelToTargetTrajectories((0.3, 0.0, 0.0, 0.1), t0, x, horizon) for x in x0]
+
+    def second_and_third(mpc):
+        out = []
+        x0 = sc.perturbed_initial_states(itf, 2)
+        step = bp.ModeSchedule(np.array([0.3, 0.9]), np.array([3, 1, 3], np.int32))      # stance, one lift-off inside the horizon, touch-down behind it
+        warm_x, warm_u = np.repeat(x0[:, None, :], N + 1, axis=1), np.zeros((2, N, itf.inputDim))
+        warm_u[:, :, [2, 5, 8, 11]] = 9.81 * itf.robotMass() / 4.0
+        lay = mpc.setup(0.0, x0, step, targets(0.0, x0, 0.6), horizon=0.6, warm_x=warm_x, warm_u=warm_u)
+        assert lay["batch"] == 2 and lay["n_grids"] == 1 and 40 < lay["n_nodes_max"] <= N
+        mpc.enqueue()
+        out.append(mpc.fetch())
+        x1 = x0 + 1e-3 * np.sin(np.arange(x0.size)).reshape(x0.shape)
+        mpc.setup_from_previous(0.015, x1, step, targets(0.015, x1, 0.6), horizon=0.6)
+        mpc.enqueue()
+        out.append(mpc.fetch())
+        return out
+
+    P = bp.BatchedSqpMpc(itf, max_batch=4, max_nodes=N, sqp_iterations=2)
+    prob = sc.trot_problem(itf, batch=4, n_intervals=20, gait="stance")
+    lay = P.setup(prob["t0"], prob["x0"], prob["schedule"], prob["targets"], horizon=prob["horizon"])
+    assert lay["batch"] == 4 and lay["n_nodes_max"] == 20
+    P.enqueue()
+    P.fetch()
+    got = second_and_third(P)
+    want = second_and_third(bp.BatchedSqpMpc(itf, max_batch=4, max_nodes=N, sqp_iterations=2))
+    for (_, x, u, _, st), (_, xf, uf, _, stf) in zip(got, want):
+        assert np.isfinite(x).all() and np.isfinite(u).all() and np.abs(u).max() > 0
+        assert np.array_equal(x, xf) and np.array_equal(u, uf)
+        assert [(s.iterations, s.status) for s in st] == [(s.iterations, s.status) for s in stf]
