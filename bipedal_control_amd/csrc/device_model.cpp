@@ -41,6 +41,7 @@ DeviceModel make_device_model(const RobotModel& m) {
   }
   for (int i = 0; i < m.nx * m.nx; ++i) d.Q[i] = m.Q[i];
   for (int i = 0; i < m.nu * m.nu; ++i) d.R[i] = m.R[i];
+  d.ws = find_weight_structure(d.Q, m.nx, d.R, m.nu);
   d.friction = m.friction_coefficient;
   d.cone_reg = m.cone_regularization;
   d.cone_grip = m.cone_gripper_force;

@@ -2,6 +2,7 @@
 // Everything here is wave-uniform when read inside a kernel, so the compiler turns the accesses into scalar loads.
 #pragma once
 #include "robot_model.h"
+#include "weight_structure.h"
 
 namespace bpmpc {
 
@@ -27,7 +28,11 @@ struct DeviceModel {
   // 1: the joints form two serial legs of nj / 2 joints each in body order (body b hangs on b - 1, the leg heads 1 and nj / 2 + 1 on the base):
   // the lane-per-coordinate kernels then walk the tree by DPP shifts between neighbouring lanes (linearize_fast.h, CHAIN)
   int serial_legs;
+  // the non-zero lists of Q and R, their largest row counts, q_diagonal and the diagonal of Q (weight_structure.h).  ws.compact: the kernels sum
+  // over the lists; the solver clears it where BPMPC_DENSE_WEIGHTS=1 asks for the dense sums (sweep_plan.h)
+  WeightStructure ws;
 };
+static_assert(kWeightDim == kMaxState, "weight_structure.h sizes its lists for the largest state");
 
 DeviceModel make_device_model(const RobotModel& m);
 

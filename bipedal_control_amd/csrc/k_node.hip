@@ -363,7 +363,7 @@ __global__ __launch_bounds__(kTailThreads) void k_ls_tail(Launch L, int first_ro
       unsigned opaque = 0;
       asm volatile("" : "+v"(opaque));
       const auto& sh = *reinterpret_cast<const LinFastShared<NJ, false>*>(reinterpret_cast<const char*>(&shared) + opaque);
-      trial_fast<NJ, C>(*L.model, sh, lds[sub], valid, in, al, dx, L.buf.du + s * NU, dx + NX, L.buf.trial_perf + s * 3, g);
+      trial_fast<NJ, C, false, LinFastNodeLds<NJ, false, CHAIN>, false>(*L.model, sh, lds[sub], valid, in, al, dx, L.buf.du + s * NU, dx + NX, L.buf.trial_perf + s * 3, g);
     }
     __threadfence();
     __syncthreads();

@@ -71,10 +71,10 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(4, 6))) v
 
 // (amdgpu_waves_per_eu(3): 168 registers and 60 B of scratch instead of 186 registers, three waves per SIMD instead of two - measured
 //  slower, 0.272 against 0.255 ms on the same box)
-template <int NJ, bool PK, bool WJ>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PK ? 3 : 2, 4))) void k_project_fast(Launch L) {
+// QD: the model's Q as its diagonal (Launch::weights_q_diagonal; kernel k_project_fast_qd below)
+template <int NJ, bool PK, bool WJ, bool QD>
+__device__ __forceinline__ void project_fast_node(ProjectMfmaWorkspace<NJ, PK>& ws, const Launch& L) {
   constexpr int NX = 12 + NJ, NU = 12 + NJ;
-  __shared__ ProjectMfmaWorkspace<NJ, PK> ws;
   const int b = blockIdx.x / L.klen, k = L.k0 + blockIdx.x % L.klen;
   if (!L.buf.active[b]) return;
   const int g = L.buf.p_grid[b];
@@ -97,7 +97,19 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PK ? 3 : 
   out.Wt = L.buf.Wt + s * PackedLq<NJ>::W_SIZE; out.Qp = L.buf.Qp + s * PackedLq<NJ>::Q_SIZE; out.Mt = L.buf.Mt + s * PackedLq<NJ>::M_SIZE;
   if constexpr (PK) { in.zero = L.buf.zero_page; in.Vt = L.buf.Vt + s * NJ * PackedLq<NJ>::WP; in.mode = L.buf.g_mode[(size_t)g * L.N + k] & 3; }   // written by the structured elimination
   else out.Vt = L.buf.Vt + s * NJ * PackedLq<NJ>::WP;   // FullPivLU elimination (Px, Pu, Pe): this kernel packs the joint rows for the sweep's loaders
-  project_apply_mfma<NJ, PK, WJ>(ws, in, out, dt, dt * (1.0 / L.model->robot_mass), L.model->Q, L.model->R, L.reg_prim);   // as written by linearize_fast
+  project_apply_mfma<NJ, PK, WJ, QD>(ws, in, out, dt, dt * (1.0 / L.model->robot_mass), L.model->Q, L.model->ws.q_diag, L.model->R, L.reg_prim);   // as written by linearize_fast
+}
+template <int NJ, bool PK, bool WJ>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PK ? 3 : 2, 4))) void k_project_fast(Launch L) {
+  __shared__ ProjectMfmaWorkspace<NJ, PK> ws;
+  project_fast_node<NJ, PK, WJ, false>(ws, L);
+}
+// the same with a diagonal Q (every robot of the reference): [Q | q | 0] from the diagonal, a kernel of its own name - as a branch inside
+// k_project_fast it cost the packed variant with joint rows its third wave per SIMD
+template <int NJ, bool PK, bool WJ>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PK ? 3 : 2, 4))) void k_project_fast_qd(Launch L) {
+  __shared__ ProjectMfmaWorkspace<NJ, PK> ws;
+  project_fast_node<NJ, PK, WJ, true>(ws, L);
 }
 
 namespace kl {
@@ -120,9 +132,16 @@ void project_lu_s(int nj, int max_vel_rows, bool packed, int nodes, hipStream_t 
 // joint_rows false: the joint rows of Wt are left to the sweep (packed operands and a sweep that completes them only: riccati_wave2.h)
 void project_fast(int nj, bool packed, bool joint_rows, int nodes, hipStream_t st, const Launch& L) {
   KL_NJ(nj, {
-    if (packed && !joint_rows) hipLaunchKernelGGL((k_project_fast<NJ, true, false>), dim3(nodes), dim3(kWave), 0, st, L);
-    else if (packed) hipLaunchKernelGGL((k_project_fast<NJ, true, true>), dim3(nodes), dim3(kWave), 0, st, L);
-    else hipLaunchKernelGGL((k_project_fast<NJ, false, true>), dim3(nodes), dim3(kWave), 0, st, L);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nodes), dim3(kWave), 0, st, L); };
+    if (L.weights_q_diagonal) {
+      if (packed && !joint_rows) launch(k_project_fast_qd<NJ, true, false>);
+      else if (packed) launch(k_project_fast_qd<NJ, true, true>);
+      else launch(k_project_fast_qd<NJ, false, true>);
+    } else {
+      if (packed && !joint_rows) launch(k_project_fast<NJ, true, false>);
+      else if (packed) launch(k_project_fast<NJ, true, true>);
+      else launch(k_project_fast<NJ, false, true>);
+    }
   });
 }
 

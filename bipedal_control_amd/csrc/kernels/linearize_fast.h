@@ -13,6 +13,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "node_lq.h"
 #include "riccati_fast.h"   // lds_wave_sync
 
@@ -52,6 +54,9 @@ struct LinFastScalars {
   unsigned contact_path[kNumContacts];
   int contact_body[kNumContacts];
   int max_depth, cone_gauss_newton;
+  // cost weights (weight_structure.h): w_compact: the value-only kernels sum over the non-zero lists of the model (DeviceModel::ws), w_kq / w_kr terms per
+  // row of Q / of R.  (The lineariser keeps its dense sums: they run under its row stores and the lists bought it nothing, experiments/LOG.md.)
+  int w_compact, w_kq, w_kr, w_pad;
 };
 // Layout: the scalars and the kinematic constants first, the cost weights LAST - the block of the value-only kernels (COST = false) is a prefix of the
 // full one, so both are staged from one image by a flat copy.
@@ -74,6 +79,7 @@ template <int NJ>
 inline void fill_shared_image(const DeviceModel& md, LinFastShared<NJ, true>& sh) {      // host
   using C = LinFastCfg<NJ>;
   for (int i = 0; i < C::NX * C::NX; ++i) { sh.Q[i] = md.Q[i]; sh.R[i] = md.R[i]; }
+  sh.sc.w_compact = md.ws.compact; sh.sc.w_kq = md.ws.k_q; sh.sc.w_kr = md.ws.k_r; sh.sc.w_pad = 0;
   for (int b = 0; b < C::NB; ++b) {
     for (int i = 0; i < 9; ++i) sh.Rfix[b][i] = md.Rfix[b][i];
     for (int i = 0; i < 6; ++i) sh.inertia[b][i] = md.inertia[b][i];
@@ -192,6 +198,30 @@ __device__ __forceinline__ double lane_pick6(const double (&v)[6], int g) {
     out = (g == i) ? vi : out;
   }
   return out;
+}
+
+// Gradient sums of the cost over the non-zero lists of a weight (weight_structure.h): acc += W[c][r] d[r] over the non-zero columns r of row c in
+// ascending order - the dense sum without its products with exact zeros, hence the same bits.  The count K is wave-uniform and small: one unrolled
+// body per count, so that all reads of the sums of a lane are in flight together (a loop over a run-time K waits for every term's reads in turn).
+template <int K>
+__device__ __forceinline__ void weight_row_sum(const WeightTerms& t, int c, const double* d, double& acc) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) acc += t.val[j][c] * d[t.idx[j][c]];
+}
+template <class F>
+__device__ __forceinline__ void with_weight_terms(int k, F&& f) {
+  static_assert(kMaxWeightTerms == 8, "one case per count");
+  switch (k) {
+    case 0: break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
 }
 
 // per-lane tree bookkeeping of the body this lane owns (the inertial constants are read from the model at their
@@ -1143,7 +1173,9 @@ __device__ __forceinline__ TrialPre trial_preload(const double* x, const double*
   p.d = linearize_preload<Cfg>(dx, dxn, du, dx /* unused */, ln);
   return p;
 }
-template <int NJ, class Cfg = LinFastCfg<NJ, true>, bool EQV = false, class NL = LinFastNodeLds<NJ, false, Cfg::CHAIN>>
+// LISTS = false: the dense cost sums whatever the model says (the back-tracking tail, k_ls_tail: 248 .. 256 registers before this choice existed,
+// and both sums in one kernel sent it to scratch memory; the same bits either way)
+template <int NJ, class Cfg = LinFastCfg<NJ, true>, bool EQV = false, class NL = LinFastNodeLds<NJ, false, Cfg::CHAIN>, bool LISTS = true>
 __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastShared<NJ, false>& sh, NL& nl, bool valid,
                                            const NodeInputs& in, double alpha, const double* dx, const double* du, const double* dxn,
                                            double* perf, int ln, double* eqv = nullptr, const TrialPre* pre = nullptr) {
@@ -1284,6 +1316,24 @@ __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastS
   {
     const int cq = 6 + g, ch = ln, cf = ln, cj = 12 + g - 6, ct = 6 + ln;
     double accq = 0.0, acch = 0.0, accf = 0.0, accj = 0.0, acct = 0.0;
+    if (LISTS && __builtin_amdgcn_readfirstlane(sc.w_compact)) {
+      // the non-zero lists of the weights from global memory (cache resident, as the dense weights below): term j of the rows of sixteen lanes is one
+      // 128-byte line - 26 coalesced requests on the 22-state robots where the dense rows, 176 bytes apart from lane to lane, took 110 that touch
+      // sixteen lines each.  A lane without a role sums row 0 and drops it (no execution mask around the loads).
+      const int cqs = g < G ? cq : 0, chs = ln < 6 ? ch : 0, cfs = ln < 12 ? cf : 0, cjs = is_joint ? cj : 0, cts = tr ? ct : 0;
+      const WeightStructure& wl = md.ws;
+      with_weight_terms(__builtin_amdgcn_readfirstlane(sc.w_kq), [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        weight_row_sum<K>(wl.q, cqs, nl.dx, accq);
+        if constexpr (G0 > 0) weight_row_sum<K>(wl.q, cts, nl.dx, acct);
+        weight_row_sum<K>(wl.q, chs, nl.dx, acch);
+      });
+      with_weight_terms(__builtin_amdgcn_readfirstlane(sc.w_kr), [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        weight_row_sum<K>(wl.r, cfs, nl.du, accf);
+        weight_row_sum<K>(wl.r, cjs, nl.du, accj);
+      });
+    } else
     for (int r = 0; r < NX; ++r) {
       const double dxr = nl.dx[r], dur = nl.du[r];
       if (g < G) accq += md.Q[cq * NX + r] * dxr;       // cost weights from global memory (cache resident): this kernel stores next to nothing,

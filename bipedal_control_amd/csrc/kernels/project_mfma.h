@@ -47,9 +47,9 @@ struct ProjectMfmaWorkspace {
 // [Px | Pe | Pu]) = Vt, which the wave-per-problem sweeps load anyway and complete themselves (riccati_wave2.h, JW): at the batch sizes where
 // this kernel streams (4.7 TB/s) that is 3.8 KB per node it does not write and the sweep does not read, and the whole second block row of
 // the first product (rows 16..) is not issued.
-template <int NJ, int NBC, bool PK, bool WJ, class IssueX, class WriteX>
+template <int NJ, int NBC, bool PK, bool WJ, bool QD, class IssueX, class WriteX>
 __device__ __forceinline__ void project_apply_blocks(ProjectMfmaWorkspace<NJ, PK>& ws, const ProjectIn& in, const ProjectOut& out, double dt,
-                                                     double dt_over_mass, const double* Qc, const double* Rc, double reg, int nut,
+                                                     double dt_over_mass, const double* Qc, const double* Qd, const double* Rc, double reg, int nut,
                                                      IssueX&& issue_x, WriteX&& write_x, const double& pev) {
   using WS = ProjectMfmaWorkspace<NJ, PK>;
   constexpr int NX = WS::NX, NU = WS::NU, KR = WS::KR, KS = KR / 4, BC = NX + 1, WP = PackedLq<NJ>::WP, QP = PackedLq<NJ>::QP;
@@ -110,6 +110,7 @@ __device__ __forceinline__ void project_apply_blocks(ProjectMfmaWorkspace<NJ, PK
       const int rr = 16 * bi + lk + 4 * r;
       const bool rin = rr < NX;
       cR[bi][r] = in.r[rin ? rr : 0];
+      if constexpr (QD) continue;
 #pragma unroll
       for (int bj = 0; bj < NBC; ++bj) {
         const int col = 16 * bj + li;
@@ -117,6 +118,24 @@ __device__ __forceinline__ void project_apply_blocks(ProjectMfmaWorkspace<NJ, PK
         cQ[bi][bj][r] = *(in_m ? Qc + rr * NX + col : (in_v ? in.q + rr : in.q));
       }
     }
+  }
+  // QD (the model's Q is diagonal, weight_structure.h): the constant part of [Q | q | 0] is one diagonal entry per row, which lies in the
+  // diagonal blocks - only those and the block that holds column nx request anything (12 words per lane instead of 24 with three block columns)
+  if constexpr (QD) {
+#pragma unroll
+    for (int bi = 0; bi < 2; ++bi)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rr = 16 * bi + lk + 4 * r;
+        const bool rin = rr < NX;
+#pragma unroll
+        for (int bj = 0; bj < NBC; ++bj) {
+          const int col = 16 * bj + li;
+          if (bj == bi) cQ[bi][bj][r] = *((rin && rr == col) ? Qd + rr : ((rin && col == NX) ? in.q + rr : in.q));
+          else if (bj == 1) cQ[bi][bj][r] = *((rin && col == NX) ? in.q + rr : in.q);
+          else cQ[bi][bj][r] = 0.0;
+        }
+      }
   }
   // ---- the arithmetic on the operands of the first product
 #pragma unroll
@@ -203,6 +222,15 @@ __device__ __forceinline__ void project_apply_blocks(ProjectMfmaWorkspace<NJ, PK
       const int rr = 16 * bi + lk + 4 * r;
       const bool rin = rr < NX;
       cR[bi][r] = (li == NX - 16 && rin) ? cR[bi][r] : 0.0;      // column nx lives in block column 1 (nx in 16..31)
+      if constexpr (QD) {                                        // dt (Q_rr + shift) on the diagonal, q in column nx, zero elsewhere
+#pragma unroll
+        for (int bj = 0; bj < NBC; ++bj) {
+          const int col = 16 * bj + li;
+          if (bj == bi) { const double qv = cQ[bi][bj][r]; cQ[bi][bj][r] = (rin && rr == col) ? dt * (qv + shift) : ((rin && col == NX) ? qv : 0.0); }
+          else if (bj == 1) cQ[bi][bj][r] = (rin && col == NX) ? cQ[bi][bj][r] : 0.0;
+        }
+        continue;
+      }
 #pragma unroll
       for (int bj = 0; bj < NBC; ++bj) {
         const int col = 16 * bj + li;
@@ -269,9 +297,11 @@ __device__ __forceinline__ void project_apply_blocks(ProjectMfmaWorkspace<NJ, PK
 
 // PK: [Px | Pe | Pu] arrives as the packed joint rows of the structured elimination (in.Vt; the force rows are generated from in.mode)
 // instead of as Px, Pu, Pe - a compile-time choice: both paths in one kernel cost nx = 24 its third wave per SIMD.
-template <int NJ, bool PK = false, bool WJ = true>
+// QD: Q of the model is diagonal and arrives as its diagonal Qd (DeviceModel::ws.q_diag); else as the dense Qc - a compile-time choice as PK: both
+// in one kernel cost the packed variant with joint rows its third wave per SIMD (167 registers and scratch memory)
+template <int NJ, bool PK = false, bool WJ = true, bool QD = false>
 __device__ __forceinline__ void project_apply_mfma(ProjectMfmaWorkspace<NJ, PK>& ws, const ProjectIn& in, const ProjectOut& out, double dt,
-                                                   double dt_over_mass, const double* Qc, const double* Rc, double reg = 0.0) {
+                                                   double dt_over_mass, const double* Qc, const double* Qd, const double* Rc, double reg = 0.0) {
   using WS = ProjectMfmaWorkspace<NJ, PK>;
   constexpr int NX = WS::NX, NU = WS::NU, LDW = WS::LDW, KR = WS::KR, BC = NX + 1, WC = WS::WC;
   static_assert(NX == NU, "packed layout assumes nx == nu");
@@ -320,8 +350,8 @@ __device__ __forceinline__ void project_apply_mfma(ProjectMfmaWorkspace<NJ, PK>&
         if (idx < NV) ws.X[idx / 48][idx % 48] = vv[it];
       }
     };
-    if (nbc <= 2) project_apply_blocks<NJ, 2, true, WJ>(ws, in, out, dt, dt_over_mass, Qc, Rc, reg, nut, issue_x, write_x, pev);
-    else project_apply_blocks<NJ, WS::NBC_MAX, true, WJ>(ws, in, out, dt, dt_over_mass, Qc, Rc, reg, nut, issue_x, write_x, pev);
+    if (nbc <= 2) project_apply_blocks<NJ, 2, true, WJ, QD>(ws, in, out, dt, dt_over_mass, Qc, Qd, Rc, reg, nut, issue_x, write_x, pev);
+    else project_apply_blocks<NJ, WS::NBC_MAX, true, WJ, QD>(ws, in, out, dt, dt_over_mass, Qc, Qd, Rc, reg, nut, issue_x, write_x, pev);
   } else {
     auto issue_x = [&]() {                             // (test path, FullPivLU-format inputs: staged in one go)
       constexpr int IT = (NU * NX + kWave - 1) / kWave;
@@ -352,8 +382,8 @@ __device__ __forceinline__ void project_apply_mfma(ProjectMfmaWorkspace<NJ, PK>&
     };
     auto write_x = []() {};
     const double no_pe = 0.0;
-    if (nbc <= 2) project_apply_blocks<NJ, 2, false, WJ>(ws, in, out, dt, dt_over_mass, Qc, Rc, reg, nut, issue_x, write_x, no_pe);
-    else project_apply_blocks<NJ, WS::NBC_MAX, false, WJ>(ws, in, out, dt, dt_over_mass, Qc, Rc, reg, nut, issue_x, write_x, no_pe);
+    if (nbc <= 2) project_apply_blocks<NJ, 2, false, WJ, QD>(ws, in, out, dt, dt_over_mass, Qc, Qd, Rc, reg, nut, issue_x, write_x, no_pe);
+    else project_apply_blocks<NJ, WS::NBC_MAX, false, WJ, QD>(ws, in, out, dt, dt_over_mass, Qc, Qd, Rc, reg, nut, issue_x, write_x, no_pe);
   }
 }
 

@@ -138,6 +138,7 @@ struct bpmpc_solver {
     L.klen = n_nodes_max > 0 ? n_nodes_max : settings.max_nodes;
     L.cold = cold ? 1 : 0;
     L.serial_legs = serial_legs() ? 1 : 0;
+    L.weights_q_diagonal = (dm.ws.compact && dm.ws.q_diagonal) ? 1 : 0;
     L.feedback = feedback();
     L.ls = ls;
     L.reg_prim = settings.reg_prim;

@@ -902,6 +902,7 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
         for (int j = 12; j < s->nu; ++j) block_diagonal = block_diagonal && s->dm.R[c * s->nu + j] == 0.0 && s->dm.R[j * s->nu + c] == 0.0;
       s->structured_project = block_diagonal && !s->sw.dense_project;
     }
+    if (s->sw.dense_weights) s->dm.ws.compact = 0;      // the dense sums also where the lists exist (a model with more than kMaxWeightTerms non-zeros in a row runs them unasked)
     if (s->is_ddp() && !s->serial_legs()) s->settings.reference_kernels = 1;
     if (settings->stream) { s->stream = static_cast<hipStream_t>(settings->stream); }
     else { HIP_CHECK(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking)); s->own_stream = true; }
@@ -924,6 +925,11 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
     s->ls = LineSearchSettings{q.g_max, q.g_min, q.alpha_decay, q.alpha_min, q.gamma_c, q.armijo_factor, q.delta_tol, q.cost_tol,
                                settings->sqp_iterations > 0 ? settings->sqp_iterations : q.sqp_iteration};
     allocate(s.get());
+    {   // bpmpc_solver_read("weights_compact"): 1 while the kernels sum over the non-zero lists of the cost weights, 0 on the dense paths
+      int* flag = s->alloc<int>("weights_compact", 1, true);
+      const int v = s->dm.ws.compact;
+      HIP_CHECK(hipMemcpyAsync(flag, &v, sizeof(int), hipMemcpyHostToDevice, s->stream));
+    }
     HIP_CHECK(hipStreamSynchronize(s->stream));
     return BPMPC_OK;
   });

@@ -1,4 +1,4 @@
-// Which kernels a solver handle launches, as plain C++: the seven environment switches (read once, when the handle is created) and the Riccati sweep
+// Which kernels a solver handle launches, as plain C++: the eight environment switches (read once, when the handle is created) and the Riccati sweep
 // of a batch.  Host-only on purpose - no HIP header, no kernel header - so that tests/test_sweep_plan.py compiles it alone and walks the table.
 // A new switch or a new regime goes HERE; solver.hip only maps a Sweep to its launcher.
 #pragma once
@@ -22,6 +22,7 @@ struct Switches {
   bool lin_tables = false;                                 // BPMPC_LIN_TABLES=1: the table walks also on a robot of two serial legs (tests)
   bool lin_compact = true;                                 // BPMPC_LIN_COMPACT=0: the lineariser keeps the event nodes in line (A/B, tests)
   bool dense_project = false;                              // BPMPC_DENSE_PROJECT=1: the general elimination also where the input weight allows the structured one
+  bool dense_weights = false;                              // BPMPC_DENSE_WEIGHTS=1: the cost weights as dense matrices also where their non-zero lists exist (weight_structure.h; A/B, tests)
 };
 
 // `get` has the shape of std::getenv (a test passes its own)
@@ -40,6 +41,7 @@ inline Switches read_switches(const char* (*get)(const char*)) {
   sw.lin_tables = is("BPMPC_LIN_TABLES", '1');
   sw.lin_compact = !is("BPMPC_LIN_COMPACT", '0');
   sw.dense_project = is("BPMPC_DENSE_PROJECT", '1');
+  sw.dense_weights = is("BPMPC_DENSE_WEIGHTS", '1');
   return sw;
 }
 
