@@ -1103,6 +1103,34 @@ class PlantParams:
         return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0, 0.0])
 
 
+class SensorParams:
+    """A row of the plant's sensor model (include/bpmpc.h "Plant", sensors; BPMPC_PLANT_SENSOR_PARAM_STRIDE) with named fields: white noise, bias
+    random walk and turn-on bias of the gyro [rad/s, rad/s/sqrt(s), rad/s] and of the accelerometer [m/s^2 ...], orientation noise [rad], joint
+    position noise and encoder resolution [rad; 0: not quantised], joint velocity noise [rad/s], the probability that a closed contact reports
+    open, and the latency in control steps (an integer 0..8).  Every default is 0: the sensors read the truth."""
+
+    STRIDE = 16
+    FIELDS = ("gyro_noise", "gyro_bias_walk", "gyro_bias_init", "accel_noise", "accel_bias_walk", "accel_bias_init", "orientation_noise", "joint_pos_noise",
+              "joint_pos_resolution", "joint_vel_noise", "contact_dropout", "delay_steps")
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name in self.FIELDS:
+            setattr(self, name, float(fields.get(name, 0.0)))
+
+    @classmethod
+    def fromRow(cls, row):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
+
+    def toRow(self):
+        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
+
+
 class BatchedPlant(_Handle):
     """A rigid-body simulation of a batch of robots on one MI355X (bpmpc_plant; include/bpmpc.h "Plant" is its specification): joint commands ->
     the sensors BatchedStateEstimate.update takes and the ground-truth rbd.  This engine's own model - penalty contacts with implicit damping, a
@@ -1207,6 +1235,53 @@ class BatchedPlant(_Handle):
         anchor, anchored = np.zeros((B, 4, 2)), np.zeros((B, 4), np.int32)
         self._call("bpmpc_plant_get_anchors", B, _d(anchor), _i(anchored))
         return anchor, anchored
+
+    def setSensorParams(self, rows, mask=None):
+        """The sensor rows (SensorParams.toRow) of the robots with mask[b] != 0 (None: every one): rows [16], [1, 16] or [B, 16].  numpy rows are
+        validated and the call synchronises; device tensors are only enqueued, ordered before the next step.  From this call on every step measures
+        (k_plant_sense) and BatchedStateEstimate.update_from_plant reads sensed(); resetSensorParams ends that."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], SensorParams.STRIDE, self.max_batch)
+        self._call("bpmpc_plant_set_sensor_params", B, mp, rp, n_rows, dev)
+        del keep
+
+    def getSensorParams(self, robot=-1):
+        """The sensor row [16] of `robot` (SensorParams.fromRow names its entries), or with robot < 0 the row of the task file (the keys
+        plantSensors.<name>; absent: 0)."""
+        row = np.zeros(SensorParams.STRIDE)
+        self._call("bpmpc_plant_get_sensor_params", int(robot), _d(row))
+        return row
+
+    def resetSensorParams(self):
+        """Every sensor row, bias and counter zero, every key the start key (plantSensors.seed): the plant is the one without a sensor model again."""
+        self._call("bpmpc_plant_reset_sensor_params")
+
+    def seedSensors(self, seed, mask=None):
+        """Restarts the random streams of the robots with mask[b] != 0 (None: every one of the batch of the last set_state; before it: max_batch)
+        under `seed`: tick and sample count 0, the biases drawn anew from gyro_bias_init / accel_bias_init of the robot's current row.  A numpy
+        mask synchronises, an int32 device tensor is only enqueued."""
+        B = _count(mask) if mask is not None else (self.batch or self.max_batch)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, B))
+        self._call("bpmpc_plant_seed_sensors", B, mp, int(seed), dev)
+        del keep
+
+    def sensorState(self):
+        """{"gyro_bias" [B, 3], "accel_bias" [B, 3], "tick" [B], "samples" [B]} of the batch of the last set_state (before it: max_batch): the
+        biases, the generator's tick and the samples since the last (re)start; synchronises."""
+        B = self.batch or self.max_batch
+        bg, ba, ticks = np.zeros((B, 3)), np.zeros((B, 3)), np.zeros((B, 2))
+        self._call("bpmpc_plant_get_sensor_state", B, _d(bg), _d(ba), _d(ticks))
+        return {"gyro_bias": bg, "accel_bias": ba, "tick": ticks[:, 0].astype(np.uint64), "samples": ticks[:, 1].astype(np.uint64)}
+
+    def sensed(self):
+        """What the sensors report after the last step, where it lives: a dict of DeviceArray with the sensor names of outputs().  joint_pos,
+        joint_vel, quat, angular_vel_local, linear_accel_local and contact are the sensor model's; feet_heights and the odom_* channels are the
+        truth's buffers."""
+        o = _SensorInputs()
+        self._call("bpmpc_plant_sensed_outputs", C.byref(o))
+        B, nj = self.batch or self.max_batch, self.nj
+        shapes = {"joint_pos": (B, nj), "joint_vel": (B, nj), "quat": (B, 4), "angular_vel_local": (B, 3), "linear_accel_local": (B, 3), "contact": (B, 4),
+                  "feet_heights": (B, 4), "odom_pos": (B, 3), "odom_quat": (B, 4), "odom_lin_vel": (B, 3), "odom_ang_vel": (B, 3)}
+        return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k == "contact" else "<f8") for k, shp in shapes.items()}
 
 
 class BatchedDdpMpc(BatchedSqpMpc):

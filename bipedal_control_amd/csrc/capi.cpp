@@ -92,6 +92,41 @@ double plant_load_stiction(const char* task_info_path) {
   }
   return kt;
 }
+
+namespace {
+const char* const kSensorParamNames[] = {"gyro_noise", "gyro_bias_walk", "gyro_bias_init", "accel_noise", "accel_bias_walk", "accel_bias_init", "orientation_noise",
+                                         "joint_pos_noise", "joint_pos_resolution", "joint_vel_noise", "contact_dropout", "delay_steps"};
+static_assert(sizeof(kSensorParamNames) / sizeof(kSensorParamNames[0]) == kSensorParamUsed, "a name per used entry of a sensor row");
+}
+
+void plant_check_sensor_row(const char* who, const double* row, int r) {
+  for (int e = 0; e < kSensorParamStride; ++e) {
+    const char* name = e < kSensorParamUsed ? kSensorParamNames[e] : "reserved";
+    const char* why = !std::isfinite(row[e])                                            ? "not finite"
+                      : row[e] < 0.0                                                    ? "negative"
+                      : e == kSensContactDropout && row[e] > 1.0                        ? "above 1"
+                      : e == kSensDelaySteps && row[e] != std::floor(row[e])            ? "not an integer"
+                      : e == kSensDelaySteps && row[e] > (double)kSensorMaxDelay        ? "above 8"
+                      : e >= kSensorParamUsed && row[e] != 0.0                          ? "not zero"
+                                                                                        : nullptr;
+    if (why) throw std::invalid_argument(std::string(who) + ": row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + name + ") is " + why);
+  }
+}
+
+void plant_load_sensor_settings(const char* task_info_path, double* row, long* seed) {
+  double v[kSensorParamStride] = {};
+  double s = 0.0;
+  if (task_info_path) {
+    const auto t = read_info_file(task_info_path);
+    for (int e = 0; e < kSensorParamUsed; ++e) (void)t->get(std::string("plantSensors.") + kSensorParamNames[e], v + e);
+    plant_check_sensor_row("plantSensors settings", v, 0);
+    (void)t->get("plantSensors.seed", &s);
+    if (!std::isfinite(s) || s != std::floor(s) || std::fabs(s) > 9007199254740992.0)
+      throw std::invalid_argument("plantSensors settings: seed is not an integer a double holds exactly");
+  }
+  std::copy(v, v + kSensorParamStride, row);
+  if (seed) *seed = (long)s;
+}
 }  // namespace bpmpc
 
 using namespace bpmpc;
@@ -237,6 +272,35 @@ int bpmpc_plant_check_params(const double* rows, int n_rows) {
     for (int r = 0; r < n_rows; ++r) plant_check_param_row("bpmpc_plant_check_params", rows + (size_t)r * kPlantParamStride, r);
     return (int)BPMPC_OK;
   });
+}
+
+int bpmpc_plant_load_sensor_params(const char* task_info_path, double* row) {
+  if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_sensor_params: null row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    double v[kSensorParamStride];
+    plant_load_sensor_settings(task_info_path, v, nullptr);      // (the seed is validated with the row)
+    std::copy(v, v + kSensorParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_check_sensor_params(const double* rows, int n_rows) {
+  if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_sensor_params: null rows");
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) plant_check_sensor_row("bpmpc_plant_check_sensor_params", rows + (size_t)r * kSensorParamStride, r);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_sensor_draw(long seed, int robot, long tick, double* z, double* u) {
+  if (!z || !u) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_sensor_draw: null z or u");
+  if (robot < 0 || tick < -1) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_sensor_draw: robot must not be negative and tick must be -1 (the turn-on draw) or not negative");
+  const unsigned long long s = (unsigned long long)seed, t = tick < 0 ? kSensorTurnOnTick : (unsigned long long)tick;
+  const unsigned k0 = (unsigned)s, k1 = (unsigned)(s >> 32);
+  for (int g = 0; g < kSensorGaussians; ++g) z[g] = sensor_gaussian(t, (unsigned)robot, k0, k1, g);
+  const Philox4 block = sensor_block(t, (unsigned)robot, kSensorUniformBlock, k0, k1);
+  for (int i = 0; i < kSensorUniforms; ++i) u[i] = sensor_uniform(block.w[i]);
+  return BPMPC_OK;
 }
 
 int bpmpc_gait_create(const bpmpc_model* m, bpmpc_gait** out) {

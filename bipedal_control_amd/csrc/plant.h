@@ -7,6 +7,7 @@
 #include "device_handle.h"
 #include "robot_model.h"
 #include "kernels/plant.h"
+#include "kernels/sensor_noise.h"
 
 struct bpmpc_plant {
   bpmpc::RobotModel rm;
@@ -34,6 +35,19 @@ struct bpmpc_plant {
   int* d_anchored = nullptr;            // [max_batch][4]
   double* d_out = nullptr;              // the output block of k_plant_step (kernels/plant.h PlantOut)
   bpmpc_plant_outputs out{};            // its sections (leading dimension max_batch)
+  // sensor model (include/bpmpc.h "Plant", sensors): per-robot rows, generator state, biases, the ring of measured samples, the sensed block
+  double sensor_start[bpmpc::kSensorParamStride] = {};      // the keys plantSensors.<name> of task.info (absent: 0): every row after create
+  long sensor_seed = 0;                 // the key plantSensors.seed (absent: 0): every robot's key after create / reset_sensor_params
+  bool sense = false;                   // steps launch k_plant_sense behind the step kernel: the handle is switched (not untouched)
+  bool sensed_valid = false;            // a step has run since the switch: the sensed block holds measurements
+  double* d_sparams = nullptr;          // [max_batch][kSensorParamStride]
+  double* d_srows = nullptr;            // [max_batch + 1][kSensorParamStride] device copy of host rows; the last row holds sensor_start
+  unsigned* d_skey = nullptr;           // [max_batch][2]
+  unsigned long long* d_sticks = nullptr;      // [max_batch][2]: tick t, samples n since the last (re)start
+  double* d_sbias = nullptr;            // [max_batch][6]: gyro bias, accelerometer bias
+  double* d_sring = nullptr;            // [max_batch][kSensorRing][sensor_sample_width(nj)]
+  double* d_sensed = nullptr;           // the sensed block: the sections of sensor_sensed_offset, leading dimension max_batch
+  bpmpc_sensor_inputs sensed{};         // its members; what the sensor model leaves alone points into `out`
 };
 
 static_assert(bpmpc::kPlantParamStride == BPMPC_PLANT_PARAM_STRIDE, "PlantSettings follows the row layout of include/bpmpc.h");
@@ -48,6 +62,40 @@ double plant_load_stiction(const char* task_info_path);
 
 // plant_stick.hip: one launch of k_plant_stick_step<nj> for a.batch robots on `stream`
 void launch_plant_stick_step(int nj, hipStream_t stream, const DeviceModel* model, const PlantArgs& a, const PlantStickArgs& sa);
+
+// A measured sample, in doubles: joint_pos[nj], joint_vel[nj], quat[4], angular_vel_local[3], linear_accel_local[3], contact[4] (0.0 or 1.0): one
+// slot of the ring.  The sensed block holds the same members as sections of leading dimension max_batch, the contacts as four ints (2 doubles).
+__host__ __device__ constexpr int sensor_sample_width(int nj) { return 2 * nj + 14; }
+enum SensorSection { kSensedJointPos, kSensedJointVel, kSensedQuat, kSensedAngLocal, kSensedAccLocal, kSensedContact, kSensedEnd };
+__host__ __device__ constexpr int sensor_sensed_offset(int s, int nj) {
+  return s == kSensedJointPos ? 0 : s == kSensedJointVel ? nj : s == kSensedQuat ? 2 * nj : s == kSensedAngLocal ? 2 * nj + 4 : s == kSensedAccLocal ? 2 * nj + 7
+         : s == kSensedContact ? 2 * nj + 10 : 2 * nj + 12;
+}
+
+struct PlantSenseArgs {
+  int batch, max_batch;
+  double sqrt_period;                               // sqrt of the step's period: the scale of the bias walks
+  const double* params;                             // [max_batch][kSensorParamStride]
+  const unsigned* key;                              // [max_batch][2]
+  unsigned long long* ticks;                        // [max_batch][2]: t, n; read and advanced
+  double* bias;                                     // [max_batch][6]; read and walked
+  double* ring;                                     // [max_batch][kSensorRing][sensor_sample_width(nj)]
+  const double* truth;                              // the output block of the step kernel (PlantArgs::out)
+  double* sensed;                                   // the sensed block
+};
+
+// plant_sense.hip: one launch of k_plant_sense<nj> for a.batch robots on `stream`, behind the step kernel
+void launch_plant_sense(int nj, hipStream_t stream, const PlantSenseArgs& a);
+// bpmpc_plant_seed_sensors for the robots of `mask` (device; NULL: every robot below `batch`): key, t = n = 0, the turn-on biases under the robot's row
+void launch_plant_seed_sensors(hipStream_t stream, int batch, const int* mask, long seed, const double* params, unsigned* key, unsigned long long* ticks, double* bias);
+// n = 0 for the robots of `mask`: what bpmpc_plant_set_state does to the sensor model
+void launch_plant_forget_samples(hipStream_t stream, int batch, const int* mask, unsigned long long* ticks);
+
+// The keys plantSensors.<name> of task.info over zeros (NULL: zeros) and the key plantSensors.seed; host only (capi.cpp)
+void plant_load_sensor_settings(const char* task_info_path, double* row, long* seed);
+// A host row before it is accepted: every entry finite and not negative, contact_dropout <= 1, delay_steps an integer <= 8, the reserved entries 0;
+// throws std::invalid_argument naming the entry
+void plant_check_sensor_row(const char* who, const double* row, int r);
 
 // What bpmpc_plant_step_controlled reads of a controller (controller.cpp): the last tick's joint_cmd ([batch][3][nj]) and the joint gains where they
 // live, the stream they are written on, the batch of the last tick (0: none yet)

@@ -108,13 +108,36 @@ PlantArgs step_args(const bpmpc_plant* p, int batch, double period, int substeps
   return a;
 }
 
-void launch_step(bpmpc_plant* p, const PlantArgs& a) {
+// the step kernel and, on a switched handle, the sensor model behind it: `period` is the control step's
+void launch_step(bpmpc_plant* p, const PlantArgs& a, double period) {
   if (p->stick) {
     const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
     launch_plant_stick_step(p->nj, p->hs.stream, p->d_model, a, sa);
   }
   else KL_NJ(p->nj, hipLaunchKernelGGL(k_plant_step<NJ>, dim3(a.batch), dim3(kWave), 0, p->hs.stream, p->d_model, a));
   HIP_CHECK(hipGetLastError());
+  if (p->sense) {
+    const PlantSenseArgs sa{a.batch, p->max_batch, std::sqrt(period), p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias, p->d_sring, p->d_out, p->d_sensed};
+    launch_plant_sense(p->nj, p->hs.stream, sa);
+    p->sensed_valid = true;
+  }
+}
+
+// the handle leaves the untouched state: from now on every step measures, and the sensed block holds nothing until one has
+void switch_sensors(bpmpc_plant* p) {
+  if (!p->sense) p->sensed_valid = false;
+  p->sense = true;
+}
+
+// every sensor row zero, every bias and counter zero, every key the start key: the handle is untouched
+void write_untouched_sensors(bpmpc_plant* p) {
+  const size_t B = p->max_batch;
+  hipStream_t st = p->hs.stream;
+  HIP_CHECK(hipMemsetAsync(p->d_sparams, 0, B * kSensorParamStride * sizeof(double), st));
+  launch_plant_seed_sensors(st, p->max_batch, nullptr, p->sensor_seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);      // keys and counters
+  HIP_CHECK(hipMemsetAsync(p->d_sbias, 0, B * 6 * sizeof(double), st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  p->sense = false; p->sensed_valid = false;
 }
 
 void record(hipEvent_t* ev, hipStream_t on) {
@@ -162,6 +185,26 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
     HIP_CHECK(hipMemcpy(p->d_rows + B * kPlantParamStride, &p->defaults, sizeof(PlantSettings), hipMemcpyHostToDevice));
     write_default_params(p.get());
     write_default_stiction(p.get());
+    // sensor model: the members it measures live in the sensed block, the others are the truth's
+    plant_load_sensor_settings(task_info_path, p->sensor_start, &p->sensor_seed);
+    p->d_sparams = m.alloc<double>(B * kSensorParamStride); p->d_srows = m.alloc<double>((B + 1) * kSensorParamStride);
+    p->d_skey = m.alloc<unsigned>(B * 2); p->d_sticks = m.alloc<unsigned long long>(B * 2); p->d_sbias = m.alloc<double>(B * 6);
+    p->d_sring = m.alloc<double>(B * kSensorRing * sensor_sample_width(p->nj), true);
+    p->d_sensed = m.alloc<double>(B * sensor_sensed_offset(kSensedEnd, p->nj), true);
+    auto measured = [&](int sec) { return p->d_sensed + B * sensor_sensed_offset(sec, p->nj); };
+    p->sensed = s;
+    p->sensed.joint_pos = measured(kSensedJointPos); p->sensed.joint_vel = measured(kSensedJointVel); p->sensed.quat = measured(kSensedQuat);
+    p->sensed.angular_vel_local = measured(kSensedAngLocal); p->sensed.linear_accel_local = measured(kSensedAccLocal);
+    p->sensed.contact = reinterpret_cast<int*>(measured(kSensedContact));
+    HIP_CHECK(hipMemcpy(p->d_srows + B * kSensorParamStride, p->sensor_start, sizeof(p->sensor_start), hipMemcpyHostToDevice));
+    write_untouched_sensors(p.get());
+    bool configured = false;
+    for (int e = 0; e < kSensorParamUsed; ++e) configured = configured || p->sensor_start[e] != 0.0;
+    if (configured) {      // a task file with sensor settings: its row for every robot, turned on under the start key
+      write_rows(p->hs.stream, max_batch, kSensorParamStride, kSensorParamUsed, nullptr, 1, {p->d_srows + B * kSensorParamStride, nullptr, p->d_sparams});
+      launch_plant_seed_sensors(p->hs.stream, max_batch, nullptr, p->sensor_seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);
+      switch_sensors(p.get());
+    }
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
     return BPMPC_OK;
   });
@@ -191,6 +234,7 @@ int bpmpc_plant_set_state(bpmpc_plant* p, int batch, const int* mask, const doub
     hipLaunchKernelGGL(k_plant_set_state, dim3((batch * (int)E + 255) / 256), dim3(256), 0, st, batch, p->nv, dmask, drbd, p->d_state, p->out.rbd,
                        p->d_anchor, p->d_anchored);
     HIP_CHECK(hipGetLastError());
+    if (p->sense) launch_plant_forget_samples(st, batch, dmask, p->d_sticks);      // n = 0: the robots' sample history is forgotten
     p->last_batch = batch;
     if (!inputs_on_device) p->hs.synchronise_own();
     else p->hs.enqueued_own();
@@ -219,7 +263,7 @@ int bpmpc_plant_step(bpmpc_plant* p, int batch, const bpmpc_joint_command* c, in
     a.kd = staged(c->kd, p->d_kd, B * nj, inputs_on_device, st);
     a.base_force = staged(c->base_force, p->d_force, B * 3, inputs_on_device, st);
     a.ground = staged(c->feet_heights, p->d_ground, B * 4, inputs_on_device, st);
-    launch_step(p, a);
+    launch_step(p, a, period);
     if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
     else p->hs.enqueued_own();
   });
@@ -254,7 +298,7 @@ int bpmpc_plant_step_controlled(bpmpc_plant* p, bpmpc_controller* controller, in
     a.ground = staged(feet_heights, p->d_ground, B * 4, inputs_on_device, st);
     record(&p->ev_tick, cc.stream);
     HIP_CHECK(hipStreamWaitEvent(st, p->ev_tick, 0));
-    launch_step(p, a);
+    launch_step(p, a, period);
     record(&p->ev_step, st);
     HIP_CHECK(hipStreamWaitEvent(cc.stream, p->ev_step, 0));
     if (!inputs_on_device && (base_force || feet_heights)) p->hs.synchronise_own();      // the caller's host arrays
@@ -270,8 +314,10 @@ int bpmpc_estimator_update_from_plant(bpmpc_estimator* e, bpmpc_plant* p, int ba
     if (e->nj != p->nj) throw std::invalid_argument("bpmpc_estimator_update_from_plant: the estimator and the plant are built for different robots");
     if (e->device != p->device) throw std::invalid_argument("bpmpc_estimator_update_from_plant: the estimator and the plant live on different devices");
     if (batch != p->last_batch) throw std::invalid_argument("bpmpc_estimator_update_from_plant: batch differs from the batch of the plant's last set_state");
+    if (p->sense && !p->sensed_valid)
+      throw std::invalid_argument("bpmpc_estimator_update_from_plant: the plant's sensor model has been switched on and no step has run since: there is no measurement");
     p->hs.before_foreign(e->hs.stream);
-    const int rc = bpmpc_estimator_update(e, batch, &p->out.sensors, 1, period, host_rbd);
+    const int rc = bpmpc_estimator_update(e, batch, p->sense ? &p->sensed : &p->out.sensors, 1, period, host_rbd);
     p->hs.after_foreign(e->hs.stream);
     return rc;
   });
@@ -341,6 +387,66 @@ int bpmpc_plant_get_anchors(bpmpc_plant* p, int batch, double* host_anchor, int*
     HIP_CHECK(hipMemcpyAsync(host_anchored, p->d_anchored, (size_t)batch * kNumContacts * sizeof(int), hipMemcpyDeviceToHost, p->hs.stream));
     p->hs.synchronise_own();
   });
+}
+
+int bpmpc_plant_get_sensor_params(const bpmpc_plant* p, int robot, double* row) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_sensor_params: null handle or row", row != nullptr, [&] {
+    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_sensor_params: robot exceeds max_batch");
+    const double* src = robot < 0 ? p->d_srows + (size_t)p->max_batch * kSensorParamStride : p->d_sparams + (size_t)robot * kSensorParamStride;
+    HIP_CHECK(hipMemcpyAsync(row, src, kSensorParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_set_sensor_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_sensor_params: null handle or rows", rows != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_sensor_params");
+    set_rows("bpmpc_plant_set_sensor_params", p->hs.stream, batch, kSensorParamStride, kSensorParamUsed, mask, p->d_mask, n_rows, inputs_on_device,
+             [&](int r) { plant_check_sensor_row("bpmpc_plant_set_sensor_params", rows + (size_t)r * kSensorParamStride, r); }, {rows, p->d_srows, p->d_sparams});
+    switch_sensors(p);
+    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_reset_sensor_params(bpmpc_plant* p) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_sensor_params: null handle", [&] { write_untouched_sensors(p); });
+}
+
+int bpmpc_plant_seed_sensors(bpmpc_plant* p, int batch, const int* mask, long seed, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_seed_sensors: null handle", [&] {
+    check_batch(p, batch, "bpmpc_plant_seed_sensors");
+    hipStream_t st = p->hs.stream;
+    const int* dmask = staged(mask, p->d_mask, (size_t)batch, inputs_on_device, st);
+    launch_plant_seed_sensors(st, batch, dmask, seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);
+    switch_sensors(p);
+    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host mask
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_get_sensor_state(bpmpc_plant* p, int batch, double* gyro_bias, double* accel_bias, double* ticks) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_sensor_state: null handle", [&] {
+    check_batch(p, batch, "bpmpc_plant_get_sensor_state");
+    const size_t B = batch;
+    std::vector<double> bias(B * 6);
+    std::vector<unsigned long long> counters(B * 2);
+    HIP_CHECK(hipMemcpyAsync(bias.data(), p->d_sbias, B * 6 * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipMemcpyAsync(counters.data(), p->d_sticks, B * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, p->hs.stream));
+    p->hs.synchronise_own();
+    for (size_t b = 0; b < B; ++b)
+      for (int i = 0; i < 3; ++i) {
+        if (gyro_bias) gyro_bias[b * 3 + i] = bias[b * 6 + i];
+        if (accel_bias) accel_bias[b * 3 + i] = bias[b * 6 + 3 + i];
+      }
+    if (ticks) for (size_t i = 0; i < B * 2; ++i) ticks[i] = (double)counters[i];
+  });
+}
+
+int bpmpc_plant_sensed_outputs(bpmpc_plant* p, bpmpc_sensor_inputs* o) {
+  if (!p || !o) { set_last_error("bpmpc_plant_sensed_outputs: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  *o = p->sensed;
+  return BPMPC_OK;
 }
 
 }  // extern "C"

@@ -666,8 +666,55 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *     flags [batch*4] (synchronises).  A handle on which stiction was never set - start value 0, no set_stiction since create or
  *     reset_stiction - launches the kernel without stick-slip contacts, k_plant_step; any other launches k_plant_stick_step, in which a robot with
  *     kt = 0 computes the same bits.
+ *   sensors: a sensor model behind the step kernels, per robot: noise, bias, quantisation, latency and contact dropout on what the IMU, the joint
+ *     encoders and the contact switches report.  The step kernels and their outputs (the truth) are not changed by it; it writes a second block,
+ *     the sensed block.  It is off until it is used (see "switching").
+ *     random numbers: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with counter = (tick low word, tick
+ *       high word, robot index in the batch, block) and key = (seed low word, seed high word): every draw is a function of (seed, robot, tick) and
+ *       of nothing else.  A word w gives the uniform (w + 0.5) 2^-32.  The Gaussian z[g], g = 0..63, comes from block g >> 1, words (0, 1) for even
+ *       g and (2, 3) for odd g: z = sqrt(-2 ln u1) cos(2 pi u2), so |z| <= 6.76.  The contact uniforms u[0..3] are the four words of block 32.  The
+ *       turn-on draw is the same table at the tick with all 64 bits set.
+ *     state per robot: key (2 words), tick t (64 bit), samples n since the last (re)start, gyro bias bg[3], accelerometer bias ba[3], a ring of 9
+ *       measured samples; one sample is joint_pos[nj], joint_vel[nj], quat[4], angular_vel_local[3], linear_accel_local[3], contact[4].
+ *     settings: a row of BPMPC_PLANT_SENSOR_PARAM_STRIDE doubles per robot, [gyro_noise rad/s, gyro_bias_walk rad/s/sqrt(s), gyro_bias_init rad/s,
+ *       accel_noise m/s^2, accel_bias_walk m/s^2/sqrt(s), accel_bias_init m/s^2, orientation_noise rad, joint_pos_noise rad, joint_pos_resolution rad
+ *       (0: not quantised), joint_vel_noise rad/s, contact_dropout (probability 0..1), delay_steps (integer valued, 0..8), reserved 0 x 4].  Every
+ *       row starts as the keys plantSensors.<name> of task_info_path, an absent key or a NULL path gives 0; the key plantSensors.seed (absent: 0) is
+ *       every robot's start key.  Host rows are validated - every entry finite and not negative, contact_dropout <= 1, delay_steps an integer <= 8,
+ *       the reserved entries 0 - and a bad entry is named in bpmpc_last_error() and changes nothing.  A device row cannot be looked at: the kernel
+ *       clamps its delay_steps to 0..8 (the integer part; not a number: 0).
+ *     one measurement per control step of length period, by k_plant_sense behind the step kernel on the plant's stream:
+ *       1. the draws z[0..63], u[0..3] at (t, robot, key)
+ *       2. bias walk: bg += gyro_bias_walk sqrt(period) z[3..5]; ba += accel_bias_walk sqrt(period) z[9..11]
+ *       3. the measured sample: angular_vel_local + bg + gyro_noise z[0..2]; linear_accel_local + ba + accel_noise z[6..8]; with
+ *          orientation_noise > 0 quat (x) dq, normalised, where delta = orientation_noise z[12..14] and dq = (delta sin(|delta| / 2) / |delta|,
+ *          cos(|delta| / 2)) (x y z w, Hamilton product: a rotation by delta in the body frame), else quat as it is; joint_pos_j + joint_pos_noise
+ *          z[16 + j], then rint(. / D) D when D = joint_pos_resolution > 0 (ties to even); joint_vel_j + joint_vel_noise z[32 + j];
+ *          contact_i = truth_i and not (u[i] < contact_dropout)
+ *       4. the sample goes into ring slot n mod 9; the sensed block receives the sample with index max(n - delay_steps, 0)
+ *       5. t += 1, n += 1
+ *       feet_heights, odom_pos, odom_quat, odom_lin_vel, odom_ang_vel, rbd and contact_force stay the truth: the sensed block shares those pointers,
+ *       and its mode is NULL.  A robot whose row is all zero (and whose biases are zero) reads the truth, equal as numbers.
+ *     calls: bpmpc_plant_get_sensor_params / set_sensor_params have the shapes, masks, n_rows and host / device semantics of bpmpc_plant_get_params
+ *       / set_params (robot < 0: the row of the task file).  bpmpc_plant_seed_sensors, for the robots of mask (NULL: every robot below batch; host
+ *       or device by inputs_on_device): key = seed reinterpreted as unsigned, t = 0, n = 0, bg = gyro_bias_init z0[0..2], ba = accel_bias_init
+ *       z0[3..5] with z0 the turn-on draw under the new key and the robot's current row; robots outside the mask do not change by one bit.
+ *       bpmpc_plant_get_sensor_state: host copies of bg [batch*3], ba [batch*3] and ticks [batch*2] = (t, n) per robot as doubles (exact below
+ *       2^53); each pointer nullable; synchronises.  bpmpc_plant_sensed_outputs: the sensed block where it lives (leading dimension max_batch), an
+ *       argument of bpmpc_estimator_update (inputs_on_device = 1) as it stands.  bpmpc_plant_load_sensor_params / check_sensor_params: the ingest
+ *       (row[16]; a bad plantSensors.seed is refused there too) and the row validation as host-only functions.  bpmpc_plant_sensor_draw: z[64] and
+ *       u[4] of (seed, robot, tick) from the text the kernels compile, on the host; tick = -1 is the turn-on draw.
+ *     switching: a handle is untouched when its task file has no non-zero plantSensors.<name> key and it has had no set_sensor_params or
+ *       seed_sensors since create or reset_sensor_params.  An untouched handle launches nothing beside its step kernel, and
+ *       bpmpc_estimator_update_from_plant reads the truth.  Any other handle is switched: every step launches k_plant_sense behind the step kernel,
+ *       bpmpc_estimator_update_from_plant reads the sensed block behind it, and until a step has run since the switch it returns
+ *       BPMPC_ERR_INVALID_ARGUMENT (there is no measurement yet).  A handle whose task file has a non-zero key is created switched, every row the
+ *       file's, turned on as by seed_sensors(plantSensors.seed).  bpmpc_plant_set_state sets n = 0 for the robots of its mask - their history is
+ *       forgotten, the next sample is the first of a new one - and touches neither bias, key nor t, and does not write the sensed block.
+ *       bpmpc_plant_reset_sensor_params zeroes every row, bias, t and n, restores the start key and returns the handle to untouched.
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_PLANT_PARAM_STRIDE 8
+#define BPMPC_PLANT_SENSOR_PARAM_STRIDE 16
 typedef struct bpmpc_plant bpmpc_plant;
 typedef struct {
   const double *pos_des, *vel_des, *tau_ff, *kp, *kd;   /* [batch*nj] */
@@ -697,6 +744,15 @@ int bpmpc_plant_get_stiction(const bpmpc_plant* plant, int robot, double* kt);
 int bpmpc_plant_reset_stiction(bpmpc_plant* plant);
 int bpmpc_plant_load_stiction(const char* task_info_path, double* kt);
 int bpmpc_plant_get_anchors(bpmpc_plant* plant, int batch, double* host_anchor, int* host_anchored);
+int bpmpc_plant_get_sensor_params(const bpmpc_plant* plant, int robot, double* row);
+int bpmpc_plant_set_sensor_params(bpmpc_plant* plant, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_plant_reset_sensor_params(bpmpc_plant* plant);
+int bpmpc_plant_load_sensor_params(const char* task_info_path, double* row);
+int bpmpc_plant_check_sensor_params(const double* rows, int n_rows);
+int bpmpc_plant_seed_sensors(bpmpc_plant* plant, int batch, const int* mask, long seed, int inputs_on_device);
+int bpmpc_plant_get_sensor_state(bpmpc_plant* plant, int batch, double* gyro_bias, double* accel_bias, double* ticks);
+int bpmpc_plant_sensed_outputs(bpmpc_plant* plant, bpmpc_sensor_inputs* dev_out);
+int bpmpc_plant_sensor_draw(long seed, int robot, long tick, double* z, double* u);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Policy buffer = MPC_MRT_Interface between the solve and the control tick for a BATCH of robots, on the device.  In the reference a thread calls
