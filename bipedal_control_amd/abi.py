@@ -68,7 +68,7 @@ MIRRORS = {"bpmpc_settings": _Settings, "bpmpc_mode_schedule": _Schedule, "bpmpc
 
 # (base type, pointer depth) of a declaration without its const; void is a return type only
 _CTYPES = {("int", 0): C.c_int, ("double", 0): C.c_double, ("long", 0): C.c_long, ("char", 1): C.c_char_p, ("double", 1): _dp, ("int", 1): _ip,
-           ("double", 2): C.POINTER(_dp)}
+           ("double", 2): C.POINTER(_dp), ("int", 2): C.POINTER(_ip)}
 
 
 def declarations(header_path=HEADER):

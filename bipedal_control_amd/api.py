@@ -1011,6 +1011,14 @@ class BatchedController(_Handle):
         self._call("bpmpc_controller_attach_policy", None if policy is None else policy._h)
         self.policy = policy
 
+    def attachTelemetry(self, telemetry):
+        """Every tick takes a sample of `telemetry` (a BatchedTelemetry of the same robot and device) behind its commands, on the controller's
+        stream and the tick's own device buffers (bpmpc_controller_attach_telemetry); None detaches: a tick is its three launches again."""
+        self._call("bpmpc_controller_attach_telemetry", None if telemetry is None else telemetry._h)
+        self.telemetry = telemetry
+        if telemetry is not None:
+            telemetry.batch = self.mpc.batch or telemetry.batch
+
     def reset(self):
         """yaw_last = 0 for every robot (BipedalController::starting)."""
         self._call("bpmpc_controller_reset")
@@ -1073,6 +1081,112 @@ class PolicyBuffer(_Handle):
         out = {"generation": np.zeros(B, np.int32), "t0": np.zeros(B), "status": np.zeros(B, np.int32)}
         self._call("bpmpc_policy_info", B, _i(out["generation"]), _d(out["t0"]), _i(out["status"]))
         return out
+
+
+class TelemetrySample:
+    """The fields of a telemetry sample row (include/bpmpc.h "Tracking telemetry"): STRIDE(nj) doubles; fields(nj) maps a name to its
+    (offset, shape); split(rows, nj) slices rows [..., STRIDE(nj)] into a dict of named arrays."""
+
+    GROUPS = ("base_pos", "base_zyx", "contact_0", "contact_1", "contact_2", "contact_3", "joint_pos")      # the error groups e0..e6
+    STATS_STRIDE = 40
+
+    @staticmethod
+    def STRIDE(nj):
+        return 40 + 2 * nj
+
+    @staticmethod
+    def fields(nj):
+        return {"base_pos_desired": (0, (3,)), "base_zyx_desired": (3, (3,)), "base_pos_measured": (6, (3,)), "base_zyx_measured": (9, (3,)),
+                "contact_pos_desired": (12, (4, 3)), "contact_pos_measured": (24, (4, 3)), "joint_pos_desired": (36, (nj,)),
+                "joint_pos_measured": (36 + nj, (nj,)), "t": (36 + 2 * nj, ()), "safe": (37 + 2 * nj, ()), "planned_mode": (38 + 2 * nj, ()),
+                "n": (39 + 2 * nj, ())}
+
+    @classmethod
+    def split(cls, rows, nj):
+        rows = np.asarray(rows, float)
+        if rows.shape[-1] != cls.STRIDE(nj):
+            raise ValueError("a sample of a robot with %d joints has %d entries, got %d" % (nj, cls.STRIDE(nj), rows.shape[-1]))
+        return {k: rows[..., off:off + int(np.prod(shp, dtype=int))].reshape(rows.shape[:-1] + shp) for k, (off, shp) in cls.fields(nj).items()}
+
+
+class BatchedTelemetry(_Handle):
+    """DebugPublisher::update (bipedal_controllers/src/debug/DebugPublisher.cpp; BipedalController.cpp:270) for a batch of robots, kept on the
+    device (bpmpc_telemetry): per update a sample of the desired beside the measured base pose, contact points and joints, tracking-error
+    statistics over the episode, and a ring of the last `ring_len` samples per robot that freezes when the robot falls.  Attach it to a
+    BatchedController (attachTelemetry) and every tick takes a sample on the controller's stream; nothing reaches the host until stats() or
+    ring() ask for it."""
+
+    _DESTROY = "bpmpc_telemetry_destroy"
+
+    def __init__(self, interface, max_batch, ring_len=0, device=0):
+        self.interface, self.max_batch, self.ring_len = interface, int(max_batch), int(ring_len)
+        self.nj = interface.actuatedDofNum
+        super().__init__()
+        _check(load_library().bpmpc_telemetry_create(interface.handle, int(device), self.max_batch, self.ring_len, C.byref(self._h)))
+        s, r, n = C.c_int(), C.c_int(), C.c_int()
+        self._call("bpmpc_telemetry_dims", C.byref(s), C.byref(r), C.byref(n))
+        self.sample_stride, self.stats_stride = s.value, r.value
+        self.batch = self.max_batch
+
+    def update(self, x_opt, rbd, t=None, safe=None, planned_mode=None):
+        """One sample for B = len(x_opt) robots, outside a controller: x_opt [B, 12 + nj], rbd [B, 2 (6 + nj)], t [B], safe [B], planned_mode [B]
+        (each of the last three may be None).  numpy arrays (the call synchronises), or float64 / int32 device arrays - torch tensors or
+        DeviceArray, e.g. BatchedController.device_outputs() - which are only enqueued on the handle's stream."""
+        B = _shape(x_opt)[0]
+        nv = 6 + self.nj
+        (tp, xp, rp, sp, mp), dev, keep = _restart_args((t, C.c_double, B), (x_opt, C.c_double, B * (12 + self.nj)), (rbd, C.c_double, B * 2 * nv),
+                                                        (safe, C.c_int, B), (planned_mode, C.c_int, B))
+        self._call("bpmpc_telemetry_update", B, tp, xp, rp, sp, mp, dev)
+        del keep
+        self.batch = B
+
+    def configure(self, every=1, freeze_on_unsafe=True):
+        """Every `every`-th update of a robot goes into its ring; freeze_on_unsafe: a robot's record freezes at its first sample that is unsafe
+        or not finite."""
+        self._call("bpmpc_telemetry_configure", int(every), int(bool(freeze_on_unsafe)))
+
+    def reset(self, mask=None):
+        """The record of the robots with mask[b] != 0 (None: every robot) starts over; the others do not change by one bit.  A numpy mask, or an
+        int32 device tensor - e.g. the (safe == 0) mask of BatchedController.restart - which is only enqueued."""
+        B = self.max_batch if mask is None else _count(mask)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, B))
+        self._call("bpmpc_telemetry_reset", B, mp, dev)
+        del keep
+
+    def stats(self, batch=None):
+        """The statistics of the first B robots (None: the batch of the last update() or the attached controller's; synchronises): rms [B, 7] and
+        max [B, 7] of the error groups TelemetrySample.GROUPS, max_at [B, 7] (the update counter n at the maximum), samples [B], first_unsafe [B]
+        (-1: none), joint_max [B, nj], frozen [B]."""
+        B = int(batch or self.batch)
+        rows, frozen = np.zeros((B, self.stats_stride)), np.zeros(B, np.int32)
+        self._call("bpmpc_telemetry_get_stats", B, _d(rows), _i(frozen))
+        g = rows[:, :21].reshape(B, 7, 3)
+        samples = rows[:, 21]
+        return {"rms": np.sqrt(g[:, :, 0] / np.maximum(samples, 1.0)[:, None]), "max": g[:, :, 1].copy(), "max_at": g[:, :, 2].astype(np.int64),
+                "samples": samples.astype(np.int64), "first_unsafe": rows[:, 22].astype(np.int64), "joint_max": rows[:, 23:23 + self.nj].copy(),
+                "frozen": frozen, "rows": rows}
+
+    def ring(self, robots=None, batch=None):
+        """The ring of `robots` (a list of indices; None: every robot of the batch), oldest sample first: the fields of TelemetrySample over
+        [R, ring_len, ...], `samples` [R, ring_len, stride] and `count` [R] - the slots behind a robot's count are zero.  Synchronises."""
+        B = int(batch or self.batch)
+        idx = None if robots is None else np.ascontiguousarray(robots, np.int32).reshape(-1)
+        R = B if idx is None else idx.size
+        rows, count = np.zeros((R, self.ring_len, self.sample_stride)), np.zeros(R, np.int32)
+        self._call("bpmpc_telemetry_fetch_ring", B, None if idx is None else _i(idx), R, _d(rows), _i(count))
+        out = TelemetrySample.split(rows, self.nj)
+        out["samples"], out["count"] = rows, count
+        return out
+
+    def outputs(self):
+        """The last sample [max_batch, stride], the statistics rows [max_batch, 40] and the frozen flags [max_batch] where they live: a dict of
+        DeviceArray."""
+        s, r, f = _dp(), _dp(), _ip()
+        self._call("bpmpc_telemetry_device_outputs", C.byref(s), C.byref(r), C.byref(f))
+        B = self.max_batch
+        return {"sample": DeviceArray(C.cast(s, C.c_void_p).value, (B, self.sample_stride), "<f8"),
+                "stats": DeviceArray(C.cast(r, C.c_void_p).value, (B, self.stats_stride), "<f8"),
+                "frozen": DeviceArray(C.cast(f, C.c_void_p).value, (B,), "<i4")}
 
 
 class PlantParams:

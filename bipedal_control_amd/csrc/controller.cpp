@@ -20,6 +20,7 @@
 #include "plant.h"
 #include "policy.h"
 #include "solver.h"
+#include "telemetry.h"
 #include "wbc.h"
 #include "kernels/tick.h"
 
@@ -36,6 +37,7 @@ struct bpmpc_controller {
   double *d_kp_in = nullptr, *d_kd_in = nullptr;                     // device copies of host gain rows
   int last_tick_batch = 0;                                           // rows of d_cmd that hold the commands of a tick (0: no tick yet)
   bpmpc_policy* p = nullptr;                                         // the attached policy buffer (NULL: ticks read the solver's arrays on its stream)
+  bpmpc_telemetry* tel = nullptr;                                    // the attached tracking telemetry (NULL: a tick is its three launches and nothing else)
 };
 
 namespace {
@@ -79,6 +81,7 @@ void check_tick(const bpmpc_controller* c, int batch, const char* who) {
     if (batch != c->s->batch) throw std::invalid_argument(std::string(who) + ": batch differs from the batch of the solver's last setup");
   }
   if (batch > c->max_batch) throw std::length_error(std::string(who) + ": batch exceeds the WBC's max_batch");
+  if (c->tel && batch > c->tel->max_batch) throw std::length_error(std::string(who) + ": batch exceeds the attached telemetry's max_batch");
 }
 
 // the three launches of a tick on the controller's stream, from device inputs
@@ -97,6 +100,8 @@ void enqueue_tick(bpmpc_controller* c, int batch, const double* dt, const double
   ca.cmd = c->d_cmd; ca.joint_torque = c->d_torque;
   kl::tick_commands(c->nj, st, ca);
   HIP_CHECK(hipGetLastError());
+  // DebugPublisher::update (:270) behind the commands, on the tick's own device buffers
+  if (c->tel) telemetry_launch_on(c->tel, batch, dt, c->d_xopt, drbd, c->d_safe, c->d_mode, st);
   c->last_tick_batch = batch;
   enqueued(c);
 }
@@ -306,6 +311,15 @@ int bpmpc_controller_attach_policy(bpmpc_controller* c, bpmpc_policy* p) {
     if (p) HIP_CHECK(hipStreamSynchronize(p->hs.stream));
     detach(c);
     if (p) { c->p = p; ++p->attached; c->s->tick_hs = &p->hs; }
+  });
+}
+
+// NULL detaches.  Nothing is drained: the telemetry's own stream and the controller's are ordered by events around every launch (telemetry.h).
+int bpmpc_controller_attach_telemetry(bpmpc_controller* c, bpmpc_telemetry* tm) {
+  return guarded(c, BPMPC_ERR_DEVICE, "bpmpc_controller_attach_telemetry: null controller handle", [&] {
+    if (tm && tm->nj != c->nj) throw std::invalid_argument("bpmpc_controller_attach_telemetry: the telemetry's model and the controller are built for different robots");
+    if (tm && tm->device != c->device) throw std::invalid_argument("bpmpc_controller_attach_telemetry: the telemetry and the controller live on different devices");
+    c->tel = tm;
   });
 }
 

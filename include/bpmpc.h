@@ -811,6 +811,76 @@ int bpmpc_policy_update(bpmpc_policy* policy, int wait, int* adopted);
 int bpmpc_policy_info(bpmpc_policy* policy, int batch, int* generation, double* t0, int* status);
 int bpmpc_controller_attach_policy(bpmpc_controller* controller, bpmpc_policy* policy);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Tracking telemetry = DebugPublisher::update (bipedal_controllers/src/debug/DebugPublisher.cpp, called from BipedalController.cpp:270;
+ * msg/TrackingError.msg) for a BATCH of robots, kept on the device: per update and robot one SAMPLE of what the policy asks for beside what was
+ * measured, error STATISTICS accumulated over an episode, and a RING of the last samples that freezes when the robot falls.  Nothing reaches the
+ * host unless it is asked for.  The handle is off until it is attached: a controller without one launches and changes nothing of this.
+ *   sample, BPMPC_TELEMETRY_SAMPLE_STRIDE(nj) = 40 + 2 nj doubles (60 at nj = 10, 64 at nj = 12):
+ *       0..2, 3..5         base_pos_desired, base_zyx_desired     x*[6:9], x*[9:12] (the yaw as the policy has it, unwrapped)
+ *       6..8, 9..11        base_pos_measured, base_zyx_measured   rbd[3:6], rbd[0:3]
+ *       12..23             contact_pos_desired[4][3]              world positions of the model's four contact points at q_des = x*[6:12 + nj]
+ *       24..35             contact_pos_measured[4][3]             the same at q_meas = [rbd[3:6], rbd[0:3], rbd[6:6 + nj]]
+ *       36.., 36 + nj..    joint_pos_desired[nj], joint_pos_measured[nj]      x*[12:], rbd[6:6 + nj]
+ *       36 + 2 nj .. + 3   t, safe, planned_mode, n               as doubles; 0 where the caller gave none; n: the robot's update counter at the sample
+ *     The contact points, their order and the kinematic tree are the WBC's (the contact frames of the model, in its order).  The desired
+ *     velocities that the reference computes and never publishes are not part of it.
+ *   errors of a sample, Euclidean norms: e0 = |base_pos_desired - base_pos_measured|, e1 = |normalize_angle(base_zyx_desired - base_zyx_measured)|
+ *     (per component, onto (-pi, pi]: a desired yaw of 3.1 against a measured yaw of -3.1 is an error of 0.083), e2..e5 = |contact_pos_desired_i -
+ *     contact_pos_measured_i|, e6 = |joint_pos_desired - joint_pos_measured|; beside them |joint error| of every joint.
+ *   state per robot:
+ *     n             updates since the robot's last reset.
+ *     statistics    BPMPC_TELEMETRY_STATS_STRIDE = 40 doubles: for group k = 0..6 at 3 k the sum of e_k^2, the largest e_k and the n at which it
+ *                   occurred (the first, among equals); 21 the number of samples accumulated; 22 first_unsafe_n (-1: none); 23..34 the largest
+ *                   |joint error| per joint (unused ones 0); 35..39 reserved, 0.
+ *     ring          ring_len samples (fixed at create; 0: no ring) in device memory, [robot][slot][stride].  With n mod every == 0 the sample is
+ *                   recorded into slot r mod ring_len, r the number of samples the robot has recorded since its reset (n / every while `every`
+ *                   has not changed since).
+ *     frozen        with freeze_on_unsafe (the default) a robot freezes at the first sample whose `safe` is given and 0 or that holds a measured or
+ *                   desired entry (0 .. 35 + 2 nj) that is not finite.  That sample is recorded into the ring whatever `every` says, sets
+ *                   first_unsafe_n, and is accumulated only if all its errors are finite.  Afterwards the robot's ring, statistics, last sample and n
+ *                   do not change until it is reset: the ring holds the last ring_len recorded samples up to and including the fall.  A frozen
+ *                   robot costs its wavefront the flag test.  With freeze_on_unsafe off nothing freezes: a sample that is not finite is recorded
+ *                   and not accumulated, first_unsafe_n is still set once.
+ *   bpmpc_telemetry_create: ring_len < 0 or max_batch < 1: BPMPC_ERR_INVALID_ARGUMENT; BPMPC_ERR_NO_DEVICE without a GPU.  The ring takes
+ *     max_batch * ring_len * stride * 8 bytes.  Every robot starts reset.  The handle owns a stream.
+ *   bpmpc_telemetry_update: the stand-alone entry, as bpmpc_wbc_update is for the WBC.  x_opt [batch][12 + nj], rbd [batch][2 (6 + nj)]; t [batch],
+ *     safe [batch] and planned_mode [batch] are nullable.  Host arrays (inputs_on_device == 0) are copied first and the call synchronises; device
+ *     pointers are only enqueued on the handle's stream.  BPMPC_ERR_CAPACITY above max_batch.
+ *   bpmpc_telemetry_configure: every >= 1 (else BPMPC_ERR_INVALID_ARGUMENT) and freeze_on_unsafe, from the next update on; 1 and on after create.
+ *   bpmpc_telemetry_reset: for the robots with mask[b] != 0 (NULL: every robot below batch) n = 0, not frozen, the statistics and the last sample
+ *     cleared, the ring empty; the other robots do not change by one bit.  With a device mask the call only enqueues: the (safe == 0) mask of
+ *     bpmpc_controller_restart restarts the robot and its record.
+ *   bpmpc_telemetry_device_outputs: where the last sample [max_batch][stride], the statistics [max_batch][40] and the frozen flags [max_batch] live.
+ *   bpmpc_telemetry_get_stats: host copies for the first `batch` robots, each nullable; synchronises the handle's stream.
+ *   bpmpc_telemetry_fetch_ring: for robots[0 .. n_robots) (NULL: the robots 0 .. batch - 1, n_robots ignored) host_counts[r] <= ring_len samples
+ *     into host_samples [n_robots][ring_len][stride] (nullable), oldest first, the slots behind the count untouched; synchronises.  A robot index
+ *     outside [0, batch): BPMPC_ERR_INVALID_ARGUMENT.
+ *   bpmpc_controller_attach_telemetry (NULL detaches): while attached, every bpmpc_controller_tick and bpmpc_controller_tick_estimated enqueues
+ *     the telemetry's kernel behind the tick's commands on the controller's stream (the solver's, or the attached policy buffer's), on the tick's
+ *     own device buffers: t, x_opt, the measured rbd the tick ran on, safe and planned_mode.  It adds no synchronise and copies nothing to the
+ *     host; the tick's outputs are bit for bit those of a detached tick.  The handle's stream and the controller's are ordered by events, so a
+ *     stand-alone update, a reset or a read may follow a tick without a synchronise.  BPMPC_ERR_INVALID_ARGUMENT for a handle of another robot or
+ *     on another device, BPMPC_ERR_CAPACITY for a tick whose batch exceeds the handle's max_batch.  Detach before the handle is destroyed.
+ *   the loop, with the record restarted beside the robot:
+ *       bpmpc_plant_step_controlled -> bpmpc_estimator_update_from_plant -> bpmpc_controller_tick_estimated (the sample is taken here)
+ *       on a fall: bpmpc_controller_restart(mask = (safe == 0)); read bpmpc_telemetry_fetch_ring of the fallen robots; bpmpc_telemetry_reset(mask)
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_TELEMETRY_SAMPLE_STRIDE(nj) (40 + 2 * (nj))
+#define BPMPC_TELEMETRY_STATS_STRIDE 40
+typedef struct bpmpc_telemetry bpmpc_telemetry;
+int bpmpc_telemetry_create(const bpmpc_model* model, int device, int max_batch, int ring_len, bpmpc_telemetry** out);
+void bpmpc_telemetry_destroy(bpmpc_telemetry* telemetry);
+int bpmpc_telemetry_dims(const bpmpc_telemetry* telemetry, int* sample_stride, int* stats_stride, int* ring_len);
+int bpmpc_telemetry_update(bpmpc_telemetry* telemetry, int batch, const double* t, const double* x_opt, const double* rbd, const int* safe,
+                           const int* planned_mode, int inputs_on_device);
+int bpmpc_telemetry_configure(bpmpc_telemetry* telemetry, int every, int freeze_on_unsafe);
+int bpmpc_telemetry_reset(bpmpc_telemetry* telemetry, int batch, const int* mask, int inputs_on_device);
+int bpmpc_telemetry_device_outputs(bpmpc_telemetry* telemetry, double** sample, double** stats, int** frozen);
+int bpmpc_telemetry_get_stats(bpmpc_telemetry* telemetry, int batch, double* host_stats, int* host_frozen);
+int bpmpc_telemetry_fetch_ring(bpmpc_telemetry* telemetry, int batch, const int* robots, int n_robots, double* host_samples, int* host_counts);
+int bpmpc_controller_attach_telemetry(bpmpc_controller* controller, bpmpc_telemetry* telemetry);
+
 #ifdef __cplusplus
 }
 #endif

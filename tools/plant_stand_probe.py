@@ -9,7 +9,10 @@ tick after which a robot's state is not finite (ticks_run, state_finite; that ro
 its outcome.  Each run is a child process of its own under a time limit (--limit seconds); a run that fails or runs out of time
 ends the probe.  One JSON line per run on stdout; --out appends them to a file (profiles/plant_stand_probe.jsonl is where the published one
 belongs).
-usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--commit ID] [--out FILE]
+--telemetry RING_LEN attaches a tracking-telemetry handle (BatchedTelemetry) with a ring of RING_LEN samples to the controller after the first
+tick and appends, per run, one line to --telemetry-out (profiles/plant_stand_telemetry.jsonl): the statistics of all robots and the ring of the
+first robot that froze (it went unsafe or its state stopped being finite), otherwise of the robot with the largest joint error.
+usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--telemetry RING_LEN [--telemetry-every N]] [--commit ID] [--out FILE]
 """
 import argparse
 import json
@@ -24,7 +27,7 @@ if ROOT not in sys.path:
 PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
 
 
-def run(kt, B, seconds):
+def run(kt, B, seconds, ring_len=None, every=1):
     import numpy as np
     import torch
     import bipedal_control_amd as bp
@@ -73,6 +76,11 @@ def run(kt, B, seconds):
     arm(0.0, True)
     torch.cuda.synchronize()
     ctrl.tick(torch.zeros(B, dtype=torch.float64, device="cuda"), plant.outputs()["rbd"].torch(), period=PERIOD, fetch=False)
+    tel = None
+    if ring_len is not None:
+        tel = bp.BatchedTelemetry(itf, B, ring_len=ring_len)
+        tel.configure(every=every)
+        ctrl.attachTelemetry(tel)
     first_unsafe = [None] * B
     lowest = np.full(B, np.inf)
     drift = np.zeros(B)
@@ -101,14 +109,43 @@ def run(kt, B, seconds):
             if first_unsafe[b] is None and safe[b] == 0:
                 first_unsafe[b] = k
     anchored = plant.anchors()[1]
-    return dict(robot="h1", batch=B, seconds=seconds, ticks_run=k + 1, period=PERIOD, substeps=SUBSTEPS, rearm_every=REARM, kt=float(plant.getStiction(0)),
+    record = None
+    if tel is not None:
+        record = telemetry_record(tel, B, kt=float(plant.getStiction(0)), seconds=seconds, ticks_run=k + 1, period=PERIOD, every=every)
+        ctrl.attachTelemetry(None)
+    return record, dict(robot="h1", batch=B, seconds=seconds, ticks_run=k + 1, period=PERIOD, substeps=SUBSTEPS, rearm_every=REARM, kt=float(plant.getStiction(0)),
                 state_finite=finite, first_unsafe_tick=first_unsafe, lowest_base_height=num(lowest), final_base_height=num(rbd[:, 5]),
                 start_base_height=num(rbd0[:, 5]), largest_foot_drift=num(drift), anchored_at_end=[int(x) for x in anchored.sum(axis=1)])
+
+
+def telemetry_record(tel, B, **head):
+    """The statistics of all robots and one robot's ring, oldest sample first, as plain lists (null for a value that is not finite)."""
+    import numpy as np
+    import bipedal_control_amd as bp
+
+    def plain(a):
+        a = np.asarray(a)
+        return [plain(x) for x in a] if a.ndim else (int(a) if a.dtype.kind in "iu" else (float(a) if np.isfinite(a) else None))
+
+    s = tel.stats(B)
+    frozen = np.flatnonzero(s["frozen"])
+    if len(frozen):
+        robot, why = int(frozen[np.argmin(s["first_unsafe"][frozen])]), "the first robot that froze"
+    else:
+        robot, why = int(np.argmax(s["joint_max"].max(axis=1))), "no robot froze: the robot with the largest joint error"
+    ring = tel.ring([robot], batch=B)
+    n = int(ring["count"][0])
+    fields = {k: plain(v[0, :n]) for k, v in ring.items() if k not in ("samples", "count")}
+    return dict(head, robot="h1", batch=B, ring_len=tel.ring_len, groups=list(bp.TelemetrySample.GROUPS),
+                stats={k: plain(v) for k, v in s.items() if k != "rows"}, ring_robot=robot, ring_choice=why, ring_count=n, ring=fields)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--telemetry", type=int, metavar="RING_LEN", help="attach a telemetry handle with a ring of RING_LEN samples and write its record")
+    ap.add_argument("--telemetry-every", type=int, default=1, help="every how many ticks a sample goes into the ring")
+    ap.add_argument("--telemetry-out", default=os.path.join(ROOT, "profiles", "plant_stand_telemetry.jsonl"))
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--kts", default="0,kn")
     ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
@@ -117,15 +154,23 @@ def main():
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.child is not None:
-        line = run(a.child, a.batch, a.seconds)
+        record, line = run(a.child, a.batch, a.seconds, a.telemetry, a.telemetry_every)
         if a.commit:
             line["commit"] = a.commit
+        if record is not None:
+            if a.commit:
+                record["commit"] = a.commit
+            os.makedirs(os.path.dirname(os.path.abspath(a.telemetry_out)), exist_ok=True)
+            with open(a.telemetry_out, "a") as f:
+                f.write(json.dumps(record) + "\n")
         print(json.dumps(line), flush=True)
         return 0
     lines = []
     kts = a.kts.split(",")
     for kt in kts:
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch)]
+        if a.telemetry is not None:
+            cmd += ["--telemetry", str(a.telemetry), "--telemetry-every", str(a.telemetry_every), "--telemetry-out", a.telemetry_out]
         r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
         if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
             print("plant_stand_probe: kt = %s ended with status %d; stopping" % (kt, r.returncode), file=sys.stderr)
