@@ -1189,6 +1189,129 @@ class BatchedTelemetry(_Handle):
                 "frozen": DeviceArray(C.cast(f, C.c_void_p).value, (B,), "<i4")}
 
 
+class PlanNode:
+    """The fields of a node row of the plan geometry (include/bpmpc.h "Plan geometry"): STRIDE doubles; FIELDS maps a name to its
+    (offset, shape); split(rows) slices rows [..., STRIDE] into a dict of named arrays.  SUMMARY names the entries of a summary row and FOOTHOLD
+    those of a foothold entry the same way."""
+
+    STRIDE, MAX_FOOTHOLDS, FOOTHOLD_STRIDE, SUMMARY_STRIDE = 24, 16, 6, 16
+    FIELDS = {"base_pos": (0, (3,)), "contact_pos": (3, (4, 3)), "cop": (15, (3,)), "t": (18, ()), "mode": (19, ()), "kind": (20, ()), "sum_z": (21, ()),
+              "contact_mask": (22, ()), "not_finite": (23, ())}
+    FOOTHOLD = {"t": (0, ()), "contact": (1, ()), "pos": (2, (3,)), "node": (5, ())}
+    SUMMARY = {"n_nodes": (0, ()), "footholds": (1, ()), "base_path_length": (2, ()), "apex": (3, (4,)), "stance_drift": (7, (4,)), "min_sum_z": (11, ()),
+               "not_finite": (12, ()), "reserved": (13, (3,))}
+
+    @staticmethod
+    def _split(rows, fields, stride):
+        rows = np.asarray(rows, float)
+        if rows.shape[-1] != stride:
+            raise ValueError("a row of %d entries was expected, got %d" % (stride, rows.shape[-1]))
+        return {k: rows[..., off:off + int(np.prod(shp, dtype=int))].reshape(rows.shape[:-1] + shp) for k, (off, shp) in fields.items()}
+
+    @classmethod
+    def split(cls, rows):
+        return cls._split(rows, cls.FIELDS, cls.STRIDE)
+
+    @classmethod
+    def split_footholds(cls, entries):
+        return cls._split(entries, cls.FOOTHOLD, cls.FOOTHOLD_STRIDE)
+
+    @classmethod
+    def split_summary(cls, rows):
+        return cls._split(rows, cls.SUMMARY, cls.SUMMARY_STRIDE)
+
+
+class PlanGeometry(_Handle):
+    """BipedalControllerVisualizer::update (bipedal_controllers/src/BipedalControllerVisualizer.cpp:73-87) for a batch of robots, kept on the
+    device (bpmpc_plan): for every node of a plan the base position, the four contact points, the centre of pressure and the contact forces'
+    sum; the future footholds; a summary row per robot.  A plan comes from a solver (update), from the front slot of a PolicyBuffer
+    (update_from_policy) or from arrays (update_arrays); nothing reaches the host until nodes(), footholds() or summary() ask for it."""
+
+    _DESTROY = "bpmpc_plan_destroy"
+
+    def __init__(self, interface, max_batch, max_nodes, device=0):
+        self.interface, self.max_batch, self.max_nodes = interface, int(max_batch), int(max_nodes)
+        self.nj = interface.actuatedDofNum
+        super().__init__()
+        _check(load_library().bpmpc_plan_create(interface.handle, int(device), self.max_batch, self.max_nodes, C.byref(self._h)))
+        self.batch = self.max_batch
+
+    def configure(self, launches=0):
+        """How an update is launched: 1 one kernel, 2 a kernel over the node tiles and one for footholds and summary, 0 the handle chooses."""
+        self._call("bpmpc_plan_configure", int(launches))
+
+    def update(self, solver):
+        """The current iterate of the solver's last setup (after a run: the solution), enqueued on the solver's stream; nothing synchronises."""
+        self._call("bpmpc_plan_update_from_solver", solver._h)
+        self.batch = solver.batch
+
+    def update_from_policy(self, buffer):
+        """The front slot of a PolicyBuffer, enqueued on the buffer's stream; the desired block is not written."""
+        self._call("bpmpc_plan_update_from_policy", buffer._h)
+        self.batch = buffer.mpc.batch
+
+    def update_arrays(self, n_nodes, t, x, mode, kind, u=None, xref=None):
+        """A plan per robot with the handle's strides, N = max_nodes: n_nodes [B], t [B, N + 1], x [B, N + 1, nx], mode and kind [B, N],
+        u [B, N, nu] and xref [B, N, nx] (each of the last two may be None).  numpy arrays (the call synchronises), or float64 / int32 device
+        arrays - torch tensors or DeviceArray - which are only enqueued on the handle's stream."""
+        B, N, nx = _shape(n_nodes)[0], self.max_nodes, 12 + self.nj
+        (np_, tp, xp, up, mp, kp, rp), dev, keep = _restart_args(
+            (n_nodes, C.c_int, B), (t, C.c_double, B * (N + 1)), (x, C.c_double, B * (N + 1) * nx), (u, C.c_double, B * N * nx), (mode, C.c_int, B * N),
+            (kind, C.c_int, B * N), (xref, C.c_double, B * N * nx))
+        self._call("bpmpc_plan_update", B, np_, tp, xp, up, mp, kp, rp, dev)
+        del keep
+        self.batch = B
+
+    def outputs(self):
+        """Where the outputs live: a dict of DeviceArray - optimized and desired [max_batch, N + 1, 24], footholds [max_batch, 16, 6], summary
+        [max_batch, 16], foothold_count [max_batch]."""
+        o = abi._PlanOutputs()
+        self._call("bpmpc_plan_device_outputs", C.byref(o))
+        B, K = self.max_batch, self.max_nodes + 1
+        ptr = lambda p: C.cast(p, C.c_void_p).value      # noqa: E731
+        return {"optimized": DeviceArray(ptr(o.optimized), (B, K, PlanNode.STRIDE), "<f8"), "desired": DeviceArray(ptr(o.desired), (B, K, PlanNode.STRIDE), "<f8"),
+                "footholds": DeviceArray(ptr(o.footholds), (B, PlanNode.MAX_FOOTHOLDS, PlanNode.FOOTHOLD_STRIDE), "<f8"),
+                "summary": DeviceArray(ptr(o.summary), (B, PlanNode.SUMMARY_STRIDE), "<f8"), "foothold_count": DeviceArray(ptr(o.foothold_count), (B,), "<i4")}
+
+    def nodes(self, which="optimized", batch=None):
+        """The node rows [B, N + 1, 24] of the first B robots (None: the batch of the last update; synchronises): which = "optimized" or
+        "desired".  PlanNode.split names the entries; rows beyond a robot's n_nodes hold what they held before."""
+        B = int(batch or self.batch)
+        rows = np.zeros((B, self.max_nodes + 1, PlanNode.STRIDE))
+        self._call("bpmpc_plan_get_nodes", B, {"optimized": 0, "desired": 1}[which], _d(rows))
+        return rows
+
+    def footholds(self, batch=None):
+        """(entries [B, 16, 6], count [B]): the future footholds (t, contact point, x, y, z, node) in the order (node, contact point); count is
+        the true number, of which the first 16 are stored.  Synchronises."""
+        B = int(batch or self.batch)
+        entries, count = np.zeros((B, PlanNode.MAX_FOOTHOLDS, PlanNode.FOOTHOLD_STRIDE)), np.zeros(B, np.int32)
+        self._call("bpmpc_plan_get_footholds", B, _d(entries), _i(count))
+        return entries, count
+
+    def summary(self, batch=None):
+        """The summary rows [B, 16] (PlanNode.split_summary names the entries).  Synchronises."""
+        B = int(batch or self.batch)
+        rows = np.zeros((B, PlanNode.SUMMARY_STRIDE))
+        self._call("bpmpc_plan_get_summary", B, _d(rows))
+        return rows
+
+    @staticmethod
+    def rows_host(interface, t, x, mode, kind, u=None):
+        """bpmpc_plan_rows_host: (rows [n + 1, 24], footholds [16, 6], count, summary [16]) of one robot on the host, no device: t [n + 1],
+        x [n + 1, nx], mode and kind [n], u [n, nu] or None."""
+        t, x = _f64(t).reshape(-1), _f64(x)
+        n = t.size - 1
+        mode, kind = np.ascontiguousarray(mode, np.int32).reshape(-1), np.ascontiguousarray(kind, np.int32).reshape(-1)
+        nx = 12 + interface.actuatedDofNum
+        if x.shape != (n + 1, nx) or mode.size != n or kind.size != n or (u is not None and np.shape(u) != (n, nx)):
+            raise ValueError("a plan of %d nodes needs t [%d], x [%d, %d], mode and kind [%d], u [%d, %d] or None" % (n, n + 1, n + 1, nx, n, n, nx))
+        u = None if u is None else _f64(u)
+        rows, foot, count, summ = np.zeros((n + 1, PlanNode.STRIDE)), np.zeros((PlanNode.MAX_FOOTHOLDS, PlanNode.FOOTHOLD_STRIDE)), C.c_int(0), np.zeros(PlanNode.SUMMARY_STRIDE)
+        _check(load_library().bpmpc_plan_rows_host(interface.handle, n, _d(t), _d(x), _d(u), _i(mode), _i(kind), _d(rows), _d(foot), C.byref(count), _d(summ)))
+        return rows, foot, count.value, summ
+
+
 class PlantParams:
     """A parameter row of the plant (include/bpmpc.h "Plant", BPMPC_PLANT_PARAM_STRIDE) with named fields: contact stiffness kn [N/m], normal damping
     cn [N s/m], the penetration d0 [m] at which the normal damping is fully on, friction coefficient mu, the velocity v_eps [m/s] that regularises

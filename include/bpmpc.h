@@ -881,6 +881,112 @@ int bpmpc_telemetry_get_stats(bpmpc_telemetry* telemetry, int batch, double* hos
 int bpmpc_telemetry_fetch_ring(bpmpc_telemetry* telemetry, int batch, const int* robots, int n_robots, double* host_samples, int* host_counts);
 int bpmpc_controller_attach_telemetry(bpmpc_controller* controller, bpmpc_telemetry* telemetry);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Plan geometry = BipedalControllerVisualizer::update (bipedal_controllers/src/BipedalControllerVisualizer.cpp:73-87, and its twin
+ * ocs2_bipedal_robot_ros/src/visualization/BipedalRobotVisualizer.cpp) for a BATCH of robots, kept on the device: a plan - the centroidal states
+ * and inputs on a shooting grid - turned into task-space quantities for EVERY node: the base path, the paths of the four contact points, the
+ * centre of pressure, the contact forces' sum; where the plan puts the feet down next (FUTURE FOOTHOLDS); and a SUMMARY row per robot, so that a
+ * fleet can be watched without moving node rows.  Nothing reaches the host unless it is asked for.  A process that never creates the handle
+ * launches nothing of this.  N = max_nodes of the handle; every output has the leading dimension max_batch.
+ *   node rows, two blocks [max_batch][N + 1][BPMPC_PLAN_NODE_STRIDE = 24] doubles, OPTIMIZED (from the states x) and DESIRED (from the node
+ *   references xref).  Row of robot b, node k <= n_nodes[b]:
+ *       0..2      base position x_k[6:9]
+ *       3..14     world positions of the model's four contact points at q = x_k[6:12 + nj]; tree, contact frames and order are the WBC's, as in
+ *                 the tracking telemetry
+ *       15..17    centre of pressure: sum_z = ((fz_0 + fz_1) + fz_2) + fz_3 with fz_i = u_k[3 i + 2]; with sum_z > 0 per component
+ *                 ((w_0 p_0 + w_1 p_1) + w_2 p_2) + w_3 p_3, w_i = fz_i / sum_z, over all four points; else 0.  This is getCenterOfPressureMarker
+ *                 of VisualizationHelpers.h as recalled ([OCS2-upstream], unpinned: the file is not part of the reference tree)
+ *       18        t_k
+ *       19        mode of node k (the entry of the grid's mode table; -1 for the last node, which has none)
+ *       20        kind of node k (0 intermediate, 1 pre-event; -1 for the last node)
+ *       21        sum_z
+ *       22        the contact flags of the mode as a bit mask, bit i for contact point i (points 0, 1 the left foot, 2, 3 the right foot: modes
+ *                 FLY 0, LF 3, RF 12, STANCE 15; 0 for the last node)
+ *       23        1 when an entry of the node's state (any of its 12 + nj) is not finite, else 0.  The entries 0..17 of such a row are unspecified
+ *     The last node has no input: its entries 15..17 and 21 are 0, as are those of a plan without inputs (u == NULL).  Rows beyond n_nodes[b] and
+ *     robots beyond the batch are not written.  Sums of products are formed without multiply-add contraction.
+ *     The desired block is publishDesiredTrajectory (:170-228) evaluated at the SHOOTING NODES instead of at the points of the target trajectories:
+ *     the same row with xref in the place of x, entries 15..17 and 21 zero.  A reference exists for the nodes that carry a cost, 0 .. n_nodes - 1;
+ *     the desired row of node n_nodes is not written.  A source without references (a policy slot, xref == NULL) leaves the block as it is.
+ *   future footholds, [max_batch][BPMPC_PLAN_MAX_FOOTHOLDS = 16][6] doubles (t, contact point i, x, y, z, node index) and count[max_batch]:
+ *     publishOptimizedStateTrajectory (:277-309) on the grid tables.  Every node k with kind 1 and t_0 < t_k < t_{n_nodes} (strict, as tStart <
+ *     eventTimes[event] < tEnd) is an event inside the horizon.  pre = the mode of the nearest intermediate node (kind 0) before k, post = that of the
+ *     nearest intermediate node after k, both among the nodes 0 .. n_nodes - 1; without either there is no foothold.  Every contact point with
+ *     !flag(pre, i) && flag(post, i) gives one entry, taken from the optimized row of node k + 1, the POST-EVENT node: its time, i, its contact
+ *     point i, k + 1.  (The reference interpolates its time trajectory at the event time, where two entries share one time; here the post-event
+ *     node is taken.)  Entries are ordered by (k, i).  count is the true number; only the first 16 entries are stored, and slots behind the count
+ *     keep what they held.
+ *   summary, [max_batch][BPMPC_PLAN_SUMMARY_STRIDE = 16] doubles from the optimized rows of the nodes 0 .. n_nodes:
+ *       0         n_nodes (a device n_nodes as clamped)
+ *       1         the foothold count
+ *       2         base path length, the sum of sqrt((dx dx + dy dy) + dz dz) over consecutive nodes k, k + 1
+ *       3..6      apex of each contact point: the largest z over the nodes
+ *       7..10     stance drift of each contact point: the largest sqrt(dx dx + dy dy) between two consecutive nodes whose modes both hold the
+ *                 point in contact (the masks of entry 22; 0 when there are none)
+ *       11        the smallest sum_z over the intermediate nodes whose mode has a contact (0 when there are none)
+ *       12        the number of rows flagged not finite
+ *       13..15    reserved, 0
+ *     A flagged row is counted in entry 12 and takes part in nothing else, nor does a path segment or a drift with a flagged end.  Comparisons
+ *     are > and <: a sum_z that is not a number changes nothing.  Order: 64 accumulators; node k, k ascending, updates accumulator k mod 64 (its
+ *     segment and drift are those to node k + 1); the path length is the sum of the accumulators' path lengths, accumulator 0, 1, .. 63; maxima,
+ *     minimum and count are exact in any order.  An apex or minimum that nothing contributed to is 0.
+ *   sources of a plan.  All describe it alike: x [.][in_N + 1][nx], u [.][in_N][nu], node times [.][in_N + 1], kinds and modes [.][in_N], a node
+ *   count, and a grid index per robot.
+ *     bpmpc_plan_update_from_solver: the current iterate of the solver's last setup (after a run: the solution), its grid tables through the
+ *       robots' grid indices, and its node references.  Enqueued on the SOLVER's stream behind what is there; the handle's stream and the solver's
+ *       are ordered by events, so a read may follow without a synchronise; nothing is copied to the host and nothing synchronises.  The solver's
+ *       arrays do not change.  BPMPC_ERR_INVALID_ARGUMENT: no setup yet, a solver of another robot or on another device; BPMPC_ERR_CAPACITY: the
+ *       batch of the setup above max_batch, the solver's max_nodes above N; BPMPC_ERR_UNSUPPORTED: the DDP solver (its solution lives on the time
+ *       points of its own roll-out).
+ *     bpmpc_plan_update_from_policy: the FRONT slot of a policy buffer, what the ticks run on, on the BUFFER's stream, ordered the same way; the
+ *       grid index is the identity.  A slot holds no references: the desired block is not written.  BPMPC_ERR_INVALID_ARGUMENT until the buffer
+ *       holds an adopted policy for every robot (as a buffered tick) and for another robot or device; BPMPC_ERR_CAPACITY as above.
+ *     bpmpc_plan_update: the stand-alone entry, as bpmpc_telemetry_update.  One row per robot with the HANDLE's strides: n_nodes [batch],
+ *       t [batch][N + 1], x [batch][N + 1][nx], u [batch][N][nu] nullable, mode and kind [batch][N], xref [batch][N][nx] nullable.  Host arrays
+ *       (inputs_on_device == 0) are copied first and the call synchronises; device pointers are only enqueued on the handle's stream.  A host
+ *       n_nodes outside 1 .. N is refused (BPMPC_ERR_INVALID_ARGUMENT, "n_nodes[b]" in bpmpc_last_error()) before anything is enqueued; a device
+ *       n_nodes is clamped into 0 .. N by the kernel.  BPMPC_ERR_CAPACITY above max_batch.
+ *   bpmpc_plan_create: max_batch < 1 or max_nodes < 1: BPMPC_ERR_INVALID_ARGUMENT, before a device is looked for; BPMPC_ERR_NO_DEVICE without a
+ *     GPU.  The outputs start as zeros.  The handle owns a stream.  Destroy it before the solvers and buffers it was updated from.
+ *   bpmpc_plan_dims: max_batch, N and the three strides, each nullable.
+ *   bpmpc_plan_configure: how an update is launched - 1: one kernel, a workgroup per robot; 2: a kernel over the node tiles and a second one for
+ *     footholds and summary; 0 (after create): the handle chooses.  The outputs do not depend on it.
+ *   bpmpc_plan_device_outputs: where the outputs live.
+ *   bpmpc_plan_get_nodes (which: 0 optimized, 1 desired; [batch][N + 1][24]), bpmpc_plan_get_footholds ([batch][16][6], [batch]) and
+ *     bpmpc_plan_get_summary ([batch][16]): host copies for the first `batch` robots, each pointer nullable; they synchronise the handle's stream.
+ *   bpmpc_plan_rows_host: host only, no device: rows [n_nodes + 1][24], footholds [16][6], count [1] and summary [16] (each nullable) of ONE robot
+ *     from t [n_nodes + 1], x [n_nodes + 1][nx], u [n_nodes][nu] (nullable), mode and kind [n_nodes], compiled from the text the kernels are
+ *     compiled from; the sines and cosines are the host library's.
+ *   Null handles and required pointers: BPMPC_ERR_INVALID_ARGUMENT ("null" and the function's name in bpmpc_last_error()).
+ *   Not reproduced: the tf broadcast and joint states (:133-162 publishes the observation; node 0 of a plan that starts at the observation holds
+ *     its base and contact points), marker colours and scales, the support-polygon message, the rate limit of maxUpdateFrequency.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_PLAN_NODE_STRIDE 24
+#define BPMPC_PLAN_MAX_FOOTHOLDS 16
+#define BPMPC_PLAN_SUMMARY_STRIDE 16
+typedef struct bpmpc_plan bpmpc_plan;
+typedef struct {
+  double* optimized;      /* [max_batch][N + 1][24] */
+  double* desired;        /* [max_batch][N + 1][24] */
+  double* footholds;      /* [max_batch][16][6] */
+  double* summary;        /* [max_batch][16] */
+  int* foothold_count;    /* [max_batch] */
+} bpmpc_plan_outputs;
+int bpmpc_plan_create(const bpmpc_model* model, int device, int max_batch, int max_nodes, bpmpc_plan** out);
+void bpmpc_plan_destroy(bpmpc_plan* plan);
+int bpmpc_plan_dims(const bpmpc_plan* plan, int* max_batch, int* max_nodes, int* node_stride, int* max_footholds, int* summary_stride);
+int bpmpc_plan_configure(bpmpc_plan* plan, int launches);
+int bpmpc_plan_update_from_solver(bpmpc_plan* plan, bpmpc_solver* solver);
+int bpmpc_plan_update_from_policy(bpmpc_plan* plan, bpmpc_policy* policy);
+int bpmpc_plan_update(bpmpc_plan* plan, int batch, const int* n_nodes, const double* t, const double* x, const double* u, const int* mode,
+                      const int* kind, const double* xref, int inputs_on_device);
+int bpmpc_plan_device_outputs(bpmpc_plan* plan, bpmpc_plan_outputs* out);
+int bpmpc_plan_get_nodes(bpmpc_plan* plan, int batch, int which, double* host_rows);
+int bpmpc_plan_get_footholds(bpmpc_plan* plan, int batch, double* host_entries, int* host_counts);
+int bpmpc_plan_get_summary(bpmpc_plan* plan, int batch, double* host_rows);
+int bpmpc_plan_rows_host(const bpmpc_model* model, int n_nodes, const double* t, const double* x, const double* u, const int* mode, const int* kind,
+                         double* rows, double* footholds, int* count, double* summary);
+
 #ifdef __cplusplus
 }
 #endif
