@@ -65,11 +65,16 @@ class _PlanOutputs(C.Structure):
     _fields_ = [("optimized", _dp), ("desired", _dp), ("footholds", _dp), ("summary", _dp), ("foothold_count", _ip)]
 
 
+class _SupervisorOutputs(C.Structure):
+    _fields_ = [(n, _dp) for n in ("pos_des", "vel_des", "tau_ff", "kp", "kd")] + [(n, _ip) for n in ("state", "cause", "unsafe", "ready", "counts")] + \
+               [("elapsed", _dp), ("stream", C.c_void_p)]
+
+
 # every `typedef struct { ... } bpmpc_X;` of the header and its mirror: what a `bpmpc_X*` parameter is bound to
 MIRRORS = {"bpmpc_settings": _Settings, "bpmpc_mode_schedule": _Schedule, "bpmpc_target": _Target, "bpmpc_stats": Stats,
            "bpmpc_gait_template": _GaitTemplate, "bpmpc_tick_outputs": _TickOutputs, "bpmpc_sensor_inputs": _SensorInputs,
            "bpmpc_estimator_outputs": _EstimatorOutputs, "bpmpc_joint_command": _JointCommand, "bpmpc_plant_outputs": _PlantOutputs,
-           "bpmpc_plan_outputs": _PlanOutputs}
+           "bpmpc_plan_outputs": _PlanOutputs, "bpmpc_supervisor_outputs": _SupervisorOutputs}
 
 # (base type, pointer depth) of a declaration without its const; void is a return type only
 _CTYPES = {("int", 0): C.c_int, ("double", 0): C.c_double, ("long", 0): C.c_long, ("char", 1): C.c_char_p, ("double", 1): _dp, ("int", 1): _ip,

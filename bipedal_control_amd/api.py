@@ -19,7 +19,7 @@ import numpy as np
 
 from . import abi
 from .abi import (Stats, _dp, _EstimatorOutputs, _GaitTemplate, _ip, _JointCommand, _PlantOutputs, _Schedule, _SensorInputs, _Settings,  # noqa: F401
-                  _Target, _TickOutputs)
+                  _SupervisorOutputs, _Target, _TickOutputs)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -1422,6 +1422,14 @@ class BatchedPlant(_Handle):
         self._call("bpmpc_plant_step_controlled", controller._h, B, period, int(substeps), fp, gp, dev)
         del keep
 
+    def step_supervised(self, supervisor, base_force=None, feet_heights=None, period=0.002, substeps=4):
+        """One control step on the commands of the last update of `supervisor` (BatchedSupervisor), read on the device; ordered by events like
+        step_controlled."""
+        B = self.batch
+        (fp, gp), dev, keep = _restart_args((base_force, C.c_double, B * 3), (feet_heights, C.c_double, B * 4))
+        self._call("bpmpc_plant_step_supervised", supervisor._h, B, period, int(substeps), fp, gp, dev)
+        del keep
+
     def outputs(self):
         """The outputs of the last step where they live: a dict of DeviceArray (`.torch()` wraps one without a copy) over the batch of the last
         set_state - the sensors of BatchedStateEstimate.update by name (joint_pos, joint_vel, quat, angular_vel_local, linear_accel_local, contact,
@@ -1519,6 +1527,164 @@ class BatchedPlant(_Handle):
         shapes = {"joint_pos": (B, nj), "joint_vel": (B, nj), "quat": (B, 4), "angular_vel_local": (B, 3), "linear_accel_local": (B, 3), "contact": (B, 4),
                   "feet_heights": (B, 4), "odom_pos": (B, 3), "odom_quat": (B, 4), "odom_lin_vel": (B, 3), "odom_ang_vel": (B, 3)}
         return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k == "contact" else "<f8") for k, shp in shapes.items()}
+
+
+class SupervisorParams:
+    """A parameter row of the supervisor (include/bpmpc.h "Supervisor", BPMPC_SUP_PARAM_STRIDE) with named fields: the tilt limit [rad] of
+    SafetyChecker, the base height [m] below which a robot is unsafe (0: no limit), the time [s] over which INIT ramps from the latched joints
+    to q_init (0: the reference's jump), the settle test's position [rad] and velocity [rad/s] tolerances and the time [s] it must hold, and
+    the damping gain of a stopped robot.  The defaults are the values without arguments."""
+
+    STRIDE = 8
+    FIELDS = ("tilt_limit", "min_base_height", "ramp_time", "settle_pos_tol", "settle_vel_tol", "settle_time", "stop_kd")
+    DEFAULTS = (np.pi / 3.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name, default in zip(self.FIELDS, self.DEFAULTS):
+            setattr(self, name, float(fields.get(name, default)))
+
+    @classmethod
+    def fromRow(cls, row):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
+
+    def toRow(self):
+        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0])
+
+
+class BatchedSupervisor(_Handle):
+    """Which controller drives which robot of a batch, decided on the device (bpmpc_supervisor; include/bpmpc.h "Supervisor" is its
+    specification): InitialJointPositionController (state INIT), SafetyChecker with stopRequest (RUN to STOPPED) and the operator's switch
+    script (request).  taskFile (None: the interface's) is read for the keys supervisor.<name>."""
+
+    _DESTROY = "bpmpc_supervisor_destroy"
+    INIT, RUN, STOPPED = 0, 1, 2
+    JOINT_ROWS = ("q_init", "kp_init", "kd_init", "lower", "upper")
+    COUNTS = ("init", "run", "stopped", "ready", "unsafe")
+
+    def __init__(self, interface, max_batch=1, taskFile=None, device=0):
+        self.interface, self.max_batch = interface, int(max_batch)
+        self.nj = interface.actuatedDofNum
+        super().__init__()
+        _check(load_library().bpmpc_supervisor_create(interface.handle, str(taskFile or interface.taskFile).encode(), int(device), self.max_batch,
+                                                      C.byref(self._h)))
+        self.batch = self.max_batch
+
+    def update(self, rbd, run_cmd=None, period=0.002):
+        """One update of B = len(rbd) robots: rbd [B, 2 (6 + nj)]; run_cmd None or (pos_des, vel_des, tau_ff, kp, kd), [B, nj] each, the command a
+        robot in RUN passes on.  numpy arrays (the call synchronises) or float64 device arrays - torch tensors or DeviceArray, e.g.
+        BatchedPlant.outputs()["rbd"] - which are only enqueued on the supervisor's stream."""
+        B = _shape(rbd)[0]
+        specs = [(rbd, C.c_double, B * 2 * (6 + self.nj))] + [(a, C.c_double, B * self.nj) for a in (run_cmd or ())]
+        if run_cmd is not None and len(run_cmd) != 5:
+            raise ValueError("run_cmd is (pos_des, vel_des, tau_ff, kp, kd)")
+        ptrs, dev, keep = _restart_args(*specs)
+        cmd = _JointCommand(*ptrs[1:]) if run_cmd is not None else None
+        self._call("bpmpc_supervisor_update", B, ptrs[0], None if cmd is None else C.byref(cmd), dev, float(period))
+        del keep
+        self.batch = B
+
+    def update_controlled(self, controller, estimator=None, rbd=None, period=0.002):
+        """One update on the last tick of `controller` (BatchedController), read on the device, and on the rbd of `estimator`
+        (BatchedStateEstimate) or, without one, on the float64 device array rbd [B, 2 (6 + nj)]; the streams are ordered by events and nothing
+        synchronises.  B is the batch of the controller's last tick."""
+        B = controller.mpc.batch
+        rp, keep = None, None
+        if estimator is None:
+            (rp,), dev, keep = _restart_args((rbd, C.c_double, B * 2 * (6 + self.nj)))
+            if not dev:
+                raise ValueError("update_controlled reads rbd on the device: pass a float64 device array, or an estimator")
+        self._call("bpmpc_supervisor_update_controlled", controller._h, None if estimator is None else estimator._h, rp, B, float(period))
+        del keep
+        self.batch = B
+
+    def request(self, target, mask=None, only_ready=False):
+        """Asks for the state `target` (INIT, RUN or STOPPED) for the robots with mask[b] != 0 (None: every robot): INIT and STOPPED apply to all
+        of them, RUN only to robots in INIT and with only_ready only to those that are ready; the others do not change by one bit.  A numpy
+        mask, or an int32 device tensor, which is only enqueued."""
+        B = self.max_batch if mask is None else _count(mask)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, B))
+        self._call("bpmpc_supervisor_request", B, mp, int(target), int(bool(only_ready)), dev)
+        del keep
+
+    getParams, setParams, resetParams = _param_methods(
+        "bpmpc_supervisor", SupervisorParams.STRIDE,
+        """The parameter row [8] of `robot` (SupervisorParams.fromRow names its entries), or with robot < 0 the values every row starts from.""",
+        """rows [8], [1, 8] or [B, 8]; mask as WeightedWbc.setParams.  numpy rows are validated (finite, not negative, tilt_limit positive) and
+        the call synchronises; device tensors are only enqueued, ordered before the next update.""",
+        """Every row back to the values it started from.""")
+
+    def _which(self, which):
+        return self.JOINT_ROWS.index(which) if isinstance(which, str) else int(which)
+
+    def setJointRows(self, which, rows, mask=None):
+        """The joint row `which` ("q_init", "kp_init", "kd_init", "lower", "upper" or 0..4) of the robots of `mask`: rows [nj], [1, nj] or [B, nj],
+        host (validated; lower <= upper against the robot's other limit, which may be infinite) or device, as setParams."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], self.nj, self.max_batch)
+        self._call("bpmpc_supervisor_set_joint_rows", B, mp, self._which(which), rp, n_rows, dev)
+        del keep
+
+    def getJointRows(self, which, robot=-1):
+        """The joint row `which` [nj] of `robot`, or with robot < 0 the values every row starts from; synchronises."""
+        row = np.zeros(self.nj)
+        self._call("bpmpc_supervisor_get_joint_rows", int(robot), self._which(which), _d(row))
+        return row
+
+    def state(self, batch=None, commands=False):
+        """Host copies for the first B robots (None: the batch of the last update; synchronises): state, cause, unsafe, ready [B] int32, elapsed
+        [B], counts = {"init", "run", "stopped", "ready", "unsafe"} of the last update; with commands=True also pos_des, vel_des, tau_ff, kp,
+        kd [B, nj]."""
+        B = int(batch or self.batch)
+        ints = {k: np.zeros(B, np.int32) for k in ("state", "cause", "unsafe", "ready")}
+        elapsed, counts = np.zeros(B), np.zeros(8, np.int32)
+        self._call("bpmpc_supervisor_get_state", B, *[_i(ints[k]) for k in ("state", "cause", "unsafe", "ready")], _d(elapsed), _i(counts))
+        out = dict(ints, elapsed=elapsed, counts=dict(zip(self.COUNTS, counts.tolist())))
+        if commands:
+            cmd = {k: np.zeros((B, self.nj)) for k in ("pos_des", "vel_des", "tau_ff", "kp", "kd")}
+            self._call("bpmpc_supervisor_get_commands", B, *[_d(a) for a in cmd.values()])
+            out.update(cmd)
+        return out
+
+    def outputs(self):
+        """The command rows [max_batch, nj], the per-robot flags [max_batch], the counters [8] and the clock `elapsed` where they live: a dict of
+        DeviceArray."""
+        o = _SupervisorOutputs()
+        self._call("bpmpc_supervisor_device_outputs", C.byref(o))
+        B = self.max_batch
+        views = {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, (B, self.nj), "<f8") for k in ("pos_des", "vel_des", "tau_ff", "kp", "kd")}
+        views.update({k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, (B,), "<i4") for k in ("state", "cause", "unsafe", "ready")})
+        views["counts"] = DeviceArray(C.cast(o.counts, C.c_void_p).value, (8,), "<i4")
+        views["elapsed"] = DeviceArray(C.cast(o.elapsed, C.c_void_p).value, (B,), "<f8")
+        return views
+
+    def stream(self):
+        """The supervisor's stream as an integer (a hipStream_t; torch.cuda.ExternalStream wraps it): what a caller that reads outputs() orders
+        its own work against."""
+        o = _SupervisorOutputs()
+        self._call("bpmpc_supervisor_device_outputs", C.byref(o))
+        return int(o.stream or 0)
+
+    @staticmethod
+    def rows_host(interface, params, joint_rows, rbd, flags, clocks, q_latch, run_cmd=None, period=0.002):
+        """One update of one robot on the host, from the text the kernel is compiled from (bpmpc_supervisor_rows_host; no device).  params [8],
+        joint_rows [5, nj], rbd [2 (6 + nj)], flags = (state, cause, unsafe, ready, latch_pending), clocks = (elapsed, settled), q_latch [nj],
+        run_cmd None or five [nj] arrays.  Returns (flags [5] int32, clocks [2], q_latch [nj], command [5, nj])."""
+        nj = interface.actuatedDofNum
+        p, j, r = _f64(params).reshape(8), _f64(joint_rows).reshape(5, nj), _f64(rbd).reshape(2 * (6 + nj))
+        f, c, ql = np.array(flags, np.int32).reshape(5), np.array(clocks, float).reshape(2), np.array(q_latch, float).reshape(nj)
+        cmd, keep = None, None
+        if run_cmd is not None:
+            keep = [_f64(a).reshape(nj) for a in run_cmd]
+            cmd = _JointCommand(*[_d(a) for a in keep], None, None)
+        out = np.zeros((5, nj))
+        _check(load_library().bpmpc_supervisor_rows_host(interface.handle, _d(p), _d(j), _d(r), None if cmd is None else C.byref(cmd), float(period), _i(f),
+                                                         _d(c), _d(ql), _d(out)))
+        return f, c, ql, out
 
 
 class BatchedDdpMpc(BatchedSqpMpc):

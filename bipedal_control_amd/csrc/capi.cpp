@@ -195,6 +195,8 @@ int bpmpc_model_get(const bpmpc_model* m, const char* name, double* out, int cap
     if (n == "joint_rotation") return copy_out(&r.Rfix[1][0], 9 * nj, out, capacity);
     if (n == "joint_offset") return copy_out(&r.pfix[1][0], 3 * nj, out, capacity);
     if (n == "joint_axis") return copy_out(&r.axis[1][0], 3 * nj, out, capacity);
+    if (n == "joint_lower") return copy_out(&r.joint_lower[1], nj, out, capacity);
+    if (n == "joint_upper") return copy_out(&r.joint_upper[1], nj, out, capacity);
     if (n == "contact_offset") return copy_out(&r.contact_off[0][0], 3 * kNumContacts, out, capacity);
     if (n == "joint_parent") { std::vector<double> t(nj); for (int j = 0; j < nj; ++j) t[j] = r.parent[j + 1]; return copy_out(t.data(), nj, out, capacity); }
     if (n == "contact_body") { std::vector<double> t(kNumContacts); for (int c = 0; c < kNumContacts; ++c) t[c] = r.contact_body[c]; return copy_out(t.data(), t.size(), out, capacity); }

@@ -14,6 +14,7 @@
 #include "info_tree.h"
 #include "kernel_launchers.h"
 #include "plant.h"
+#include "supervisor.h"
 
 namespace bpmpc {
 
@@ -301,6 +302,31 @@ int bpmpc_plant_step_controlled(bpmpc_plant* p, bpmpc_controller* controller, in
     launch_step(p, a, period);
     record(&p->ev_step, st);
     HIP_CHECK(hipStreamWaitEvent(cc.stream, p->ev_step, 0));
+    if (!inputs_on_device && (base_force || feet_heights)) p->hs.synchronise_own();      // the caller's host arrays
+    else p->hs.enqueued_own();
+  });
+}
+
+// One step on the commands of a supervisor's last update, read where the update wrote them (stride nj): bpmpc_plant_step_controlled with the
+// supervisor's five arrays and its stream in the two waits.  The plant's stream waits for an update that was only enqueued, and the supervisor's
+// stream for the step before the next update overwrites the commands; the step kernels are those of every other step
+int bpmpc_plant_step_supervised(bpmpc_plant* p, bpmpc_supervisor* sup, int batch, double period, int substeps, const double* base_force,
+                                const double* feet_heights, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_step_supervised: null plant or supervisor", sup != nullptr, [&] {
+    if (sup->nj != p->nj) throw std::invalid_argument("bpmpc_plant_step_supervised: the plant and the supervisor are built for different robots");
+    if (sup->device != p->device) throw std::invalid_argument("bpmpc_plant_step_supervised: the plant and the supervisor live on different devices");
+    check_step(p, batch, period, substeps, "bpmpc_plant_step_supervised");
+    if (batch > sup->max_batch) throw std::length_error("bpmpc_plant_step_supervised: batch exceeds the supervisor's max_batch");
+    const size_t B = batch;
+    hipStream_t st = p->hs.stream;
+    PlantArgs a = step_args(p, batch, period, substeps);
+    a.cmd_stride = p->nj;
+    a.pos_des = sup->d_cmd[0]; a.vel_des = sup->d_cmd[1]; a.tau_ff = sup->d_cmd[2]; a.kp = sup->d_cmd[3]; a.kd = sup->d_cmd[4];
+    a.base_force = staged(base_force, p->d_force, B * 3, inputs_on_device, st);
+    a.ground = staged(feet_heights, p->d_ground, B * 4, inputs_on_device, st);
+    sup->hs.before_foreign(st);
+    launch_step(p, a, period);
+    sup->hs.after_foreign(st);
     if (!inputs_on_device && (base_force || feet_heights)) p->hs.synchronise_own();      // the caller's host arrays
     else p->hs.enqueued_own();
   });

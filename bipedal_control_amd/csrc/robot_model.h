@@ -71,6 +71,7 @@ struct RobotModel {
   // kinematic tree: body 0 = floating base (welded links merged), joint j (1..nj) moves body j
   int parent[kMaxBodies] = {};
   double Rfix[kMaxBodies][9] = {}, pfix[kMaxBodies][3] = {}, axis[kMaxBodies][3] = {};
+  double joint_lower[kMaxBodies] = {}, joint_upper[kMaxBodies] = {};      // the URDF's position limits of joint j, -inf / +inf without a <limit> tag
   double mass[kMaxBodies] = {}, com[kMaxBodies][3] = {}, inertia[kMaxBodies][9] = {};
   int contact_body[kNumContacts] = {};
   double contact_off[kNumContacts][3] = {};

@@ -168,6 +168,10 @@ UrdfRobot read_urdf_file(const std::string& path) {
         parse_triplet(org->get("rpy", "0 0 0"), j.rpy);
       }
       if (const XmlElement* ax = e.child("axis")) parse_triplet(ax->get("xyz", "1 0 0"), j.axis);
+      if (const XmlElement* lim = e.child("limit"); lim && j.type == "revolute") {      // urdfdom: an absent attribute is 0
+        j.lower = parse_number(lim->get("lower", "0"));
+        j.upper = parse_number(lim->get("upper", "0"));
+      }
       robot.joints.push_back(j);
     }
   }

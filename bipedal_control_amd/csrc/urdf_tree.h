@@ -1,8 +1,9 @@
-// Minimal URDF reader: just enough XML to recover links (inertial) and joints (origin/parent/child/axis/type).
+// Minimal URDF reader: just enough XML to recover links (inertial) and joints (origin/parent/child/axis/type/limit).
 // The kinematic conventions applied on top of it are those of the reference's model construction,
 // centroidal_model::createPinocchioInterface(urdf, jointNames) (call site
 // ocs2_bipedal_robot/src/BipedalRobotInterface.cpp:117) -- see robot_model.cpp.
 #pragma once
+#include <limits>
 #include <map>
 #include <string>
 #include <vector>
@@ -21,6 +22,8 @@ struct UrdfJoint {
   double xyz[3] = {0, 0, 0};
   double rpy[3] = {0, 0, 0};
   double axis[3] = {1, 0, 0};
+  // <limit lower= upper=> of a revolute joint (urdf::Joint::limits); without the tag, or for another joint type, the joint is unbounded
+  double lower = -std::numeric_limits<double>::infinity(), upper = std::numeric_limits<double>::infinity();
 };
 
 struct UrdfRobot {

@@ -56,6 +56,7 @@ int bpmpc_model_dims(const bpmpc_model* model, int* nx, int* nu, int* n_contacts
 /* Named constant blocks, copied into out[0..capacity); returns the element count or a negative status.
  * Names: "initial_state" (BipedalRobotInterface::getInitialState), "default_joint_state", "Q", "R", "robot_mass",
  * "com_height", "body_mass", "body_com", "body_inertia", "joint_parent", "joint_rotation", "joint_offset", "joint_axis",
+ * "joint_lower", "joint_upper" (<limit lower= upper=> of the URDF's revolute joints, urdf::Joint::limits; -inf / +inf without the tag),
  * "contact_body", "contact_offset", "cone" (mu, regularization, gripper force, hessian shift, barrier mu, barrier delta),
  * "swing" (liftOffVelocity, touchDownVelocity, swingHeight, swingTimeScale), "sqp" (dt, sqpIteration, deltaTol, g_max, g_min,
  * useFeedbackPolicy, projectStateInputEqualityConstraints (always 1), integratorType (always 0 = RK2): bpmpc_model_create returns
@@ -485,7 +486,8 @@ int bpmpc_controller_restart(bpmpc_controller* controller, int batch, const int*
  *               which with zero gains is the WBC torque bit for bit.  bpmpc_controller_joint_outputs: every argument nullable; host_*
  *               [batch*nj] receive the last tick's joint_torque and the current gains and make the call synchronise; dev_* receive the handle's
  *               buffers (leading dimension the WBC's max_batch, like bpmpc_controller_device_outputs).
- * Not reproduced: per-robot MPC cost weights, the SafetyChecker limits, InitialJointController.
+ * Not reproduced: per-robot MPC cost weights, UpperJointController (the MPC models carry no upper-body joints).  The SafetyChecker limits and
+ * InitialJointController are the supervisor's ("Supervisor" below).
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_WBC_PARAM_STRIDE 32
 #define BPMPC_WBC_PARAM_BASE_KP 0
@@ -986,6 +988,119 @@ int bpmpc_plan_get_footholds(bpmpc_plan* plan, int batch, double* host_entries, 
 int bpmpc_plan_get_summary(bpmpc_plan* plan, int batch, double* host_rows);
 int bpmpc_plan_rows_host(const bpmpc_model* model, int n_nodes, const double* t, const double* x, const double* u, const int* mode, const int* kind,
                          double* rows, double* footholds, int* count, double* summary);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Supervisor = which controller drives which robot of a BATCH, decided on the device.  The reference has three pieces for it:
+ *   InitialJointPositionController::update  bipedal_controllers/src/InitialJointController.cpp:110-141: holds the robot at defaultJointState,
+ *                                           clamped to the URDF limits, with its own joint gains                              -> state INIT
+ *   SafetyChecker::check + stopRequest      SafetyChecker.h:39-52, BipedalController.cpp:232-236: stops a robot that tilts    -> RUN to STOPPED
+ *   switch_joint_init_pos_controller.py     bipedal_controllers/script: the operator hands a settled robot to the MPC         -> bpmpc_supervisor_request
+ * A handle of its own (bpmpc_supervisor) with one kernel, k_supervise; a loop without it keeps its bits and its call time.
+ *   state per robot (leading dimension max_batch):
+ *     state[b]    BPMPC_SUP_INIT 0, BPMPC_SUP_RUN 1, BPMPC_SUP_STOPPED 2; after create every robot is in INIT
+ *     elapsed[b]  seconds in the current state: the sum of the `period`s of its updates
+ *     settled[b]  seconds the settle test has held without a break
+ *     cause[b]    why the robot was stopped, a bit mask: 1 |roll| above the limit, 2 |pitch| above the limit, 4 base below the height limit,
+ *                 8 a measurement that is not finite, 16 a RUN command that is not finite or is missing, 64 stop asked for by the caller
+ *     unsafe[b]   the same bits as the last update evaluated them, in every state
+ *     ready[b]    0 or 1
+ *     q_latch[b][nj] and a latch-pending flag: the measured joints at the first update after entering INIT
+ *     counts[8]   robots in INIT, in RUN, in STOPPED, with ready, with unsafe != 0 among the `batch` robots of the last update; the rest 0
+ *   parameter row, BPMPC_SUP_PARAM_STRIDE doubles per robot, every row starting from the keys supervisor.<name> of the task file (an absent key
+ *   or a NULL path: the default):
+ *     [0] tilt_limit       pi/3 (SafetyChecker.h:41)  unsafe if |zyx[2]| > limit (bit 1) or |zyx[1]| > limit (bit 2); strict, as the reference
+ *     [1] min_base_height  0    bit 4 if > 0 and position z < it                                          (this engine's extension)
+ *     [2] ramp_time        0    seconds over which INIT moves from the latched joints to the target       (extension; 0: the reference's jump)
+ *     [3] settle_pos_tol   0    rad        [4] settle_vel_tol  0  rad/s        [5] settle_time  0  s       (extension: the operator's judgement)
+ *     [6] stop_kd          0    damping gain of a stopped robot                                           (extension)
+ *     [7] reserved, written as 0
+ *   five joint rows per robot, nj entries each (`which`): 0 q_init (default: the model's default_joint_state), 1 kp_init and 2 kd_init (default:
+ *     the start-up values of the reference's reconfigure server for this controller, cfg/InitialJointControllerParams.cfg: 80 / 5 per leg motor,
+ *     kd 3 for the sixth motor of a 12-joint robot), 3 lower and 4 upper (default: the URDF limits, bpmpc_model_get "joint_lower" / "joint_upper").
+ *   bpmpc_supervisor_get_params / set_params / reset_params and set_joint_rows / get_joint_rows: masks, n_rows and host / device semantics are
+ *     exactly those of bpmpc_wbc_get_params / set_params / reset_params (robot < 0: the start values).  Host rows are validated and a bad entry
+ *     is named in bpmpc_last_error(): every used entry finite; limits, tolerances, times and gains not negative; tilt_limit > 0; lower <= upper
+ *     against the robot's other limit, +-infinity allowed for these two rows only.  Device rows are not validated.  bpmpc_supervisor_load_params
+ *     (row[8]) / check_params: the ingest and the row validation as host-only functions.
+ *   bpmpc_supervisor_request: one masked launch on the supervisor's stream, enqueued at once like a restart (mask NULL: every robot below batch).
+ *     Target INIT or STOPPED applies to every robot of the mask.  Target RUN applies only to robots that are in INIT, and with only_ready != 0
+ *     only to those with ready == 1; the others are left unchanged bit for bit.  Entering any state sets elapsed = settled = 0 and ready = 0;
+ *     entering INIT or RUN sets cause = 0; entering INIT sets latch-pending; entering STOPPED by request sets cause = 64.
+ *   bpmpc_supervisor_update: counts zeroed on the stream, then one launch of k_supervise; per robot b < batch and in this order:
+ *     1. the measurement rbd = [zyx, position, joints, angular velocity, linear velocity, joint velocities] gives `unsafe`: bits 1, 2, 4 as in the
+ *        table; bit 8 if any of the 2 (6 + nj) entries is not finite; bit 16 if the robot is in RUN and run_cmd is NULL or any of its five
+ *        entries of any joint is not finite.  The reference's comparisons let a NaN pass; bit 8 is this engine's addition.
+ *     2. RUN and unsafe != 0: the robot goes to STOPPED with cause = unsafe, elapsed = settled = 0.  This is stopRequest.  The reference still
+ *        sends that tick's command and stops at the next cycle; here the stop command goes out in the same update.  Nothing else moves by itself.
+ *     3. elapsed += period.
+ *     4. the command (pos_des, vel_des, tau_ff, kp, kd per joint):
+ *        RUN      the five entries of run_cmd, bit for bit.
+ *        INIT     if latch-pending, q_latch = the measured joints (a non-finite entry becomes q_init) and the flag is cleared.
+ *                 s = 1 if ramp_time == 0 or elapsed >= ramp_time, else elapsed / ramp_time.  target_j = q_init_j if s == 1 (selected, not
+ *                 computed), else q_latch_j + s (q_init_j - q_latch_j), each operation rounded once.  pos_des_j = target_j clamped in the
+ *                 reference's order: above upper -> upper, else below lower -> lower.  vel_des = 0, kp = kp_init, kd = kd_init, tau_ff = 0
+ *                 (InitialJointController.cpp:114-124).  The settle test: s == 1, unsafe == 0, every |q_j - pos_des_j| <= settle_pos_tol and
+ *                 every |v_j| <= settle_vel_tol.  If it holds, settled += period, else settled = 0; ready = (settled >= settle_time) while the
+ *                 test holds, else 0.
+ *        STOPPED  pos_des_j = the measured q_j (0 if not finite), vel_des = 0, kp = 0, kd = stop_kd, tau_ff = 0; ready = 0.
+ *     5. counts.  Robots at or beyond `batch` do not change by one bit.
+ *     run_cmd (nullable) has the layout of bpmpc_plant_step's command ([batch*nj] each; base_force and feet_heights are not read).  Host arrays
+ *     (inputs_on_device == 0) make the call synchronise; device arrays only enqueue.  period must be finite and positive.
+ *   bpmpc_supervisor_update_controlled: run_cmd is the controller's last tick where the tick wrote it (joint_cmd [b][3][nj], the joint gains
+ *     [b][nj]), rbd the estimator's device buffer or, with estimator NULL, rbd_dev.  The supervisor's stream waits for the tick and for the
+ *     estimator's pending update; the controller's stream and the estimator's wait for the update before they overwrite what it read.  batch must
+ *     be the batch of the controller's last tick.  Nothing synchronises.
+ *   bpmpc_plant_step_supervised: bpmpc_plant_step_controlled with the supervisor's five command arrays and its stream in the two waits; the plant
+ *     kernels are those of every other step.
+ *   bpmpc_supervisor_device_outputs: the buffers where they live, and the supervisor's stream.  bpmpc_supervisor_get_state / get_commands: host copies for the first `batch`
+ *     robots (counts: 8 ints), every pointer nullable; they synchronise the supervisor's stream.  Nothing else synchronises unless a host
+ *     pointer asks for it.
+ *   bpmpc_supervisor_rows_host: host only, no device: one update of ONE robot from the text the kernel is compiled from.  params [8]; joint_rows
+ *     [5][nj] in the order of `which`; rbd [2 (6 + nj)]; run_cmd nullable, [nj] per member; flags [5] = state, cause, unsafe, ready,
+ *     latch-pending and clocks [2] = elapsed, settled and q_latch [nj] are read and updated; command [5][nj] = pos_des, vel_des, tau_ff, kp, kd.
+ *   batch > max_batch: BPMPC_ERR_CAPACITY.  Null handles: BPMPC_ERR_INVALID_ARGUMENT ("null" in bpmpc_last_error()).
+ *   The settle-then-start loop:
+ *     request(INIT)                                                        (after create this is already so)
+ *     loop: step_supervised -> update(rbd = plant rbd, run_cmd = NULL)     until counts[3] == B   (a 32-byte fetch every n ticks)
+ *     controller_restart(mask = ready, on device) -> setup_commands(x0 = NULL) -> run -> tick_estimated
+ *     request(mask = NULL, RUN, only_ready = 1)
+ *     loop: step_supervised -> update_from_plant -> tick_estimated -> update_controlled      (a robot that tilts is STOPPED on the device)
+ *   Not reproduced: UpperJointController; joint limits inside the plant; the tick's own `safe` flag is unchanged.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_SUP_PARAM_STRIDE 8
+#define BPMPC_SUP_INIT 0
+#define BPMPC_SUP_RUN 1
+#define BPMPC_SUP_STOPPED 2
+typedef struct bpmpc_supervisor bpmpc_supervisor;
+typedef struct {
+  double *pos_des, *vel_des, *tau_ff, *kp, *kd;       /* [max_batch][nj] each: the layout of bpmpc_joint_command */
+  int *state, *cause, *unsafe, *ready;                /* [max_batch] */
+  int *counts;                                        /* [8] */
+  double *elapsed;                                    /* [max_batch] */
+  void *stream;                                       /* the supervisor's stream (a hipStream_t): what a caller orders or times its own work against */
+} bpmpc_supervisor_outputs;
+int bpmpc_supervisor_create(const bpmpc_model* model, const char* task_info_path, int device, int max_batch, bpmpc_supervisor** out);
+void bpmpc_supervisor_destroy(bpmpc_supervisor* supervisor);
+int bpmpc_supervisor_get_params(const bpmpc_supervisor* supervisor, int robot, double* row);
+int bpmpc_supervisor_set_params(bpmpc_supervisor* supervisor, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_supervisor_reset_params(bpmpc_supervisor* supervisor);
+int bpmpc_supervisor_load_params(const char* task_info_path, double* row);
+int bpmpc_supervisor_check_params(const double* rows, int n_rows);
+int bpmpc_supervisor_set_joint_rows(bpmpc_supervisor* supervisor, int batch, const int* mask, int which, const double* rows, int n_rows,
+                                    int inputs_on_device);
+int bpmpc_supervisor_get_joint_rows(const bpmpc_supervisor* supervisor, int robot, int which, double* row);
+int bpmpc_supervisor_request(bpmpc_supervisor* supervisor, int batch, const int* mask, int target, int only_ready, int inputs_on_device);
+int bpmpc_supervisor_update(bpmpc_supervisor* supervisor, int batch, const double* rbd, const bpmpc_joint_command* run_cmd, int inputs_on_device,
+                            double period);
+int bpmpc_supervisor_update_controlled(bpmpc_supervisor* supervisor, bpmpc_controller* controller, bpmpc_estimator* estimator, const double* rbd_dev,
+                                       int batch, double period);
+int bpmpc_supervisor_device_outputs(bpmpc_supervisor* supervisor, bpmpc_supervisor_outputs* dev_out);
+int bpmpc_supervisor_get_state(bpmpc_supervisor* supervisor, int batch, int* state, int* cause, int* unsafe, int* ready, double* elapsed, int* counts);
+int bpmpc_supervisor_get_commands(bpmpc_supervisor* supervisor, int batch, double* pos_des, double* vel_des, double* tau_ff, double* kp, double* kd);
+int bpmpc_supervisor_rows_host(const bpmpc_model* model, const double* params, const double* joint_rows, const double* rbd,
+                               const bpmpc_joint_command* run_cmd, double period, int* flags, double* clocks, double* q_latch, double* command);
+int bpmpc_plant_step_supervised(bpmpc_plant* plant, bpmpc_supervisor* supervisor, int batch, double period, int substeps, const double* base_force,
+                                const double* feet_heights, int inputs_on_device);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,182 @@
+#!/usr/bin/env python3
+"""Does settling under the initial joint controller first change whether the robots stand?  The scenario of tools/plant_stand_probe.py (H1,
+batch 8, 2 s of simulated time, 2 ms ticks of 4 substeps, the MPC re-armed every 10 ticks), run
+
+  plain     as that probe runs it: from standing_state straight into the MPC loop (its own `run`, unchanged);
+  settled   under the supervisor: every robot in INIT - bpmpc_plant_step_supervised <- bpmpc_supervisor_update on the plant's rbd - until every
+            robot is ready or `--settle-seconds` have passed, then the hand-over of INTEGRATION.md "Supervisor": the solver is set up at the
+            plant's state, one tick, request(RUN, only_ready = 1), and the loop step_supervised -> update_from_plant -> tick_estimated ->
+            update_controlled for `--seconds`.  Once with the reference's start-up gains (kp 80, kd 5) and once with the PD command that holds
+            standing_state in tests/test_plant_reference.py (kp 2000, kd 40).
+
+Per settled run and robot: the tick at which it became ready (null: never), the base height at the hand-over, the first tick after the hand-over
+at which the tick's `safe` flag was 0, the tick at which the supervisor stopped it and the cause, and the base height at the end.  A run ends at
+the first tick after which a robot's state is not finite.  A probe, not a test: nothing asserts its outcome, and standing is claimed only where
+it is seen.  Each run is a child process under a time limit; a run that fails or runs out of time ends the probe.  One JSON line per run on
+stdout; --out appends them to a file (profiles/supervisor_settle_probe.jsonl is where the published one belongs).
+usage (GPU box, repository root): python tools/supervisor_settle_probe.py [--seconds 2.0] [--batch 8] [--kt kn] [--commit ID] [--out FILE]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
+GAINS = {"reference": None, "holding": (2000.0, 40.0)}
+RAMP_TIME, POS_TOL, VEL_TOL, SETTLE_TIME = 0.1, 0.05, 0.5, 0.2
+
+
+def settled(gains, kt, B, seconds, settle_seconds):
+    import numpy as np
+    import torch
+    import bipedal_control_amd as bp
+    from bipedal_control_amd import scenarios as sc
+    from oracle import wbc_py as wp
+    from tests import oracle_bridge as ob
+    from tests.test_plant_reference import standing_state
+    itf = sc.interface("h1")
+    horizon = NI * sc.DT
+    mpc = bp.BatchedSqpMpc(itf, max_batch=B, max_nodes=sc.max_nodes_for(NI, horizon), return_gains=True)
+    wbc = bp.WeightedWbc(itf, max_batch=B)
+    ctrl = bp.BatchedController(mpc, wbc)
+    est = bp.BatchedStateEstimate(itf, kind="from_topic", max_batch=B)
+    plant = bp.BatchedPlant(itf, max_batch=B)
+    sup = bp.BatchedSupervisor(itf, max_batch=B)
+    gaits = [bp.loadModeSequenceTemplate(sc.ROBOTS["h1"]["gait"], "stance")]
+    m = ob.model("h1")
+    nj = m["nj"]
+    q, v, _ = standing_state(m, depth=0.0025)
+    rng = np.random.default_rng(5)
+    rbd0 = np.array([wp.rbd_from(m, q + 0.002 * rng.standard_normal(len(q)) * np.r_[np.zeros(6), np.ones(len(q) - 6)], v) for _ in range(B)])
+    ctrl.setJointGains(np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KP), np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KD))
+    if kt != "0":
+        plant.setStiction(plant.getParams()[0] if kt == "kn" else float(kt))
+    sup.setParams(bp.SupervisorParams(ramp_time=RAMP_TIME, settle_pos_tol=POS_TOL, settle_vel_tol=VEL_TOL, settle_time=SETTLE_TIME).toRow())
+    if GAINS[gains] is not None:
+        sup.setJointRows("kp_init", np.full(nj, GAINS[gains][0]))
+        sup.setJointRows("kd_init", np.full(nj, GAINS[gains][1]))
+    plant.set_state(rbd0)
+    d_rbd = plant.outputs()["rbd"]
+
+    def num(a):
+        return [float(x) if np.isfinite(x) else None for x in a]
+
+    # ---- settle under INIT
+    ready_tick = [None] * B
+    settle_ticks = int(round(settle_seconds / PERIOD))
+    finite, k = True, -1
+    for k in range(settle_ticks):
+        sup.update(d_rbd, None, PERIOD)
+        plant.step_supervised(sup, period=PERIOD, substeps=SUBSTEPS)
+        s = sup.state(B)
+        for b in range(B):
+            if ready_tick[b] is None and s["ready"][b]:
+                ready_tick[b] = k
+        if s["counts"]["ready"] == B:
+            break
+    rbd = plant.get_state()
+    handover = dict(ticks=k + 1, ready=[int(x) for x in s["ready"]], unsafe=[int(x) for x in s["unsafe"]], base_height=num(rbd[:, 5]),
+                    largest_joint_speed=num(np.abs(rbd[:, 6 + nj + 6:]).max(axis=1)), largest_joint_offset=num(np.abs(rbd[:, 6:6 + nj] - sup.getJointRows("q_init")).max(axis=1)))
+    line = dict(robot="h1", batch=B, variant="settled", init_gains=gains, kt=float(plant.getStiction(0)), period=PERIOD, substeps=SUBSTEPS, rearm_every=REARM,
+                ramp_time=RAMP_TIME, settle_pos_tol=POS_TOL, settle_vel_tol=VEL_TOL, settle_time=SETTLE_TIME, settle_seconds_allowed=settle_seconds,
+                start_base_height=num(rbd0[:, 5]), ready_tick=ready_tick, handover=handover)
+    if not np.all(np.isfinite(rbd)) or not any(s["ready"]):
+        line.update(seconds=0.0, ticks_run=0, state_finite=bool(np.all(np.isfinite(rbd))), note="no robot became ready: no hand-over")
+        return line
+
+    # ---- the hand-over: the solver set up at the plant's state, one tick, the ready robots to RUN
+    x0 = np.tile(itf.getInitialState(), (B, 1))
+    x0[:, 6:] = np.c_[rbd[:, 3:6], rbd[:, 0:3], rbd[:, 6:6 + nj]]
+    t0 = PERIOD * (k + 1)
+
+    def arm(t, first):
+        mpc.setup_commands(t, x0 if first else None, gaits, -1, 0.0, np.zeros(4), horizon=horizon, from_previous=not first)
+        mpc.enqueue()
+
+    arm(t0, True)
+    est.update_from_plant(plant, period=PERIOD, fetch=False)
+    t = torch.full((B,), t0, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    ctrl.tick_estimated(t, est, period=PERIOD, fetch=False)
+    sup.request(sup.RUN, only_ready=True)
+    sup.update_controlled(ctrl, est, period=PERIOD)
+    ticks = int(round(seconds / PERIOD))
+    first_unsafe, stopped_tick, cause = [None] * B, [None] * B, [None] * B
+    lowest = np.full(B, np.inf)
+    j = -1
+    for j in range(ticks):
+        plant.step_supervised(sup, period=PERIOD, substeps=SUBSTEPS)
+        est.update_from_plant(plant, period=PERIOD, fetch=False)
+        t = torch.full((B,), t0 + PERIOD * (j + 1), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        ctrl.tick_estimated(t, est, period=PERIOD, fetch=False)
+        sup.update_controlled(ctrl, est, period=PERIOD)
+        if j % REARM == REARM - 1:
+            arm(t0 + PERIOD * (j + 1), False)
+        torch.cuda.synchronize()
+        rbd = plant.get_state()
+        safe = ctrl.device_outputs()["safe"].torch().cpu().numpy()
+        s = sup.state(B)
+        if not np.all(np.isfinite(rbd)):
+            finite = False
+            break
+        lowest = np.minimum(lowest, rbd[:, 5])
+        for b in range(B):
+            if first_unsafe[b] is None and safe[b] == 0:
+                first_unsafe[b] = j
+            if stopped_tick[b] is None and s["state"][b] == sup.STOPPED:
+                stopped_tick[b], cause[b] = j, int(s["cause"][b])
+    line.update(seconds=seconds, ticks_run=j + 1, state_finite=finite, first_unsafe_tick=first_unsafe, stopped_tick=stopped_tick, stop_cause=cause,
+                final_state=[int(x) for x in s["state"]], lowest_base_height=num(lowest), final_base_height=num(rbd[:, 5]))
+    return line
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--seconds", type=float, default=2.0)
+    ap.add_argument("--settle-seconds", type=float, default=2.0, help="how long the robots may take to become ready")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--kt", default="kn", help="the plant's tangential contact stiffness: 0, kn or a number (tools/plant_stand_probe.py)")
+    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
+    ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    if a.child is not None:
+        if a.child == "plain":
+            from tools.plant_stand_probe import run
+            _, line = run(a.kt, a.batch, a.seconds)
+            line["variant"] = "plain"
+        else:
+            line = settled(a.child, a.kt, a.batch, a.seconds, a.settle_seconds)
+        if a.commit:
+            line["commit"] = a.commit
+        print(json.dumps(line), flush=True)
+        return 0
+    jobs = ["plain"] + list(GAINS)
+    lines = []
+    for job in jobs:
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", job, "--seconds", repr(a.seconds), "--settle-seconds",
+               repr(a.settle_seconds), "--batch", str(a.batch), "--kt", a.kt]
+        r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
+        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
+            print("supervisor_settle_probe: %s ended with status %d; stopping" % (job, r.returncode), file=sys.stderr)
+            break
+        text = r.stdout.strip().splitlines()[-1]
+        print(text, flush=True)
+        lines.append(text)
+    if a.out and lines:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for text in lines:
+                f.write(text + "\n")
+    return 0 if len(lines) == len(jobs) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
