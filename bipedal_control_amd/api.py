@@ -1368,6 +1368,33 @@ class SensorParams:
         return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
 
 
+class InputParams:
+    """A row of the plant's input model (include/bpmpc.h "Plant", inputs; BPMPC_PLANT_INPUT_PARAM_STRIDE) with named fields: the command latency
+    delay [s] (the reference's gazebo/delay), the probability dropout that a command does not arrive (the joint holds the previous one), and
+    pushes on the base of push_force [N] for push_duration [s], one at a random time and from a random horizontal direction in every
+    push_interval [s].  Every default is 0: the step consumes the command it was called with."""
+
+    STRIDE = 8
+    FIELDS = ("delay", "dropout", "push_force", "push_interval", "push_duration")
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name in self.FIELDS:
+            setattr(self, name, float(fields.get(name, 0.0)))
+
+    @classmethod
+    def fromRow(cls, row):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
+
+    def toRow(self):
+        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
+
+
 class BatchedPlant(_Handle):
     """A rigid-body simulation of a batch of robots on one MI355X (bpmpc_plant; include/bpmpc.h "Plant" is its specification): joint commands ->
     the sensors BatchedStateEstimate.update takes and the ground-truth rbd.  This engine's own model - penalty contacts with implicit damping, a
@@ -1527,6 +1554,51 @@ class BatchedPlant(_Handle):
         shapes = {"joint_pos": (B, nj), "joint_vel": (B, nj), "quat": (B, 4), "angular_vel_local": (B, 3), "linear_accel_local": (B, 3), "contact": (B, 4),
                   "feet_heights": (B, 4), "odom_pos": (B, 3), "odom_quat": (B, 4), "odom_lin_vel": (B, 3), "odom_ang_vel": (B, 3)}
         return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k == "contact" else "<f8") for k, shp in shapes.items()}
+
+    def setInputParams(self, rows, mask=None):
+        """The input rows (InputParams.toRow) of the robots with mask[b] != 0 (None: every one): rows [8], [1, 8] or [B, 8].  numpy rows are
+        validated and the call synchronises; device tensors are only enqueued, ordered before the next step.  From this call on every step runs
+        the input model in front of its step kernel (k_plant_input) and applied() reports what the joints received; resetInputParams ends that."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], InputParams.STRIDE, self.max_batch)
+        self._call("bpmpc_plant_set_input_params", B, mp, rp, n_rows, dev)
+        del keep
+
+    def getInputParams(self, robot=-1):
+        """The input row [8] of `robot` (InputParams.fromRow names its entries), or with robot < 0 the row of the task file (the keys
+        plantInputs.<name>; absent: 0)."""
+        row = np.zeros(InputParams.STRIDE)
+        self._call("bpmpc_plant_get_input_params", int(robot), _d(row))
+        return row
+
+    def resetInputParams(self):
+        """Every input row and counter zero, every key the start key (plantInputs.seed): the plant is the one without an input model again."""
+        self._call("bpmpc_plant_reset_input_params")
+
+    def seedInputs(self, seed, mask=None):
+        """Restarts the random streams of the input model for the robots with mask[b] != 0 (None: every one of the batch of the last set_state;
+        before it: max_batch) under `seed`: tick and step count 0, the buffered commands forgotten.  A numpy mask synchronises, an int32 device
+        tensor is only enqueued."""
+        B = _count(mask) if mask is not None else (self.batch or self.max_batch)
+        (mp,), dev, keep = _restart_args((mask, C.c_int, B))
+        self._call("bpmpc_plant_seed_inputs", B, mp, int(seed), dev)
+        del keep
+
+    def inputState(self):
+        """{"tick" [B], "steps" [B], "delay_steps" [B], "lost" [B], "pushing" [B]} of the batch of the last set_state (before it: max_batch): the
+        generator's tick, the steps since the last (re)start, and what the input model did in the last step; synchronises."""
+        B = self.batch or self.max_batch
+        ticks, delay, lost, pushing = np.zeros((B, 2)), np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._call("bpmpc_plant_get_input_state", B, _d(ticks), _i(delay), _i(lost), _i(pushing))
+        return {"tick": ticks[:, 0].astype(np.uint64), "steps": ticks[:, 1].astype(np.uint64), "delay_steps": delay, "lost": lost, "pushing": pushing}
+
+    def applied(self):
+        """The command the last step's kernel consumed, where it lives: a dict of DeviceArray, pos_des, vel_des, tau_ff, kp, kd [B, nj] and
+        base_force [B, 3].  Refused on a plant whose input model is untouched and before the first step since it was switched on."""
+        o = _JointCommand()
+        self._call("bpmpc_plant_applied_command", C.byref(o))
+        B, nj = self.batch or self.max_batch, self.nj
+        shapes = {"pos_des": (B, nj), "vel_des": (B, nj), "tau_ff": (B, nj), "kp": (B, nj), "kd": (B, nj), "base_force": (B, 3)}
+        return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<f8") for k, shp in shapes.items()}
 
 
 class SupervisorParams:

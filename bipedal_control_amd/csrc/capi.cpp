@@ -127,6 +127,38 @@ void plant_load_sensor_settings(const char* task_info_path, double* row, long* s
   std::copy(v, v + kSensorParamStride, row);
   if (seed) *seed = (long)s;
 }
+
+namespace {
+const char* const kInputParamNames[] = {"delay", "dropout", "push_force", "push_interval", "push_duration"};
+static_assert(sizeof(kInputParamNames) / sizeof(kInputParamNames[0]) == kInputParamUsed, "a name per used entry of an input row");
+}
+
+void plant_check_input_row(const char* who, const double* row, int r) {
+  for (int e = 0; e < kInputParamStride; ++e) {
+    const char* name = e < kInputParamUsed ? kInputParamNames[e] : "reserved";
+    const char* why = !std::isfinite(row[e])                       ? "not finite"
+                      : row[e] < 0.0                               ? "negative"
+                      : e == kInDropout && row[e] > 1.0            ? "above 1"
+                      : e >= kInputParamUsed && row[e] != 0.0      ? "not zero"
+                                                                   : nullptr;
+    if (why) throw std::invalid_argument(std::string(who) + ": row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + name + ") is " + why);
+  }
+}
+
+void plant_load_input_settings(const char* task_info_path, double* row, long* seed) {
+  double v[kInputParamStride] = {};
+  double s = 0.0;
+  if (task_info_path) {
+    const auto t = read_info_file(task_info_path);
+    for (int e = 0; e < kInputParamUsed; ++e) (void)t->get(std::string("plantInputs.") + kInputParamNames[e], v + e);
+    plant_check_input_row("plantInputs settings", v, 0);
+    (void)t->get("plantInputs.seed", &s);
+    if (!std::isfinite(s) || s != std::floor(s) || std::fabs(s) > 9007199254740992.0)
+      throw std::invalid_argument("plantInputs settings: seed is not an integer a double holds exactly");
+  }
+  std::copy(v, v + kInputParamStride, row);
+  if (seed) *seed = (long)s;
+}
 }  // namespace bpmpc
 
 using namespace bpmpc;
@@ -302,6 +334,34 @@ int bpmpc_plant_sensor_draw(long seed, int robot, long tick, double* z, double* 
   for (int g = 0; g < kSensorGaussians; ++g) z[g] = sensor_gaussian(t, (unsigned)robot, k0, k1, g);
   const Philox4 block = sensor_block(t, (unsigned)robot, kSensorUniformBlock, k0, k1);
   for (int i = 0; i < kSensorUniforms; ++i) u[i] = sensor_uniform(block.w[i]);
+  return BPMPC_OK;
+}
+
+int bpmpc_plant_load_input_params(const char* task_info_path, double* row) {
+  if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_input_params: null row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    double v[kInputParamStride];
+    plant_load_input_settings(task_info_path, v, nullptr);      // (the seed is validated with the row)
+    std::copy(v, v + kInputParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_check_input_params(const double* rows, int n_rows) {
+  if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_input_params: null rows");
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) plant_check_input_row("bpmpc_plant_check_input_params", rows + (size_t)r * kInputParamStride, r);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_input_draw(long seed, int robot, long counter, double u[3]) {
+  if (!u) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_input_draw: null u");
+  if (robot < 0 || counter < 0) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_input_draw: robot and counter must not be negative");
+  const unsigned long long s = (unsigned long long)seed;
+  const unsigned k0 = (unsigned)s, k1 = (unsigned)(s >> 32);
+  u[0] = input_loss_draw((unsigned long long)counter, (unsigned)robot, k0, k1);
+  input_push_draw((unsigned long long)counter, (unsigned)robot, k0, k1, u + 1, u + 2);
   return BPMPC_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "device_handle.h"
 #include "robot_model.h"
 #include "kernels/plant.h"
+#include "kernels/plant_input.h"
 #include "kernels/sensor_noise.h"
 
 struct bpmpc_plant {
@@ -48,9 +49,24 @@ struct bpmpc_plant {
   double* d_sring = nullptr;            // [max_batch][kSensorRing][sensor_sample_width(nj)]
   double* d_sensed = nullptr;           // the sensed block: the sections of sensor_sensed_offset, leading dimension max_batch
   bpmpc_sensor_inputs sensed{};         // its members; what the sensor model leaves alone points into `out`
+  // input model (include/bpmpc.h "Plant", inputs): per-robot rows, generator state, the ring of arrived commands, the applied command
+  double input_start[bpmpc::kInputParamStride] = {};      // the keys plantInputs.<name> of task.info (absent: 0): every row after create
+  long input_seed = 0;                  // the key plantInputs.seed (absent: 0): every robot's key after create / reset_input_params
+  bool input = false;                   // steps launch k_plant_input in front of the step kernel: the handle is switched (not untouched)
+  bool applied_valid = false;           // a step has run since the switch: the applied block holds a command
+  const double* last_ground = nullptr;  // feet_heights as the last step consumed them: what bpmpc_plant_applied_command reports
+  double* d_iparams = nullptr;          // [max_batch][kInputParamStride]
+  double* d_irows = nullptr;            // [max_batch + 1][kInputParamStride] device copy of host rows; the last row holds input_start
+  unsigned* d_ikey = nullptr;           // [max_batch][2]
+  unsigned long long* d_iticks = nullptr;      // [max_batch][2]: tick t, steps n since the last (re)start
+  double* d_iring = nullptr;            // [max_batch][kInputRing][5 nj]
+  double* d_applied = nullptr;          // [5][max_batch][nj]: the applied pos_des, vel_des, tau_ff, kp, kd
+  double* d_applied_force = nullptr;    // [max_batch][3]
+  int* d_iflags = nullptr;              // [3][max_batch]: delay_steps, lost, pushing of the last step
 };
 
 static_assert(bpmpc::kPlantParamStride == BPMPC_PLANT_PARAM_STRIDE, "PlantSettings follows the row layout of include/bpmpc.h");
+static_assert(bpmpc::kInputParamStride == BPMPC_PLANT_INPUT_PARAM_STRIDE, "an input row follows the layout of include/bpmpc.h");
 
 namespace bpmpc {
 // The keys plant.<name> of task.info over the defaults (NULL: the defaults); host only (capi.cpp), also behind bpmpc_plant_load_params
@@ -90,6 +106,35 @@ void launch_plant_sense(int nj, hipStream_t stream, const PlantSenseArgs& a);
 void launch_plant_seed_sensors(hipStream_t stream, int batch, const int* mask, long seed, const double* params, unsigned* key, unsigned long long* ticks, double* bias);
 // n = 0 for the robots of `mask`: what bpmpc_plant_set_state does to the sensor model
 void launch_plant_forget_samples(hipStream_t stream, int batch, const int* mask, unsigned long long* ticks);
+
+struct PlantInputArgs {
+  int batch, max_batch;
+  long long period_ns;                              // P = input_period_ns(period) of the step
+  const double* params;                             // [max_batch][kInputParamStride]
+  const unsigned* key;                              // [max_batch][2]
+  unsigned long long* ticks;                        // [max_batch][2]: t, n; read and advanced
+  double* ring;                                     // [max_batch][kInputRing][5 nj]
+  const double *pos_des, *vel_des, *tau_ff;         // the incoming command: [batch] rows of nj, cmd_stride apart (PlantArgs)
+  const double *kp, *kd;                            // [batch][nj]
+  int cmd_stride;
+  const double* base_force;                         // [batch][3]; nullable: 0
+  double* applied;                                  // [5][max_batch][nj]
+  double* force;                                    // [max_batch][3]
+  int* flags;                                       // [3][max_batch]: delay_steps, lost, pushing
+};
+
+// plant_input.hip: one launch of k_plant_input<nj> for a.batch robots on `stream`, in front of the step kernel
+void launch_plant_input(int nj, hipStream_t stream, const PlantInputArgs& a);
+// bpmpc_plant_seed_inputs for the robots of `mask` (device; NULL: every robot below `batch`): key, t = n = 0
+void launch_plant_seed_inputs(hipStream_t stream, int batch, const int* mask, long seed, unsigned* key, unsigned long long* ticks);
+// n = 0 for the robots of `mask`: what bpmpc_plant_set_state does to the input model
+void launch_plant_forget_commands(hipStream_t stream, int batch, const int* mask, unsigned long long* ticks);
+
+// The keys plantInputs.<name> of task.info over zeros (NULL: zeros) and the key plantInputs.seed; host only (capi.cpp)
+void plant_load_input_settings(const char* task_info_path, double* row, long* seed);
+// A host row before it is accepted: every entry finite and not negative, dropout <= 1, the reserved entries 0; throws std::invalid_argument naming
+// the entry
+void plant_check_input_row(const char* who, const double* row, int r);
 
 // The keys plantSensors.<name> of task.info over zeros (NULL: zeros) and the key plantSensors.seed; host only (capi.cpp)
 void plant_load_sensor_settings(const char* task_info_path, double* row, long* seed);

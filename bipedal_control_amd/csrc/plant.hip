@@ -109,8 +109,23 @@ PlantArgs step_args(const bpmpc_plant* p, int batch, double period, int substeps
   return a;
 }
 
-// the step kernel and, on a switched handle, the sensor model behind it: `period` is the control step's
-void launch_step(bpmpc_plant* p, const PlantArgs& a, double period) {
+// On a handle whose input model is switched: k_plant_input in front of the step kernel, which then consumes the applied rows and force
+void launch_input(bpmpc_plant* p, PlantArgs& a, double period) {
+  p->last_ground = a.ground;
+  if (!p->input) return;
+  const size_t rows = (size_t)p->max_batch * p->nj;
+  const PlantInputArgs ia{a.batch, p->max_batch, input_period_ns(period), p->d_iparams, p->d_ikey, p->d_iticks, p->d_iring, a.pos_des, a.vel_des, a.tau_ff, a.kp, a.kd,
+                          a.cmd_stride, a.base_force, p->d_applied, p->d_applied_force, p->d_iflags};
+  launch_plant_input(p->nj, p->hs.stream, ia);
+  a.cmd_stride = p->nj;
+  a.pos_des = p->d_applied; a.vel_des = p->d_applied + rows; a.tau_ff = p->d_applied + 2 * rows; a.kp = p->d_applied + 3 * rows; a.kd = p->d_applied + 4 * rows;
+  a.base_force = p->d_applied_force;
+  p->applied_valid = true;
+}
+
+// the step kernel, on a switched handle the input model in front of it and the sensor model behind it: `period` is the control step's
+void launch_step(bpmpc_plant* p, PlantArgs a, double period) {
+  launch_input(p, a, period);
   if (p->stick) {
     const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
     launch_plant_stick_step(p->nj, p->hs.stream, p->d_model, a, sa);
@@ -139,6 +154,23 @@ void write_untouched_sensors(bpmpc_plant* p) {
   HIP_CHECK(hipMemsetAsync(p->d_sbias, 0, B * 6 * sizeof(double), st));
   HIP_CHECK(hipStreamSynchronize(st));
   p->sense = false; p->sensed_valid = false;
+}
+
+// the handle leaves the untouched state: from now on every step runs the input model, and the applied block holds nothing until one has
+void switch_inputs(bpmpc_plant* p) {
+  if (!p->input) p->applied_valid = false;
+  p->input = true;
+}
+
+// every input row zero, every counter zero, every key the start key: the handle is untouched
+void write_untouched_inputs(bpmpc_plant* p) {
+  const size_t B = p->max_batch;
+  hipStream_t st = p->hs.stream;
+  HIP_CHECK(hipMemsetAsync(p->d_iparams, 0, B * kInputParamStride * sizeof(double), st));
+  HIP_CHECK(hipMemsetAsync(p->d_iflags, 0, B * 3 * sizeof(int), st));
+  launch_plant_seed_inputs(st, p->max_batch, nullptr, p->input_seed, p->d_ikey, p->d_iticks);
+  HIP_CHECK(hipStreamSynchronize(st));
+  p->input = false; p->applied_valid = false;
 }
 
 void record(hipEvent_t* ev, hipStream_t on) {
@@ -206,6 +238,20 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
       launch_plant_seed_sensors(p->hs.stream, max_batch, nullptr, p->sensor_seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);
       switch_sensors(p.get());
     }
+    // input model: the step kernels consume the applied block on a switched handle, the caller's pointers otherwise
+    plant_load_input_settings(task_info_path, p->input_start, &p->input_seed);
+    p->d_iparams = m.alloc<double>(B * kInputParamStride); p->d_irows = m.alloc<double>((B + 1) * kInputParamStride);
+    p->d_ikey = m.alloc<unsigned>(B * 2); p->d_iticks = m.alloc<unsigned long long>(B * 2);
+    p->d_iring = m.alloc<double>(B * kInputRing * kInputRows * nj, true);
+    p->d_applied = m.alloc<double>(kInputRows * B * nj, true); p->d_applied_force = m.alloc<double>(B * 3, true); p->d_iflags = m.alloc<int>(B * 3, true);
+    HIP_CHECK(hipMemcpy(p->d_irows + B * kInputParamStride, p->input_start, sizeof(p->input_start), hipMemcpyHostToDevice));
+    write_untouched_inputs(p.get());
+    bool inputs_configured = false;
+    for (int e = 0; e < kInputParamUsed; ++e) inputs_configured = inputs_configured || p->input_start[e] != 0.0;
+    if (inputs_configured) {      // a task file with input settings: its row for every robot, under the start key
+      write_rows(p->hs.stream, max_batch, kInputParamStride, kInputParamUsed, nullptr, 1, {p->d_irows + B * kInputParamStride, nullptr, p->d_iparams});
+      switch_inputs(p.get());
+    }
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
     return BPMPC_OK;
   });
@@ -236,6 +282,7 @@ int bpmpc_plant_set_state(bpmpc_plant* p, int batch, const int* mask, const doub
                        p->d_anchor, p->d_anchored);
     HIP_CHECK(hipGetLastError());
     if (p->sense) launch_plant_forget_samples(st, batch, dmask, p->d_sticks);      // n = 0: the robots' sample history is forgotten
+    if (p->input) launch_plant_forget_commands(st, batch, dmask, p->d_iticks);     // n = 0: the robots' buffered commands are forgotten
     p->last_batch = batch;
     if (!inputs_on_device) p->hs.synchronise_own();
     else p->hs.enqueued_own();
@@ -472,6 +519,71 @@ int bpmpc_plant_get_sensor_state(bpmpc_plant* p, int batch, double* gyro_bias, d
 int bpmpc_plant_sensed_outputs(bpmpc_plant* p, bpmpc_sensor_inputs* o) {
   if (!p || !o) { set_last_error("bpmpc_plant_sensed_outputs: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
   *o = p->sensed;
+  return BPMPC_OK;
+}
+
+int bpmpc_plant_get_input_params(const bpmpc_plant* p, int robot, double* row) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_input_params: null handle or row", row != nullptr, [&] {
+    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_input_params: robot exceeds max_batch");
+    const double* src = robot < 0 ? p->d_irows + (size_t)p->max_batch * kInputParamStride : p->d_iparams + (size_t)robot * kInputParamStride;
+    HIP_CHECK(hipMemcpyAsync(row, src, kInputParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_set_input_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_input_params: null handle or rows", rows != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_input_params");
+    set_rows("bpmpc_plant_set_input_params", p->hs.stream, batch, kInputParamStride, kInputParamUsed, mask, p->d_mask, n_rows, inputs_on_device,
+             [&](int r) { plant_check_input_row("bpmpc_plant_set_input_params", rows + (size_t)r * kInputParamStride, r); }, {rows, p->d_irows, p->d_iparams});
+    switch_inputs(p);
+    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_reset_input_params(bpmpc_plant* p) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_input_params: null handle", [&] { write_untouched_inputs(p); });
+}
+
+int bpmpc_plant_seed_inputs(bpmpc_plant* p, int batch, const int* mask, long seed, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_seed_inputs: null handle", [&] {
+    check_batch(p, batch, "bpmpc_plant_seed_inputs");
+    hipStream_t st = p->hs.stream;
+    const int* dmask = staged(mask, p->d_mask, (size_t)batch, inputs_on_device, st);
+    launch_plant_seed_inputs(st, batch, dmask, seed, p->d_ikey, p->d_iticks);
+    switch_inputs(p);
+    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host mask
+    else p->hs.enqueued_own();
+  });
+}
+
+int bpmpc_plant_get_input_state(bpmpc_plant* p, int batch, double* ticks, int* delay_steps, int* lost, int* pushing) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_input_state: null handle", [&] {
+    check_batch(p, batch, "bpmpc_plant_get_input_state");
+    const size_t B = batch, MB = p->max_batch;
+    std::vector<unsigned long long> counters(B * 2);
+    hipStream_t st = p->hs.stream;
+    HIP_CHECK(hipMemcpyAsync(counters.data(), p->d_iticks, B * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (delay_steps) HIP_CHECK(hipMemcpyAsync(delay_steps, p->d_iflags, B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (lost) HIP_CHECK(hipMemcpyAsync(lost, p->d_iflags + MB, B * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (pushing) HIP_CHECK(hipMemcpyAsync(pushing, p->d_iflags + 2 * MB, B * sizeof(int), hipMemcpyDeviceToHost, st));
+    p->hs.synchronise_own();
+    if (ticks) for (size_t i = 0; i < B * 2; ++i) ticks[i] = (double)counters[i];
+  });
+}
+
+int bpmpc_plant_applied_command(bpmpc_plant* p, bpmpc_joint_command* o) {
+  if (!p || !o) { set_last_error("bpmpc_plant_applied_command: null argument"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  if (!p->input) { set_last_error("bpmpc_plant_applied_command: the plant's input model is untouched: the step kernel consumes the caller's command"); return BPMPC_ERR_INVALID_ARGUMENT; }
+  if (!p->applied_valid) {
+    set_last_error("bpmpc_plant_applied_command: the plant's input model has been switched on and no step has run since: there is no applied command");
+    return BPMPC_ERR_INVALID_ARGUMENT;
+  }
+  const size_t rows = (size_t)p->max_batch * p->nj;
+  o->pos_des = p->d_applied; o->vel_des = p->d_applied + rows; o->tau_ff = p->d_applied + 2 * rows; o->kp = p->d_applied + 3 * rows; o->kd = p->d_applied + 4 * rows;
+  o->base_force = p->d_applied_force;
+  o->feet_heights = p->last_ground;
   return BPMPC_OK;
 }
 

@@ -714,9 +714,56 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *       file's, turned on as by seed_sensors(plantSensors.seed).  bpmpc_plant_set_state sets n = 0 for the robots of its mask - their history is
  *       forgotten, the next sample is the first of a new one - and touches neither bias, key nor t, and does not write the sensed block.
  *       bpmpc_plant_reset_sensor_params zeroes every row, bias, t and n, restores the start key and returns the handle to untouched.
+ *   inputs: an input model in front of the step kernels, per robot: command latency, packet loss and pushes on the base.  It turns the command
+ *     and base force a step was called with into the command and base force the step kernel consumes; the step kernels are not changed by it.  It
+ *     is off until it is used (see "switching" below).  The latency is that of the reference's simulated hardware layer, which buffers every joint
+ *     command and applies the oldest one that is not older than gazebo/delay (BipedalHWSim::writeSim, bipedal_gazebo/src/BipedalHWSim.cpp:160-176:
+ *     entries are dropped from the back of cmdBuffer_ while stamp + delay < time, and the back is used); the shipped configurations set 9 ms (H1,
+ *     Hunter, the bipedal_gazebo default) and 2 ms (OpenLoong).  Packet loss and pushes have no counterpart in the reference.
+ *     state per robot: key (2 words), tick t (64 bit): steps since the last seeding, n (64 bit): steps since the robot's last (re)start, a ring of
+ *       R = 16 arrived commands; one slot is the five rows pos_des, vel_des, tau_ff, kp, kd, 5 nj doubles.
+ *     settings: a row of BPMPC_PLANT_INPUT_PARAM_STRIDE doubles per robot, [delay s, dropout (probability 0..1), push_force N, push_interval s,
+ *       push_duration s, reserved 0 x 3].  Every row starts as the keys plantInputs.<name> of task_info_path, an absent key or a NULL path gives 0;
+ *       the key plantInputs.seed (absent: 0) is every robot's start key.  Host rows are validated - every entry finite and not negative,
+ *       dropout <= 1, the reserved entries 0 - and a bad entry is named in bpmpc_last_error() and changes nothing.  A device row cannot be looked
+ *       at: the kernel counts an entry that is not a number or is negative as 0, dropout above 1 as 1, a time of 2^62 ns or more as 2^62 ns.
+ *     random numbers: the generator and the uniform of the sensors (Philox4x32-10, counter = (low word, high word, robot, block), key = seed words,
+ *       uniform (w + 0.5) 2^-32) with two blocks of their own, so that a handle seeded alike for sensors and inputs shares no word: block 64 at
+ *       counter t, whose word 0 is the loss draw u_drop; block 65 at counter w (a push window, below), whose words 0 and 1 are u_s and u_dir.
+ *     one control step, by k_plant_input in front of the step kernel on the plant's stream, with the incoming command c, the caller's base force f
+ *       (NULL: 0) and the call's period.  ns(x) = llrint(x 1e9): integer nanoseconds, as ros::Time / ros::Duration compare them in the reference
+ *       (that ros::Duration(double) rounds to the nearest nanosecond is recalled behaviour, not read from a source).  P = max(1, ns(period)).
+ *       1. loss: lost = (n > 0) and (u_drop < dropout); arrived = lost ? ring[(n - 1) mod R] : c; ring[n mod R] = arrived.  A lost packet leaves
+ *          the joint on what arrived last; consecutive losses keep holding it.
+ *       2. delay: k = min(R - 1, ns(delay) / P) (integer division); applied = ring[max(n - k, 0) mod R]: the oldest command whose age is at most
+ *          delay, and until the history is long enough the first one.  With k = 0 and no loss applied is c, bit for bit.
+ *       3. push, off unless push_force > 0 and ns(push_interval) > 0: W = max(1, ns(push_interval) / P), D = min(W, max(1, ns(push_duration) / P)),
+ *          w = t / W, o = t mod W, s = min(W - D, floor(u_s (W - D + 1))), pushing = (s <= o < s + D); force = f + push_force (cos 2 pi u_dir,
+ *          sin 2 pi u_dir, 0) in the world frame while pushing, else f bit for bit: exactly one push of D steps per window of W steps.
+ *       4. the applied rows (stride nj, leading dimension max_batch), the applied force [3] and the ints lost, pushing, delay_steps = k are written;
+ *          t += 1, n += 1.  The step kernel then runs on the applied rows and force.
+ *     calls: bpmpc_plant_get_input_params / set_input_params / reset_input_params have the shapes, masks, n_rows and host / device semantics of
+ *       bpmpc_plant_get_sensor_params / set_sensor_params / reset_sensor_params (robot < 0: the row of the task file).  bpmpc_plant_seed_inputs, for
+ *       the robots of mask (NULL: every robot below batch; host or device by inputs_on_device): key = seed reinterpreted as unsigned, t = 0, n = 0;
+ *       robots outside the mask do not change by one bit.  bpmpc_plant_get_input_state: host copies of ticks [batch*2] = (t, n) per robot as doubles
+ *       (exact below 2^53) and of delay_steps, lost and pushing [batch] of the last step; each pointer nullable; synchronises.
+ *       bpmpc_plant_applied_command: the applied rows and force where they live (leading dimension max_batch); feet_heights is the device pointer
+ *       the last step consumed (the caller's, or the handle's copy of a host array; NULL when none was given); BPMPC_ERR_INVALID_ARGUMENT on an
+ *       untouched handle or before the first step since the switch.  bpmpc_plant_load_input_params / check_input_params: the ingest (row[8]; a bad
+ *       plantInputs.seed is refused there too) and the row validation as host-only functions.  bpmpc_plant_input_draw: u[3] = (u_drop of block 64,
+ *       u_s and u_dir of block 65) of (seed, robot) at that counter, from the text the kernel compiles, on the host.
+ *     switching: a handle is untouched when its task file has no non-zero plantInputs.<name> key and it has had no set_input_params or seed_inputs
+ *       since create or reset_input_params.  An untouched handle launches nothing new and hands the step kernel the caller's pointers.  Any other
+ *       handle is switched: bpmpc_plant_step, bpmpc_plant_step_controlled and bpmpc_plant_step_supervised launch k_plant_input in front of the step
+ *       kernel - in the latter two inside the waits that bracket the step, so the tick's or supervisor's buffers are read in the window in which the
+ *       step kernel reads them on an untouched handle.  A switched robot whose row is all zero receives its command and force bit for bit.
+ *       bpmpc_plant_set_state sets n = 0 for the robots of its mask - their buffered commands are forgotten (writeSim's "Simulation reset":
+ *       buffer.clear()) - and touches neither key nor t.  bpmpc_plant_reset_input_params zeroes every row, t and n, restores the start key and
+ *       returns the handle to untouched.
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_PLANT_PARAM_STRIDE 8
 #define BPMPC_PLANT_SENSOR_PARAM_STRIDE 16
+#define BPMPC_PLANT_INPUT_PARAM_STRIDE 8
 typedef struct bpmpc_plant bpmpc_plant;
 typedef struct {
   const double *pos_des, *vel_des, *tau_ff, *kp, *kd;   /* [batch*nj] */
@@ -755,6 +802,15 @@ int bpmpc_plant_seed_sensors(bpmpc_plant* plant, int batch, const int* mask, lon
 int bpmpc_plant_get_sensor_state(bpmpc_plant* plant, int batch, double* gyro_bias, double* accel_bias, double* ticks);
 int bpmpc_plant_sensed_outputs(bpmpc_plant* plant, bpmpc_sensor_inputs* dev_out);
 int bpmpc_plant_sensor_draw(long seed, int robot, long tick, double* z, double* u);
+int bpmpc_plant_get_input_params(const bpmpc_plant* plant, int robot, double* row);
+int bpmpc_plant_set_input_params(bpmpc_plant* plant, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_plant_reset_input_params(bpmpc_plant* plant);
+int bpmpc_plant_load_input_params(const char* task_info_path, double row[8]);
+int bpmpc_plant_check_input_params(const double* rows, int n_rows);
+int bpmpc_plant_seed_inputs(bpmpc_plant* plant, int batch, const int* mask, long seed, int inputs_on_device);
+int bpmpc_plant_get_input_state(bpmpc_plant* plant, int batch, double* ticks, int* delay_steps, int* lost, int* pushing);
+int bpmpc_plant_applied_command(bpmpc_plant* plant, bpmpc_joint_command* dev_out);
+int bpmpc_plant_input_draw(long seed, int robot, long counter, double u[3]);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Policy buffer = MPC_MRT_Interface between the solve and the control tick for a BATCH of robots, on the device.  In the reference a thread calls

@@ -12,7 +12,9 @@ belongs).
 --telemetry RING_LEN attaches a tracking-telemetry handle (BatchedTelemetry) with a ring of RING_LEN samples to the controller after the first
 tick and appends, per run, one line to --telemetry-out (profiles/plant_stand_telemetry.jsonl): the statistics of all robots and the ring of the
 first robot that froze (it went unsafe or its state stopped being finite), otherwise of the robot with the largest joint error.
-usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--telemetry RING_LEN [--telemetry-every N]] [--commit ID] [--out FILE]
+--cmd-delay SECONDS runs the same scenario under the plant's input model with that command latency on every robot (InputParams.delay; 0.009 is
+the reference's gazebo/delay for H1); the line records it as cmd_delay and the control steps it came to as cmd_delay_steps.
+usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--cmd-delay SECONDS] [--telemetry RING_LEN [--telemetry-every N]] [--commit ID] [--out FILE]
 """
 import argparse
 import json
@@ -27,7 +29,7 @@ if ROOT not in sys.path:
 PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
 
 
-def run(kt, B, seconds, ring_len=None, every=1):
+def run(kt, B, seconds, ring_len=None, every=1, cmd_delay=0.0):
     import numpy as np
     import torch
     import bipedal_control_amd as bp
@@ -54,6 +56,8 @@ def run(kt, B, seconds, ring_len=None, every=1):
     kn = plant.getParams()[0]
     if kt != "0":      # kt = 0: a handle that never hears of stiction
         plant.setStiction(kn if kt == "kn" else float(kt))
+    if cmd_delay > 0.0:      # no delay: a handle that never hears of the input model
+        plant.setInputParams(bp.InputParams(delay=cmd_delay).toRow())
     plant.set_state(rbd0)
 
     def arm(t, first):
@@ -109,13 +113,14 @@ def run(kt, B, seconds, ring_len=None, every=1):
             if first_unsafe[b] is None and safe[b] == 0:
                 first_unsafe[b] = k
     anchored = plant.anchors()[1]
+    delayed = dict(cmd_delay=cmd_delay, cmd_delay_steps=[int(x) for x in plant.inputState()["delay_steps"]]) if cmd_delay > 0.0 else {}
     record = None
     if tel is not None:
         record = telemetry_record(tel, B, kt=float(plant.getStiction(0)), seconds=seconds, ticks_run=k + 1, period=PERIOD, every=every)
         ctrl.attachTelemetry(None)
     return record, dict(robot="h1", batch=B, seconds=seconds, ticks_run=k + 1, period=PERIOD, substeps=SUBSTEPS, rearm_every=REARM, kt=float(plant.getStiction(0)),
                 state_finite=finite, first_unsafe_tick=first_unsafe, lowest_base_height=num(lowest), final_base_height=num(rbd[:, 5]),
-                start_base_height=num(rbd0[:, 5]), largest_foot_drift=num(drift), anchored_at_end=[int(x) for x in anchored.sum(axis=1)])
+                start_base_height=num(rbd0[:, 5]), largest_foot_drift=num(drift), anchored_at_end=[int(x) for x in anchored.sum(axis=1)], **delayed)
 
 
 def telemetry_record(tel, B, **head):
@@ -148,13 +153,14 @@ def main():
     ap.add_argument("--telemetry-out", default=os.path.join(ROOT, "profiles", "plant_stand_telemetry.jsonl"))
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--kts", default="0,kn")
+    ap.add_argument("--cmd-delay", type=float, default=0.0, metavar="SECONDS", help="command latency of the plant's input model on every robot (0: none)")
     ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
     ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.child is not None:
-        record, line = run(a.child, a.batch, a.seconds, a.telemetry, a.telemetry_every)
+        record, line = run(a.child, a.batch, a.seconds, a.telemetry, a.telemetry_every, a.cmd_delay)
         if a.commit:
             line["commit"] = a.commit
         if record is not None:
@@ -168,7 +174,7 @@ def main():
     lines = []
     kts = a.kts.split(",")
     for kt in kts:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch)]
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch), "--cmd-delay", repr(a.cmd_delay)]
         if a.telemetry is not None:
             cmd += ["--telemetry", str(a.telemetry), "--telemetry-every", str(a.telemetry_every), "--telemetry-out", a.telemetry_out]
         r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
