@@ -19,10 +19,22 @@ ASSETS = os.path.join(ROOT, "assets", "h1")
 _URDF = {"h1": "h1_mpc.urdf", "openloong": "openloong_mpc.urdf", "g1": "g1_mpc.urdf", "hunter": "hunter_mpc.urdf"}
 
 
+_REGISTERED = {}      # name -> (urdf, task, reference): robots that are not under assets/ (tests/tree_variants.py writes their files at test time)
+
+
+def register(name, urdf, task, reference):
+    """Makes model(name) / oracle(name) and everything that takes a robot name work on the given files.  The first registration of a name holds: the model is
+    cached, and the files of a name are the same text wherever they were written."""
+    assert name not in _URDF
+    _REGISTERED.setdefault(name, (urdf, task, reference))
+
+
 @functools.lru_cache(maxsize=None)
 def model(robot="h1"):
     """robot name, optionally with the suffix ":hard" = BipedalRobotInterface(..., useHardFrictionConeConstraint = true)."""
     name, _, variant = robot.partition(":")
+    if name in _REGISTERED:
+        return ingest.build_model(*_REGISTERED[name], use_hard_friction_cone=(variant == "hard"))
     d = os.path.join(ROOT, "assets", name)
     return ingest.build_model(os.path.join(d, _URDF[name]), os.path.join(d, "task.info"), os.path.join(d, "reference.info"),
                               use_hard_friction_cone=(variant == "hard"))
