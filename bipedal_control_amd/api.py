@@ -1395,6 +1395,66 @@ class InputParams:
         return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
 
 
+class JointParams:
+    """A joint row of the plant (include/bpmpc.h "Plant", joints; BPMPC_PLANT_JOINT_PARAM_STRIDE) with named fields: per joint (arrays of nj)
+    armature [kg m^2], damping [N m s/rad], friction_loss [N m], lower and upper [rad, -inf / +inf: no end stop]; per robot the end-stop spring
+    k_limit [N m/rad] and damper c_limit [N m s/rad] and the velocity w_eps [rad/s] that regularises the friction law.  A per-joint field takes a
+    scalar (every joint) or nj values.  Without arguments the row is the neutral one: ideal joints."""
+
+    STRIDE = 64
+    SLOTS = 12
+    JOINT_FIELDS = ("armature", "damping", "friction_loss", "lower", "upper")
+    JOINT_DEFAULTS = (0.0, 0.0, 0.0, -np.inf, np.inf)
+    SCALAR_FIELDS = ("k_limit", "c_limit", "w_eps")
+    SCALAR_DEFAULTS = (1e4, 1e2, 0.01)
+    FIELDS = JOINT_FIELDS + SCALAR_FIELDS
+
+    def __init__(self, nj, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        self.nj = int(nj)
+        if not 1 <= self.nj <= self.SLOTS:
+            raise ValueError("a joint row holds 1..%d joints" % self.SLOTS)
+        for name, default in zip(self.JOINT_FIELDS, self.JOINT_DEFAULTS):
+            value = np.asarray(fields.get(name, default), float)
+            if value.ndim and value.shape != (self.nj,):
+                raise ValueError("%s takes a scalar or %d values" % (name, self.nj))
+            setattr(self, name, np.broadcast_to(value, (self.nj,)).copy())
+        for name, default in zip(self.SCALAR_FIELDS, self.SCALAR_DEFAULTS):
+            setattr(self, name, float(fields.get(name, default)))
+
+    @classmethod
+    def neutral(cls, nj):
+        """Ideal joints: no armature, damping or friction, no end stops."""
+        return cls(nj)
+
+    @classmethod
+    def reference_mjcf(cls, nj):
+        """armature 0.1 kg m^2 and damping 1 N m s/rad on every joint: the values the reference's H1 MJCF declares as the default of every joint
+        (`<default><joint damping="1" armature="0.1"/></default>`, unitree_h1/h1_description/mjcf/h1.xml:7), taken as data."""
+        return cls(nj, armature=0.1, damping=1.0)
+
+    @classmethod
+    def fromRow(cls, row, nj):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a joint row has %d entries" % cls.STRIDE)
+        nj = int(nj)
+        fields = {name: r[i * cls.SLOTS:i * cls.SLOTS + nj] for i, name in enumerate(cls.JOINT_FIELDS)}
+        fields.update({name: r[60 + i] for i, name in enumerate(cls.SCALAR_FIELDS)})
+        return cls(nj, **fields)
+
+    def toRow(self):
+        row = np.zeros(self.STRIDE)
+        for i, (name, default) in enumerate(zip(self.JOINT_FIELDS, self.JOINT_DEFAULTS)):
+            row[i * self.SLOTS:(i + 1) * self.SLOTS] = default
+            row[i * self.SLOTS:i * self.SLOTS + self.nj] = getattr(self, name)
+        for i, name in enumerate(self.SCALAR_FIELDS):
+            row[60 + i] = float(getattr(self, name))
+        return row
+
+
 class BatchedPlant(_Handle):
     """A rigid-body simulation of a batch of robots on one MI355X (bpmpc_plant; include/bpmpc.h "Plant" is its specification): joint commands ->
     the sensors BatchedStateEstimate.update takes and the ground-truth rbd.  This engine's own model - penalty contacts with implicit damping, a
@@ -1573,6 +1633,26 @@ class BatchedPlant(_Handle):
     def resetInputParams(self):
         """Every input row and counter zero, every key the start key (plantInputs.seed): the plant is the one without an input model again."""
         self._call("bpmpc_plant_reset_input_params")
+
+    def setJointParams(self, rows, mask=None):
+        """The joint rows (JointParams.toRow) of the robots with mask[b] != 0 (None: every one): rows [64], [1, 64] or [B, 64].  numpy rows are
+        validated and the call synchronises; device tensors are only enqueued, ordered before the next step.  From the first call on EVERY robot
+        of the plant steps in the kernel that holds the joint model (k_plant_joint_step), also those whose row stays neutral; resetJointParams
+        ends that."""
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], JointParams.STRIDE, self.max_batch)
+        self._call("bpmpc_plant_set_joint_params", B, mp, rp, n_rows, dev)
+        del keep
+
+    def getJointParams(self, robot=-1):
+        """The joint row [64] of `robot` (JointParams.fromRow(row, nj) names its entries), or with robot < 0 the start row (the neutral row under the
+        keys plantJoints.<name> of the task file)."""
+        row = np.zeros(JointParams.STRIDE)
+        self._call("bpmpc_plant_get_joint_params", int(robot), _d(row))
+        return row
+
+    def resetJointParams(self):
+        """Every joint row back to the start row; with a neutral start row the plant is the one without a joint model again."""
+        self._call("bpmpc_plant_reset_joint_params")
 
     def seedInputs(self, seed, mask=None):
         """Restarts the random streams of the input model for the robots with mask[b] != 0 (None: every one of the batch of the last set_state;

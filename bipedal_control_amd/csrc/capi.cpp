@@ -159,6 +159,71 @@ void plant_load_input_settings(const char* task_info_path, double* row, long* se
   std::copy(v, v + kInputParamStride, row);
   if (seed) *seed = (long)s;
 }
+
+namespace {
+const char* const kJointBlockNames[] = {"armature", "damping", "friction_loss", "lower", "upper"};
+}
+
+void plant_check_joint_row(const char* who, const double* row, int r, int nj) {
+  auto refuse = [&](int e, const std::string& name, const char* why) {
+    throw std::invalid_argument(std::string(who) + ": row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + name + ") is " + why);
+  };
+  for (int block = 0; block < 5; ++block)
+    for (int j = 0; j < nj; ++j) {
+      const int e = block * kPlantJointSlots + j;
+      const std::string name = std::string(kJointBlockNames[block]) + "[" + std::to_string(j) + "]";
+      const double x = row[e];
+      if (std::isnan(x)) refuse(e, name, "not a number");
+      if (block < 3 && !std::isfinite(x)) refuse(e, name, "not finite");
+      if (block < 3 && x < 0.0) refuse(e, name, "negative");
+      if (block == 3 && x == HUGE_VAL) refuse(e, name, "+inf");
+      if (block == 4 && x == -HUGE_VAL) refuse(e, name, "-inf");
+      if (block == 4 && !(row[kJointLower + j] < x)) refuse(e, name, "not above lower");
+    }
+  const char* const scalars[] = {"k_limit", "c_limit", "w_eps"};
+  for (int e = kJointKLimit; e <= kJointWEps; ++e) {
+    const double x = row[e];
+    if (!std::isfinite(x)) refuse(e, scalars[e - kJointKLimit], "not finite");
+    if (x < 0.0) refuse(e, scalars[e - kJointKLimit], "negative");
+    if (e == kJointWEps && x == 0.0) refuse(e, scalars[e - kJointKLimit], "zero");
+  }
+  if (row[kJointParamUsed] != 0.0) refuse(kJointParamUsed, "reserved", "not zero");
+}
+
+bool plant_joint_row_neutral(const double* row, int nj) {
+  for (int j = 0; j < nj; ++j)
+    if (row[kJointArmature + j] != 0.0 || row[kJointDamping + j] != 0.0 || row[kJointFriction + j] != 0.0 || row[kJointLower + j] != -HUGE_VAL ||
+        row[kJointUpper + j] != HUGE_VAL)
+      return false;
+  return true;
+}
+
+void plant_load_joint_settings(const RobotModel& rm, const char* task_info_path, double* row) {
+  double v[kPlantJointParamStride] = {};
+  for (int j = 0; j < kPlantJointSlots; ++j) { v[kJointLower + j] = -HUGE_VAL; v[kJointUpper + j] = HUGE_VAL; }
+  v[kJointKLimit] = kPlantJointKLimit; v[kJointCLimit] = kPlantJointCLimit; v[kJointWEps] = kPlantJointWEps;
+  if (task_info_path) {
+    const auto t = read_info_file(task_info_path);
+    double from_urdf = 0.0;
+    (void)t->get("plantJoints.fromUrdf", &from_urdf);
+    if (from_urdf != 0.0)
+      for (int j = 0; j < rm.nj; ++j) {
+        v[kJointLower + j] = rm.joint_lower[1 + j]; v[kJointUpper + j] = rm.joint_upper[1 + j];
+        v[kJointDamping + j] = rm.joint_damping[1 + j]; v[kJointFriction + j] = rm.joint_friction[1 + j];
+      }
+    const char* const per_joint[] = {"armature", "damping", "frictionLoss"};
+    for (int block = 0; block < 3; ++block) {
+      double x = 0.0;
+      if (t->get(std::string("plantJoints.") + per_joint[block], &x))
+        for (int j = 0; j < rm.nj; ++j) v[block * kPlantJointSlots + j] = x;
+    }
+    (void)t->get("plantJoints.kLimit", v + kJointKLimit);
+    (void)t->get("plantJoints.cLimit", v + kJointCLimit);
+    (void)t->get("plantJoints.wEps", v + kJointWEps);
+    plant_check_joint_row("plantJoints settings", v, 0, rm.nj);
+  }
+  std::copy(v, v + kPlantJointParamStride, row);
+}
 }  // namespace bpmpc
 
 using namespace bpmpc;
@@ -229,6 +294,8 @@ int bpmpc_model_get(const bpmpc_model* m, const char* name, double* out, int cap
     if (n == "joint_axis") return copy_out(&r.axis[1][0], 3 * nj, out, capacity);
     if (n == "joint_lower") return copy_out(&r.joint_lower[1], nj, out, capacity);
     if (n == "joint_upper") return copy_out(&r.joint_upper[1], nj, out, capacity);
+    if (n == "joint_damping") return copy_out(&r.joint_damping[1], nj, out, capacity);
+    if (n == "joint_friction") return copy_out(&r.joint_friction[1], nj, out, capacity);
     if (n == "contact_offset") return copy_out(&r.contact_off[0][0], 3 * kNumContacts, out, capacity);
     if (n == "joint_parent") { std::vector<double> t(nj); for (int j = 0; j < nj; ++j) t[j] = r.parent[j + 1]; return copy_out(t.data(), nj, out, capacity); }
     if (n == "contact_body") { std::vector<double> t(kNumContacts); for (int c = 0; c < kNumContacts; ++c) t[c] = r.contact_body[c]; return copy_out(t.data(), t.size(), out, capacity); }
@@ -363,6 +430,25 @@ int bpmpc_plant_input_draw(long seed, int robot, long counter, double u[3]) {
   u[0] = input_loss_draw((unsigned long long)counter, (unsigned)robot, k0, k1);
   input_push_draw((unsigned long long)counter, (unsigned)robot, k0, k1, u + 1, u + 2);
   return BPMPC_OK;
+}
+
+int bpmpc_plant_load_joint_params(const bpmpc_model* model, const char* task_info_path, double* row) {
+  if (!model || !row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_joint_params: null model or row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    double v[kPlantJointParamStride];
+    plant_load_joint_settings(model->rm, task_info_path, v);
+    std::copy(v, v + kPlantJointParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_check_joint_params(const double* rows, int n_rows, int nj) {
+  if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_joint_params: null rows");
+  if (nj < 1 || nj > kMaxJoints) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_joint_params: nj must be 1.." + std::to_string(kMaxJoints));
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) plant_check_joint_row("bpmpc_plant_check_joint_params", rows + (size_t)r * kPlantJointParamStride, r, nj);
+    return (int)BPMPC_OK;
+  });
 }
 
 int bpmpc_gait_create(const bpmpc_model* m, bpmpc_gait** out) {

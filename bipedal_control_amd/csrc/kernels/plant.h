@@ -20,6 +20,12 @@
 // handle launches the instantiation without STICK until stiction is first set on it.  The two instantiations are compiled in translation units of
 // their own (plant.hip, plant_stick.hip): each then has one call site of the rigid-body pass, and the compiler inlines and contracts k_plant_step
 // as it did before the plant had stiction - the same bits at the same speed.
+//
+// Joint model (JOINT; k_plant_joint_step, plant_joint.hip, a third translation unit for the same reason): a joint row per robot (armature, damping,
+// friction loss, end stops; include/bpmpc.h "joints").  Lanes 6..NV-1 load their joint's five constants once per launch and keep them in registers
+// over the substeps; the three scalars of the row are wave-uniform and parked in LDS.  Whether the row is neutral is one ballot per launch: a robot
+// with the neutral row takes the branch that is k_plant_stick_step, operation for operation.  Everything the model adds is lane-local: the
+// armature and the damping go onto the diagonal entry the lane owns, the end-stop torque into the lane's generalised force.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +38,13 @@ namespace bpmpc {
 
 constexpr int kPlantParamStride = 8;      // BPMPC_PLANT_PARAM_STRIDE
 constexpr double kPlantGravity = 9.81;
+constexpr int kPlantJointParamStride = 64;      // BPMPC_PLANT_JOINT_PARAM_STRIDE
+constexpr int kPlantJointSlots = 12;            // joints a row has room for
+// A joint row: five blocks of kPlantJointSlots (armature, damping, friction_loss, lower, upper), then k_limit, c_limit, w_eps, reserved
+enum PlantJointEntry { kJointArmature = 0, kJointDamping = 12, kJointFriction = 24, kJointLower = 36, kJointUpper = 48, kJointKLimit = 60, kJointCLimit = 61,
+                       kJointWEps = 62, kJointParamUsed = 63 };
+constexpr double kPlantJointKLimit = 1e4, kPlantJointCLimit = 1e2, kPlantJointWEps = 0.01;      // the scalars of the neutral row
+static_assert(kMaxJoints <= kPlantJointSlots, "a joint row holds every joint");
 
 // A parameter row
 struct PlantSettings {
@@ -79,6 +92,11 @@ struct PlantStickArgs {
   int* anchored;                                    // [max_batch][4]
 };
 
+// The joint model: what the JOINT instantiation takes beside PlantArgs and PlantStickArgs
+struct PlantJointArgs {
+  const double* rows;                               // [max_batch][kPlantJointParamStride]
+};
+
 template <int NJ>
 struct PlantLds {
   static constexpr int NV = 6 + NJ;
@@ -106,8 +124,19 @@ struct PlantStickLds : PlantLds<NJ> {
   int* anchored_row;
 };
 
-template <int NJ, bool STICK>
-__device__ void plant_robot(const DeviceModel& md, std::conditional_t<STICK, PlantStickLds<NJ>, PlantLds<NJ>>& w, const PlantArgs& a, const PlantStickArgs& sa, int b, int l) {
+// The joint model in LDS, behind the members above: the three scalars of the robot's joint row, parked here over the substeps as h is
+template <int NJ>
+struct PlantJointLds : PlantStickLds<NJ> {
+  double k_limit, c_limit, w_eps;
+};
+
+template <int NJ, bool STICK, bool JOINT>
+using PlantLdsOf = std::conditional_t<JOINT, PlantJointLds<NJ>, std::conditional_t<STICK, PlantStickLds<NJ>, PlantLds<NJ>>>;
+
+template <int NJ, bool STICK, bool JOINT = false>
+__device__ void plant_robot(const DeviceModel& md, PlantLdsOf<NJ, STICK, JOINT>& w, const PlantArgs& a, const PlantStickArgs& sa, int b, int l,
+                            const PlantJointArgs& ja = PlantJointArgs{}) {
+  static_assert(STICK || !JOINT, "the joint model is compiled with stick-slip contacts");
   constexpr int NV = 6 + NJ, NC = kNumContacts;
   WbcRbd<NJ>& r = w.rbd;
   if (l < kPlantParamStride) {      // these lanes all park the same pointers: one predicate for the prologue
@@ -135,6 +164,23 @@ __device__ void plant_robot(const DeviceModel& md, std::conditional_t<STICK, Pla
       w.anchor[l][0] = sa.anchor[((size_t)b * NC + l) * 2]; w.anchor[l][1] = sa.anchor[((size_t)b * NC + l) * 2 + 1];
       w.anchored[l] = sa.anchored[(size_t)b * NC + l];
     }
+  }
+  // this lane's joint: constant over the substeps.  The base lanes carry the neutral values, under which every term below is exactly 0
+  double arm = 0.0, damp = 0.0, fric = 0.0, lower = -HUGE_VAL, upper = HUGE_VAL;
+  bool joints = false;      // wave-uniform: the robot's row is not neutral
+  if constexpr (JOINT) {
+    const double* row = ja.rows + (size_t)b * kPlantJointParamStride;
+    if (l >= 6 && l < NV) {
+      const int j = l - 6;
+      arm = row[kJointArmature + j]; damp = row[kJointDamping + j]; fric = row[kJointFriction + j];
+      lower = row[kJointLower + j]; upper = row[kJointUpper + j];
+    }
+    if (l == 0) {
+      double weps = row[kJointWEps];
+      if (!(weps > 0.0)) weps = kPlantJointWEps;
+      w.k_limit = row[kJointKLimit]; w.c_limit = row[kJointCLimit]; w.w_eps = weps;
+    }
+    joints = __any(arm != 0.0 || damp != 0.0 || fric != 0.0 || lower != -HUGE_VAL || upper != HUGE_VAL) != 0;
   }
   double acc = 0.0;      // lanes 0..2: (v+ - v) / h of the last substep
 
@@ -209,6 +255,9 @@ __device__ void plant_robot(const DeviceModel& md, std::conditional_t<STICK, Pla
     // ---- row l of the system and entry l of the right-hand side
     const double v_old = l < NV ? r.v[l] : 0.0;
     if (l < NV) {
+      if constexpr (JOINT) {
+        if (joints) w.A[l][l] += arm;      // the M of both sides
+      }
       double mv = 0.0;
 #pragma unroll 1
       for (int g = 0; g < NV; ++g) mv += w.A[l][g] * r.v[g];
@@ -224,6 +273,16 @@ __device__ void plant_robot(const DeviceModel& md, std::conditional_t<STICK, Pla
       // base lanes carry kp = kd = tf = 0 and the other lanes wext = 0: no branch on the lane's kind
       const double tau = fmin(lim, fmax(-lim, kp * (pd - r.q[l]) + tf));
       gen += wext + tau + kd * vd;
+      double cj = 0.0;      // passive damping of this lane's joint
+      if constexpr (JOINT) {
+        if (joints) {
+          const double ql = r.q[l], weps = w.w_eps;
+          const double pen_up = fmax(ql - upper, 0.0), pen_lo = fmax(lower - ql, 0.0);
+          gen += w.k_limit * (pen_lo - pen_up);      // outside the clamp: the end stop is not the actuator
+          cj = damp + fric / sqrt(v_old * v_old + weps * weps);
+          if (pen_up > 0.0 || pen_lo > 0.0) cj += w.c_limit;
+        }
+      }
 #pragma unroll 1
       for (int i = 0; i < NC; ++i)
         if (w.closed[i])
@@ -232,7 +291,12 @@ __device__ void plant_robot(const DeviceModel& md, std::conditional_t<STICK, Pla
             const double c = h * w.D[3 * i + k] * jr[l];
             for (int g = 0; g <= l; ++g) w.A[l][g] += c * jr[g];
           }
-      w.A[l][l] += h * kd;
+      if constexpr (JOINT) {
+        if (joints) w.A[l][l] += h * (kd + cj);
+        else w.A[l][l] += h * kd;
+      } else {
+        w.A[l][l] += h * kd;
+      }
       w.A[l][NV] = mv + h * gen;
     }
     // ---- Cholesky A = L L' (row l below the diagonal), y = L^-1 rhs in column NV

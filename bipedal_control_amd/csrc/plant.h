@@ -34,6 +34,11 @@ struct bpmpc_plant {
   double* d_kt_in = nullptr;            // [max_batch] device copy of host values
   double* d_anchor = nullptr;           // [max_batch][4][2]
   int* d_anchored = nullptr;            // [max_batch][4]
+  // joint model (include/bpmpc.h "Plant", joints): per-robot joint rows
+  double joint_start[bpmpc::kPlantJointParamStride] = {};      // the start row: the neutral row under the keys plantJoints.<name> of task.info
+  bool joint = false;                   // steps launch k_plant_joint_step: the start row is not neutral, or rows have been set since create / reset_joint_params
+  double* d_jparams = nullptr;          // [max_batch][kPlantJointParamStride]
+  double* d_jrows = nullptr;            // [max_batch + 1][kPlantJointParamStride] device copy of host rows; the last row holds joint_start
   double* d_out = nullptr;              // the output block of k_plant_step (kernels/plant.h PlantOut)
   bpmpc_plant_outputs out{};            // its sections (leading dimension max_batch)
   // sensor model (include/bpmpc.h "Plant", sensors): per-robot rows, generator state, biases, the ring of measured samples, the sensed block
@@ -67,6 +72,7 @@ struct bpmpc_plant {
 
 static_assert(bpmpc::kPlantParamStride == BPMPC_PLANT_PARAM_STRIDE, "PlantSettings follows the row layout of include/bpmpc.h");
 static_assert(bpmpc::kInputParamStride == BPMPC_PLANT_INPUT_PARAM_STRIDE, "an input row follows the layout of include/bpmpc.h");
+static_assert(bpmpc::kPlantJointParamStride == BPMPC_PLANT_JOINT_PARAM_STRIDE, "a joint row follows the layout of include/bpmpc.h");
 
 namespace bpmpc {
 // The keys plant.<name> of task.info over the defaults (NULL: the defaults); host only (capi.cpp), also behind bpmpc_plant_load_params
@@ -78,6 +84,16 @@ double plant_load_stiction(const char* task_info_path);
 
 // plant_stick.hip: one launch of k_plant_stick_step<nj> for a.batch robots on `stream`
 void launch_plant_stick_step(int nj, hipStream_t stream, const DeviceModel* model, const PlantArgs& a, const PlantStickArgs& sa);
+
+// plant_joint.hip: one launch of k_plant_joint_step<nj> for a.batch robots on `stream`
+void launch_plant_joint_step(int nj, hipStream_t stream, const DeviceModel* model, const PlantArgs& a, const PlantStickArgs& sa, const PlantJointArgs& ja);
+// The start row of a handle: the neutral row, the URDF's limits and <dynamics> under plantJoints.fromUrdf 1, the scalar keys plantJoints.<name> of
+// task.info over both (NULL: the neutral row); host only (capi.cpp), also behind bpmpc_plant_load_joint_params
+void plant_load_joint_settings(const RobotModel& rm, const char* task_info_path, double* row);
+// A host row of a robot with nj joints before it is accepted (include/bpmpc.h "joints"); throws std::invalid_argument naming the entry
+void plant_check_joint_row(const char* who, const double* row, int r, int nj);
+// Whether a row is the neutral one as far as a robot with nj joints reads it: no armature, damping or friction, no finite limit
+bool plant_joint_row_neutral(const double* row, int nj);
 
 // A measured sample, in doubles: joint_pos[nj], joint_vel[nj], quat[4], angular_vel_local[3], linear_accel_local[3], contact[4] (0.0 or 1.0): one
 // slot of the ring.  The sensed block holds the same members as sections of leading dimension max_batch, the contacts as four ints (2 doubles).

@@ -86,6 +86,13 @@ void write_default_stiction(bpmpc_plant* p) {
   p->stick = p->kt_start > 0.0;
 }
 
+// every joint row becomes the start row (the last row of d_jrows), and the start row decides which kernel steps launch
+void write_start_joint_params(bpmpc_plant* p) {
+  write_rows(p->hs.stream, p->max_batch, kPlantJointParamStride, kJointParamUsed, nullptr, 1,
+             {p->d_jrows + (size_t)p->max_batch * kPlantJointParamStride, nullptr, p->d_jparams});
+  p->joint = !plant_joint_row_neutral(p->joint_start, p->nj);
+}
+
 void check_batch(const bpmpc_plant* p, int batch, const char* who) {
   if (batch < 1) throw std::invalid_argument(std::string(who) + ": batch must be positive");
   if (batch > p->max_batch) throw std::length_error(std::string(who) + ": batch exceeds max_batch");
@@ -126,7 +133,11 @@ void launch_input(bpmpc_plant* p, PlantArgs& a, double period) {
 // the step kernel, on a switched handle the input model in front of it and the sensor model behind it: `period` is the control step's
 void launch_step(bpmpc_plant* p, PlantArgs a, double period) {
   launch_input(p, a, period);
-  if (p->stick) {
+  if (p->joint) {      // the joint model is in use: one kernel holds it and stick-slip contacts
+    const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
+    launch_plant_joint_step(p->nj, p->hs.stream, p->d_model, a, sa, PlantJointArgs{p->d_jparams});
+  }
+  else if (p->stick) {
     const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
     launch_plant_stick_step(p->nj, p->hs.stream, p->d_model, a, sa);
   }
@@ -218,6 +229,10 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
     HIP_CHECK(hipMemcpy(p->d_rows + B * kPlantParamStride, &p->defaults, sizeof(PlantSettings), hipMemcpyHostToDevice));
     write_default_params(p.get());
     write_default_stiction(p.get());
+    plant_load_joint_settings(p->rm, task_info_path, p->joint_start);
+    p->d_jparams = m.alloc<double>(B * kPlantJointParamStride); p->d_jrows = m.alloc<double>((B + 1) * kPlantJointParamStride);
+    HIP_CHECK(hipMemcpy(p->d_jrows + B * kPlantJointParamStride, p->joint_start, sizeof(p->joint_start), hipMemcpyHostToDevice));
+    write_start_joint_params(p.get());
     // sensor model: the members it measures live in the sensed block, the others are the truth's
     plant_load_sensor_settings(task_info_path, p->sensor_start, &p->sensor_seed);
     p->d_sparams = m.alloc<double>(B * kSensorParamStride); p->d_srows = m.alloc<double>((B + 1) * kSensorParamStride);
@@ -417,6 +432,33 @@ int bpmpc_plant_set_params(bpmpc_plant* p, int batch, const int* mask, const dou
 int bpmpc_plant_reset_params(bpmpc_plant* p) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_params: null handle", [&] {
     write_default_params(p);
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_get_joint_params(const bpmpc_plant* p, int robot, double* row) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_joint_params: null handle or row", row != nullptr, [&] {
+    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_joint_params: robot exceeds max_batch");
+    const double* src = robot < 0 ? p->d_jrows + (size_t)p->max_batch * kPlantJointParamStride : p->d_jparams + (size_t)robot * kPlantJointParamStride;
+    HIP_CHECK(hipMemcpyAsync(row, src, kPlantJointParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_set_joint_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_joint_params: null handle or rows", rows != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_joint_params");
+    set_rows("bpmpc_plant_set_joint_params", p->hs.stream, batch, kPlantJointParamStride, kJointParamUsed, mask, p->d_mask, n_rows, inputs_on_device,
+             [&](int r) { plant_check_joint_row("bpmpc_plant_set_joint_params", rows + (size_t)r * kPlantJointParamStride, r, p->nj); },
+             {rows, p->d_jrows, p->d_jparams});
+    p->joint = true;      // from here on every robot of the handle steps in k_plant_joint_step
+    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // device rows are only enqueued on the handle's stream: the next step runs behind them
+  });
+}
+
+int bpmpc_plant_reset_joint_params(bpmpc_plant* p) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_joint_params: null handle", [&] {
+    write_start_joint_params(p);
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
   });
 }

@@ -91,6 +91,7 @@ struct TreeBuilder {
         const double n = std::sqrt(j->axis[0] * j->axis[0] + j->axis[1] * j->axis[1] + j->axis[2] * j->axis[2]);
         for (int i = 0; i < 3; ++i) out.axis[idx][i] = j->axis[i] / n;
         out.joint_lower[idx] = j->lower; out.joint_upper[idx] = j->upper;
+        out.joint_damping[idx] = j->damping; out.joint_friction[idx] = j->friction;
         out.joint_names.push_back(j->name);
         acc.emplace_back();
         descend(j->child, idx, identity());

@@ -72,6 +72,7 @@ struct RobotModel {
   int parent[kMaxBodies] = {};
   double Rfix[kMaxBodies][9] = {}, pfix[kMaxBodies][3] = {}, axis[kMaxBodies][3] = {};
   double joint_lower[kMaxBodies] = {}, joint_upper[kMaxBodies] = {};      // the URDF's position limits of joint j, -inf / +inf without a <limit> tag
+  double joint_damping[kMaxBodies] = {}, joint_friction[kMaxBodies] = {};      // the URDF's <dynamics damping friction> of joint j, 0 without the tag
   double mass[kMaxBodies] = {}, com[kMaxBodies][3] = {}, inertia[kMaxBodies][9] = {};
   int contact_body[kNumContacts] = {};
   double contact_off[kNumContacts][3] = {};

@@ -172,6 +172,10 @@ UrdfRobot read_urdf_file(const std::string& path) {
         j.lower = parse_number(lim->get("lower", "0"));
         j.upper = parse_number(lim->get("upper", "0"));
       }
+      if (const XmlElement* dyn = e.child("dynamics"); dyn && j.type == "revolute") {
+        j.damping = parse_number(dyn->get("damping", "0"));
+        j.friction = parse_number(dyn->get("friction", "0"));
+      }
       robot.joints.push_back(j);
     }
   }

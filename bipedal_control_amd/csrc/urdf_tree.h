@@ -1,4 +1,4 @@
-// Minimal URDF reader: just enough XML to recover links (inertial) and joints (origin/parent/child/axis/type/limit).
+// Minimal URDF reader: just enough XML to recover links (inertial) and joints (origin/parent/child/axis/type/limit/dynamics).
 // The kinematic conventions applied on top of it are those of the reference's model construction,
 // centroidal_model::createPinocchioInterface(urdf, jointNames) (call site
 // ocs2_bipedal_robot/src/BipedalRobotInterface.cpp:117) -- see robot_model.cpp.
@@ -24,6 +24,8 @@ struct UrdfJoint {
   double axis[3] = {1, 0, 0};
   // <limit lower= upper=> of a revolute joint (urdf::Joint::limits); without the tag, or for another joint type, the joint is unbounded
   double lower = -std::numeric_limits<double>::infinity(), upper = std::numeric_limits<double>::infinity();
+  // <dynamics damping= friction=> of a revolute joint (urdf::Joint::dynamics); an absent tag or attribute is 0
+  double damping = 0.0, friction = 0.0;
 };
 
 struct UrdfRobot {

@@ -57,6 +57,8 @@ int bpmpc_model_dims(const bpmpc_model* model, int* nx, int* nu, int* n_contacts
  * Names: "initial_state" (BipedalRobotInterface::getInitialState), "default_joint_state", "Q", "R", "robot_mass",
  * "com_height", "body_mass", "body_com", "body_inertia", "joint_parent", "joint_rotation", "joint_offset", "joint_axis",
  * "joint_lower", "joint_upper" (<limit lower= upper=> of the URDF's revolute joints, urdf::Joint::limits; -inf / +inf without the tag),
+ * "joint_damping", "joint_friction" (<dynamics damping= friction=> of the URDF's revolute joints, urdf::Joint::dynamics; 0 without the tag or
+ * the attribute),
  * "contact_body", "contact_offset", "cone" (mu, regularization, gripper force, hessian shift, barrier mu, barrier delta),
  * "swing" (liftOffVelocity, touchDownVelocity, swingHeight, swingTimeScale), "sqp" (dt, sqpIteration, deltaTol, g_max, g_min,
  * useFeedbackPolicy, projectStateInputEqualityConstraints (always 1), integratorType (always 0 = RK2): bpmpc_model_create returns
@@ -599,7 +601,8 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  * Plant = a rigid-body simulation of a BATCH of robots on the device: joint commands in, the sensors of bpmpc_sensor_inputs out, so that the
  * loop sensors -> bpmpc_estimator_update -> bpmpc_controller_tick_estimated -> joint commands closes without leaving the device.  The reference
  * closes its loop with MuJoCo or Gazebo (bipedal_mujoco, bipedal_gazebo/src/BipedalHWSim.cpp).  This plant imitates neither: it is this engine's own
- * model, this comment is its specification, and it is nowhere pinned against the reference's simulators.  It has no joint limits, no
+ * model, this comment is its specification, and it is nowhere pinned against the reference's simulators.  Its joints are ideal until a joint
+ * row says otherwise (see "joints": armature, damping, friction and end stops per robot).  It has no
  * self-collision and no torsional friction about the contact normal.  Its contacts stick and slip (a tangential anchor spring with a Coulomb cap)
  * for the robots whose tangential stiffness kt is set above 0; with kt = 0, the default, friction is the regularised Coulomb damper alone, under
  * which a loaded foot creeps.
@@ -760,8 +763,56 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *       bpmpc_plant_set_state sets n = 0 for the robots of its mask - their buffered commands are forgotten (writeSim's "Simulation reset":
  *       buffer.clear()) - and touches neither key nor t.  bpmpc_plant_reset_input_params zeroes every row, t and n, restores the start key and
  *       returns the handle to untouched.
+ *   joints: a joint model inside the step, per robot: rotor inertia (armature), viscous damping, Coulomb friction and end stops.  It is this
+ *     engine's own model like the rest of the plant; it imitates neither MuJoCo's constraint solver nor Gazebo's and is pinned against neither.  It
+ *     is off until it is used (see "switching" below).
+ *     settings: a joint row of BPMPC_PLANT_JOINT_PARAM_STRIDE = 64 doubles per robot, beside the parameter row (whose layout and reserved entries it
+ *       leaves alone):
+ *          0..11  armature[j]       kg m^2       >= 0, added to the diagonal of M at coordinate 6 + j
+ *         12..23  damping[j]        N m s/rad    >= 0, viscous, linearly implicit
+ *         24..35  friction_loss[j]  N m          >= 0, regularised Coulomb, linearly implicit
+ *         36..47  lower[j]          rad          may be -inf
+ *         48..59  upper[j]          rad          may be +inf; lower < upper
+ *         60      k_limit           N m/rad      >= 0, end-stop spring, explicit
+ *         61      c_limit           N m s/rad    >= 0, end-stop damper, implicit, acts only beyond a limit
+ *         62      w_eps             rad/s        > 0, regularisation of the friction law
+ *         63      reserved                       written as 0
+ *       Entries j >= nj are ignored.  The neutral row is armature = damping = friction_loss = 0, lower = -inf, upper = +inf, k_limit = 1e4,
+ *       c_limit = 1e2, w_eps = 0.01.  The three scalar defaults are this engine's choice; nobody has measured them on a robot.  The end-stop spring
+ *       is explicit, so it is stable only while h^2 k_limit < 4 (I_jj + armature_j + h (kd_j + c_j)) with I_jj the joint's diagonal entry of M: at
+ *       h = 0.5 ms and k_limit = 1e4 the left side is 2.5e-3 kg m^2, which a joint with no armature, no damping and no kd can fall below.
+ *     one substep for a robot whose row is not neutral, joint j, coordinate l = 6 + j, start-of-substep (q, v), in terms of steps 3 and 4 above:
+ *       a. M_ll += armature_j: the M of both sides, the system matrix and M v
+ *       b. end stop: pen_up = max(q_l - upper_j, 0), pen_lo = max(lower_j - q_l, 0), tau_lim = k_limit (pen_lo - pen_up), added to the
+ *          generalised force outside the torque clamp of step 3 (the clamp models the actuator, the end stop does not);
+ *          beyond = pen_up > 0 or pen_lo > 0
+ *       c. implicit joint damping c_j = damping_j + friction_loss_j / sqrt(v_l^2 + w_eps^2) + (beyond ? c_limit : 0)
+ *       d. the system matrix gets h (kd_j + c_j) on its diagonal where it gets h kd_j in step 4; nothing is added to the right-hand side (there is
+ *          no velDes for passive damping)
+ *       The matrix stays symmetric positive definite and is factored as before.  A robot with the neutral row (every armature, damping and
+ *       friction_loss of a joint j < nj zero, every limit infinite) runs the arithmetic of k_plant_stick_step and nothing else.
+ *     Every row starts as the start row of task_info_path: the neutral row, then the optional scalar keys plantJoints.armature, .damping,
+ *       .frictionLoss (each applied to every joint), .kLimit, .cLimit, .wEps; plantJoints.fromUrdf 1 takes lower / upper from the model's <limit>
+ *       and damping / friction_loss from its <dynamics damping friction> (bpmpc_model_get "joint_lower", "joint_upper", "joint_damping",
+ *       "joint_friction"), and the scalar keys override the URDF values where both are given.  An absent block or a NULL path gives the neutral row.
+ *     calls: bpmpc_plant_get_joint_params / set_joint_params / reset_joint_params have the shapes (row[64]), masks, n_rows, host / device semantics,
+ *       error codes and stream ordering of bpmpc_plant_get_params / set_params / reset_params (robot < 0: the start row).  Host rows are validated -
+ *       every used entry finite, except that lower may be -inf and upper +inf; armature, damping, friction_loss, k_limit and c_limit not negative;
+ *       lower < upper; w_eps > 0; reserved 0 - and a bad entry is named in bpmpc_last_error() and changes nothing.  A device row cannot be looked
+ *       at: the kernel takes a w_eps that is not > 0 as 0.01.  The state of robots outside the mask does not change by one bit, given that the same
+ *       kernel is launched.  bpmpc_plant_set_state and a restart keep the rows, as they keep the parameter rows.  bpmpc_plant_load_joint_params /
+ *       check_joint_params: the ingest (row[64], from the model and task_info_path) and the row validation (rows[n_rows*64] of a robot with nj
+ *       joints) as host-only functions.
+ *     switching: a handle whose start row is neutral (in the sense above: what a robot with nj joints reads of it) and that has had no set_joint_params since create or reset_joint_params launches
+ *       exactly what it launched before the plant had a joint model (k_plant_step or k_plant_stick_step).  Any other handle launches
+ *       k_plant_joint_step, which holds stick-slip contacts and the joint model, from bpmpc_plant_step, bpmpc_plant_step_controlled and
+ *       bpmpc_plant_step_supervised alike.  The first set_joint_params on a handle therefore changes which kernel runs for EVERY robot of it, also
+ *       those outside its mask and those whose row stays neutral: such a robot agrees with the other kernels to rounding (1e-9 relative is
+ *       asserted; on the device it returned k_plant_stick_step's bits for H1 and G1, which the tests print and nothing promises).  bpmpc_plant_reset_joint_params writes the start row into every row and returns the handle
+ *       to the kernel that start row selects.
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_PLANT_PARAM_STRIDE 8
+#define BPMPC_PLANT_JOINT_PARAM_STRIDE 64
 #define BPMPC_PLANT_SENSOR_PARAM_STRIDE 16
 #define BPMPC_PLANT_INPUT_PARAM_STRIDE 8
 typedef struct bpmpc_plant bpmpc_plant;
@@ -811,6 +862,11 @@ int bpmpc_plant_seed_inputs(bpmpc_plant* plant, int batch, const int* mask, long
 int bpmpc_plant_get_input_state(bpmpc_plant* plant, int batch, double* ticks, int* delay_steps, int* lost, int* pushing);
 int bpmpc_plant_applied_command(bpmpc_plant* plant, bpmpc_joint_command* dev_out);
 int bpmpc_plant_input_draw(long seed, int robot, long counter, double u[3]);
+int bpmpc_plant_get_joint_params(const bpmpc_plant* plant, int robot, double* row);
+int bpmpc_plant_set_joint_params(bpmpc_plant* plant, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_plant_reset_joint_params(bpmpc_plant* plant);
+int bpmpc_plant_load_joint_params(const bpmpc_model* model, const char* task_info_path, double* row);
+int bpmpc_plant_check_joint_params(const double* rows, int n_rows, int nj);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Policy buffer = MPC_MRT_Interface between the solve and the control tick for a BATCH of robots, on the device.  In the reference a thread calls
@@ -1121,7 +1177,8 @@ int bpmpc_plan_rows_host(const bpmpc_model* model, int n_nodes, const double* t,
  *     controller_restart(mask = ready, on device) -> setup_commands(x0 = NULL) -> run -> tick_estimated
  *     request(mask = NULL, RUN, only_ready = 1)
  *     loop: step_supervised -> update_from_plant -> tick_estimated -> update_controlled      (a robot that tilts is STOPPED on the device)
- *   Not reproduced: UpperJointController; joint limits inside the plant; the tick's own `safe` flag is unchanged.
+ *   Not reproduced: UpperJointController; the tick's own `safe` flag is unchanged.  The plant has end stops of its own since its joint model
+ *     (bpmpc_plant_set_joint_params); the clamp here is unchanged by them and clamps the command, not the joint.
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_SUP_PARAM_STRIDE 8
 #define BPMPC_SUP_INIT 0

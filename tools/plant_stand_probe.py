@@ -14,7 +14,10 @@ tick and appends, per run, one line to --telemetry-out (profiles/plant_stand_tel
 first robot that froze (it went unsafe or its state stopped being finite), otherwise of the robot with the largest joint error.
 --cmd-delay SECONDS runs the same scenario under the plant's input model with that command latency on every robot (InputParams.delay; 0.009 is
 the reference's gazebo/delay for H1); the line records it as cmd_delay and the control steps it came to as cmd_delay_steps.
-usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--cmd-delay SECONDS] [--telemetry RING_LEN [--telemetry-every N]] [--commit ID] [--out FILE]
+--joint-preset mjcf gives every robot the joint rows of JointParams.reference_mjcf (armature 0.1, damping 1: the <default> of the reference's H1
+MJCF); --joint-limits urdf adds the model's <limit> as end stops (the committed models carry none, so it changes nothing for them).  With either
+the plant steps in k_plant_joint_step; the line records both and the largest distance a joint went beyond a finite limit.
+usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2.0] [--batch 8] [--cmd-delay SECONDS] [--joint-preset {none,mjcf}] [--joint-limits {none,urdf}] [--telemetry RING_LEN [--telemetry-every N]] [--commit ID] [--out FILE]
 """
 import argparse
 import json
@@ -29,7 +32,7 @@ if ROOT not in sys.path:
 PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
 
 
-def run(kt, B, seconds, ring_len=None, every=1, cmd_delay=0.0):
+def run(kt, B, seconds, ring_len=None, every=1, cmd_delay=0.0, joint_preset="none", joint_limits="none"):
     import numpy as np
     import torch
     import bipedal_control_amd as bp
@@ -58,6 +61,14 @@ def run(kt, B, seconds, ring_len=None, every=1, cmd_delay=0.0):
         plant.setStiction(kn if kt == "kn" else float(kt))
     if cmd_delay > 0.0:      # no delay: a handle that never hears of the input model
         plant.setInputParams(bp.InputParams(delay=cmd_delay).toRow())
+    lower, upper = np.full(nj, -np.inf), np.full(nj, np.inf)
+    if joint_preset != "none" or joint_limits != "none":      # neither: a handle that never hears of the joint model
+        row = bp.JointParams.reference_mjcf(nj) if joint_preset == "mjcf" else bp.JointParams.neutral(nj)
+        if joint_limits == "urdf":
+            lower, upper = np.array(itf.get("joint_lower"), float), np.array(itf.get("joint_upper"), float)
+            row.lower, row.upper = lower, upper
+        plant.setJointParams(row.toRow())
+    beyond = np.zeros(B)
     plant.set_state(rbd0)
 
     def arm(t, first):
@@ -107,6 +118,7 @@ def run(kt, B, seconds, ring_len=None, every=1, cmd_delay=0.0):
         p = points(rbd)
         start = p if start is None else start
         lowest = np.minimum(lowest, rbd[:, 5])
+        beyond = np.maximum(beyond, np.maximum(rbd[:, 6:6 + nj] - upper, lower - rbd[:, 6:6 + nj]).max(axis=1).clip(min=0.0))
         moved = np.linalg.norm(p - start, axis=2) * (contact != 0)
         drift = np.maximum(drift, moved.max(axis=1))
         for b in range(B):
@@ -114,6 +126,9 @@ def run(kt, B, seconds, ring_len=None, every=1, cmd_delay=0.0):
                 first_unsafe[b] = k
     anchored = plant.anchors()[1]
     delayed = dict(cmd_delay=cmd_delay, cmd_delay_steps=[int(x) for x in plant.inputState()["delay_steps"]]) if cmd_delay > 0.0 else {}
+    if joint_preset != "none" or joint_limits != "none":
+        delayed.update(joint_preset=joint_preset, joint_limits=joint_limits, finite_limits=int(np.isfinite(lower).sum() + np.isfinite(upper).sum()),
+                       largest_limit_excess=num(beyond))
     record = None
     if tel is not None:
         record = telemetry_record(tel, B, kt=float(plant.getStiction(0)), seconds=seconds, ticks_run=k + 1, period=PERIOD, every=every)
@@ -154,13 +169,15 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--kts", default="0,kn")
     ap.add_argument("--cmd-delay", type=float, default=0.0, metavar="SECONDS", help="command latency of the plant's input model on every robot (0: none)")
+    ap.add_argument("--joint-preset", choices=["none", "mjcf"], default="none", help="joint rows of every robot: ideal joints, or the reference's MJCF defaults")
+    ap.add_argument("--joint-limits", choices=["none", "urdf"], default="none", help="end stops: none, or the model's <limit> tags")
     ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
     ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     ap.add_argument("--out")
     a = ap.parse_args()
     if a.child is not None:
-        record, line = run(a.child, a.batch, a.seconds, a.telemetry, a.telemetry_every, a.cmd_delay)
+        record, line = run(a.child, a.batch, a.seconds, a.telemetry, a.telemetry_every, a.cmd_delay, a.joint_preset, a.joint_limits)
         if a.commit:
             line["commit"] = a.commit
         if record is not None:
@@ -174,7 +191,8 @@ def main():
     lines = []
     kts = a.kts.split(",")
     for kt in kts:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch), "--cmd-delay", repr(a.cmd_delay)]
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch), "--cmd-delay", repr(a.cmd_delay),
+               "--joint-preset", a.joint_preset, "--joint-limits", a.joint_limits]
         if a.telemetry is not None:
             cmd += ["--telemetry", str(a.telemetry), "--telemetry-every", str(a.telemetry_every), "--telemetry-out", a.telemetry_out]
         r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)

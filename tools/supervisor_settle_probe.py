@@ -14,7 +14,9 @@ at which the tick's `safe` flag was 0, the tick at which the supervisor stopped 
 the first tick after which a robot's state is not finite.  A probe, not a test: nothing asserts its outcome, and standing is claimed only where
 it is seen.  Each run is a child process under a time limit; a run that fails or runs out of time ends the probe.  One JSON line per run on
 stdout; --out appends them to a file (profiles/supervisor_settle_probe.jsonl is where the published one belongs).
-usage (GPU box, repository root): python tools/supervisor_settle_probe.py [--seconds 2.0] [--batch 8] [--kt kn] [--commit ID] [--out FILE]
+--joint-preset mjcf / --joint-limits urdf give the plant the joint rows of tools/plant_stand_probe.py (the reference's MJCF defaults; the model's
+<limit> tags as end stops); --variants chooses among plain, reference and holding.
+usage (GPU box, repository root): python tools/supervisor_settle_probe.py [--seconds 2.0] [--batch 8] [--kt kn] [--joint-preset {none,mjcf}] [--joint-limits {none,urdf}] [--variants LIST] [--commit ID] [--out FILE]
 """
 import argparse
 import json
@@ -31,7 +33,7 @@ GAINS = {"reference": None, "holding": (2000.0, 40.0)}
 RAMP_TIME, POS_TOL, VEL_TOL, SETTLE_TIME = 0.1, 0.05, 0.5, 0.2
 
 
-def settled(gains, kt, B, seconds, settle_seconds):
+def settled(gains, kt, B, seconds, settle_seconds, joint_preset="none", joint_limits="none"):
     import numpy as np
     import torch
     import bipedal_control_amd as bp
@@ -56,6 +58,11 @@ def settled(gains, kt, B, seconds, settle_seconds):
     ctrl.setJointGains(np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KP), np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KD))
     if kt != "0":
         plant.setStiction(plant.getParams()[0] if kt == "kn" else float(kt))
+    if joint_preset != "none" or joint_limits != "none":      # neither: a handle that never hears of the joint model
+        row = bp.JointParams.reference_mjcf(nj) if joint_preset == "mjcf" else bp.JointParams.neutral(nj)
+        if joint_limits == "urdf":
+            row.lower, row.upper = np.array(itf.get("joint_lower"), float), np.array(itf.get("joint_upper"), float)
+        plant.setJointParams(row.toRow())
     sup.setParams(bp.SupervisorParams(ramp_time=RAMP_TIME, settle_pos_tol=POS_TOL, settle_vel_tol=VEL_TOL, settle_time=SETTLE_TIME).toRow())
     if GAINS[gains] is not None:
         sup.setJointRows("kp_init", np.full(nj, GAINS[gains][0]))
@@ -85,6 +92,8 @@ def settled(gains, kt, B, seconds, settle_seconds):
     line = dict(robot="h1", batch=B, variant="settled", init_gains=gains, kt=float(plant.getStiction(0)), period=PERIOD, substeps=SUBSTEPS, rearm_every=REARM,
                 ramp_time=RAMP_TIME, settle_pos_tol=POS_TOL, settle_vel_tol=VEL_TOL, settle_time=SETTLE_TIME, settle_seconds_allowed=settle_seconds,
                 start_base_height=num(rbd0[:, 5]), ready_tick=ready_tick, handover=handover)
+    if joint_preset != "none" or joint_limits != "none":
+        line.update(joint_preset=joint_preset, joint_limits=joint_limits)
     if not np.all(np.isfinite(rbd)) or not any(s["ready"]):
         line.update(seconds=0.0, ticks_run=0, state_finite=bool(np.all(np.isfinite(rbd))), note="no robot became ready: no hand-over")
         return line
@@ -142,6 +151,9 @@ def main():
     ap.add_argument("--settle-seconds", type=float, default=2.0, help="how long the robots may take to become ready")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--kt", default="kn", help="the plant's tangential contact stiffness: 0, kn or a number (tools/plant_stand_probe.py)")
+    ap.add_argument("--joint-preset", choices=["none", "mjcf"], default="none", help="joint rows of every robot: ideal joints, or the reference's MJCF defaults")
+    ap.add_argument("--joint-limits", choices=["none", "urdf"], default="none", help="end stops: none, or the model's <limit> tags")
+    ap.add_argument("--variants", default=",".join(["plain"] + list(GAINS)), help="which runs: plain, reference, holding")
     ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
     ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
     ap.add_argument("--child", help=argparse.SUPPRESS)
@@ -150,19 +162,19 @@ def main():
     if a.child is not None:
         if a.child == "plain":
             from tools.plant_stand_probe import run
-            _, line = run(a.kt, a.batch, a.seconds)
+            _, line = run(a.kt, a.batch, a.seconds, joint_preset=a.joint_preset, joint_limits=a.joint_limits)
             line["variant"] = "plain"
         else:
-            line = settled(a.child, a.kt, a.batch, a.seconds, a.settle_seconds)
+            line = settled(a.child, a.kt, a.batch, a.seconds, a.settle_seconds, a.joint_preset, a.joint_limits)
         if a.commit:
             line["commit"] = a.commit
         print(json.dumps(line), flush=True)
         return 0
-    jobs = ["plain"] + list(GAINS)
+    jobs = a.variants.split(",")
     lines = []
     for job in jobs:
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", job, "--seconds", repr(a.seconds), "--settle-seconds",
-               repr(a.settle_seconds), "--batch", str(a.batch), "--kt", a.kt]
+               repr(a.settle_seconds), "--batch", str(a.batch), "--kt", a.kt, "--joint-preset", a.joint_preset, "--joint-limits", a.joint_limits]
         r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
         if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
             print("supervisor_settle_probe: %s ended with status %d; stopping" % (job, r.returncode), file=sys.stderr)
