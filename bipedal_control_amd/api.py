@@ -1455,6 +1455,69 @@ class JointParams:
         return row
 
 
+class BodyParams:
+    """A body row of the plant (include/bpmpc.h "Plant", bodies; BPMPC_PLANT_BODY_PARAM_STRIDE): mass [kg], centre of mass [m, body frame] and
+    inertia about it [kg m^2, body frame: xx, xy, xz, yy, yz, zz] of every body of a robot, body 0 the base and body b the link moved by joint b.
+    BodyParams.model(interface) is the row the controller plans with; scaled / shifted / payload return a new row built from this one by
+    bpmpc_plant_compose_body_row, so the rules of the header hold for every row made here.  `row` [160] is what BatchedPlant.setBodyParams takes."""
+
+    STRIDE = 160
+    SLOTS = 16
+    MASS, COM, INERTIA = 0, 16, 64
+
+    def __init__(self, model, row=None):
+        self._model = model
+        self.nj = int(model.actuatedDofNum)
+        if row is None:
+            row = np.zeros(self.STRIDE)
+            model._call("bpmpc_plant_load_body_params", None, _d(row))
+        self.row = _f64(row).reshape(-1).copy()
+        if self.row.size != self.STRIDE:
+            raise ValueError("a body row has %d entries" % self.STRIDE)
+
+    @classmethod
+    def model(cls, model):
+        """The model row: bpmpc_model_get "body_mass", "body_com" and "body_inertia" in the layout of a body row."""
+        return cls(model)
+
+    def _compose(self, body, scale, shift, mass, pos):
+        out = np.zeros(self.STRIDE)
+        shift = None if shift is None else _f64(shift).reshape(3)
+        pos = None if pos is None else _f64(pos).reshape(3)
+        self._model._call("bpmpc_plant_compose_body_row", _d(self.row), int(body), float(scale), _d(shift), float(mass), _d(pos), _d(out))
+        return type(self)(self._model, out)
+
+    def scaled(self, s, body=None):
+        """Mass and inertia of `body` (None: of every body) times s: the same shape at another uniform density."""
+        return self._compose(-1 if body is None else body, s, None, 0.0, None)
+
+    def shifted(self, body, d):
+        """The centre of mass of `body` moved by d [3] (body frame); its inertia about the new centre of mass is the one it had."""
+        return self._compose(body, 1.0, d, 0.0, None)
+
+    def payload(self, m, pos, body=0):
+        """A point mass m at pos [3] (body frame) merged into `body`: new mass, new centre of mass, new inertia by the parallel-axis theorem."""
+        return self._compose(body, 1.0, None, m, pos)
+
+    @property
+    def mass(self):
+        return self.row[self.MASS:self.MASS + self.nj + 1].copy()
+
+    @property
+    def com(self):
+        """[nj + 1, 3]"""
+        return self.row[self.COM:self.INERTIA].reshape(3, self.SLOTS)[:, :self.nj + 1].T.copy()
+
+    @property
+    def inertia(self):
+        """[nj + 1, 6]: xx, xy, xz, yy, yz, zz"""
+        return self.row[self.INERTIA:].reshape(6, self.SLOTS)[:, :self.nj + 1].T.copy()
+
+    @property
+    def total_mass(self):
+        return float(self.mass.sum())
+
+
 class BatchedPlant(_Handle):
     """A rigid-body simulation of a batch of robots on one MI355X (bpmpc_plant; include/bpmpc.h "Plant" is its specification): joint commands ->
     the sensors BatchedStateEstimate.update takes and the ground-truth rbd.  This engine's own model - penalty contacts with implicit damping, a
@@ -1653,6 +1716,30 @@ class BatchedPlant(_Handle):
     def resetJointParams(self):
         """Every joint row back to the start row; with a neutral start row the plant is the one without a joint model again."""
         self._call("bpmpc_plant_reset_joint_params")
+
+    def setBodyParams(self, rows, mask=None):
+        """The body rows (BodyParams.row) of the robots with mask[b] != 0 (None: every one): rows [160], [1, 160] or [B, 160].  numpy rows are
+        validated and the call synchronises; device tensors are only enqueued, ordered before the next step, and not looked at.  From the first
+        call on EVERY robot of the plant steps in the kernel that holds the body rows (k_plant_body_step), also those whose row stays the
+        model's; resetBodyParams ends that.  The controller keeps planning with the model's masses: the mismatch is the point."""
+        if isinstance(rows, BodyParams):
+            rows = rows.row
+        elif isinstance(rows, (list, tuple)):
+            rows = np.array([r.row if isinstance(r, BodyParams) else r for r in rows])
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], BodyParams.STRIDE, self.max_batch)
+        self._call("bpmpc_plant_set_body_params", B, mp, rp, n_rows, dev)
+        del keep
+
+    def getBodyParams(self, robot=-1):
+        """The body row [160] of `robot` (BodyParams(interface, row) names its entries), or with robot < 0 the start row (the model row under
+        the keys plantBodies.<name> of the task file)."""
+        row = np.zeros(BodyParams.STRIDE)
+        self._call("bpmpc_plant_get_body_params", int(robot), _d(row))
+        return row
+
+    def resetBodyParams(self):
+        """Every body row back to the start row; with the model row as start row the plant is the one without body rows again."""
+        self._call("bpmpc_plant_reset_body_params")
 
     def seedInputs(self, seed, mask=None):
         """Restarts the random streams of the input model for the robots with mask[b] != 0 (None: every one of the batch of the last set_state;

@@ -224,6 +224,145 @@ void plant_load_joint_settings(const RobotModel& rm, const char* task_info_path,
   }
   std::copy(v, v + kPlantJointParamStride, row);
 }
+
+namespace {
+const char* const kBodyBlockNames[] = {"mass", "com_x", "com_y", "com_z", "ixx", "ixy", "ixz", "iyy", "iyz", "izz"};
+
+// The eigenvalues of the symmetric 3 x 3 (xx, xy, xz, yy, yz, zz) by cyclic Jacobi rotations, ascending
+void sym3_eigenvalues(const double* s, double* ev) {
+  double a[3][3] = {{s[0], s[1], s[2]}, {s[1], s[3], s[4]}, {s[2], s[4], s[5]}};
+  for (int sweep = 0; sweep < 32; ++sweep) {
+    const double off = std::fabs(a[0][1]) + std::fabs(a[0][2]) + std::fabs(a[1][2]);
+    if (off == 0.0) break;
+    for (int p = 0; p < 2; ++p)
+      for (int q = p + 1; q < 3; ++q) {
+        if (a[p][q] == 0.0) continue;
+        const double theta = (a[q][q] - a[p][p]) / (2.0 * a[p][q]);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < 3; ++k) { const double akp = a[k][p], akq = a[k][q]; a[k][p] = c * akp - sn * akq; a[k][q] = sn * akp + c * akq; }
+        for (int k = 0; k < 3; ++k) { const double apk = a[p][k], aqk = a[q][k]; a[p][k] = c * apk - sn * aqk; a[q][k] = sn * apk + c * aqk; }
+        a[p][q] = a[q][p] = 0.0;
+      }
+  }
+  ev[0] = a[0][0]; ev[1] = a[1][1]; ev[2] = a[2][2];
+  std::sort(ev, ev + 3);
+}
+}  // namespace
+
+void plant_body_model_row(const RobotModel& rm, double* row) {
+  std::fill(row, row + kPlantBodyParamStride, 0.0);
+  for (int b = 0; b <= rm.nj; ++b) {
+    row[kBodyMass + b] = rm.mass[b];
+    for (int k = 0; k < 3; ++k) row[kBodyCom + k * kPlantBodySlots + b] = rm.com[b][k];
+    const double* I = rm.inertia[b];      // 3 x 3, row major: the entries of its upper triangle
+    const double six[6] = {I[0], I[1], I[2], I[4], I[5], I[8]};
+    for (int k = 0; k < 6; ++k) row[kBodyInertia + k * kPlantBodySlots + b] = six[k];
+  }
+}
+
+void plant_check_body_row(const char* who, const double* row, int r, int nj) {
+  auto refuse = [&](int e, const std::string& name, const char* why) {
+    throw std::invalid_argument(std::string(who) + ": row " + std::to_string(r) + ", entry " + std::to_string(e) + " (" + name + ") is " + why);
+  };
+  for (int b = 0; b <= nj; ++b) {
+    const std::string at = "[" + std::to_string(b) + "]";
+    for (int block = 0; block < 10; ++block) {
+      const int e = block * kPlantBodySlots + b;
+      const double x = row[e];
+      if (std::isnan(x)) refuse(e, kBodyBlockNames[block] + at, "not a number");
+      if (!std::isfinite(x)) refuse(e, kBodyBlockNames[block] + at, "not finite");
+      if (block == 0 && x < 0.0) refuse(e, kBodyBlockNames[block] + at, "negative");
+      if (block == 0 && x == 0.0) refuse(e, kBodyBlockNames[block] + at, "zero");
+    }
+    double s[6], ev[3];
+    for (int k = 0; k < 6; ++k) s[k] = row[kBodyInertia + k * kPlantBodySlots + b];
+    sym3_eigenvalues(s, ev);
+    if (!(ev[0] > 0.0)) refuse(kBodyInertia + b, "inertia" + at, "not positive definite");
+    // no mass distribution has a principal moment above the sum of the other two; 1e-9: the rounding of a rod's or a point's row, not a licence
+    if (ev[2] > (ev[0] + ev[1]) * (1.0 + 1e-9)) refuse(kBodyInertia + b, "inertia" + at, "against the triangle inequality of its principal moments");
+  }
+}
+
+void plant_compose_body_row(const char* who, const double* row_in, int nj, int body, double mass_scale, const double* com_shift, double payload_mass,
+                            const double* payload_pos, double* row_out) {
+  const std::string w(who);
+  if (body < -1 || body > nj) throw std::invalid_argument(w + ": body must be -1 or 0.." + std::to_string(nj));
+  if (!std::isfinite(mass_scale) || mass_scale <= 0.0) throw std::invalid_argument(w + ": mass_scale must be finite and positive");
+  if (!std::isfinite(payload_mass) || payload_mass < 0.0) throw std::invalid_argument(w + ": payload_mass must be finite and not negative");
+  for (int k = 0; k < 3; ++k) {
+    if (com_shift && !std::isfinite(com_shift[k])) throw std::invalid_argument(w + ": com_shift is not finite");
+    if (payload_pos && !std::isfinite(payload_pos[k])) throw std::invalid_argument(w + ": payload_pos is not finite");
+  }
+  if (body >= 0 && payload_mass > 0.0 && !payload_pos) throw std::invalid_argument(w + ": a payload needs payload_pos");
+  double v[kPlantBodyParamStride];
+  std::copy(row_in, row_in + kPlantBodyParamStride, v);
+  auto scale = [&](int b) {
+    v[kBodyMass + b] *= mass_scale;
+    for (int k = 0; k < 6; ++k) v[kBodyInertia + k * kPlantBodySlots + b] *= mass_scale;
+  };
+  if (body < 0) {
+    for (int b = 0; b <= nj; ++b) scale(b);
+  } else {
+    scale(body);
+    double c[3], I[6];
+    for (int k = 0; k < 3; ++k) c[k] = v[kBodyCom + k * kPlantBodySlots + body] + (com_shift ? com_shift[k] : 0.0);
+    for (int k = 0; k < 6; ++k) I[k] = v[kBodyInertia + k * kPlantBodySlots + body];
+    double m = v[kBodyMass + body];
+    if (payload_mass > 0.0) {
+      const double total = m + payload_mass;
+      double cn[3];
+      for (int k = 0; k < 3; ++k) cn[k] = (m * c[k] + payload_mass * payload_pos[k]) / total;
+      // parallel axes: each part's inertia about the common centre of mass gains mass (|d|^2 E - d d')
+      auto shift = [&](double mass, const double* from) {
+        const double d[3] = {from[0] - cn[0], from[1] - cn[1], from[2] - cn[2]};
+        const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+        I[0] += mass * (dd - d[0] * d[0]); I[1] -= mass * d[0] * d[1]; I[2] -= mass * d[0] * d[2];
+        I[3] += mass * (dd - d[1] * d[1]); I[4] -= mass * d[1] * d[2]; I[5] += mass * (dd - d[2] * d[2]);
+      };
+      shift(m, c);
+      shift(payload_mass, payload_pos);
+      m = total;
+      for (int k = 0; k < 3; ++k) c[k] = cn[k];
+    }
+    v[kBodyMass + body] = m;
+    for (int k = 0; k < 3; ++k) v[kBodyCom + k * kPlantBodySlots + body] = c[k];
+    for (int k = 0; k < 6; ++k) v[kBodyInertia + k * kPlantBodySlots + body] = I[k];
+  }
+  for (int block = 0; block < 10; ++block)
+    for (int b = nj + 1; b < kPlantBodySlots; ++b) v[block * kPlantBodySlots + b] = 0.0;
+  std::copy(v, v + kPlantBodyParamStride, row_out);
+}
+
+bool plant_body_rows_equal(const double* a, const double* b, int nj) {
+  for (int block = 0; block < 10; ++block)
+    if (std::memcmp(a + block * kPlantBodySlots, b + block * kPlantBodySlots, (size_t)(nj + 1) * sizeof(double)) != 0) return false;
+  return true;
+}
+
+void plant_load_body_settings(const RobotModel& rm, const char* task_info_path, double* row) {
+  double v[kPlantBodyParamStride];
+  plant_body_model_row(rm, v);
+  if (task_info_path) {
+    const auto t = read_info_file(task_info_path);
+    double scale = 1.0, payload = 0.0;
+    int body = 0;
+    const bool scaled = t->get("plantBodies.massScale", &scale);
+    const bool loaded = t->get("plantBodies.payloadMass", &payload);
+    (void)t->get("plantBodies.payloadBody", &body);
+    if (scaled && scale != 1.0) plant_compose_body_row("plantBodies settings (massScale)", v, rm.nj, -1, scale, nullptr, 0.0, nullptr, v);
+    if (loaded && payload != 0.0) {
+      double pos[3] = {0.0, 0.0, 0.0};
+      if (t->find("plantBodies.payloadOffset")) {
+        const std::vector<double> off = load_matrix(*t, "plantBodies.payloadOffset", 3, 1);
+        for (int k = 0; k < 3; ++k) pos[k] = off[k];
+      }
+      plant_compose_body_row("plantBodies settings (payload)", v, rm.nj, body, 1.0, nullptr, payload, pos, v);
+    }
+    if (scaled || loaded) plant_check_body_row("plantBodies settings", v, 0, rm.nj);
+  }
+  std::copy(v, v + kPlantBodyParamStride, row);
+}
 }  // namespace bpmpc
 
 using namespace bpmpc;
@@ -447,6 +586,36 @@ int bpmpc_plant_check_joint_params(const double* rows, int n_rows, int nj) {
   if (nj < 1 || nj > kMaxJoints) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_joint_params: nj must be 1.." + std::to_string(kMaxJoints));
   return guarded(BPMPC_ERR_IO, [&] {
     for (int r = 0; r < n_rows; ++r) plant_check_joint_row("bpmpc_plant_check_joint_params", rows + (size_t)r * kPlantJointParamStride, r, nj);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_load_body_params(const bpmpc_model* model, const char* task_info_path, double* row) {
+  if (!model || !row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_body_params: null model or row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    double v[kPlantBodyParamStride];
+    plant_load_body_settings(model->rm, task_info_path, v);
+    std::copy(v, v + kPlantBodyParamStride, row);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_check_body_params(const double* rows, int n_rows, int nj) {
+  if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_body_params: null rows");
+  if (nj < 1 || nj > kMaxJoints) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_body_params: nj must be 1.." + std::to_string(kMaxJoints));
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) plant_check_body_row("bpmpc_plant_check_body_params", rows + (size_t)r * kPlantBodyParamStride, r, nj);
+    return (int)BPMPC_OK;
+  });
+}
+
+int bpmpc_plant_compose_body_row(const bpmpc_model* model, const double* row_in, int body, double mass_scale, const double* com_shift, double payload_mass,
+                                 const double* payload_pos, double* row_out) {
+  if (!model || !row_out) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_compose_body_row: null model or row_out");
+  return guarded(BPMPC_ERR_IO, [&] {
+    double start[kPlantBodyParamStride];
+    if (!row_in) plant_body_model_row(model->rm, start);
+    plant_compose_body_row("bpmpc_plant_compose_body_row", row_in ? row_in : start, model->rm.nj, body, mass_scale, com_shift, payload_mass, payload_pos, row_out);
     return (int)BPMPC_OK;
   });
 }

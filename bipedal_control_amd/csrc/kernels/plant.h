@@ -26,6 +26,13 @@
 // over the substeps; the three scalars of the row are wave-uniform and parked in LDS.  Whether the row is neutral is one ballot per launch: a robot
 // with the neutral row takes the branch that is k_plant_stick_step, operation for operation.  Everything the model adds is lane-local: the
 // armature and the damping go onto the diagonal entry the lane owns, the end-stop torque into the lane's generalised force.
+//
+// Bodies (BODY; k_plant_body_step, plant_body.hip, a fourth translation unit for the same reason): a body row per robot (mass, centre of mass and
+// inertia of every body; include/bpmpc.h "bodies").  Lanes 0..NJ load their body's ten numbers once per launch - entry-major rows, so consecutive
+// lanes read consecutive words - into LDS (PlantBodyLds::body), not into registers: the joint kernel has none to spare.  The rigid-body pass then
+// takes the three inertial constants of a body from there (wbc_rbd_pass on a PlantBodyModel, kernels/wbc.h) where it takes them from the model, each
+// lane its own body's, and everything else - geometry, axes, contact offsets, gravity - from the model as before.  Nothing else changes: there
+// is no branch on whether a row is the model's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,6 +52,11 @@ enum PlantJointEntry { kJointArmature = 0, kJointDamping = 12, kJointFriction = 
                        kJointWEps = 62, kJointParamUsed = 63 };
 constexpr double kPlantJointKLimit = 1e4, kPlantJointCLimit = 1e2, kPlantJointWEps = 0.01;      // the scalars of the neutral row
 static_assert(kMaxJoints <= kPlantJointSlots, "a joint row holds every joint");
+constexpr int kPlantBodyParamStride = 160;      // BPMPC_PLANT_BODY_PARAM_STRIDE
+constexpr int kPlantBodySlots = 16;             // bodies a block of a body row has room for
+// A body row: ten blocks of kPlantBodySlots, body b at slot b of each (mass; com x, y, z; inertia xx, xy, xz, yy, yz, zz)
+enum PlantBodyEntry { kBodyMass = 0, kBodyCom = 16, kBodyInertia = 64 };
+static_assert(kMaxBodies <= kPlantBodySlots, "a body row holds every body");
 
 // A parameter row
 struct PlantSettings {
@@ -97,6 +109,11 @@ struct PlantJointArgs {
   const double* rows;                               // [max_batch][kPlantJointParamStride]
 };
 
+// Bodies: what the BODY instantiation takes beside the three above
+struct PlantBodyArgs {
+  const double* rows;                               // [max_batch][kPlantBodyParamStride]
+};
+
 template <int NJ>
 struct PlantLds {
   static constexpr int NV = 6 + NJ;
@@ -130,13 +147,38 @@ struct PlantJointLds : PlantStickLds<NJ> {
   double k_limit, c_limit, w_eps;
 };
 
-template <int NJ, bool STICK, bool JOINT>
-using PlantLdsOf = std::conditional_t<JOINT, PlantJointLds<NJ>, std::conditional_t<STICK, PlantStickLds<NJ>, PlantLds<NJ>>>;
+// The inertial constants of a robot's bodies as the rigid-body pass reads them (the members of DeviceModel it takes them from otherwise)
+template <int NJ>
+struct PlantBodyConstants {
+  double mass[NJ + 1], com[NJ + 1][3];
+  double inertia[NJ + 1][6];             // xx, xy, xz, yy, yz, zz about the com, body frame
+};
 
-template <int NJ, bool STICK, bool JOINT = false>
-__device__ void plant_robot(const DeviceModel& md, PlantLdsOf<NJ, STICK, JOINT>& w, const PlantArgs& a, const PlantStickArgs& sa, int b, int l,
-                            const PlantJointArgs& ja = PlantJointArgs{}) {
+// The model the rigid-body pass sees in the BODY instantiation: the handle's model with the inertial constants of one robot's row
+template <int NJ>
+struct PlantBodyModel {
+  const DeviceModel& md;
+  const PlantBodyConstants<NJ>& body;
+};
+template <int NJ>
+__device__ __forceinline__ const DeviceModel& wbc_geometry(const PlantBodyModel<NJ>& m) { return m.md; }
+template <int NJ>
+__device__ __forceinline__ const PlantBodyConstants<NJ>& wbc_inertial(const PlantBodyModel<NJ>& m) { return m.body; }
+
+// Bodies in LDS, behind the members above: the robot's body row, body-major, over the substeps
+template <int NJ>
+struct PlantBodyLds : PlantJointLds<NJ> {
+  PlantBodyConstants<NJ> body;
+};
+
+template <int NJ, bool STICK, bool JOINT, bool BODY = false>
+using PlantLdsOf = std::conditional_t<BODY, PlantBodyLds<NJ>, std::conditional_t<JOINT, PlantJointLds<NJ>, std::conditional_t<STICK, PlantStickLds<NJ>, PlantLds<NJ>>>>;
+
+template <int NJ, bool STICK, bool JOINT = false, bool BODY = false>
+__device__ void plant_robot(const DeviceModel& md, PlantLdsOf<NJ, STICK, JOINT, BODY>& w, const PlantArgs& a, const PlantStickArgs& sa, int b, int l,
+                            const PlantJointArgs& ja = PlantJointArgs{}, const PlantBodyArgs& ba = PlantBodyArgs{}) {
   static_assert(STICK || !JOINT, "the joint model is compiled with stick-slip contacts");
+  static_assert(JOINT || !BODY, "the body rows are compiled with the joint model");
   constexpr int NV = 6 + NJ, NC = kNumContacts;
   WbcRbd<NJ>& r = w.rbd;
   if (l < kPlantParamStride) {      // these lanes all park the same pointers: one predicate for the prologue
@@ -182,12 +224,24 @@ __device__ void plant_robot(const DeviceModel& md, PlantLdsOf<NJ, STICK, JOINT>&
     }
     joints = __any(arm != 0.0 || damp != 0.0 || fric != 0.0 || lower != -HUGE_VAL || upper != HUGE_VAL) != 0;
   }
+  // this lane's body: into LDS, read by the rigid-body pass behind its first barrier
+  if constexpr (BODY) {
+    static_assert(NJ + 1 <= kPlantBodySlots && NJ + 1 <= kWave, "one lane per body of the row");
+    if (l < NJ + 1) {
+      const double* row = ba.rows + (size_t)b * kPlantBodyParamStride + l;
+      w.body.mass[l] = row[kBodyMass];
+      for (int k = 0; k < 3; ++k) w.body.com[l][k] = row[kBodyCom + k * kPlantBodySlots];
+      for (int k = 0; k < 6; ++k) w.body.inertia[l][k] = row[kBodyInertia + k * kPlantBodySlots];
+    }
+  }
   double acc = 0.0;      // lanes 0..2: (v+ - v) / h of the last substep
 
 #pragma unroll 1
   for (int step = 0; step < a.substeps; ++step) {
     int lp = l;
     asm volatile("" : "+v"(lp));      // the lane, opaque: the pass's lane predicates are formed in each substep and not held in scalar registers over the loop
+    if constexpr (BODY) wbc_rbd_pass<NJ>(PlantBodyModel<NJ>{md, w.body}, r, true, lp);      // the robot's own masses, centres of mass and inertias
+    else
     wbc_rbd_pass<NJ>(md, r, true, lp);      // synchronises at entry and exit
     // ---- mass matrix, nonlinear effects, contact Jacobian (the assembly of wbc_robot)
 #pragma unroll 1

@@ -106,9 +106,17 @@ __device__ __forceinline__ bool wbc_on_chain(const DeviceModel& md, int h, int g
   return (md.subtree[h - 5] >> (g - 5)) & 1u;
 }
 
+// What the rigid-body pass reads of its model argument: the tree, the frames, the axes and the contact offsets (always a DeviceModel's), and the
+// three inertial constants of every body - mass[b], com[b][3], inertia[b][6].  For a DeviceModel both are the model itself; the plant's body
+// kernel hands in a model whose inertial constants are a robot's own row (kernels/plant.h PlantBodyModel).
+__device__ __forceinline__ const DeviceModel& wbc_geometry(const DeviceModel& md) { return md; }
+__device__ __forceinline__ const DeviceModel& wbc_inertial(const DeviceModel& md) { return md; }
+
 // q, v must be in r.q / r.v.  gravity: bias accelerations start from [0 ; +g e_z] (nonlinear effects) or from zero (Adot v).
-template <int NJ>
-__device__ void wbc_rbd_pass(const DeviceModel& md, WbcRbd<NJ>& r, bool gravity, int l) {
+template <int NJ, class Model = DeviceModel>
+__device__ void wbc_rbd_pass(const Model& model, WbcRbd<NJ>& r, bool gravity, int l) {
+  const DeviceModel& md = wbc_geometry(model);
+  const auto& in = wbc_inertial(model);
   constexpr int NV = 6 + NJ, NB = NJ + 1;
   lds_wave_sync();
   // ---- body frames by a chain walk per body
@@ -149,9 +157,9 @@ __device__ void wbc_rbd_pass(const DeviceModel& md, WbcRbd<NJ>& r, bool gravity,
     }
     // inertial quantities of the body in the world frame
     double cb[3];
-    w_mat3_vec(R, md.com[l], cb);
+    w_mat3_vec(R, in.com[l], cb);
     const double c[3] = {o[0] + cb[0], o[1] + cb[1], o[2] + cb[2]};
-    const double* I = md.inertia[l];
+    const double* I = in.inertia[l];
     const double Ib[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
     double T[9];
     w_mat3_mul(R, Ib, T);
@@ -162,7 +170,7 @@ __device__ void wbc_rbd_pass(const DeviceModel& md, WbcRbd<NJ>& r, bool gravity,
     Iw[3] = T[3] * R[3] + T[4] * R[4] + T[5] * R[5];
     Iw[4] = T[3] * R[6] + T[4] * R[7] + T[5] * R[8];
     Iw[5] = T[6] * R[6] + T[7] * R[7] + T[8] * R[8];
-    const double m = md.mass[l], cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
+    const double m = in.mass[l], cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
     for (int i = 0; i < 3; ++i) r.cw[l][i] = c[i];
     for (int i = 0; i < 6; ++i) r.Iw[l][i] = Iw[i];
     double* cm = r.comp[l];
@@ -195,7 +203,7 @@ __device__ void wbc_rbd_pass(const DeviceModel& md, WbcRbd<NJ>& r, bool gravity,
     w_cross(Aw, c, t);
     w_cross(Vw, vc, t4);
     for (int i = 0; i < 3; ++i) ac[i] = Ao[i] + t[i] + t4[i];
-    for (int i = 0; i < 3; ++i) f[i] = md.mass[l] * ac[i];
+    for (int i = 0; i < 3; ++i) f[i] = in.mass[l] * ac[i];
     w_cross(c, f, n);
     w_sym3_vec(r.Iw[l], Aw, Ia);
     w_sym3_vec(r.Iw[l], Vw, Iw_w);

@@ -39,6 +39,11 @@ struct bpmpc_plant {
   bool joint = false;                   // steps launch k_plant_joint_step: the start row is not neutral, or rows have been set since create / reset_joint_params
   double* d_jparams = nullptr;          // [max_batch][kPlantJointParamStride]
   double* d_jrows = nullptr;            // [max_batch + 1][kPlantJointParamStride] device copy of host rows; the last row holds joint_start
+  // bodies (include/bpmpc.h "Plant", bodies): per-robot body rows
+  double body_start[bpmpc::kPlantBodyParamStride] = {};      // the start row: the model row under the keys plantBodies.<name> of task.info
+  bool body = false;                    // steps launch k_plant_body_step: the start row is not the model row, or rows have been set since create / reset_body_params
+  double* d_bparams = nullptr;          // [max_batch][kPlantBodyParamStride]
+  double* d_brows = nullptr;            // [max_batch + 1][kPlantBodyParamStride] device copy of host rows; the last row holds body_start
   double* d_out = nullptr;              // the output block of k_plant_step (kernels/plant.h PlantOut)
   bpmpc_plant_outputs out{};            // its sections (leading dimension max_batch)
   // sensor model (include/bpmpc.h "Plant", sensors): per-robot rows, generator state, biases, the ring of measured samples, the sensed block
@@ -73,6 +78,7 @@ struct bpmpc_plant {
 static_assert(bpmpc::kPlantParamStride == BPMPC_PLANT_PARAM_STRIDE, "PlantSettings follows the row layout of include/bpmpc.h");
 static_assert(bpmpc::kInputParamStride == BPMPC_PLANT_INPUT_PARAM_STRIDE, "an input row follows the layout of include/bpmpc.h");
 static_assert(bpmpc::kPlantJointParamStride == BPMPC_PLANT_JOINT_PARAM_STRIDE, "a joint row follows the layout of include/bpmpc.h");
+static_assert(bpmpc::kPlantBodyParamStride == BPMPC_PLANT_BODY_PARAM_STRIDE, "a body row follows the layout of include/bpmpc.h");
 
 namespace bpmpc {
 // The keys plant.<name> of task.info over the defaults (NULL: the defaults); host only (capi.cpp), also behind bpmpc_plant_load_params
@@ -94,6 +100,22 @@ void plant_load_joint_settings(const RobotModel& rm, const char* task_info_path,
 void plant_check_joint_row(const char* who, const double* row, int r, int nj);
 // Whether a row is the neutral one as far as a robot with nj joints reads it: no armature, damping or friction, no finite limit
 bool plant_joint_row_neutral(const double* row, int nj);
+
+// plant_body.hip: one launch of k_plant_body_step<nj> for a.batch robots on `stream`
+void launch_plant_body_step(int nj, hipStream_t stream, const DeviceModel* model, const PlantArgs& a, const PlantStickArgs& sa, const PlantJointArgs& ja,
+                            const PlantBodyArgs& ba);
+// The model row: what bpmpc_model_get returns for "body_mass", "body_com" and "body_inertia", in the layout of a body row; slots b > nj are 0
+void plant_body_model_row(const RobotModel& rm, double* row);
+// The start row of a handle: the model row, then the keys plantBodies.<name> of task.info (NULL: the model row); host only (capi.cpp), also behind
+// bpmpc_plant_load_body_params
+void plant_load_body_settings(const RobotModel& rm, const char* task_info_path, double* row);
+// A host row of a robot with nj joints before it is accepted (include/bpmpc.h "bodies"); throws std::invalid_argument naming the entry
+void plant_check_body_row(const char* who, const double* row, int r, int nj);
+// bpmpc_plant_compose_body_row behind its null checks: row_out from row_in (both [kPlantBodyParamStride]; they may be the same array)
+void plant_compose_body_row(const char* who, const double* row_in, int nj, int body, double mass_scale, const double* com_shift, double payload_mass,
+                            const double* payload_pos, double* row_out);
+// Whether two rows are the same as far as a robot with nj joints reads them, bit for bit
+bool plant_body_rows_equal(const double* a, const double* b, int nj);
 
 // A measured sample, in doubles: joint_pos[nj], joint_vel[nj], quat[4], angular_vel_local[3], linear_accel_local[3], contact[4] (0.0 or 1.0): one
 // slot of the ring.  The sensed block holds the same members as sections of leading dimension max_batch, the contacts as four ints (2 doubles).

@@ -93,6 +93,15 @@ void write_start_joint_params(bpmpc_plant* p) {
   p->joint = !plant_joint_row_neutral(p->joint_start, p->nj);
 }
 
+// every body row becomes the start row (the last row of d_brows), and the start row decides which kernel steps launch
+void write_start_body_params(bpmpc_plant* p) {
+  write_rows(p->hs.stream, p->max_batch, kPlantBodyParamStride, kPlantBodyParamStride, nullptr, 1,
+             {p->d_brows + (size_t)p->max_batch * kPlantBodyParamStride, nullptr, p->d_bparams});
+  double model_row[kPlantBodyParamStride];
+  plant_body_model_row(p->rm, model_row);
+  p->body = !plant_body_rows_equal(p->body_start, model_row, p->nj);
+}
+
 void check_batch(const bpmpc_plant* p, int batch, const char* who) {
   if (batch < 1) throw std::invalid_argument(std::string(who) + ": batch must be positive");
   if (batch > p->max_batch) throw std::length_error(std::string(who) + ": batch exceeds max_batch");
@@ -133,7 +142,11 @@ void launch_input(bpmpc_plant* p, PlantArgs& a, double period) {
 // the step kernel, on a switched handle the input model in front of it and the sensor model behind it: `period` is the control step's
 void launch_step(bpmpc_plant* p, PlantArgs a, double period) {
   launch_input(p, a, period);
-  if (p->joint) {      // the joint model is in use: one kernel holds it and stick-slip contacts
+  if (p->body) {      // body rows are in use: one kernel holds them, the joint model and stick-slip contacts
+    const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
+    launch_plant_body_step(p->nj, p->hs.stream, p->d_model, a, sa, PlantJointArgs{p->d_jparams}, PlantBodyArgs{p->d_bparams});
+  }
+  else if (p->joint) {      // the joint model is in use: one kernel holds it and stick-slip contacts
     const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
     launch_plant_joint_step(p->nj, p->hs.stream, p->d_model, a, sa, PlantJointArgs{p->d_jparams});
   }
@@ -233,6 +246,10 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
     p->d_jparams = m.alloc<double>(B * kPlantJointParamStride); p->d_jrows = m.alloc<double>((B + 1) * kPlantJointParamStride);
     HIP_CHECK(hipMemcpy(p->d_jrows + B * kPlantJointParamStride, p->joint_start, sizeof(p->joint_start), hipMemcpyHostToDevice));
     write_start_joint_params(p.get());
+    plant_load_body_settings(p->rm, task_info_path, p->body_start);
+    p->d_bparams = m.alloc<double>(B * kPlantBodyParamStride); p->d_brows = m.alloc<double>((B + 1) * kPlantBodyParamStride);
+    HIP_CHECK(hipMemcpy(p->d_brows + B * kPlantBodyParamStride, p->body_start, sizeof(p->body_start), hipMemcpyHostToDevice));
+    write_start_body_params(p.get());
     // sensor model: the members it measures live in the sensed block, the others are the truth's
     plant_load_sensor_settings(task_info_path, p->sensor_start, &p->sensor_seed);
     p->d_sparams = m.alloc<double>(B * kSensorParamStride); p->d_srows = m.alloc<double>((B + 1) * kSensorParamStride);
@@ -459,6 +476,35 @@ int bpmpc_plant_set_joint_params(bpmpc_plant* p, int batch, const int* mask, con
 int bpmpc_plant_reset_joint_params(bpmpc_plant* p) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_joint_params: null handle", [&] {
     write_start_joint_params(p);
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+  });
+}
+
+int bpmpc_plant_get_body_params(const bpmpc_plant* p, int robot, double* row) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_body_params: null handle or row", row != nullptr, [&] {
+    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_body_params: robot exceeds max_batch");
+    const double* src = robot < 0 ? p->d_brows + (size_t)p->max_batch * kPlantBodyParamStride : p->d_bparams + (size_t)robot * kPlantBodyParamStride;
+    double got[kPlantBodyParamStride];
+    HIP_CHECK(hipMemcpyAsync(got, src, kPlantBodyParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
+    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    for (int e = 0; e < kPlantBodyParamStride; ++e) row[e] = e % kPlantBodySlots <= p->nj ? got[e] : 0.0;      // slots of bodies the robot does not have
+  });
+}
+
+int bpmpc_plant_set_body_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_body_params: null handle or rows", rows != nullptr, [&] {
+    check_batch(p, batch, "bpmpc_plant_set_body_params");
+    set_rows("bpmpc_plant_set_body_params", p->hs.stream, batch, kPlantBodyParamStride, kPlantBodyParamStride, mask, p->d_mask, n_rows, inputs_on_device,
+             [&](int r) { plant_check_body_row("bpmpc_plant_set_body_params", rows + (size_t)r * kPlantBodyParamStride, r, p->nj); },
+             {rows, p->d_brows, p->d_bparams});
+    p->body = true;      // from here on every robot of the handle steps in k_plant_body_step
+    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // device rows are only enqueued on the handle's stream: the next step runs behind them
+  });
+}
+
+int bpmpc_plant_reset_body_params(bpmpc_plant* p) {
+  return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_body_params: null handle", [&] {
+    write_start_body_params(p);
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
   });
 }

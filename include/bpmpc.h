@@ -810,9 +810,48 @@ int bpmpc_controller_tick_estimated(bpmpc_controller* controller, bpmpc_estimato
  *       those outside its mask and those whose row stays neutral: such a robot agrees with the other kernels to rounding (1e-9 relative is
  *       asserted; on the device it returned k_plant_stick_step's bits for H1 and G1, which the tests print and nothing promises).  bpmpc_plant_reset_joint_params writes the start row into every row and returns the handle
  *       to the kernel that start row selects.
+ *   bodies: the rigid bodies themselves, per robot: mass, centre of mass and inertia of every body.  Without a body row every robot of a batch is
+ *     simulated with exactly the inertial constants its controller plans with (the model's); with one the plant can be heavier, lighter, carry a
+ *     payload or have a shifted centre of mass while the WBC and the MPC keep the model's: the mismatch is the point.  The controller side is not
+ *     touched.  It is off until it is used (see "switching" below).
+ *     settings: a body row of BPMPC_PLANT_BODY_PARAM_STRIDE = 160 doubles per robot: ten blocks of 16 slots, body b (0 = base, b = 1..nj the link
+ *       moved by joint b) at slot b of each block.  Entry-major, so the lanes of consecutive bodies read consecutive words:
+ *           0..15   mass[b]                              kg                          > 0
+ *          16..63   com_x[b], com_y[b], com_z[b]         m, body frame               finite
+ *          64..159  ixx, ixy, ixz, iyy, iyz, izz[b]      kg m^2, about the com,      symmetric positive definite, principal moments obey the
+ *                                                        body frame                  triangle inequality (none above the sum of the other two)
+ *       Slots b > nj are ignored on input and written as 0 by the getters.  The model row is what bpmpc_model_get returns for "body_mass",
+ *       "body_com" and "body_inertia" (of the 3 x 3 its upper triangle), bit for bit.
+ *     one substep for a robot with a body row is the substep above as it stands, with the three constants of every body - m_b, c_b, I_b in the
+ *       rigid-body quantities of step 1 - taken from the robot's row.  Everything else still comes from the model: geometry, axes, contact
+ *       offsets and gravity.
+ *     Every row starts as the start row of task_info_path: the model row, then the optional keys plantBodies.massScale (every body's mass and
+ *       inertia times it), plantBodies.payloadMass [kg], plantBodies.payloadBody (default 0, the base) and plantBodies.payloadOffset (a 3 x 1
+ *       block "(0,0) x (1,0) y (2,0) z", body frame, default 0 0 0): a point mass merged into that body as bpmpc_plant_compose_body_row does.  An
+ *       absent block or a NULL path gives the model row.
+ *     calls: bpmpc_plant_get_body_params / set_body_params / reset_body_params have the shapes (row[160]), masks, n_rows, host / device semantics,
+ *       error codes and stream ordering of bpmpc_plant_get_joint_params / set_joint_params / reset_joint_params (robot < 0: the start row).  Host
+ *       rows are validated against the rules of the table - the principal moments by a Jacobi eigen-solve of the 3 x 3, the triangle inequality to
+ *       1e-9 relative - and a bad entry is named in bpmpc_last_error() and changes nothing.  Device rows are not looked at: a row that breaks
+ *       the rules gives a mass matrix that need not be positive definite, and the state of that robot, and of that robot only, is then anything.
+ *       bpmpc_plant_set_state and a restart keep the rows.  bpmpc_plant_load_body_params / check_body_params: the ingest (row[160], from the model
+ *       and task_info_path) and the row validation (rows[n_rows*160] of a robot with nj joints) as host-only functions.
+ *       bpmpc_plant_compose_body_row(model, row_in, body, mass_scale, com_shift, payload_mass, payload_pos, row_out), host only, builds a row from
+ *       row_in (NULL: the model row), in this order: mass and inertia of `body` times mass_scale (> 0; uniform density); its com moved by
+ *       com_shift[3] (NULL: 0; the inertia about the new com unchanged); a point mass payload_mass (>= 0) at payload_pos[3] (body frame) merged
+ *       into the body: new mass, new com, and the new inertia about the new com by the parallel-axis theorem.  body = -1 applies mass_scale to
+ *       every body and takes no shift or payload.  row_out may be row_in.
+ *     switching: a handle whose start row is the model row (what a robot with nj joints reads of it, bit for bit) and that has had no
+ *       set_body_params since create or reset_body_params launches exactly what it launches without body rows (k_plant_step, k_plant_stick_step
+ *       or k_plant_joint_step).  Any other handle launches k_plant_body_step, which holds stick-slip contacts, the joint model and the body rows,
+ *       from bpmpc_plant_step, bpmpc_plant_step_controlled and bpmpc_plant_step_supervised alike, for every robot of it, also those outside the
+ *       mask and those whose row is the model row: such a robot agrees with the other kernels to rounding (1e-9 relative is asserted; whether
+ *       the bits are equal the tests print and nothing promises).  bpmpc_plant_reset_body_params writes the start row into every row and returns
+ *       the handle to the kernel that start row selects.  The sensor and input kernels in front of and behind the step are unaffected.
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_PLANT_PARAM_STRIDE 8
 #define BPMPC_PLANT_JOINT_PARAM_STRIDE 64
+#define BPMPC_PLANT_BODY_PARAM_STRIDE 160
 #define BPMPC_PLANT_SENSOR_PARAM_STRIDE 16
 #define BPMPC_PLANT_INPUT_PARAM_STRIDE 8
 typedef struct bpmpc_plant bpmpc_plant;
@@ -867,6 +906,13 @@ int bpmpc_plant_set_joint_params(bpmpc_plant* plant, int batch, const int* mask,
 int bpmpc_plant_reset_joint_params(bpmpc_plant* plant);
 int bpmpc_plant_load_joint_params(const bpmpc_model* model, const char* task_info_path, double* row);
 int bpmpc_plant_check_joint_params(const double* rows, int n_rows, int nj);
+int bpmpc_plant_get_body_params(const bpmpc_plant* plant, int robot, double* row);
+int bpmpc_plant_set_body_params(bpmpc_plant* plant, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_plant_reset_body_params(bpmpc_plant* plant);
+int bpmpc_plant_load_body_params(const bpmpc_model* model, const char* task_info_path, double* row);
+int bpmpc_plant_check_body_params(const double* rows, int n_rows, int nj);
+int bpmpc_plant_compose_body_row(const bpmpc_model* model, const double* row_in, int body, double mass_scale, const double* com_shift, double payload_mass,
+                                 const double* payload_pos, double* row_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Policy buffer = MPC_MRT_Interface between the solve and the control tick for a BATCH of robots, on the device.  In the reference a thread calls
