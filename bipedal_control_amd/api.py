@@ -146,24 +146,50 @@ def _rows_args(mask, arrays, width, max_batch):
     return batch, n_rows, ptrs, dev, keep
 
 
-def _param_methods(prefix, stride, get_doc, set_doc, reset_doc=None):
+def _param_methods(prefix, stride, get_doc, set_doc, reset_doc=None, stem=""):
     """getParams / setParams / resetParams of a handle class with max_batch, over <prefix>_get_params / _set_params / _reset_params and parameter
-    rows of `stride` doubles; the docstrings are the class's own."""
+    rows of `stride` doubles; the docstrings are the class's own.  With the stem of another table of the handle ("Sensor"): getSensorParams /
+    setSensorParams / resetSensorParams over <prefix>_get_sensor_params and the rest."""
+    table = stem.lower() + "_" if stem else ""
+
     def getParams(self, robot=-1):
         row = np.zeros(stride)
-        self._call(prefix + "_get_params", int(robot), _d(row))
+        self._call("%s_get_%sparams" % (prefix, table), int(robot), _d(row))
         return row
 
     def setParams(self, rows, mask=None):
         B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], stride, self.max_batch)
-        self._call(prefix + "_set_params", B, mp, rp, n_rows, dev)
+        self._call("%s_set_%sparams" % (prefix, table), B, mp, rp, n_rows, dev)
         del keep
 
     def resetParams(self):
-        self._call(prefix + "_reset_params")
+        self._call("%s_reset_%sparams" % (prefix, table))
 
-    getParams.__doc__, setParams.__doc__, resetParams.__doc__ = get_doc, set_doc, reset_doc
+    for method, verb, doc in ((getParams, "get", get_doc), (setParams, "set", set_doc), (resetParams, "reset", reset_doc)):
+        method.__name__, method.__doc__ = "%s%sParams" % (verb, stem), doc
     return getParams, setParams, resetParams
+
+
+class _RowParams:
+    """What the rows with one named float per entry share: the FIELDS of a subclass name the leading entries of its row of STRIDE doubles, the
+    entries behind them are 0, and its DEFAULTS (absent: zeros) are the values without arguments."""
+
+    def __init__(self, **fields):
+        unknown = set(fields) - set(self.FIELDS)
+        if unknown:
+            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
+        for name, default in zip(self.FIELDS, getattr(self, "DEFAULTS", (0.0,) * len(self.FIELDS))):
+            setattr(self, name, float(fields.get(name, default)))
+
+    @classmethod
+    def fromRow(cls, row):
+        r = np.asarray(row, float).reshape(-1)
+        if r.size != cls.STRIDE:
+            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
+        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
+
+    def toRow(self):
+        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
 
 
 class WbcParams:
@@ -745,7 +771,7 @@ class WeightedWbc(_Handle):
         """Every row back to the task.info values (bpmpc_wbc_reset_params).""")
 
 
-class KalmanParams:
+class KalmanParams(_RowParams):
     """A parameter row of the Kalman state estimator (include/bpmpc.h "State estimation", BPMPC_EST_PARAM_STRIDE) with named fields: the seven
     settings of KalmanFilterEstimate (LinearKalmanFilter.h:45-51), whose defaults are the values without arguments."""
 
@@ -753,23 +779,6 @@ class KalmanParams:
     FIELDS = ("footRadius", "imuProcessNoisePosition", "imuProcessNoiseVelocity", "footProcessNoisePosition", "footSensorNoisePosition",
               "footSensorNoiseVelocity", "footHeightSensorNoise")
     DEFAULTS = (0.02, 0.02, 0.02, 0.002, 0.005, 0.1, 0.01)
-
-    def __init__(self, **fields):
-        unknown = set(fields) - set(self.FIELDS)
-        if unknown:
-            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
-        for name, default in zip(self.FIELDS, self.DEFAULTS):
-            setattr(self, name, float(fields.get(name, default)))
-
-    @classmethod
-    def fromRow(cls, row):
-        r = np.asarray(row, float).reshape(-1)
-        if r.size != cls.STRIDE:
-            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
-        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
-
-    def toRow(self):
-        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0])
 
 
 ESTIMATOR_KINDS = {"from_topic": 0, "kalman": 1}
@@ -1312,7 +1321,7 @@ class PlanGeometry(_Handle):
         return rows, foot, count.value, summ
 
 
-class PlantParams:
+class PlantParams(_RowParams):
     """A parameter row of the plant (include/bpmpc.h "Plant", BPMPC_PLANT_PARAM_STRIDE) with named fields: contact stiffness kn [N/m], normal damping
     cn [N s/m], the penetration d0 [m] at which the normal damping is fully on, friction coefficient mu, the velocity v_eps [m/s] that regularises
     the Coulomb law, and the normal force contact_threshold [N] above which a contact point reports contact.  The defaults are the values without
@@ -1322,25 +1331,8 @@ class PlantParams:
     FIELDS = ("kn", "cn", "d0", "mu", "v_eps", "contact_threshold")
     DEFAULTS = (5e4, 5e2, 1e-3, 0.7, 0.01, 1.0)
 
-    def __init__(self, **fields):
-        unknown = set(fields) - set(self.FIELDS)
-        if unknown:
-            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
-        for name, default in zip(self.FIELDS, self.DEFAULTS):
-            setattr(self, name, float(fields.get(name, default)))
 
-    @classmethod
-    def fromRow(cls, row):
-        r = np.asarray(row, float).reshape(-1)
-        if r.size != cls.STRIDE:
-            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
-        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
-
-    def toRow(self):
-        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0, 0.0])
-
-
-class SensorParams:
+class SensorParams(_RowParams):
     """A row of the plant's sensor model (include/bpmpc.h "Plant", sensors; BPMPC_PLANT_SENSOR_PARAM_STRIDE) with named fields: white noise, bias
     random walk and turn-on bias of the gyro [rad/s, rad/s/sqrt(s), rad/s] and of the accelerometer [m/s^2 ...], orientation noise [rad], joint
     position noise and encoder resolution [rad; 0: not quantised], joint velocity noise [rad/s], the probability that a closed contact reports
@@ -1350,25 +1342,8 @@ class SensorParams:
     FIELDS = ("gyro_noise", "gyro_bias_walk", "gyro_bias_init", "accel_noise", "accel_bias_walk", "accel_bias_init", "orientation_noise", "joint_pos_noise",
               "joint_pos_resolution", "joint_vel_noise", "contact_dropout", "delay_steps")
 
-    def __init__(self, **fields):
-        unknown = set(fields) - set(self.FIELDS)
-        if unknown:
-            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
-        for name in self.FIELDS:
-            setattr(self, name, float(fields.get(name, 0.0)))
 
-    @classmethod
-    def fromRow(cls, row):
-        r = np.asarray(row, float).reshape(-1)
-        if r.size != cls.STRIDE:
-            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
-        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
-
-    def toRow(self):
-        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
-
-
-class InputParams:
+class InputParams(_RowParams):
     """A row of the plant's input model (include/bpmpc.h "Plant", inputs; BPMPC_PLANT_INPUT_PARAM_STRIDE) with named fields: the command latency
     delay [s] (the reference's gazebo/delay), the probability dropout that a command does not arrive (the joint holds the previous one), and
     pushes on the base of push_force [N] for push_duration [s], one at a random time and from a random horizontal direction in every
@@ -1376,23 +1351,6 @@ class InputParams:
 
     STRIDE = 8
     FIELDS = ("delay", "dropout", "push_force", "push_interval", "push_duration")
-
-    def __init__(self, **fields):
-        unknown = set(fields) - set(self.FIELDS)
-        if unknown:
-            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
-        for name in self.FIELDS:
-            setattr(self, name, float(fields.get(name, 0.0)))
-
-    @classmethod
-    def fromRow(cls, row):
-        r = np.asarray(row, float).reshape(-1)
-        if r.size != cls.STRIDE:
-            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
-        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
-
-    def toRow(self):
-        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0] * (self.STRIDE - len(self.FIELDS)))
 
 
 class JointParams:
@@ -1631,24 +1589,15 @@ class BatchedPlant(_Handle):
         self._call("bpmpc_plant_get_anchors", B, _d(anchor), _i(anchored))
         return anchor, anchored
 
-    def setSensorParams(self, rows, mask=None):
+    getSensorParams, setSensorParams, resetSensorParams = _param_methods(
+        "bpmpc_plant", SensorParams.STRIDE,
+        """The sensor row [16] of `robot` (SensorParams.fromRow names its entries), or with robot < 0 the row of the task file (the keys
+        plantSensors.<name>; absent: 0).""",
         """The sensor rows (SensorParams.toRow) of the robots with mask[b] != 0 (None: every one): rows [16], [1, 16] or [B, 16].  numpy rows are
         validated and the call synchronises; device tensors are only enqueued, ordered before the next step.  From this call on every step measures
-        (k_plant_sense) and BatchedStateEstimate.update_from_plant reads sensed(); resetSensorParams ends that."""
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], SensorParams.STRIDE, self.max_batch)
-        self._call("bpmpc_plant_set_sensor_params", B, mp, rp, n_rows, dev)
-        del keep
-
-    def getSensorParams(self, robot=-1):
-        """The sensor row [16] of `robot` (SensorParams.fromRow names its entries), or with robot < 0 the row of the task file (the keys
-        plantSensors.<name>; absent: 0)."""
-        row = np.zeros(SensorParams.STRIDE)
-        self._call("bpmpc_plant_get_sensor_params", int(robot), _d(row))
-        return row
-
-    def resetSensorParams(self):
-        """Every sensor row, bias and counter zero, every key the start key (plantSensors.seed): the plant is the one without a sensor model again."""
-        self._call("bpmpc_plant_reset_sensor_params")
+        (k_plant_sense) and BatchedStateEstimate.update_from_plant reads sensed(); resetSensorParams ends that.""",
+        """Every sensor row, bias and counter zero, every key the start key (plantSensors.seed): the plant is the one without a sensor model again.""",
+        stem="Sensor")
 
     def seedSensors(self, seed, mask=None):
         """Restarts the random streams of the robots with mask[b] != 0 (None: every one of the batch of the last set_state; before it: max_batch)
@@ -1678,44 +1627,34 @@ class BatchedPlant(_Handle):
                   "feet_heights": (B, 4), "odom_pos": (B, 3), "odom_quat": (B, 4), "odom_lin_vel": (B, 3), "odom_ang_vel": (B, 3)}
         return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<i4" if k == "contact" else "<f8") for k, shp in shapes.items()}
 
-    def setInputParams(self, rows, mask=None):
+    getInputParams, setInputParams, resetInputParams = _param_methods(
+        "bpmpc_plant", InputParams.STRIDE,
+        """The input row [8] of `robot` (InputParams.fromRow names its entries), or with robot < 0 the row of the task file (the keys
+        plantInputs.<name>; absent: 0).""",
         """The input rows (InputParams.toRow) of the robots with mask[b] != 0 (None: every one): rows [8], [1, 8] or [B, 8].  numpy rows are
         validated and the call synchronises; device tensors are only enqueued, ordered before the next step.  From this call on every step runs
-        the input model in front of its step kernel (k_plant_input) and applied() reports what the joints received; resetInputParams ends that."""
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], InputParams.STRIDE, self.max_batch)
-        self._call("bpmpc_plant_set_input_params", B, mp, rp, n_rows, dev)
-        del keep
+        the input model in front of its step kernel (k_plant_input) and applied() reports what the joints received; resetInputParams ends that.""",
+        """Every input row and counter zero, every key the start key (plantInputs.seed): the plant is the one without an input model again.""",
+        stem="Input")
 
-    def getInputParams(self, robot=-1):
-        """The input row [8] of `robot` (InputParams.fromRow names its entries), or with robot < 0 the row of the task file (the keys
-        plantInputs.<name>; absent: 0)."""
-        row = np.zeros(InputParams.STRIDE)
-        self._call("bpmpc_plant_get_input_params", int(robot), _d(row))
-        return row
-
-    def resetInputParams(self):
-        """Every input row and counter zero, every key the start key (plantInputs.seed): the plant is the one without an input model again."""
-        self._call("bpmpc_plant_reset_input_params")
-
-    def setJointParams(self, rows, mask=None):
+    getJointParams, setJointParams, resetJointParams = _param_methods(
+        "bpmpc_plant", JointParams.STRIDE,
+        """The joint row [64] of `robot` (JointParams.fromRow(row, nj) names its entries), or with robot < 0 the start row (the neutral row under the
+        keys plantJoints.<name> of the task file).""",
         """The joint rows (JointParams.toRow) of the robots with mask[b] != 0 (None: every one): rows [64], [1, 64] or [B, 64].  numpy rows are
         validated and the call synchronises; device tensors are only enqueued, ordered before the next step.  From the first call on EVERY robot
         of the plant steps in the kernel that holds the joint model (k_plant_joint_step), also those whose row stays neutral; resetJointParams
-        ends that."""
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], JointParams.STRIDE, self.max_batch)
-        self._call("bpmpc_plant_set_joint_params", B, mp, rp, n_rows, dev)
-        del keep
+        ends that.""",
+        """Every joint row back to the start row; with a neutral start row the plant is the one without a joint model again.""",
+        stem="Joint")
 
-    def getJointParams(self, robot=-1):
-        """The joint row [64] of `robot` (JointParams.fromRow(row, nj) names its entries), or with robot < 0 the start row (the neutral row under the
-        keys plantJoints.<name> of the task file)."""
-        row = np.zeros(JointParams.STRIDE)
-        self._call("bpmpc_plant_get_joint_params", int(robot), _d(row))
-        return row
-
-    def resetJointParams(self):
-        """Every joint row back to the start row; with a neutral start row the plant is the one without a joint model again."""
-        self._call("bpmpc_plant_reset_joint_params")
+    getBodyParams, _setBodyRows, resetBodyParams = _param_methods(
+        "bpmpc_plant", BodyParams.STRIDE,
+        """The body row [160] of `robot` (BodyParams(interface, row) names its entries), or with robot < 0 the start row (the model row under
+        the keys plantBodies.<name> of the task file).""",
+        None,
+        """Every body row back to the start row; with the model row as start row the plant is the one without body rows again.""",
+        stem="Body")
 
     def setBodyParams(self, rows, mask=None):
         """The body rows (BodyParams.row) of the robots with mask[b] != 0 (None: every one): rows [160], [1, 160] or [B, 160].  numpy rows are
@@ -1726,20 +1665,7 @@ class BatchedPlant(_Handle):
             rows = rows.row
         elif isinstance(rows, (list, tuple)):
             rows = np.array([r.row if isinstance(r, BodyParams) else r for r in rows])
-        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], BodyParams.STRIDE, self.max_batch)
-        self._call("bpmpc_plant_set_body_params", B, mp, rp, n_rows, dev)
-        del keep
-
-    def getBodyParams(self, robot=-1):
-        """The body row [160] of `robot` (BodyParams(interface, row) names its entries), or with robot < 0 the start row (the model row under
-        the keys plantBodies.<name> of the task file)."""
-        row = np.zeros(BodyParams.STRIDE)
-        self._call("bpmpc_plant_get_body_params", int(robot), _d(row))
-        return row
-
-    def resetBodyParams(self):
-        """Every body row back to the start row; with the model row as start row the plant is the one without body rows again."""
-        self._call("bpmpc_plant_reset_body_params")
+        self._setBodyRows(rows, mask)
 
     def seedInputs(self, seed, mask=None):
         """Restarts the random streams of the input model for the robots with mask[b] != 0 (None: every one of the batch of the last set_state;
@@ -1768,7 +1694,7 @@ class BatchedPlant(_Handle):
         return {k: DeviceArray(C.cast(getattr(o, k), C.c_void_p).value, shp, "<f8") for k, shp in shapes.items()}
 
 
-class SupervisorParams:
+class SupervisorParams(_RowParams):
     """A parameter row of the supervisor (include/bpmpc.h "Supervisor", BPMPC_SUP_PARAM_STRIDE) with named fields: the tilt limit [rad] of
     SafetyChecker, the base height [m] below which a robot is unsafe (0: no limit), the time [s] over which INIT ramps from the latched joints
     to q_init (0: the reference's jump), the settle test's position [rad] and velocity [rad/s] tolerances and the time [s] it must hold, and
@@ -1777,23 +1703,6 @@ class SupervisorParams:
     STRIDE = 8
     FIELDS = ("tilt_limit", "min_base_height", "ramp_time", "settle_pos_tol", "settle_vel_tol", "settle_time", "stop_kd")
     DEFAULTS = (np.pi / 3.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
-
-    def __init__(self, **fields):
-        unknown = set(fields) - set(self.FIELDS)
-        if unknown:
-            raise ValueError("unknown parameter(s): %s" % sorted(unknown))
-        for name, default in zip(self.FIELDS, self.DEFAULTS):
-            setattr(self, name, float(fields.get(name, default)))
-
-    @classmethod
-    def fromRow(cls, row):
-        r = np.asarray(row, float).reshape(-1)
-        if r.size != cls.STRIDE:
-            raise ValueError("a parameter row has %d entries" % cls.STRIDE)
-        return cls(**{name: r[i] for i, name in enumerate(cls.FIELDS)})
-
-    def toRow(self):
-        return np.array([float(getattr(self, n)) for n in self.FIELDS] + [0.0])
 
 
 class BatchedSupervisor(_Handle):

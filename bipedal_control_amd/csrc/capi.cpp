@@ -375,6 +375,24 @@ int copy_out(const double* src, size_t n, double* out, int capacity) {
   std::copy(src, src + n, out);
   return (int)n;
 }
+
+// A bpmpc_*_load_*params call behind its null check: load(v) fills a row of STRIDE doubles, which is copied out only when nothing was thrown
+template <int STRIDE, typename Load>
+int load_into_row(double* row, Load&& load) {
+  return guarded(BPMPC_ERR_IO, [&] {
+    double v[STRIDE];
+    load(v);
+    std::copy(v, v + STRIDE, row);
+  });
+}
+
+// A bpmpc_*_check_*params call behind its refusals: check(row, r) for each of the n_rows rows of `stride` doubles
+template <typename Check>
+int check_n_rows(const double* rows, int n_rows, int stride, Check&& check) {
+  return guarded(BPMPC_ERR_IO, [&] {
+    for (int r = 0; r < n_rows; ++r) check(rows + (size_t)r * stride, r);
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -474,27 +492,22 @@ int bpmpc_model_joint_name(const bpmpc_model* m, int j, char* out, int capacity)
 
 int bpmpc_estimator_load_params(const char* task_info_path, double* row) {
   if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_estimator_load_params: null row");
-  return guarded(BPMPC_ERR_IO, [&] {
+  return load_into_row<kEstParamStride>(row, [&](double* v) {
     const EstSettings s = estimator_load_settings(task_info_path);
-    std::copy(&s.foot_radius, &s.foot_radius + kEstParamStride, row);
-    return (int)BPMPC_OK;
+    std::copy(&s.foot_radius, &s.foot_radius + kEstParamStride, v);
   });
 }
 
 int bpmpc_estimator_check_params(const double* rows, int n_rows) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_estimator_check_params: null rows");
-  return guarded(BPMPC_ERR_IO, [&] {
-    for (int r = 0; r < n_rows; ++r) estimator_check_param_row("bpmpc_estimator_check_params", rows + (size_t)r * kEstParamStride, r);
-    return (int)BPMPC_OK;
-  });
+  return check_n_rows(rows, n_rows, kEstParamStride, [](const double* row, int r) { estimator_check_param_row("bpmpc_estimator_check_params", row, r); });
 }
 
 int bpmpc_plant_load_params(const char* task_info_path, double* row) {
   if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_params: null row");
-  return guarded(BPMPC_ERR_IO, [&] {
+  return load_into_row<kPlantParamStride>(row, [&](double* v) {
     const PlantSettings s = plant_load_settings(task_info_path);
-    std::copy(&s.kn, &s.kn + kPlantParamStride, row);
-    return (int)BPMPC_OK;
+    std::copy(&s.kn, &s.kn + kPlantParamStride, v);
   });
 }
 
@@ -508,28 +521,17 @@ int bpmpc_plant_load_stiction(const char* task_info_path, double* kt) {
 
 int bpmpc_plant_check_params(const double* rows, int n_rows) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_params: null rows");
-  return guarded(BPMPC_ERR_IO, [&] {
-    for (int r = 0; r < n_rows; ++r) plant_check_param_row("bpmpc_plant_check_params", rows + (size_t)r * kPlantParamStride, r);
-    return (int)BPMPC_OK;
-  });
+  return check_n_rows(rows, n_rows, kPlantParamStride, [](const double* row, int r) { plant_check_param_row("bpmpc_plant_check_params", row, r); });
 }
 
 int bpmpc_plant_load_sensor_params(const char* task_info_path, double* row) {
   if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_sensor_params: null row");
-  return guarded(BPMPC_ERR_IO, [&] {
-    double v[kSensorParamStride];
-    plant_load_sensor_settings(task_info_path, v, nullptr);      // (the seed is validated with the row)
-    std::copy(v, v + kSensorParamStride, row);
-    return (int)BPMPC_OK;
-  });
+  return load_into_row<kSensorParamStride>(row, [&](double* v) { plant_load_sensor_settings(task_info_path, v, nullptr); });      // (the seed is validated with the row)
 }
 
 int bpmpc_plant_check_sensor_params(const double* rows, int n_rows) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_sensor_params: null rows");
-  return guarded(BPMPC_ERR_IO, [&] {
-    for (int r = 0; r < n_rows; ++r) plant_check_sensor_row("bpmpc_plant_check_sensor_params", rows + (size_t)r * kSensorParamStride, r);
-    return (int)BPMPC_OK;
-  });
+  return check_n_rows(rows, n_rows, kSensorParamStride, [](const double* row, int r) { plant_check_sensor_row("bpmpc_plant_check_sensor_params", row, r); });
 }
 
 int bpmpc_plant_sensor_draw(long seed, int robot, long tick, double* z, double* u) {
@@ -545,20 +547,12 @@ int bpmpc_plant_sensor_draw(long seed, int robot, long tick, double* z, double* 
 
 int bpmpc_plant_load_input_params(const char* task_info_path, double* row) {
   if (!row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_input_params: null row");
-  return guarded(BPMPC_ERR_IO, [&] {
-    double v[kInputParamStride];
-    plant_load_input_settings(task_info_path, v, nullptr);      // (the seed is validated with the row)
-    std::copy(v, v + kInputParamStride, row);
-    return (int)BPMPC_OK;
-  });
+  return load_into_row<kInputParamStride>(row, [&](double* v) { plant_load_input_settings(task_info_path, v, nullptr); });      // (the seed is validated with the row)
 }
 
 int bpmpc_plant_check_input_params(const double* rows, int n_rows) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_input_params: null rows");
-  return guarded(BPMPC_ERR_IO, [&] {
-    for (int r = 0; r < n_rows; ++r) plant_check_input_row("bpmpc_plant_check_input_params", rows + (size_t)r * kInputParamStride, r);
-    return (int)BPMPC_OK;
-  });
+  return check_n_rows(rows, n_rows, kInputParamStride, [](const double* row, int r) { plant_check_input_row("bpmpc_plant_check_input_params", row, r); });
 }
 
 int bpmpc_plant_input_draw(long seed, int robot, long counter, double u[3]) {
@@ -573,40 +567,24 @@ int bpmpc_plant_input_draw(long seed, int robot, long counter, double u[3]) {
 
 int bpmpc_plant_load_joint_params(const bpmpc_model* model, const char* task_info_path, double* row) {
   if (!model || !row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_joint_params: null model or row");
-  return guarded(BPMPC_ERR_IO, [&] {
-    double v[kPlantJointParamStride];
-    plant_load_joint_settings(model->rm, task_info_path, v);
-    std::copy(v, v + kPlantJointParamStride, row);
-    return (int)BPMPC_OK;
-  });
+  return load_into_row<kPlantJointParamStride>(row, [&](double* v) { plant_load_joint_settings(model->rm, task_info_path, v); });
 }
 
 int bpmpc_plant_check_joint_params(const double* rows, int n_rows, int nj) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_joint_params: null rows");
   if (nj < 1 || nj > kMaxJoints) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_joint_params: nj must be 1.." + std::to_string(kMaxJoints));
-  return guarded(BPMPC_ERR_IO, [&] {
-    for (int r = 0; r < n_rows; ++r) plant_check_joint_row("bpmpc_plant_check_joint_params", rows + (size_t)r * kPlantJointParamStride, r, nj);
-    return (int)BPMPC_OK;
-  });
+  return check_n_rows(rows, n_rows, kPlantJointParamStride, [&](const double* row, int r) { plant_check_joint_row("bpmpc_plant_check_joint_params", row, r, nj); });
 }
 
 int bpmpc_plant_load_body_params(const bpmpc_model* model, const char* task_info_path, double* row) {
   if (!model || !row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_load_body_params: null model or row");
-  return guarded(BPMPC_ERR_IO, [&] {
-    double v[kPlantBodyParamStride];
-    plant_load_body_settings(model->rm, task_info_path, v);
-    std::copy(v, v + kPlantBodyParamStride, row);
-    return (int)BPMPC_OK;
-  });
+  return load_into_row<kPlantBodyParamStride>(row, [&](double* v) { plant_load_body_settings(model->rm, task_info_path, v); });
 }
 
 int bpmpc_plant_check_body_params(const double* rows, int n_rows, int nj) {
   if (!rows) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_body_params: null rows");
   if (nj < 1 || nj > kMaxJoints) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_plant_check_body_params: nj must be 1.." + std::to_string(kMaxJoints));
-  return guarded(BPMPC_ERR_IO, [&] {
-    for (int r = 0; r < n_rows; ++r) plant_check_body_row("bpmpc_plant_check_body_params", rows + (size_t)r * kPlantBodyParamStride, r, nj);
-    return (int)BPMPC_OK;
-  });
+  return check_n_rows(rows, n_rows, kPlantBodyParamStride, [&](const double* row, int r) { plant_check_body_row("bpmpc_plant_check_body_params", row, r, nj); });
 }
 
 int bpmpc_plant_compose_body_row(const bpmpc_model* model, const double* row_in, int body, double mass_scale, const double* com_shift, double payload_mass,

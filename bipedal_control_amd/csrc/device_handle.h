@@ -1,6 +1,6 @@
 // What the device handles beside the solver (bpmpc_wbc, bpmpc_estimator, bpmpc_controller; the gait batch for its memory) share on the host:
 // owned device buffers, the handshake between a handle's own stream and another handle's, the staging of host inputs, the masked per-robot
-// row write (device_handle.hip), opening and entering a handle.  Plain structs and free functions; the kernels stay with their handles.
+// row write (device_handle.hip) and the per-robot row table it fills, opening and entering a handle.  Plain structs and free functions; the kernels stay with their handles.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,13 +57,17 @@ struct StreamHandshake {
     HIP_CHECK(hipStreamSynchronize(stream));
     own_pending = false;
   }
+  // the end of a call that enqueued on the own stream: host inputs are waited for (the caller's arrays), device inputs are only enqueued
+  void finish(bool on_device) {
+    if (!on_device) synchronise_own();
+    else enqueued_own();
+  }
   void destroy() {
     if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
     if (ev_foreign) (void)hipEventDestroy(ev_foreign);
     if (ev_own) (void)hipEventDestroy(ev_own);
   }
-
- private:
+  // `*ev` (created on first use) marks what has been enqueued on `on` so far; also for the events a handle keeps beside these two
   static void record(hipEvent_t* ev, hipStream_t on) {
     if (!*ev) HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(*ev, on));
@@ -103,6 +107,36 @@ void set_rows(const char* who, hipStream_t stream, int batch, int width, int use
   b.src = staged(b.src, b.staging, (size_t)n_rows * width, on_device, stream);
   write_rows(stream, batch, width, used, mask, n_rows, a, b);
 }
+
+// A per-robot row table of a handle: d_params [max_batch][stride], which the kernels read, and d_rows [max_batch + 1][stride], the device copy
+// of host rows, whose last row holds the start row.  A written row keeps its first `used` entries; the others read 0.
+struct ParamTable {
+  int stride = 0, used = 0;
+  double* d_params = nullptr;
+  double* d_rows = nullptr;
+
+  void create(DeviceBuffers& mem, int max_batch, int stride_, int used_, const double* start_row) {
+    stride = stride_; used = used_;
+    d_params = mem.alloc<double>((size_t)max_batch * stride);
+    d_rows = mem.alloc<double>((size_t)(max_batch + 1) * stride);
+    HIP_CHECK(hipMemcpy(start(max_batch), start_row, stride * sizeof(double), hipMemcpyHostToDevice));
+  }
+  double* start(int max_batch) const { return d_rows + (size_t)max_batch * stride; }
+  double* row(int b) const { return d_params + (size_t)b * stride; }
+  // every robot's row becomes the start row; enqueued on `stream`
+  void fill_from_start(hipStream_t stream, int max_batch) { write_rows(stream, max_batch, stride, used, nullptr, 1, {start(max_batch), nullptr, d_params}); }
+  // out[stride] = the row of `robot`, or with robot < 0 the start row; synchronises `stream`
+  void get(const char* who, hipStream_t stream, int max_batch, int robot, double* out) const {
+    if (robot >= max_batch) throw std::length_error(std::string(who) + ": robot exceeds max_batch");
+    HIP_CHECK(hipMemcpyAsync(out, robot < 0 ? start(max_batch) : row(robot), stride * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  // set_rows on the table's own pair; check_row(row, r) throws for host row r
+  template <typename CheckRow>
+  void set(const char* who, hipStream_t stream, int batch, const int* mask, int* mask_staging, const double* rows, int n_rows, bool on_device, CheckRow&& check_row) {
+    set_rows(who, stream, batch, stride, used, mask, mask_staging, n_rows, on_device, [&](int r) { check_row(rows + (size_t)r * stride, r); }, {rows, d_rows, d_params});
+  }
+};
 
 // What bpmpc_wbc_create and bpmpc_estimator_create (`who`) begin with, inside their guard: the device and the joint count are refused (status
 // returned, bpmpc_last_error() set), then the device model, the handle's non-blocking stream and the model on the device.

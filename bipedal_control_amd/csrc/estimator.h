@@ -19,8 +19,7 @@ struct bpmpc_estimator {
   bpmpc::StreamHandshake hs;            // the handle's stream; foreign launches: a controller tick on the solver's stream that reads d_rbd
   double *d_rbd = nullptr, *d_xhat = nullptr, *d_cov = nullptr;      // [max_batch][2 nv], [max_batch][18], [max_batch][18][18]
   int* d_xy_reset = nullptr;                                        // [max_batch]
-  double* d_params = nullptr;           // [max_batch][kEstParamStride]
-  double* d_rows = nullptr;             // [max_batch + 1][kEstParamStride] device copy of host rows; the last row holds `defaults`
+  bpmpc::ParamTable params;             // the robots' parameter rows (kernels/estimator.h EstSettings); the start row is `defaults`
   int* d_mask = nullptr;                // [max_batch] device copy of a host mask
   double *d_xhat_in = nullptr, *d_cov_in = nullptr;                 // device copies of host states (set_state)
   // device copies of host sensor arrays

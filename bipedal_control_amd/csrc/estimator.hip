@@ -47,11 +47,6 @@ using namespace bpmpc;
 
 namespace {
 
-// every parameter row becomes the defaults (the last row of d_rows)
-void write_default_params(bpmpc_estimator* e) {
-  write_rows(e->hs.stream, e->max_batch, kEstParamStride, kEstParamStride - 1, nullptr, 1, {e->d_rows + (size_t)e->max_batch * kEstParamStride, nullptr, e->d_params});
-}
-
 void set_state_on_device(bpmpc_estimator* e, int batch, const int* mask, const double* x_in, const double* cov_in, int reset) {
   constexpr int E = kEstStates + kEstStates * kEstStates;
   hipLaunchKernelGGL(k_est_set_state, dim3((batch * E + 255) / 256), dim3(256), 0, e->hs.stream, batch, mask, x_in, cov_in, reset, e->d_xhat, e->d_cov);
@@ -96,13 +91,13 @@ int bpmpc_estimator_create(const bpmpc_model* model, const char* task_info_path,
     const size_t B = max_batch, N = kEstStates, nj = e->nj;
     DeviceBuffers& m = e->mem;
     e->d_rbd = m.alloc<double>(B * 2 * e->nv, true); e->d_xhat = m.alloc<double>(B * N); e->d_cov = m.alloc<double>(B * N * N); e->d_xy_reset = m.alloc<int>(B, true);
-    e->d_params = m.alloc<double>(B * kEstParamStride); e->d_rows = m.alloc<double>((B + 1) * kEstParamStride); e->d_mask = m.alloc<int>(B);
+    e->d_mask = m.alloc<int>(B);
     e->d_xhat_in = m.alloc<double>(B * N); e->d_cov_in = m.alloc<double>(B * N * N);
     e->d_jp = m.alloc<double>(B * nj); e->d_jv = m.alloc<double>(B * nj); e->d_quat = m.alloc<double>(B * 4); e->d_w = m.alloc<double>(B * 3); e->d_a = m.alloc<double>(B * 3);
     e->d_fh = m.alloc<double>(B * 4); e->d_opos = m.alloc<double>(B * 3); e->d_oquat = m.alloc<double>(B * 4); e->d_olin = m.alloc<double>(B * 3); e->d_oang = m.alloc<double>(B * 3);
     e->d_contact = m.alloc<int>(B * 4); e->d_mode = m.alloc<int>(B);
-    HIP_CHECK(hipMemcpy(e->d_rows + B * kEstParamStride, &e->defaults, sizeof(EstSettings), hipMemcpyHostToDevice));
-    write_default_params(e.get());
+    e->params.create(m, max_batch, kEstParamStride, kEstParamStride - 1, &e->defaults.foot_radius);
+    e->params.fill_from_start(e->hs.stream, max_batch);
     set_state_on_device(e.get(), max_batch, nullptr, nullptr, nullptr, 1);
     HIP_CHECK(hipStreamSynchronize(e->hs.stream));
     return BPMPC_OK;
@@ -149,7 +144,7 @@ int bpmpc_estimator_update(bpmpc_estimator* e, int batch, const bpmpc_sensor_inp
       a.odom_lin = input(in->odom_lin_vel, e->d_olin, 3);
       a.odom_ang = input(in->odom_ang_vel, e->d_oang, 3);
     }
-    a.params = e->d_params; a.x_hat = e->d_xhat; a.cov = e->d_cov; a.rbd = e->d_rbd; a.xy_reset = e->d_xy_reset;
+    a.params = e->params.d_params; a.x_hat = e->d_xhat; a.cov = e->d_cov; a.rbd = e->d_rbd; a.xy_reset = e->d_xy_reset;
     KL_NJ(e->nj, hipLaunchKernelGGL(k_estimate<NJ>, dim3(batch), dim3(kWave), 0, e->hs.stream, e->d_model, a));
     HIP_CHECK(hipGetLastError());
     e->last_batch = batch;
@@ -207,26 +202,23 @@ int bpmpc_estimator_set_state(bpmpc_estimator* e, int batch, const int* mask, co
 
 int bpmpc_estimator_get_params(const bpmpc_estimator* e, int robot, double* row) {
   return guarded(e, BPMPC_ERR_IO, "bpmpc_estimator_get_params: null handle or row", row != nullptr, [&] {
-    if (robot >= e->max_batch) throw std::length_error("bpmpc_estimator_get_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? e->d_rows + (size_t)e->max_batch * kEstParamStride : e->d_params + (size_t)robot * kEstParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(EstSettings), hipMemcpyDeviceToHost, e->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(e->hs.stream));
+    e->params.get("bpmpc_estimator_get_params", e->hs.stream, e->max_batch, robot, row);
   });
 }
 
 int bpmpc_estimator_set_params(bpmpc_estimator* e, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(e, BPMPC_ERR_IO, "bpmpc_estimator_set_params: null handle or rows", rows != nullptr, [&] {
     check_batch(e, batch, "bpmpc_estimator_set_params");
-    set_rows("bpmpc_estimator_set_params", e->hs.stream, batch, kEstParamStride, kEstParamStride - 1, mask, e->d_mask, n_rows, inputs_on_device,
-             [&](int r) { estimator_check_param_row("bpmpc_estimator_set_params", rows + (size_t)r * kEstParamStride, r); }, {rows, e->d_rows, e->d_params});
-    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(e->hs.stream));      // device rows are only enqueued on the handle's stream: the next update runs behind them
+    e->params.set("bpmpc_estimator_set_params", e->hs.stream, batch, mask, e->d_mask, rows, n_rows, inputs_on_device,
+                  [](const double* row, int r) { estimator_check_param_row("bpmpc_estimator_set_params", row, r); });
+    e->hs.finish(inputs_on_device);      // device rows are only enqueued on the handle's stream: the next update runs behind them
   });
 }
 
 int bpmpc_estimator_reset_params(bpmpc_estimator* e) {
   return guarded(e, BPMPC_ERR_IO, "bpmpc_estimator_reset_params: null handle", [&] {
-    write_default_params(e);
-    HIP_CHECK(hipStreamSynchronize(e->hs.stream));
+    e->params.fill_from_start(e->hs.stream, e->max_batch);
+    e->hs.synchronise_own();
   });
 }
 

@@ -235,8 +235,7 @@ int bpmpc_plan_update(bpmpc_plan* pl, int batch, const int* n_nodes, const doubl
     a.xref = staged(xref, pl->d_xref, B * N * NX, dev, st);
     a.p_grid = nullptr;
     launch(pl, a, longest, st);
-    if (dev) pl->hs.enqueued_own();      // the next update from a solver or a policy buffer waits for it
-    else pl->hs.synchronise_own();       // the caller's host arrays
+    pl->hs.finish(dev);      // host arrays are the caller's; the next update from a solver or a policy buffer waits for what was only enqueued
   });
 }
 

@@ -22,8 +22,12 @@ struct bpmpc_plant {
   bpmpc::StreamHandshake hs;            // the handle's stream; foreign launches: an estimator update on the estimator's stream that reads the outputs
   hipEvent_t ev_tick = nullptr, ev_step = nullptr;      // step_controlled: the tick on the solver's stream, the step on the plant's
   double* d_state = nullptr;            // [max_batch][2 nv]: q, v
-  double* d_params = nullptr;           // [max_batch][kPlantParamStride]
-  double* d_rows = nullptr;             // [max_batch + 1][kPlantParamStride] device copy of host rows; the last row holds `defaults`
+  // the per-robot row tables; each start row is the host member named beside it
+  bpmpc::ParamTable params;             // contact parameters (kernels/plant.h PlantSettings): `defaults`
+  bpmpc::ParamTable joints;             // joint rows: joint_start
+  bpmpc::ParamTable bodies;             // body rows: body_start
+  bpmpc::ParamTable sensors;            // sensor rows: sensor_start
+  bpmpc::ParamTable inputs;             // input rows: input_start
   int* d_mask = nullptr;                // [max_batch] device copy of a host mask
   // device copies of host inputs
   double *d_rbd_in = nullptr, *d_pd = nullptr, *d_vd = nullptr, *d_tf = nullptr, *d_kp = nullptr, *d_kd = nullptr, *d_force = nullptr, *d_ground = nullptr;
@@ -37,13 +41,9 @@ struct bpmpc_plant {
   // joint model (include/bpmpc.h "Plant", joints): per-robot joint rows
   double joint_start[bpmpc::kPlantJointParamStride] = {};      // the start row: the neutral row under the keys plantJoints.<name> of task.info
   bool joint = false;                   // steps launch k_plant_joint_step: the start row is not neutral, or rows have been set since create / reset_joint_params
-  double* d_jparams = nullptr;          // [max_batch][kPlantJointParamStride]
-  double* d_jrows = nullptr;            // [max_batch + 1][kPlantJointParamStride] device copy of host rows; the last row holds joint_start
   // bodies (include/bpmpc.h "Plant", bodies): per-robot body rows
   double body_start[bpmpc::kPlantBodyParamStride] = {};      // the start row: the model row under the keys plantBodies.<name> of task.info
   bool body = false;                    // steps launch k_plant_body_step: the start row is not the model row, or rows have been set since create / reset_body_params
-  double* d_bparams = nullptr;          // [max_batch][kPlantBodyParamStride]
-  double* d_brows = nullptr;            // [max_batch + 1][kPlantBodyParamStride] device copy of host rows; the last row holds body_start
   double* d_out = nullptr;              // the output block of k_plant_step (kernels/plant.h PlantOut)
   bpmpc_plant_outputs out{};            // its sections (leading dimension max_batch)
   // sensor model (include/bpmpc.h "Plant", sensors): per-robot rows, generator state, biases, the ring of measured samples, the sensed block
@@ -51,8 +51,6 @@ struct bpmpc_plant {
   long sensor_seed = 0;                 // the key plantSensors.seed (absent: 0): every robot's key after create / reset_sensor_params
   bool sense = false;                   // steps launch k_plant_sense behind the step kernel: the handle is switched (not untouched)
   bool sensed_valid = false;            // a step has run since the switch: the sensed block holds measurements
-  double* d_sparams = nullptr;          // [max_batch][kSensorParamStride]
-  double* d_srows = nullptr;            // [max_batch + 1][kSensorParamStride] device copy of host rows; the last row holds sensor_start
   unsigned* d_skey = nullptr;           // [max_batch][2]
   unsigned long long* d_sticks = nullptr;      // [max_batch][2]: tick t, samples n since the last (re)start
   double* d_sbias = nullptr;            // [max_batch][6]: gyro bias, accelerometer bias
@@ -65,8 +63,6 @@ struct bpmpc_plant {
   bool input = false;                   // steps launch k_plant_input in front of the step kernel: the handle is switched (not untouched)
   bool applied_valid = false;           // a step has run since the switch: the applied block holds a command
   const double* last_ground = nullptr;  // feet_heights as the last step consumed them: what bpmpc_plant_applied_command reports
-  double* d_iparams = nullptr;          // [max_batch][kInputParamStride]
-  double* d_irows = nullptr;            // [max_batch + 1][kInputParamStride] device copy of host rows; the last row holds input_start
   unsigned* d_ikey = nullptr;           // [max_batch][2]
   unsigned long long* d_iticks = nullptr;      // [max_batch][2]: tick t, steps n since the last (re)start
   double* d_iring = nullptr;            // [max_batch][kInputRing][5 nj]

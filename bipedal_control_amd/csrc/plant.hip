@@ -70,11 +70,6 @@ using namespace bpmpc;
 
 namespace {
 
-// every parameter row becomes the defaults (the last row of d_rows)
-void write_default_params(bpmpc_plant* p) {
-  write_rows(p->hs.stream, p->max_batch, kPlantParamStride, kPlantParamStride - 2, nullptr, 1, {p->d_rows + (size_t)p->max_batch * kPlantParamStride, nullptr, p->d_params});
-}
-
 // every robot's kt becomes the handle's start value and every anchor is cleared
 void write_default_stiction(bpmpc_plant* p) {
   const size_t B = p->max_batch;
@@ -86,17 +81,15 @@ void write_default_stiction(bpmpc_plant* p) {
   p->stick = p->kt_start > 0.0;
 }
 
-// every joint row becomes the start row (the last row of d_jrows), and the start row decides which kernel steps launch
+// every joint row becomes the start row, and the start row decides which kernel steps launch
 void write_start_joint_params(bpmpc_plant* p) {
-  write_rows(p->hs.stream, p->max_batch, kPlantJointParamStride, kJointParamUsed, nullptr, 1,
-             {p->d_jrows + (size_t)p->max_batch * kPlantJointParamStride, nullptr, p->d_jparams});
+  p->joints.fill_from_start(p->hs.stream, p->max_batch);
   p->joint = !plant_joint_row_neutral(p->joint_start, p->nj);
 }
 
-// every body row becomes the start row (the last row of d_brows), and the start row decides which kernel steps launch
+// every body row becomes the start row, and the start row decides which kernel steps launch
 void write_start_body_params(bpmpc_plant* p) {
-  write_rows(p->hs.stream, p->max_batch, kPlantBodyParamStride, kPlantBodyParamStride, nullptr, 1,
-             {p->d_brows + (size_t)p->max_batch * kPlantBodyParamStride, nullptr, p->d_bparams});
+  p->bodies.fill_from_start(p->hs.stream, p->max_batch);
   double model_row[kPlantBodyParamStride];
   plant_body_model_row(p->rm, model_row);
   p->body = !plant_body_rows_equal(p->body_start, model_row, p->nj);
@@ -117,11 +110,14 @@ void check_step(const bpmpc_plant* p, int batch, double period, int substeps, co
                                 "): the other robots have no state");
 }
 
-PlantArgs step_args(const bpmpc_plant* p, int batch, double period, int substeps) {
+// what every step passes its kernel, the command apart: base_force and feet_heights (nullable) are staged as the step's other host inputs are
+PlantArgs step_args(const bpmpc_plant* p, int batch, double period, int substeps, const double* base_force, const double* feet_heights, bool on_device) {
   PlantArgs a{};
-  a.batch = batch; a.substeps = substeps; a.h = period / substeps; a.params = p->d_params; a.state = p->d_state;
+  a.batch = batch; a.substeps = substeps; a.h = period / substeps; a.params = p->params.d_params; a.state = p->d_state;
   for (int i = 0; i < kMaxJoints / 2; ++i) a.torque_limits[i] = p->torque_limits[i];
   a.out = p->d_out; a.max_batch = p->max_batch;
+  a.base_force = staged(base_force, p->d_force, (size_t)batch * 3, on_device, p->hs.stream);
+  a.ground = staged(feet_heights, p->d_ground, (size_t)batch * 4, on_device, p->hs.stream);
   return a;
 }
 
@@ -130,7 +126,7 @@ void launch_input(bpmpc_plant* p, PlantArgs& a, double period) {
   p->last_ground = a.ground;
   if (!p->input) return;
   const size_t rows = (size_t)p->max_batch * p->nj;
-  const PlantInputArgs ia{a.batch, p->max_batch, input_period_ns(period), p->d_iparams, p->d_ikey, p->d_iticks, p->d_iring, a.pos_des, a.vel_des, a.tau_ff, a.kp, a.kd,
+  const PlantInputArgs ia{a.batch, p->max_batch, input_period_ns(period), p->inputs.d_params, p->d_ikey, p->d_iticks, p->d_iring, a.pos_des, a.vel_des, a.tau_ff, a.kp, a.kd,
                           a.cmd_stride, a.base_force, p->d_applied, p->d_applied_force, p->d_iflags};
   launch_plant_input(p->nj, p->hs.stream, ia);
   a.cmd_stride = p->nj;
@@ -142,23 +138,16 @@ void launch_input(bpmpc_plant* p, PlantArgs& a, double period) {
 // the step kernel, on a switched handle the input model in front of it and the sensor model behind it: `period` is the control step's
 void launch_step(bpmpc_plant* p, PlantArgs a, double period) {
   launch_input(p, a, period);
-  if (p->body) {      // body rows are in use: one kernel holds them, the joint model and stick-slip contacts
-    const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
-    launch_plant_body_step(p->nj, p->hs.stream, p->d_model, a, sa, PlantJointArgs{p->d_jparams}, PlantBodyArgs{p->d_bparams});
-  }
-  else if (p->joint) {      // the joint model is in use: one kernel holds it and stick-slip contacts
-    const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
-    launch_plant_joint_step(p->nj, p->hs.stream, p->d_model, a, sa, PlantJointArgs{p->d_jparams});
-  }
-  else if (p->stick) {
-    const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
-    launch_plant_stick_step(p->nj, p->hs.stream, p->d_model, a, sa);
-  }
+  const PlantStickArgs sa{p->d_kt, p->d_anchor, p->d_anchored};
+  const PlantJointArgs ja{p->joints.d_params};
+  if (p->body) launch_plant_body_step(p->nj, p->hs.stream, p->d_model, a, sa, ja, PlantBodyArgs{p->bodies.d_params});      // body rows, the joint model and stick-slip contacts
+  else if (p->joint) launch_plant_joint_step(p->nj, p->hs.stream, p->d_model, a, sa, ja);      // the joint model and stick-slip contacts
+  else if (p->stick) launch_plant_stick_step(p->nj, p->hs.stream, p->d_model, a, sa);
   else KL_NJ(p->nj, hipLaunchKernelGGL(k_plant_step<NJ>, dim3(a.batch), dim3(kWave), 0, p->hs.stream, p->d_model, a));
   HIP_CHECK(hipGetLastError());
   if (p->sense) {
-    const PlantSenseArgs sa{a.batch, p->max_batch, std::sqrt(period), p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias, p->d_sring, p->d_out, p->d_sensed};
-    launch_plant_sense(p->nj, p->hs.stream, sa);
+    const PlantSenseArgs se{a.batch, p->max_batch, std::sqrt(period), p->sensors.d_params, p->d_skey, p->d_sticks, p->d_sbias, p->d_sring, p->d_out, p->d_sensed};
+    launch_plant_sense(p->nj, p->hs.stream, se);
     p->sensed_valid = true;
   }
 }
@@ -173,8 +162,8 @@ void switch_sensors(bpmpc_plant* p) {
 void write_untouched_sensors(bpmpc_plant* p) {
   const size_t B = p->max_batch;
   hipStream_t st = p->hs.stream;
-  HIP_CHECK(hipMemsetAsync(p->d_sparams, 0, B * kSensorParamStride * sizeof(double), st));
-  launch_plant_seed_sensors(st, p->max_batch, nullptr, p->sensor_seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);      // keys and counters
+  HIP_CHECK(hipMemsetAsync(p->sensors.d_params, 0, B * kSensorParamStride * sizeof(double), st));
+  launch_plant_seed_sensors(st, p->max_batch, nullptr, p->sensor_seed, p->sensors.d_params, p->d_skey, p->d_sticks, p->d_sbias);      // keys and counters
   HIP_CHECK(hipMemsetAsync(p->d_sbias, 0, B * 6 * sizeof(double), st));
   HIP_CHECK(hipStreamSynchronize(st));
   p->sense = false; p->sensed_valid = false;
@@ -190,16 +179,104 @@ void switch_inputs(bpmpc_plant* p) {
 void write_untouched_inputs(bpmpc_plant* p) {
   const size_t B = p->max_batch;
   hipStream_t st = p->hs.stream;
-  HIP_CHECK(hipMemsetAsync(p->d_iparams, 0, B * kInputParamStride * sizeof(double), st));
+  HIP_CHECK(hipMemsetAsync(p->inputs.d_params, 0, B * kInputParamStride * sizeof(double), st));
   HIP_CHECK(hipMemsetAsync(p->d_iflags, 0, B * 3 * sizeof(int), st));
   launch_plant_seed_inputs(st, p->max_batch, nullptr, p->input_seed, p->d_ikey, p->d_iticks);
   HIP_CHECK(hipStreamSynchronize(st));
   p->input = false; p->applied_valid = false;
 }
 
-void record(hipEvent_t* ev, hipStream_t on) {
-  if (!*ev) HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(*ev, on));
+// The pieces of bpmpc_plant_create, in its order.  Each allocates its zero-filled buffers before its table: the fills run on the null stream, and
+// the upload of a start row (ParamTable::create) waits for them before anything is enqueued on the handle's stream.
+
+// the state, the mask and the device copies of host inputs
+void create_state_and_staging(bpmpc_plant* p) {
+  const size_t B = p->max_batch, nj = p->nj, nv = p->nv;
+  DeviceBuffers& m = p->mem;
+  p->d_state = m.alloc<double>(B * 2 * nv, true);
+  p->d_mask = m.alloc<int>(B);
+  p->d_rbd_in = m.alloc<double>(B * 2 * nv);
+  p->d_pd = m.alloc<double>(B * nj); p->d_vd = m.alloc<double>(B * nj); p->d_tf = m.alloc<double>(B * nj); p->d_kp = m.alloc<double>(B * nj); p->d_kd = m.alloc<double>(B * nj);
+  p->d_force = m.alloc<double>(B * 3); p->d_ground = m.alloc<double>(B * 4);
+}
+
+// the output block and its section pointers
+void create_outputs(bpmpc_plant* p) {
+  const size_t B = p->max_batch;
+  p->d_out = p->mem.alloc<double>(B * plant_out_offset(kPlantOutEnd, p->nj), true);
+  auto section = [&](int sec) { return p->d_out + B * plant_out_offset(sec, p->nj); };
+  bpmpc_sensor_inputs& s = p->out.sensors;
+  s.joint_pos = section(kPlantJointPos); s.joint_vel = section(kPlantJointVel); s.quat = section(kPlantQuat);
+  s.angular_vel_local = section(kPlantAngLocal); s.linear_accel_local = section(kPlantAccLocal);
+  s.contact = reinterpret_cast<int*>(section(kPlantContact)); s.mode = nullptr;
+  s.feet_heights = section(kPlantFeetHeights); s.odom_pos = section(kPlantOdomPos); s.odom_quat = section(kPlantOdomQuat);
+  s.odom_lin_vel = section(kPlantOdomLin); s.odom_ang_vel = section(kPlantOdomAng);
+  p->out.rbd = section(kPlantRbd); p->out.contact_force = section(kPlantContactForce);
+}
+
+// contact parameters and stick-slip contacts: `defaults` and kt_start are loaded
+void create_contacts(bpmpc_plant* p) {
+  const size_t B = p->max_batch;
+  DeviceBuffers& m = p->mem;
+  p->d_kt = m.alloc<double>(B); p->d_kt_in = m.alloc<double>(B);
+  p->d_anchor = m.alloc<double>(B * kNumContacts * 2); p->d_anchored = m.alloc<int>(B * kNumContacts);
+  p->params.create(m, p->max_batch, kPlantParamStride, kPlantParamStride - 2, &p->defaults.kn);
+  p->params.fill_from_start(p->hs.stream, p->max_batch);
+  write_default_stiction(p);
+}
+
+void create_joints(bpmpc_plant* p, const char* task_info_path) {
+  plant_load_joint_settings(p->rm, task_info_path, p->joint_start);
+  p->joints.create(p->mem, p->max_batch, kPlantJointParamStride, kJointParamUsed, p->joint_start);
+  write_start_joint_params(p);
+}
+
+void create_bodies(bpmpc_plant* p, const char* task_info_path) {
+  plant_load_body_settings(p->rm, task_info_path, p->body_start);
+  p->bodies.create(p->mem, p->max_batch, kPlantBodyParamStride, kPlantBodyParamStride, p->body_start);
+  write_start_body_params(p);
+}
+
+// A task file with settings for the sensor or the input model (a non-zero used entry of the start row): its row for every robot; true: the handle
+// is to be switched
+bool fill_if_configured(bpmpc_plant* p, ParamTable& table, const double* start_row) {
+  if (std::all_of(start_row, start_row + table.used, [](double v) { return v == 0.0; })) return false;
+  table.fill_from_start(p->hs.stream, p->max_batch);
+  return true;
+}
+
+// sensor model: the members it measures live in the sensed block, the others are the truth's
+void create_sensors(bpmpc_plant* p, const char* task_info_path) {
+  plant_load_sensor_settings(task_info_path, p->sensor_start, &p->sensor_seed);
+  const size_t B = p->max_batch;
+  DeviceBuffers& m = p->mem;
+  p->d_skey = m.alloc<unsigned>(B * 2); p->d_sticks = m.alloc<unsigned long long>(B * 2); p->d_sbias = m.alloc<double>(B * 6);
+  p->d_sring = m.alloc<double>(B * kSensorRing * sensor_sample_width(p->nj), true);
+  p->d_sensed = m.alloc<double>(B * sensor_sensed_offset(kSensedEnd, p->nj), true);
+  auto measured = [&](int sec) { return p->d_sensed + B * sensor_sensed_offset(sec, p->nj); };
+  p->sensed = p->out.sensors;
+  p->sensed.joint_pos = measured(kSensedJointPos); p->sensed.joint_vel = measured(kSensedJointVel); p->sensed.quat = measured(kSensedQuat);
+  p->sensed.angular_vel_local = measured(kSensedAngLocal); p->sensed.linear_accel_local = measured(kSensedAccLocal);
+  p->sensed.contact = reinterpret_cast<int*>(measured(kSensedContact));
+  p->sensors.create(m, p->max_batch, kSensorParamStride, kSensorParamUsed, p->sensor_start);
+  write_untouched_sensors(p);
+  if (fill_if_configured(p, p->sensors, p->sensor_start)) {      // turned on under the start key
+    launch_plant_seed_sensors(p->hs.stream, p->max_batch, nullptr, p->sensor_seed, p->sensors.d_params, p->d_skey, p->d_sticks, p->d_sbias);
+    switch_sensors(p);
+  }
+}
+
+// input model: the step kernels consume the applied block on a switched handle, the caller's pointers otherwise
+void create_inputs(bpmpc_plant* p, const char* task_info_path) {
+  plant_load_input_settings(task_info_path, p->input_start, &p->input_seed);
+  const size_t B = p->max_batch, nj = p->nj;
+  DeviceBuffers& m = p->mem;
+  p->d_ikey = m.alloc<unsigned>(B * 2); p->d_iticks = m.alloc<unsigned long long>(B * 2);
+  p->d_iring = m.alloc<double>(B * kInputRing * kInputRows * nj, true);
+  p->d_applied = m.alloc<double>(kInputRows * B * nj, true); p->d_applied_force = m.alloc<double>(B * 3, true); p->d_iflags = m.alloc<int>(B * 3, true);
+  p->inputs.create(m, p->max_batch, kInputParamStride, kInputParamUsed, p->input_start);
+  write_untouched_inputs(p);
+  if (fill_if_configured(p, p->inputs, p->input_start)) switch_inputs(p);      // under the start key, which write_untouched_inputs has set
 }
 
 }  // namespace
@@ -221,69 +298,13 @@ int bpmpc_plant_create(const bpmpc_model* model, const char* task_info_path, int
       const std::vector<double> lim = load_matrix(*t, "torqueLimitsTask", p->nj / 2, 1);
       for (int i = 0; i < p->nj / 2; ++i) p->torque_limits[i] = lim[i];
     }
-    const size_t B = max_batch, nj = p->nj, nv = p->nv;
-    DeviceBuffers& m = p->mem;
-    p->d_state = m.alloc<double>(B * 2 * nv, true);
-    p->d_params = m.alloc<double>(B * kPlantParamStride); p->d_rows = m.alloc<double>((B + 1) * kPlantParamStride); p->d_mask = m.alloc<int>(B);
-    p->d_rbd_in = m.alloc<double>(B * 2 * nv);
-    p->d_pd = m.alloc<double>(B * nj); p->d_vd = m.alloc<double>(B * nj); p->d_tf = m.alloc<double>(B * nj); p->d_kp = m.alloc<double>(B * nj); p->d_kd = m.alloc<double>(B * nj);
-    p->d_force = m.alloc<double>(B * 3); p->d_ground = m.alloc<double>(B * 4);
-    p->d_kt = m.alloc<double>(B); p->d_kt_in = m.alloc<double>(B);
-    p->d_anchor = m.alloc<double>(B * kNumContacts * 2); p->d_anchored = m.alloc<int>(B * kNumContacts);
-    p->d_out = m.alloc<double>(B * plant_out_offset(kPlantOutEnd, p->nj), true);
-    auto section = [&](int sec) { return p->d_out + B * plant_out_offset(sec, p->nj); };
-    bpmpc_sensor_inputs& s = p->out.sensors;
-    s.joint_pos = section(kPlantJointPos); s.joint_vel = section(kPlantJointVel); s.quat = section(kPlantQuat);
-    s.angular_vel_local = section(kPlantAngLocal); s.linear_accel_local = section(kPlantAccLocal);
-    s.contact = reinterpret_cast<int*>(section(kPlantContact)); s.mode = nullptr;
-    s.feet_heights = section(kPlantFeetHeights); s.odom_pos = section(kPlantOdomPos); s.odom_quat = section(kPlantOdomQuat);
-    s.odom_lin_vel = section(kPlantOdomLin); s.odom_ang_vel = section(kPlantOdomAng);
-    p->out.rbd = section(kPlantRbd); p->out.contact_force = section(kPlantContactForce);
-    HIP_CHECK(hipMemcpy(p->d_rows + B * kPlantParamStride, &p->defaults, sizeof(PlantSettings), hipMemcpyHostToDevice));
-    write_default_params(p.get());
-    write_default_stiction(p.get());
-    plant_load_joint_settings(p->rm, task_info_path, p->joint_start);
-    p->d_jparams = m.alloc<double>(B * kPlantJointParamStride); p->d_jrows = m.alloc<double>((B + 1) * kPlantJointParamStride);
-    HIP_CHECK(hipMemcpy(p->d_jrows + B * kPlantJointParamStride, p->joint_start, sizeof(p->joint_start), hipMemcpyHostToDevice));
-    write_start_joint_params(p.get());
-    plant_load_body_settings(p->rm, task_info_path, p->body_start);
-    p->d_bparams = m.alloc<double>(B * kPlantBodyParamStride); p->d_brows = m.alloc<double>((B + 1) * kPlantBodyParamStride);
-    HIP_CHECK(hipMemcpy(p->d_brows + B * kPlantBodyParamStride, p->body_start, sizeof(p->body_start), hipMemcpyHostToDevice));
-    write_start_body_params(p.get());
-    // sensor model: the members it measures live in the sensed block, the others are the truth's
-    plant_load_sensor_settings(task_info_path, p->sensor_start, &p->sensor_seed);
-    p->d_sparams = m.alloc<double>(B * kSensorParamStride); p->d_srows = m.alloc<double>((B + 1) * kSensorParamStride);
-    p->d_skey = m.alloc<unsigned>(B * 2); p->d_sticks = m.alloc<unsigned long long>(B * 2); p->d_sbias = m.alloc<double>(B * 6);
-    p->d_sring = m.alloc<double>(B * kSensorRing * sensor_sample_width(p->nj), true);
-    p->d_sensed = m.alloc<double>(B * sensor_sensed_offset(kSensedEnd, p->nj), true);
-    auto measured = [&](int sec) { return p->d_sensed + B * sensor_sensed_offset(sec, p->nj); };
-    p->sensed = s;
-    p->sensed.joint_pos = measured(kSensedJointPos); p->sensed.joint_vel = measured(kSensedJointVel); p->sensed.quat = measured(kSensedQuat);
-    p->sensed.angular_vel_local = measured(kSensedAngLocal); p->sensed.linear_accel_local = measured(kSensedAccLocal);
-    p->sensed.contact = reinterpret_cast<int*>(measured(kSensedContact));
-    HIP_CHECK(hipMemcpy(p->d_srows + B * kSensorParamStride, p->sensor_start, sizeof(p->sensor_start), hipMemcpyHostToDevice));
-    write_untouched_sensors(p.get());
-    bool configured = false;
-    for (int e = 0; e < kSensorParamUsed; ++e) configured = configured || p->sensor_start[e] != 0.0;
-    if (configured) {      // a task file with sensor settings: its row for every robot, turned on under the start key
-      write_rows(p->hs.stream, max_batch, kSensorParamStride, kSensorParamUsed, nullptr, 1, {p->d_srows + B * kSensorParamStride, nullptr, p->d_sparams});
-      launch_plant_seed_sensors(p->hs.stream, max_batch, nullptr, p->sensor_seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);
-      switch_sensors(p.get());
-    }
-    // input model: the step kernels consume the applied block on a switched handle, the caller's pointers otherwise
-    plant_load_input_settings(task_info_path, p->input_start, &p->input_seed);
-    p->d_iparams = m.alloc<double>(B * kInputParamStride); p->d_irows = m.alloc<double>((B + 1) * kInputParamStride);
-    p->d_ikey = m.alloc<unsigned>(B * 2); p->d_iticks = m.alloc<unsigned long long>(B * 2);
-    p->d_iring = m.alloc<double>(B * kInputRing * kInputRows * nj, true);
-    p->d_applied = m.alloc<double>(kInputRows * B * nj, true); p->d_applied_force = m.alloc<double>(B * 3, true); p->d_iflags = m.alloc<int>(B * 3, true);
-    HIP_CHECK(hipMemcpy(p->d_irows + B * kInputParamStride, p->input_start, sizeof(p->input_start), hipMemcpyHostToDevice));
-    write_untouched_inputs(p.get());
-    bool inputs_configured = false;
-    for (int e = 0; e < kInputParamUsed; ++e) inputs_configured = inputs_configured || p->input_start[e] != 0.0;
-    if (inputs_configured) {      // a task file with input settings: its row for every robot, under the start key
-      write_rows(p->hs.stream, max_batch, kInputParamStride, kInputParamUsed, nullptr, 1, {p->d_irows + B * kInputParamStride, nullptr, p->d_iparams});
-      switch_inputs(p.get());
-    }
+    create_state_and_staging(p.get());
+    create_outputs(p.get());
+    create_contacts(p.get());
+    create_joints(p.get(), task_info_path);
+    create_bodies(p.get(), task_info_path);
+    create_sensors(p.get(), task_info_path);
+    create_inputs(p.get(), task_info_path);
     HIP_CHECK(hipStreamSynchronize(p->hs.stream));
     return BPMPC_OK;
   });
@@ -316,8 +337,7 @@ int bpmpc_plant_set_state(bpmpc_plant* p, int batch, const int* mask, const doub
     if (p->sense) launch_plant_forget_samples(st, batch, dmask, p->d_sticks);      // n = 0: the robots' sample history is forgotten
     if (p->input) launch_plant_forget_commands(st, batch, dmask, p->d_iticks);     // n = 0: the robots' buffered commands are forgotten
     p->last_batch = batch;
-    if (!inputs_on_device) p->hs.synchronise_own();
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 
@@ -332,20 +352,13 @@ int bpmpc_plant_get_state(bpmpc_plant* p, int batch, double* host_rbd) {
 int bpmpc_plant_step(bpmpc_plant* p, int batch, const bpmpc_joint_command* c, int inputs_on_device, double period, int substeps) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_step: null handle or command", c && c->pos_des && c->vel_des && c->tau_ff && c->kp && c->kd, [&] {
     check_step(p, batch, period, substeps, "bpmpc_plant_step");
-    const size_t B = batch, nj = p->nj;
-    hipStream_t st = p->hs.stream;
-    PlantArgs a = step_args(p, batch, period, substeps);
+    PlantArgs a = step_args(p, batch, period, substeps, c->base_force, c->feet_heights, inputs_on_device);
+    auto input = [&](const double* src, double* staging) { return staged(src, staging, (size_t)batch * p->nj, inputs_on_device, p->hs.stream); };
     a.cmd_stride = p->nj;
-    a.pos_des = staged(c->pos_des, p->d_pd, B * nj, inputs_on_device, st);
-    a.vel_des = staged(c->vel_des, p->d_vd, B * nj, inputs_on_device, st);
-    a.tau_ff = staged(c->tau_ff, p->d_tf, B * nj, inputs_on_device, st);
-    a.kp = staged(c->kp, p->d_kp, B * nj, inputs_on_device, st);
-    a.kd = staged(c->kd, p->d_kd, B * nj, inputs_on_device, st);
-    a.base_force = staged(c->base_force, p->d_force, B * 3, inputs_on_device, st);
-    a.ground = staged(c->feet_heights, p->d_ground, B * 4, inputs_on_device, st);
+    a.pos_des = input(c->pos_des, p->d_pd); a.vel_des = input(c->vel_des, p->d_vd); a.tau_ff = input(c->tau_ff, p->d_tf);
+    a.kp = input(c->kp, p->d_kp); a.kd = input(c->kd, p->d_kd);
     launch_step(p, a, period);
-    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 
@@ -368,21 +381,17 @@ int bpmpc_plant_step_controlled(bpmpc_plant* p, bpmpc_controller* controller, in
     if (batch != cc.last_tick_batch)
       throw std::invalid_argument("bpmpc_plant_step_controlled: batch " + std::to_string(batch) + " differs from the batch of the controller's last tick (" +
                                   std::to_string(cc.last_tick_batch) + ")");
-    const size_t B = batch;
     hipStream_t st = p->hs.stream;
-    PlantArgs a = step_args(p, batch, period, substeps);
+    PlantArgs a = step_args(p, batch, period, substeps, base_force, feet_heights, inputs_on_device);
     a.cmd_stride = 3 * p->nj;
     a.pos_des = cc.joint_cmd; a.vel_des = cc.joint_cmd + p->nj; a.tau_ff = cc.joint_cmd + 2 * p->nj;
     a.kp = cc.kp; a.kd = cc.kd;
-    a.base_force = staged(base_force, p->d_force, B * 3, inputs_on_device, st);
-    a.ground = staged(feet_heights, p->d_ground, B * 4, inputs_on_device, st);
-    record(&p->ev_tick, cc.stream);
+    StreamHandshake::record(&p->ev_tick, cc.stream);
     HIP_CHECK(hipStreamWaitEvent(st, p->ev_tick, 0));
     launch_step(p, a, period);
-    record(&p->ev_step, st);
+    StreamHandshake::record(&p->ev_step, st);
     HIP_CHECK(hipStreamWaitEvent(cc.stream, p->ev_step, 0));
-    if (!inputs_on_device && (base_force || feet_heights)) p->hs.synchronise_own();      // the caller's host arrays
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device || !(base_force || feet_heights));      // waited for only when a host array of the caller's was staged
   });
 }
 
@@ -396,18 +405,14 @@ int bpmpc_plant_step_supervised(bpmpc_plant* p, bpmpc_supervisor* sup, int batch
     if (sup->device != p->device) throw std::invalid_argument("bpmpc_plant_step_supervised: the plant and the supervisor live on different devices");
     check_step(p, batch, period, substeps, "bpmpc_plant_step_supervised");
     if (batch > sup->max_batch) throw std::length_error("bpmpc_plant_step_supervised: batch exceeds the supervisor's max_batch");
-    const size_t B = batch;
     hipStream_t st = p->hs.stream;
-    PlantArgs a = step_args(p, batch, period, substeps);
+    PlantArgs a = step_args(p, batch, period, substeps, base_force, feet_heights, inputs_on_device);
     a.cmd_stride = p->nj;
     a.pos_des = sup->d_cmd[0]; a.vel_des = sup->d_cmd[1]; a.tau_ff = sup->d_cmd[2]; a.kp = sup->d_cmd[3]; a.kd = sup->d_cmd[4];
-    a.base_force = staged(base_force, p->d_force, B * 3, inputs_on_device, st);
-    a.ground = staged(feet_heights, p->d_ground, B * 4, inputs_on_device, st);
     sup->hs.before_foreign(st);
     launch_step(p, a, period);
     sup->hs.after_foreign(st);
-    if (!inputs_on_device && (base_force || feet_heights)) p->hs.synchronise_own();      // the caller's host arrays
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device || !(base_force || feet_heights));      // waited for only when a host array of the caller's was staged
   });
 }
 
@@ -430,63 +435,53 @@ int bpmpc_estimator_update_from_plant(bpmpc_estimator* e, bpmpc_plant* p, int ba
 
 int bpmpc_plant_get_params(const bpmpc_plant* p, int robot, double* row) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_params: null handle or row", row != nullptr, [&] {
-    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? p->d_rows + (size_t)p->max_batch * kPlantParamStride : p->d_params + (size_t)robot * kPlantParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(PlantSettings), hipMemcpyDeviceToHost, p->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->params.get("bpmpc_plant_get_params", p->hs.stream, p->max_batch, robot, row);
   });
 }
 
 int bpmpc_plant_set_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_params: null handle or rows", rows != nullptr, [&] {
     check_batch(p, batch, "bpmpc_plant_set_params");
-    set_rows("bpmpc_plant_set_params", p->hs.stream, batch, kPlantParamStride, kPlantParamStride - 2, mask, p->d_mask, n_rows, inputs_on_device,
-             [&](int r) { plant_check_param_row("bpmpc_plant_set_params", rows + (size_t)r * kPlantParamStride, r); }, {rows, p->d_rows, p->d_params});
-    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // device rows are only enqueued on the handle's stream: the next step runs behind them
+    p->params.set("bpmpc_plant_set_params", p->hs.stream, batch, mask, p->d_mask, rows, n_rows, inputs_on_device,
+                  [](const double* row, int r) { plant_check_param_row("bpmpc_plant_set_params", row, r); });
+    p->hs.finish(inputs_on_device);      // device rows are only enqueued on the handle's stream: the next step runs behind them
   });
 }
 
 int bpmpc_plant_reset_params(bpmpc_plant* p) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_params: null handle", [&] {
-    write_default_params(p);
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->params.fill_from_start(p->hs.stream, p->max_batch);
+    p->hs.synchronise_own();
   });
 }
 
 int bpmpc_plant_get_joint_params(const bpmpc_plant* p, int robot, double* row) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_joint_params: null handle or row", row != nullptr, [&] {
-    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_joint_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? p->d_jrows + (size_t)p->max_batch * kPlantJointParamStride : p->d_jparams + (size_t)robot * kPlantJointParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, kPlantJointParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->joints.get("bpmpc_plant_get_joint_params", p->hs.stream, p->max_batch, robot, row);
   });
 }
 
 int bpmpc_plant_set_joint_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_joint_params: null handle or rows", rows != nullptr, [&] {
     check_batch(p, batch, "bpmpc_plant_set_joint_params");
-    set_rows("bpmpc_plant_set_joint_params", p->hs.stream, batch, kPlantJointParamStride, kJointParamUsed, mask, p->d_mask, n_rows, inputs_on_device,
-             [&](int r) { plant_check_joint_row("bpmpc_plant_set_joint_params", rows + (size_t)r * kPlantJointParamStride, r, p->nj); },
-             {rows, p->d_jrows, p->d_jparams});
+    p->joints.set("bpmpc_plant_set_joint_params", p->hs.stream, batch, mask, p->d_mask, rows, n_rows, inputs_on_device,
+                  [&](const double* row, int r) { plant_check_joint_row("bpmpc_plant_set_joint_params", row, r, p->nj); });
     p->joint = true;      // from here on every robot of the handle steps in k_plant_joint_step
-    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // device rows are only enqueued on the handle's stream: the next step runs behind them
+    p->hs.finish(inputs_on_device);      // device rows are only enqueued on the handle's stream: the next step runs behind them
   });
 }
 
 int bpmpc_plant_reset_joint_params(bpmpc_plant* p) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_joint_params: null handle", [&] {
     write_start_joint_params(p);
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->hs.synchronise_own();
   });
 }
 
 int bpmpc_plant_get_body_params(const bpmpc_plant* p, int robot, double* row) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_body_params: null handle or row", row != nullptr, [&] {
-    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_body_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? p->d_brows + (size_t)p->max_batch * kPlantBodyParamStride : p->d_bparams + (size_t)robot * kPlantBodyParamStride;
     double got[kPlantBodyParamStride];
-    HIP_CHECK(hipMemcpyAsync(got, src, kPlantBodyParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->bodies.get("bpmpc_plant_get_body_params", p->hs.stream, p->max_batch, robot, got);
     for (int e = 0; e < kPlantBodyParamStride; ++e) row[e] = e % kPlantBodySlots <= p->nj ? got[e] : 0.0;      // slots of bodies the robot does not have
   });
 }
@@ -494,18 +489,17 @@ int bpmpc_plant_get_body_params(const bpmpc_plant* p, int robot, double* row) {
 int bpmpc_plant_set_body_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_body_params: null handle or rows", rows != nullptr, [&] {
     check_batch(p, batch, "bpmpc_plant_set_body_params");
-    set_rows("bpmpc_plant_set_body_params", p->hs.stream, batch, kPlantBodyParamStride, kPlantBodyParamStride, mask, p->d_mask, n_rows, inputs_on_device,
-             [&](int r) { plant_check_body_row("bpmpc_plant_set_body_params", rows + (size_t)r * kPlantBodyParamStride, r, p->nj); },
-             {rows, p->d_brows, p->d_bparams});
+    p->bodies.set("bpmpc_plant_set_body_params", p->hs.stream, batch, mask, p->d_mask, rows, n_rows, inputs_on_device,
+                  [&](const double* row, int r) { plant_check_body_row("bpmpc_plant_set_body_params", row, r, p->nj); });
     p->body = true;      // from here on every robot of the handle steps in k_plant_body_step
-    if (!inputs_on_device) HIP_CHECK(hipStreamSynchronize(p->hs.stream));      // device rows are only enqueued on the handle's stream: the next step runs behind them
+    p->hs.finish(inputs_on_device);      // device rows are only enqueued on the handle's stream: the next step runs behind them
   });
 }
 
 int bpmpc_plant_reset_body_params(bpmpc_plant* p) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_reset_body_params: null handle", [&] {
     write_start_body_params(p);
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->hs.synchronise_own();
   });
 }
 
@@ -523,8 +517,7 @@ int bpmpc_plant_set_stiction(bpmpc_plant* p, int batch, const int* mask, const d
     hipLaunchKernelGGL(k_plant_set_stiction, dim3((batch + 255) / 256), dim3(256), 0, st, batch, dmask, dkt, n_rows, p->d_kt, p->d_anchor, p->d_anchored);
     HIP_CHECK(hipGetLastError());
     p->stick = true;
-    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 
@@ -552,21 +545,17 @@ int bpmpc_plant_get_anchors(bpmpc_plant* p, int batch, double* host_anchor, int*
 
 int bpmpc_plant_get_sensor_params(const bpmpc_plant* p, int robot, double* row) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_sensor_params: null handle or row", row != nullptr, [&] {
-    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_sensor_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? p->d_srows + (size_t)p->max_batch * kSensorParamStride : p->d_sparams + (size_t)robot * kSensorParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, kSensorParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->sensors.get("bpmpc_plant_get_sensor_params", p->hs.stream, p->max_batch, robot, row);
   });
 }
 
 int bpmpc_plant_set_sensor_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_sensor_params: null handle or rows", rows != nullptr, [&] {
     check_batch(p, batch, "bpmpc_plant_set_sensor_params");
-    set_rows("bpmpc_plant_set_sensor_params", p->hs.stream, batch, kSensorParamStride, kSensorParamUsed, mask, p->d_mask, n_rows, inputs_on_device,
-             [&](int r) { plant_check_sensor_row("bpmpc_plant_set_sensor_params", rows + (size_t)r * kSensorParamStride, r); }, {rows, p->d_srows, p->d_sparams});
+    p->sensors.set("bpmpc_plant_set_sensor_params", p->hs.stream, batch, mask, p->d_mask, rows, n_rows, inputs_on_device,
+                   [](const double* row, int r) { plant_check_sensor_row("bpmpc_plant_set_sensor_params", row, r); });
     switch_sensors(p);
-    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 
@@ -579,10 +568,9 @@ int bpmpc_plant_seed_sensors(bpmpc_plant* p, int batch, const int* mask, long se
     check_batch(p, batch, "bpmpc_plant_seed_sensors");
     hipStream_t st = p->hs.stream;
     const int* dmask = staged(mask, p->d_mask, (size_t)batch, inputs_on_device, st);
-    launch_plant_seed_sensors(st, batch, dmask, seed, p->d_sparams, p->d_skey, p->d_sticks, p->d_sbias);
+    launch_plant_seed_sensors(st, batch, dmask, seed, p->sensors.d_params, p->d_skey, p->d_sticks, p->d_sbias);
     switch_sensors(p);
-    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host mask
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 
@@ -612,21 +600,17 @@ int bpmpc_plant_sensed_outputs(bpmpc_plant* p, bpmpc_sensor_inputs* o) {
 
 int bpmpc_plant_get_input_params(const bpmpc_plant* p, int robot, double* row) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_get_input_params: null handle or row", row != nullptr, [&] {
-    if (robot >= p->max_batch) throw std::length_error("bpmpc_plant_get_input_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? p->d_irows + (size_t)p->max_batch * kInputParamStride : p->d_iparams + (size_t)robot * kInputParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, kInputParamStride * sizeof(double), hipMemcpyDeviceToHost, p->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(p->hs.stream));
+    p->inputs.get("bpmpc_plant_get_input_params", p->hs.stream, p->max_batch, robot, row);
   });
 }
 
 int bpmpc_plant_set_input_params(bpmpc_plant* p, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(p, BPMPC_ERR_IO, "bpmpc_plant_set_input_params: null handle or rows", rows != nullptr, [&] {
     check_batch(p, batch, "bpmpc_plant_set_input_params");
-    set_rows("bpmpc_plant_set_input_params", p->hs.stream, batch, kInputParamStride, kInputParamUsed, mask, p->d_mask, n_rows, inputs_on_device,
-             [&](int r) { plant_check_input_row("bpmpc_plant_set_input_params", rows + (size_t)r * kInputParamStride, r); }, {rows, p->d_irows, p->d_iparams});
+    p->inputs.set("bpmpc_plant_set_input_params", p->hs.stream, batch, mask, p->d_mask, rows, n_rows, inputs_on_device,
+                  [](const double* row, int r) { plant_check_input_row("bpmpc_plant_set_input_params", row, r); });
     switch_inputs(p);
-    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host arrays
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 
@@ -641,8 +625,7 @@ int bpmpc_plant_seed_inputs(bpmpc_plant* p, int batch, const int* mask, long see
     const int* dmask = staged(mask, p->d_mask, (size_t)batch, inputs_on_device, st);
     launch_plant_seed_inputs(st, batch, dmask, seed, p->d_ikey, p->d_iticks);
     switch_inputs(p);
-    if (!inputs_on_device) p->hs.synchronise_own();      // the caller's host mask
-    else p->hs.enqueued_own();
+    p->hs.finish(inputs_on_device);
   });
 }
 

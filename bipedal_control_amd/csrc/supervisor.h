@@ -16,8 +16,7 @@ struct bpmpc_supervisor {
   bpmpc::DeviceBuffers mem;             // every d_* below
   bpmpc::StreamHandshake hs;            // the handle's stream; nothing is launched on a foreign stream: foreign streams wait for ev_done instead
   hipEvent_t ev_in = nullptr, ev_done = nullptr;      // update_controlled / step_supervised: a foreign stream's work, the supervisor's
-  double* d_params = nullptr;           // [max_batch][kSupParamStride]
-  double* d_rows = nullptr;             // [max_batch + 1][kSupParamStride] device copy of host rows; the last row holds `defaults`
+  bpmpc::ParamTable params;             // the robots' parameter rows; the start row is `defaults`
   double* d_joint[5] = {};              // q_init, kp_init, kd_init, lower, upper: [max_batch][nj]
   double* d_joint_defaults = nullptr;   // [5][nj]
   double* d_joint_rows = nullptr;       // [max_batch][nj] device copy of host rows

@@ -79,10 +79,6 @@ void check_period(double period, const char* who) {
   if (!std::isfinite(period) || period <= 0.0) throw std::invalid_argument(std::string(who) + ": period must be finite and positive");
 }
 
-void write_default_params(bpmpc_supervisor* s) {
-  write_rows(s->hs.stream, s->max_batch, kSupParamStride, kSupParamUsed, nullptr, 1, {s->d_rows + (size_t)s->max_batch * kSupParamStride, nullptr, s->d_params});
-}
-
 void request_on_device(bpmpc_supervisor* s, int batch, const int* mask, int target, int only_ready) {
   hipLaunchKernelGGL(k_supervisor_request, dim3((batch + 255) / 256), dim3(256), 0, s->hs.stream, batch, mask, target, only_ready, s->d_state, s->d_cause,
                      s->d_ready, s->d_latch, s->d_elapsed, s->d_settled);
@@ -94,7 +90,7 @@ void launch(bpmpc_supervisor* s, int batch, const double* rbd, const double* con
   SupervisorArgs a{};
   a.batch = batch; a.nj = s->nj; a.cmd_stride = cmd_stride; a.period = period; a.rbd = rbd;
   a.run_pos = run[0]; a.run_vel = run[1]; a.run_tau = run[2]; a.run_kp = run[3]; a.run_kd = run[4];
-  a.params = s->d_params;
+  a.params = s->params.d_params;
   a.q_init = s->d_joint[0]; a.kp_init = s->d_joint[1]; a.kd_init = s->d_joint[2]; a.lower = s->d_joint[3]; a.upper = s->d_joint[4];
   a.state = s->d_state; a.cause = s->d_cause; a.unsafe = s->d_unsafe; a.ready = s->d_ready; a.latch = s->d_latch; a.counts = s->d_counts;
   a.elapsed = s->d_elapsed; a.settled = s->d_settled; a.q_latch = s->d_qlatch;
@@ -103,11 +99,6 @@ void launch(bpmpc_supervisor* s, int batch, const double* rbd, const double* con
   constexpr int RPW = 64 / kSupGroup;
   hipLaunchKernelGGL(k_supervise, dim3((batch + RPW - 1) / RPW), dim3(64), 0, s->hs.stream, a);
   HIP_CHECK(hipGetLastError());
-}
-
-void record(hipEvent_t* ev, hipStream_t on) {
-  if (!*ev) HIP_CHECK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-  HIP_CHECK(hipEventRecord(*ev, on));
 }
 
 // the default joint rows of a model: defaultJointState; the start-up values of InitialJointControllerParams.cfg (kp 80, kd 5, kd 3 for the
@@ -138,7 +129,7 @@ int bpmpc_supervisor_create(const bpmpc_model* model, const char* task_info_path
     s->nj = s->rm.nj; s->nv = 6 + s->nj;
     const size_t B = max_batch, nj = s->nj;
     DeviceBuffers& m = s->mem;
-    s->d_params = m.alloc<double>(B * kSupParamStride); s->d_rows = m.alloc<double>((B + 1) * kSupParamStride);
+    s->params.create(m, max_batch, kSupParamStride, kSupParamUsed, s->defaults);
     s->d_joint_defaults = m.alloc<double>(5 * nj); s->d_joint_rows = m.alloc<double>(B * nj); s->d_mask = m.alloc<int>(B);
     s->d_state = m.alloc<int>(B, true); s->d_cause = m.alloc<int>(B, true); s->d_unsafe = m.alloc<int>(B, true); s->d_ready = m.alloc<int>(B, true);
     s->d_latch = m.alloc<int>(B, true); s->d_counts = m.alloc<int>(kSupCounts, true);
@@ -148,9 +139,8 @@ int bpmpc_supervisor_create(const bpmpc_model* model, const char* task_info_path
     std::vector<double> rows(5 * nj);
     default_joint_rows(s->rm, rows.data());
     HIP_CHECK(hipMemcpy(s->d_joint_defaults, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(s->d_rows + B * kSupParamStride, s->defaults, sizeof(s->defaults), hipMemcpyHostToDevice));
     HIP_CHECK(hipDeviceSynchronize());      // the zero fills run on the null stream
-    write_default_params(s.get());
+    s->params.fill_from_start(s->hs.stream, max_batch);
     for (int k = 0; k < 5; ++k) write_rows(s->hs.stream, max_batch, s->nj, s->nj, nullptr, 1, {s->d_joint_defaults + k * nj, nullptr, s->d_joint[k]});
     request_on_device(s.get(), max_batch, nullptr, kSupInit, 0);      // every robot in INIT, its latch pending
     s->hs.synchronise_own();
@@ -170,26 +160,22 @@ void bpmpc_supervisor_destroy(bpmpc_supervisor* s) {
 
 int bpmpc_supervisor_get_params(const bpmpc_supervisor* s, int robot, double* row) {
   return guarded(s, BPMPC_ERR_IO, "bpmpc_supervisor_get_params: null handle or row", row != nullptr, [&] {
-    if (robot >= s->max_batch) throw std::length_error("bpmpc_supervisor_get_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? s->d_rows + (size_t)s->max_batch * kSupParamStride : s->d_params + (size_t)robot * kSupParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, kSupParamStride * sizeof(double), hipMemcpyDeviceToHost, s->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(s->hs.stream));
+    s->params.get("bpmpc_supervisor_get_params", s->hs.stream, s->max_batch, robot, row);
   });
 }
 
 int bpmpc_supervisor_set_params(bpmpc_supervisor* s, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(s, BPMPC_ERR_IO, "bpmpc_supervisor_set_params: null handle or rows", rows != nullptr, [&] {
     check_batch(s, batch, "bpmpc_supervisor_set_params");
-    set_rows("bpmpc_supervisor_set_params", s->hs.stream, batch, kSupParamStride, kSupParamUsed, mask, s->d_mask, n_rows, inputs_on_device != 0,
-             [&](int r) { check_param_row("bpmpc_supervisor_set_params", rows + (size_t)r * kSupParamStride, r); }, {rows, s->d_rows, s->d_params});
-    if (!inputs_on_device) s->hs.synchronise_own();
-    else s->hs.enqueued_own();
+    s->params.set("bpmpc_supervisor_set_params", s->hs.stream, batch, mask, s->d_mask, rows, n_rows, inputs_on_device != 0,
+                  [](const double* row, int r) { check_param_row("bpmpc_supervisor_set_params", row, r); });
+    s->hs.finish(inputs_on_device != 0);
   });
 }
 
 int bpmpc_supervisor_reset_params(bpmpc_supervisor* s) {
   return guarded(s, BPMPC_ERR_IO, "bpmpc_supervisor_reset_params: null handle", [&] {
-    write_default_params(s);
+    s->params.fill_from_start(s->hs.stream, s->max_batch);
     s->hs.synchronise_own();
   });
 }
@@ -234,8 +220,7 @@ int bpmpc_supervisor_set_joint_rows(bpmpc_supervisor* s, int batch, const int* m
                }
              },
              {rows, s->d_joint_rows, s->d_joint[which]});
-    if (!inputs_on_device) s->hs.synchronise_own();
-    else s->hs.enqueued_own();
+    s->hs.finish(inputs_on_device != 0);
   });
 }
 
@@ -273,8 +258,7 @@ int bpmpc_supervisor_update(bpmpc_supervisor* s, int batch, const double* rbd, c
       for (int k = 0; k < 5; ++k) run[k] = staged(src[k], s->d_run[k], B * nj, dev, st);
     }
     launch(s, batch, staged(rbd, s->d_rbd, B * 2 * s->nv, dev, st), run, s->nj, period);
-    if (dev) s->hs.enqueued_own();       // a plant step on the plant's stream waits for it
-    else s->hs.synchronise_own();        // the caller's host arrays
+    s->hs.finish(dev);      // host arrays are the caller's; a plant step on the plant's stream waits for an update that was only enqueued
   });
 }
 
@@ -296,7 +280,7 @@ int bpmpc_supervisor_update_controlled(bpmpc_supervisor* s, bpmpc_controller* co
       throw std::invalid_argument(std::string(who) + ": batch " + std::to_string(batch) + " differs from the batch of the controller's last tick (" +
                                   std::to_string(cc.last_tick_batch) + ")");
     hipStream_t st = s->hs.stream;
-    record(&s->ev_in, cc.stream);
+    StreamHandshake::record(&s->ev_in, cc.stream);
     HIP_CHECK(hipStreamWaitEvent(st, s->ev_in, 0));
     if (estimator) estimator_before_foreign_read(estimator, batch, st);
     const double* run[5] = {cc.joint_cmd, cc.joint_cmd + s->nj, cc.joint_cmd + 2 * s->nj, cc.kp, cc.kd};

@@ -126,8 +126,7 @@ int bpmpc_telemetry_update(bpmpc_telemetry* tm, int batch, const double* t, cons
     const bool dev = inputs_on_device != 0;
     launch(tm, batch, staged(t, tm->d_t, B, dev, st), staged(x_opt, tm->d_xopt, B * tm->nx, dev, st), staged(rbd, tm->d_rbd, B * 2 * tm->nv, dev, st),
            staged(safe, tm->d_safe, B, dev, st), staged(planned_mode, tm->d_mode, B, dev, st), st);
-    if (dev) tm->hs.enqueued_own();      // the next tick of a controller this handle is attached to waits for it
-    else tm->hs.synchronise_own();       // the caller's host arrays
+    tm->hs.finish(dev);      // host arrays are the caller's; the next tick of a controller this handle is attached to waits for what was only enqueued
   });
 }
 

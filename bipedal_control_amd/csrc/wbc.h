@@ -21,8 +21,7 @@ struct bpmpc_wbc {
   double *d_x = nullptr, *d_u = nullptr, *d_rbd = nullptr, *d_sol = nullptr, *d_debug = nullptr;
   int *d_mode = nullptr, *d_status = nullptr;
   int* d_mask = nullptr;                // [max_batch] device copy of a host mask (restart, set_params)
-  double* d_params = nullptr;           // [max_batch][kWbcParamStride] the robots' parameter rows (kernels/wbc.h WbcSettings), read by k_wbc
-  double* d_rows = nullptr;             // [max_batch + 1][kWbcParamStride] device copy of host rows; the last row holds `defaults`
+  bpmpc::ParamTable params;             // the robots' parameter rows (kernels/wbc.h WbcSettings), read by k_wbc; the start row is `defaults`
 };
 
 static_assert(bpmpc::kWbcParamStride == BPMPC_WBC_PARAM_STRIDE && offsetof(bpmpc::WbcSettings, base_kd) == 8 * BPMPC_WBC_PARAM_BASE_KD &&

@@ -70,12 +70,6 @@ void launch_wbc(const bpmpc_wbc* w, const WbcArgs& a, hipStream_t stream) {
   HIP_CHECK(hipGetLastError());
 }
 
-// every parameter row becomes the task.info values (the last row of d_rows), on the handle's own stream
-void write_default_params(bpmpc_wbc* w) {
-  write_rows(w->hs.stream, w->max_batch, kWbcParamStride, BPMPC_WBC_PARAM_RESERVED, nullptr, 1, {w->d_rows + (size_t)w->max_batch * kWbcParamStride, nullptr, w->d_params});
-  w->hs.synchronise_own();
-}
-
 // A host row before it is accepted: every used entry finite; gains, weights, friction and torque limits not negative
 void check_param_row(const double* row, int r, int nj) {
   static const char* const kNames[] = {"base kp", "base kd", "swing kp", "swing kd", "weight swing leg", "weight base acceleration", "weight contact force",
@@ -98,7 +92,7 @@ void wbc_launch_on(bpmpc_wbc* w, int batch, const double* state_des, const doubl
   w->hs.before_foreign(stream);
   WbcArgs a{};
   a.batch = batch; a.nx = w->rm.nx; a.state_des = state_des; a.input_des = input_des; a.rbd_meas = rbd_meas; a.mode = mode;
-  a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr; a.params = w->d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
+  a.sol = w->d_sol; a.status = w->d_status; a.debug = nullptr; a.params = w->params.d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
   launch_wbc(w, a, stream);
   w->hs.after_foreign(stream);
 }
@@ -130,9 +124,9 @@ int bpmpc_wbc_create(const bpmpc_model* model, const char* task_info_path, int d
     w->d_sol = m.alloc<double>(B * w->n, true);      // lastQpSol_ starts at zero (WeightedWbc.h)
     w->d_debug = m.alloc<double>(B * kWbcDebugStride);
     w->d_mode = m.alloc<int>(B); w->d_status = m.alloc<int>(B); w->d_mask = m.alloc<int>(B);
-    w->d_params = m.alloc<double>(B * kWbcParamStride); w->d_rows = m.alloc<double>((B + 1) * kWbcParamStride);
-    HIP_CHECK(hipMemcpy(w->d_rows + B * kWbcParamStride, &w->defaults, sizeof(WbcSettings), hipMemcpyHostToDevice));
-    write_default_params(w.get());
+    w->params.create(m, max_batch, kWbcParamStride, BPMPC_WBC_PARAM_RESERVED, w->defaults.base_kp);
+    w->params.fill_from_start(w->hs.stream, max_batch);
+    w->hs.synchronise_own();
     return BPMPC_OK;
   });
   if (rc != BPMPC_OK) { bpmpc_wbc_destroy(w.release()); return rc; }
@@ -163,7 +157,7 @@ int bpmpc_wbc_update(bpmpc_wbc* w, int batch, const double* state_desired, const
     WbcArgs a{};
     a.batch = batch; a.nx = w->rm.nx; a.state_des = w->d_x; a.input_des = w->d_u; a.rbd_meas = w->d_rbd; a.mode = w->d_mode;
     a.sol = w->d_sol; a.status = w->d_status; a.debug = debug ? w->d_debug : nullptr;
-    a.params = w->d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
+    a.params = w->params.d_params; a.max_working_set_changes = kWbcMaxWorkingSetChanges;
     launch_wbc(w, a, w->hs.stream);
     HIP_CHECK(hipMemcpyAsync(solution, w->d_sol, B * w->n * sizeof(double), hipMemcpyDeviceToHost, w->hs.stream));
     if (status) HIP_CHECK(hipMemcpyAsync(status, w->d_status, B * sizeof(int), hipMemcpyDeviceToHost, w->hs.stream));
@@ -183,32 +177,30 @@ int bpmpc_wbc_restart(bpmpc_wbc* w, int batch, const int* mask, int inputs_on_de
   return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_restart: null handle or mask", mask != nullptr, [&] {
     if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_restart: batch exceeds max_batch");
     wbc_restart_on(w, batch, staged(mask, w->d_mask, batch, inputs_on_device, w->hs.stream), w->hs.stream);
-    if (!inputs_on_device) w->hs.synchronise_own();
-    else w->hs.enqueued_own();      // only enqueued: the next launch on another stream (a controller tick) waits for it
+    w->hs.finish(inputs_on_device);      // device inputs are only enqueued: the next launch on another stream (a controller tick) waits for it
   });
 }
 
 int bpmpc_wbc_get_params(const bpmpc_wbc* w, int robot, double* row) {
   return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_get_params: null handle or row", row != nullptr, [&] {
-    if (robot >= w->max_batch) throw std::length_error("bpmpc_wbc_get_params: robot exceeds max_batch");
-    const double* src = robot < 0 ? w->d_rows + (size_t)w->max_batch * kWbcParamStride : w->d_params + (size_t)robot * kWbcParamStride;
-    HIP_CHECK(hipMemcpyAsync(row, src, sizeof(WbcSettings), hipMemcpyDeviceToHost, w->hs.stream));
-    HIP_CHECK(hipStreamSynchronize(w->hs.stream));
+    w->params.get("bpmpc_wbc_get_params", w->hs.stream, w->max_batch, robot, row);
   });
 }
 
 int bpmpc_wbc_set_params(bpmpc_wbc* w, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device) {
   return guarded(w, BPMPC_ERR_IO, "bpmpc_wbc_set_params: null handle or rows", rows != nullptr, [&] {
     if (batch < 1 || batch > w->max_batch) throw std::length_error("bpmpc_wbc_set_params: batch exceeds max_batch");
-    set_rows("bpmpc_wbc_set_params", w->hs.stream, batch, kWbcParamStride, BPMPC_WBC_PARAM_RESERVED, mask, w->d_mask, n_rows, inputs_on_device,
-             [&](int r) { check_param_row(rows + (size_t)r * kWbcParamStride, r, w->rm.nj); }, {rows, w->d_rows, w->d_params});
-    if (!inputs_on_device) w->hs.synchronise_own();
-    else w->hs.enqueued_own();      // only enqueued, as bpmpc_wbc_restart
+    w->params.set("bpmpc_wbc_set_params", w->hs.stream, batch, mask, w->d_mask, rows, n_rows, inputs_on_device,
+                  [&](const double* row, int r) { check_param_row(row, r, w->rm.nj); });
+    w->hs.finish(inputs_on_device);      // as bpmpc_wbc_restart
   });
 }
 
 int bpmpc_wbc_reset_params(bpmpc_wbc* w) {
-  return guarded(w, BPMPC_ERR_IO, "null wbc handle", [&] { write_default_params(w); });
+  return guarded(w, BPMPC_ERR_IO, "null wbc handle", [&] {
+    w->params.fill_from_start(w->hs.stream, w->max_batch);
+    w->hs.synchronise_own();
+  });
 }
 
 }  // extern "C"

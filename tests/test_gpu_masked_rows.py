@@ -106,3 +106,85 @@ def test_masked_row_writes_of_the_three_entry_points(robot):
         for case in CASES:
             src = _rows(rng, B, width, used)
             before = _check_write(name, case, used, set_rows, get_rows, before, src)
+
+
+@pytest.mark.parametrize("robot", ["h1", "g1"])
+def test_masked_row_writes_of_the_supervisor_and_plant_tables(robot):
+    """The same statements for the six row tables the test above does not reach: the supervisor's parameter rows and the plant's parameter,
+    sensor, input, joint and body rows.  At 9 robots the 160-wide body rows are 1440 entries, five full workgroups and a partial one; the 64-wide
+    joint rows straddle one workgroup boundary; the 8- and 16-wide rows end inside the first workgroup.  Every row passes the host validation of
+    its table and differs from robot to robot.  A body row has no reserved entries: what reads back as 0.0 are the slots of the bodies the robot
+    does not have (bpmpc_plant_get_body_params), so the body rows are compared with those slots moved behind the others, and a device source holds
+    its NaN there.  Nothing is stepped: that the sensor and input writes switch the plant's models on changes nothing that is read here."""
+    import bipedal_control_amd as bp
+    from bipedal_control_amd import scenarios as sc
+    itf = sc.interface(robot)
+    nj = itf.actuatedDofNum
+    sup = bp.BatchedSupervisor(itf, max_batch=B)
+    plant = bp.BatchedPlant(itf, max_batch=B)
+    rng = np.random.default_rng({"h1": 103, "g1": 123}[robot])
+    Sp, Ip, Jp, Bp = bp.SensorParams, bp.InputParams, bp.JointParams, bp.BodyParams
+    assert (_macro("BPMPC_SUP_PARAM_STRIDE"), _macro("BPMPC_PLANT_PARAM_STRIDE")) == (bp.SupervisorParams.STRIDE, bp.PlantParams.STRIDE)
+    assert [_macro("BPMPC_PLANT_%s_PARAM_STRIDE" % t) for t in ("SENSOR", "INPUT", "JOINT", "BODY")] == [Sp.STRIDE, Ip.STRIDE, Jp.STRIDE, Bp.STRIDE]
+
+    def sensor_rows(n):
+        r = np.zeros((n, Sp.STRIDE))
+        r[:, :11] = rng.uniform(0.0, 1.0, (n, 11))
+        r[:, 11] = rng.integers(0, 9, n)                  # delay_steps
+        return r
+
+    def input_rows(n):
+        r = np.zeros((n, Ip.STRIDE))
+        r[:, :len(Ip.FIELDS)] = rng.uniform(0.0, 1.0, (n, len(Ip.FIELDS)))
+        return r
+
+    def joint_rows(n):
+        def draw():
+            return rng.uniform(0.5, 50.0, nj)
+        rows = []
+        for _ in range(n):
+            x = draw()
+            rows.append(Jp(nj, armature=draw(), damping=draw(), friction_loss=draw(), lower=-x, upper=x).toRow())
+        return np.array(rows)
+
+    # body rows with the slots of the robot's nj + 1 bodies first and the slots of the bodies it does not have behind them
+    order = np.array([e for e in range(Bp.STRIDE) if e % Bp.SLOTS <= nj] + [e for e in range(Bp.STRIDE) if e % Bp.SLOTS > nj])
+    back = np.argsort(order)
+    body_used = (Bp.STRIDE // Bp.SLOTS) * (nj + 1)
+    model_row = Bp.model(itf)
+
+    def body_rows(n):
+        r = np.array([model_row.scaled(s).row for s in rng.uniform(0.5, 2.0, n)])[:, order]
+        assert not r[:, body_used:].any()
+        return r
+
+    held = []                                            # the device rows in the layout of the library: alive until the read that follows their write
+
+    def set_body_rows(rows, mask):
+        if hasattr(rows, "data_ptr"):
+            held[:] = [rows[..., torch.tensor(back, device="cuda")].contiguous()]
+            torch.cuda.synchronize()
+        else:
+            held[:] = [np.ascontiguousarray(rows[..., back])]
+        plant.setBodyParams(held[0], mask=mask)
+
+    def reader(get):
+        return lambda: np.array([get(b) for b in range(B)])
+
+    positive = lambda width, used: lambda n: _rows(rng, n, width, used)      # noqa: E731
+    targets = [("supervisor", len(bp.SupervisorParams.FIELDS), positive(bp.SupervisorParams.STRIDE, len(bp.SupervisorParams.FIELDS)),
+                lambda r, m: sup.setParams(r, mask=m), reader(sup.getParams)),
+               ("plant", len(bp.PlantParams.FIELDS), positive(bp.PlantParams.STRIDE, len(bp.PlantParams.FIELDS)),
+                lambda r, m: plant.setParams(r, mask=m), reader(plant.getParams)),
+               ("sensors", len(Sp.FIELDS), sensor_rows, lambda r, m: plant.setSensorParams(r, mask=m), reader(plant.getSensorParams)),
+               ("inputs", len(Ip.FIELDS), input_rows, lambda r, m: plant.setInputParams(r, mask=m), reader(plant.getInputParams)),
+               ("joints", Jp.STRIDE - 1, joint_rows, lambda r, m: plant.setJointParams(r, mask=m), reader(plant.getJointParams)),
+               ("bodies", body_used, body_rows, set_body_rows, lambda: np.array([plant.getBodyParams(b)[order] for b in range(B)]))]
+    for name, used, draw_rows, set_rows, get_rows in targets:
+        first = draw_rows(B)
+        set_rows(first, None)
+        before = get_rows()
+        assert np.array_equal(before, first), name
+        assert len({before[b].tobytes() for b in range(B)}) == B
+        for case in CASES:
+            before = _check_write(name, case, used, set_rows, get_rows, before, draw_rows(B))
