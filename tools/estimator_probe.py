@@ -9,25 +9,26 @@ tick as a caller sees it - are reported, with a host clock around the same calls
 loaded beside this tree's in the same process) a third fleet ticks through that library in the same alternation: the same-box pair that says
 whether the plain tick moved, `--repeats` medians of each giving the spread of the pair.  The estimator's stream is its own, so k_estimate itself is
 taken from a separate `rocprofv3 --kernel-trace --stats` run of this tool (--profile, a child process, no counters) and set beside k_wbc of the
-same run.  One JSON line per shape on stdout; --out writes them all to a file as well (profiles/estimator_probe.jsonl is where the published one belongs).
+same run.  Every shape runs in a child process of its own under a time limit (--limit seconds), the alternation with the parent's library inside
+that child; the first shape that fails or runs out of time, a failed profiler run included, ends the probe.  One JSON line per shape on stdout;
+--out appends them to a file (profiles/estimator_probe.jsonl is where the published one belongs).
 usage (GPU box, repository root): python tools/estimator_probe.py [--shapes h1:1,h1:256,h1:4096,g1:1024] [--ticks 50] [--profile] [--out FILE]
 """
 import argparse
-import glob
-import json
 import os
-import sqlite3
-import subprocess
 import sys
-import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tools.controller_tick_probe import SHAPES, _setup      # noqa: E402
-from tools.wbc_params_probe import library      # noqa: E402
+from tools import probekit as pk      # noqa: E402
+from tools.probekit import library      # noqa: E402
+
+SHAPES = "h1:1,h1:256,h1:4096,g1:1024"
+RATIO = ("estimate_over_wbc", "k_estimate", "k_wbc")
+KERNELS = ("k_estimate", "k_tick_observe_policy", "k_wbc", "k_tick_commands")
 
 
 def measure(robot, B, ticks, warmup, parent=None, repeats=1):
@@ -36,12 +37,12 @@ def measure(robot, B, ticks, warmup, parent=None, repeats=1):
     import bipedal_control_amd as bp
     from bipedal_control_amd import api
     stream = torch.cuda.Stream()
-    mpc, ctrl, rbd = _setup(robot, B, stream.cuda_stream)
+    mpc, ctrl, rbd = pk.tick_fleet(robot, B, stream.cuda_stream)
     p_stream = p_mpc = p_ctrl = None
     if parent is not None:
         p_stream = torch.cuda.Stream()
         with library(api, parent):
-            p_mpc, p_ctrl, _ = _setup(robot, B, p_stream.cuda_stream)
+            p_mpc, p_ctrl, _ = pk.tick_fleet(robot, B, p_stream.cuda_stream)
     nj = ctrl.nj
     est = bp.BatchedStateEstimate(mpc.interface, kind="kalman", max_batch=B)
     dev = lambda a, dt=torch.float64: torch.tensor(a, dtype=dt, device="cuda")      # noqa: E731
@@ -127,27 +128,6 @@ def ctrl_solution(api, lib, ctrl):
     return api.DeviceArray(C.cast(o.wbc_solution, C.c_void_p).value, (B, ctrl.wbc.numDecisionVars), "<f8").torch().cpu()
 
 
-def kernel_split(robot, B, ticks, timeout):
-    """Per-kernel averages from a separate rocprofv3 --kernel-trace --stats run of this tool (child process)."""
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "run", "--", sys.executable, os.path.abspath(__file__),
-               "--shapes", "%s:%d" % (robot, B), "--ticks", str(ticks), "--warmup", "2"]
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
-        dbs = glob.glob(os.path.join(d, "**", "*.db"), recursive=True)
-        if r.returncode != 0 or not dbs:
-            return {"error": "rocprofv3 exit %d" % r.returncode, "stderr_tail": r.stderr[-400:]}
-        db = sqlite3.connect(dbs[0])
-        rows = db.execute("select name, count(*), avg(duration), min(duration) from kernels group by name").fetchall()
-    split = {}
-    for name, calls, avg, mn in rows:
-        for k in ("k_estimate", "k_tick_observe_policy", "k_wbc", "k_tick_commands"):
-            if k in name:
-                split[k] = dict(calls=int(calls), avg_us=avg / 1e3, min_us=mn / 1e3)
-    if "k_estimate" in split and "k_wbc" in split:
-        split["estimate_over_wbc"] = split["k_estimate"]["avg_us"] / split["k_wbc"]["avg_us"]
-    return split
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default=SHAPES)
@@ -156,30 +136,18 @@ def main():
     ap.add_argument("--repeats", type=int, default=1)
     ap.add_argument("--parent-lib", help="libbpmpc.so built from the parent commit: its plain tick is timed in the same alternation")
     ap.add_argument("--profile", action="store_true")
-    ap.add_argument("--profile-timeout", type=int, default=240)
-    ap.add_argument("--out")
-    args = ap.parse_args()
-    lines = []
-    parent = None
-    if args.parent_lib:
-        import ctypes as C
-        from bipedal_control_amd import abi
-        parent = abi.bind(C.CDLL(os.path.abspath(args.parent_lib)), strict=False)      # the parent exports less than the header declares
-        if hasattr(parent, "bpmpc_estimator_update"):
-            raise SystemExit("--parent-lib already has bpmpc_estimator_update: not the parent commit's library")
-    for shape in args.shapes.split(","):
-        robot, B = shape.split(":")
-        rec = measure(robot, int(B), args.ticks, args.warmup, parent, args.repeats)
-        if args.profile:
-            rec["kernels"] = kernel_split(robot, int(B), min(args.ticks, 20), args.profile_timeout)
-        print(json.dumps(rec), flush=True)
-        lines.append(rec)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            for rec in lines:
-                f.write(json.dumps(rec) + "\n")
+    pk.driver_options(ap, limit=240)
+    a = ap.parse_args()
+    if a.child:      # one shape, in this process
+        parent = None
+        if a.parent_lib:
+            parent = pk.parent_library(a.parent_lib)      # the parent exports less than the header declares
+            if hasattr(parent, "bpmpc_estimator_update"):
+                raise SystemExit("--parent-lib already has bpmpc_estimator_update: not the parent commit's library")
+        robot, B = a.child.split(":")
+        return pk.child_line(a, measure(robot, int(B), a.ticks, a.warmup, parent, a.repeats))
+    return pk.run_jobs(__file__, a.shapes.split(","), pk.forwarded(a), a.limit, a.out, run=pk.run_child_profiled(KERNELS, RATIO))
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())

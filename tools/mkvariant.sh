@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds a variant of libbpmpc.so in which ONE translation unit is compiled with extra flags (or from the working tree as it is) and the
 # others are taken from csrc/build/default:   bash tools/mkvariant.sh <name> <unit, e.g. k_node> ["-DFLAG=1 ..."]
-# -> tools/probes/lib_<name>.bin, cycled through bench lines on one box by tools/ab_libs.sh
+# -> tools/probes/lib_<name>.bin, cycled through bench lines on one box by tools/ab.py --lib <name>=tools/probes/lib_<name>.bin
 set -e
 NAME=$1; UNIT=${2:-k_node}; FLAGS=${3:-}
 ROOT=$(cd $(dirname $0)/.. && pwd)

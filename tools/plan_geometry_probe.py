@@ -15,14 +15,14 @@ Every child runs under a time limit; the first that fails or runs out of time en
 usage (GPU box, repository root): python tools/plan_geometry_probe.py [--batches 1,256,4096] [--calls 200] [--commit ID] [--out FILE]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools import probekit as pk      # noqa: E402
 
 NI = 100
 
@@ -92,36 +92,13 @@ def main():
     ap.add_argument("--batches", default="1,256,4096")
     ap.add_argument("--calls", type=int, default=200)
     ap.add_argument("--runs", type=int, default=10)
-    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
-    ap.add_argument("--limit", type=int, default=240, help="time limit of one child process [s]")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    ap.add_argument("--out")
+    pk.driver_options(ap, limit=240)
     a = ap.parse_args()
     if a.child:      # one measurement, in this process
         B, launches = (int(v) for v in a.child.split(":"))
-        line = measure(B, launches, a.calls, a.runs)
-        if a.commit:
-            line["commit"] = a.commit
-        print(json.dumps(line), flush=True)
-        return 0
+        return pk.child_line(a, measure(B, launches, a.calls, a.runs))
     jobs = ["%s:%d" % (B, launches) for B in a.batches.split(",") for launches in (1, 2)]
-    lines = []
-    for job in jobs:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", job, "--calls", str(a.calls), "--runs", str(a.runs)]
-        cmd += ["--commit", a.commit] if a.commit else []
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        text = (r.stdout.strip().splitlines() or [""])[-1]
-        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
-            print("plan_geometry_probe: %s ended with status %d; stopping" % (job, r.returncode), file=sys.stderr)
-            break
-        print(text, flush=True)
-        lines.append(text)
-    if a.out and lines:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for text in lines:
-                f.write(text + "\n")
-    return 0 if len(lines) == len(jobs) else 1
+    return pk.run_jobs(__file__, jobs, pk.forwarded(a), a.limit, a.out)
 
 
 if __name__ == "__main__":

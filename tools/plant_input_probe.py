@@ -18,9 +18,7 @@ Every measurement runs in a child process of its own under a time limit; the fir
 usage (GPU box, repository root): python tools/plant_input_probe.py [--shapes h1:1,h1:256,h1:4096] [--parent-lib FILE] [--commit ID] [--out FILE]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
@@ -28,49 +26,28 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tools.plant_sensor_probe import IMU_GRADE, _standing  # noqa: E402
+from tools import probekit as pk      # noqa: E402
+from tools.probekit import IMU_GRADE      # noqa: E402
 
 SHAPES = "h1:1,h1:256,h1:4096"
 INPUTS = dict(delay=0.009, dropout=0.05, push_force=50.0, push_interval=1.0, push_duration=0.1)
 
 
 def measure(robot, B, variant, parent_lib, samples, warmup, block, substeps, period):
-    import ctypes as C
     import numpy as np
     import torch
     import bipedal_control_amd as bp
-    from bipedal_control_amd import abi, api
     if variant == "parent":
-        api._LIB = abi.bind(C.CDLL(os.path.abspath(parent_lib)), strict=False)      # an earlier commit's library: what it lacks is skipped
-    itf, rbd, cmd = _standing(robot, B)
+        pk.use_parent_library(parent_lib)
+    itf, plant, r_dev, cmd = pk.standing_plant(robot, B)
     nj = itf.actuatedDofNum
-    plant = bp.BatchedPlant(itf, max_batch=B)
-    dev = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda")      # noqa: E731
-    r_dev, cmd = dev(rbd), [dev(a) for a in cmd]
-    torch.cuda.synchronize()
-    plant.set_state(r_dev)
-
-    def stats(prefix, us):
-        p05, p95 = (float(x) for x in np.percentile(us, [5, 95]))
-        return {prefix + "_us_median": float(np.median(us)), prefix + "_us_min": float(np.min(us)), prefix + "_us_p05": p05, prefix + "_us_p95": p95}
 
     def steps():
-        out = []
-        for k in range(warmup + samples):
-            plant.set_state(r_dev)
-            plant.get_state(1)
-            t0 = time.perf_counter()
-            for _ in range(block):
-                plant.step(*cmd, period=period, substeps=substeps)
-            plant.get_state(1)
-            dt = time.perf_counter() - t0
-            if k >= warmup:
-                out.append(1e6 * dt / block)
-        return np.array(out)
+        return pk.steps(plant, r_dev, cmd, samples, warmup, block, substeps, period)
 
     line = dict(probe="plant_input", robot=robot, batch=B, variant=variant, samples=samples, block=block, substeps=substeps, period=period,
-                clock="host clock around a drained block of enqueued steps, per step")
-    line.update(stats("step", steps()))
+                clock=pk.STEPS_CLOCK)
+    line.update(pk.host_stats("step", steps(), "us"))
     if variant == "switched":
         plant.setInputParams(bp.InputParams(**INPUTS).toRow())
         plant.seedInputs(1)
@@ -95,9 +72,9 @@ def measure(robot, B, variant, parent_lib, samples, warmup, block, substeps, per
             if k >= warmup:
                 copies.append(1e6 * dt / block)
         base = line["step_us_median"]
-        line.update(stats("step_inputs", with_inputs))
-        line.update(stats("step_sensors", with_sensors))
-        line.update(stats("copy", np.array(copies)))
+        line.update(pk.host_stats("step_inputs", with_inputs, "us"))
+        line.update(pk.host_stats("step_sensors", with_sensors, "us"))
+        line.update(pk.host_stats("copy", np.array(copies), "us"))
         line.update(inputs=INPUTS, sensors=IMU_GRADE, input_ticks=int(state["tick"][0]), input_delay_steps=int(state["delay_steps"][0]),
                     input_extra_us=float(np.median(with_inputs) - base), sensor_extra_us=float(np.median(with_sensors) - base),
                     bytes_moved=int(bytes_moved), copy_bytes_each_way=int(8 * words))
@@ -115,38 +92,14 @@ def main():
     ap.add_argument("--period", type=float, default=0.002)
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--parent-lib", help="libbpmpc.so built from the parent commit: timed beside this one on an untouched handle")
-    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
-    ap.add_argument("--limit", type=int, default=120, help="time limit of one child process [s]")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    ap.add_argument("--out")
+    pk.driver_options(ap, limit=120)
     a = ap.parse_args()
     if a.child:      # one measurement, in this process
         what, robot, B = a.child.split(":")
-        line = measure(robot, int(B), what, a.parent_lib, a.samples, a.warmup, a.block, a.substeps, a.period)
-        if a.commit:
-            line["commit"] = a.commit
-        print(json.dumps(line), flush=True)
-        return 0
+        return pk.child_line(a, measure(robot, int(B), what, a.parent_lib, a.samples, a.warmup, a.block, a.substeps, a.period))
     variants = (["parent"] if a.parent_lib else []) + ["untouched", "switched"]
     jobs = ["%s:%s" % (v, shape) for shape in a.shapes.split(",") for _ in range(a.repeats) for v in variants]
-    lines = []
-    for job in jobs:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", job, "--samples", str(a.samples), "--warmup", str(a.warmup),
-               "--block", str(a.block), "--substeps", str(a.substeps), "--period", repr(a.period)]
-        cmd += (["--parent-lib", a.parent_lib] if a.parent_lib else []) + (["--commit", a.commit] if a.commit else [])
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
-            print("plant_input_probe: %s ended with status %d; stopping" % (job, r.returncode), file=sys.stderr)
-            break
-        text = r.stdout.strip().splitlines()[-1]
-        print(text, flush=True)
-        lines.append(text)
-    if a.out and lines:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for text in lines:
-                f.write(text + "\n")
-    return 0 if len(lines) == len(jobs) else 1
+    return pk.run_jobs(__file__, jobs, pk.forwarded(a), a.limit, a.out)
 
 
 if __name__ == "__main__":

@@ -18,9 +18,7 @@ the first shape that fails or runs out of time ends the probe.
 usage (GPU box, repository root): python tools/plant_probe.py [--shapes h1:1,h1:256,h1:4096] [--ticks 200] [--substeps 4] [--kt K] [--commit ID] [--out FILE]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
@@ -28,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from tools.controller_tick_probe import _setup      # noqa: E402
+from tools import probekit as pk      # noqa: E402
 
 SHAPES = "h1:1,h1:256,h1:4096"
 
@@ -38,7 +36,7 @@ def measure(robot, B, ticks, warmup, substeps, period, kt=None):
     import torch
     import bipedal_control_amd as bp
     stream = torch.cuda.Stream()
-    mpc, ctrl, rbd = _setup(robot, B, stream.cuda_stream)
+    mpc, ctrl, rbd = pk.tick_fleet(robot, B, stream.cuda_stream)
     nj = ctrl.nj
     ctrl.setJointGains(np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KP), np.full(nj, bp.WbcParams.RECONFIGURE_MOTOR_KD))
     rbd[:, 5] -= 0.0025                                    # the soles a little in the ground: every contact closed
@@ -85,9 +83,7 @@ def measure(robot, B, ticks, warmup, substeps, period, kt=None):
         line["kt"] = float(plant.getStiction(0))
         line["anchored"] = int(plant.anchors()[1].sum())
     for name, _ in variants:
-        line[name + "_host_ms_median"] = float(np.median(times[name]))
-        line[name + "_host_ms_min"] = float(np.min(times[name]))
-        line[name + "_host_ms_p05"], line[name + "_host_ms_p95"] = (float(x) for x in np.percentile(times[name], [5, 95]))
+        line.update(pk.host_stats(name + "_host", times[name], "ms"))
     return line
 
 
@@ -99,35 +95,12 @@ def main():
     ap.add_argument("--substeps", type=int, default=4)
     ap.add_argument("--period", type=float, default=0.002)
     ap.add_argument("--kt", help="tangential stiffness of every robot [N/m], or kn")
-    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
-    ap.add_argument("--limit", type=int, default=240, help="time limit of one shape's child process [s]")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    ap.add_argument("--out")
+    pk.driver_options(ap, limit=240)
     a = ap.parse_args()
     if a.child:      # one shape, in this process
         robot, B = a.child.split(":")
-        line = measure(robot, int(B), a.ticks, a.warmup, a.substeps, a.period, a.kt)
-        if a.commit:
-            line["commit"] = a.commit
-        print(json.dumps(line), flush=True)
-        return 0
-    lines = []
-    for shape in a.shapes.split(","):
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", shape, "--ticks", str(a.ticks), "--warmup", str(a.warmup),
-               "--substeps", str(a.substeps), "--period", repr(a.period)] + (["--kt", a.kt] if a.kt else []) + (["--commit", a.commit] if a.commit else [])
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
-            print("plant_probe: shape %s ended with status %d; stopping" % (shape, r.returncode), file=sys.stderr)
-            break
-        text = r.stdout.strip().splitlines()[-1]
-        print(text, flush=True)
-        lines.append(text)
-    if a.out and lines:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for text in lines:
-                f.write(text + "\n")
-    return 0 if len(lines) == len(a.shapes.split(",")) else 1
+        return pk.child_line(a, measure(robot, int(B), a.ticks, a.warmup, a.substeps, a.period, a.kt))
+    return pk.run_jobs(__file__, a.shapes.split(","), pk.forwarded(a), a.limit, a.out)
 
 
 if __name__ == "__main__":

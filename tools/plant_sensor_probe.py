@@ -17,9 +17,7 @@ Every measurement runs in a child process of its own under a time limit; the fir
 usage (GPU box, repository root): python tools/plant_sensor_probe.py [--shapes h1:1,h1:256,h1:4096] [--parent-lib FILE] [--estimate] [--commit ID] [--out FILE]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 import time
 
@@ -27,37 +25,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tools import probekit as pk      # noqa: E402
+from tools.probekit import IMU_GRADE      # noqa: E402
+
 SHAPES = "h1:1,h1:256,h1:4096"
-IMU_GRADE = dict(gyro_noise=2e-3, accel_noise=2e-2, joint_pos_noise=1e-4, delay_steps=1.0)
-
-
-def _standing(robot, B):
-    """(interface, rbd [B, 2 nv] at rest at the planned configuration with the soles 2.5 mm in the ground, the holding command)"""
-    import numpy as np
-    from bipedal_control_amd import scenarios as sc
-    itf = sc.interface(robot)
-    nj = itf.actuatedDofNum
-    q = sc.perturbed_initial_states(itf, B)[:, 6:]
-    rbd = np.concatenate([q[:, 3:6], q[:, 0:3], q[:, 6:], np.zeros((B, 6 + nj))], axis=1)
-    rbd[:, 5] -= 0.0025
-    cmd = [rbd[:, 6:6 + nj].copy(), np.zeros((B, nj)), np.zeros((B, nj)), np.full((B, nj), 1000.0), np.full((B, nj), 20.0)]
-    return itf, rbd, cmd
 
 
 def measure(robot, B, variant, parent_lib, ticks, warmup, substeps, period):
-    import ctypes as C
     import numpy as np
-    import torch
     import bipedal_control_amd as bp
-    from bipedal_control_amd import abi, api
     if variant == "parent":
-        api._LIB = abi.bind(C.CDLL(os.path.abspath(parent_lib)), strict=False)      # an earlier commit's library: what it lacks is skipped
-    itf, rbd, cmd = _standing(robot, B)
-    plant = bp.BatchedPlant(itf, max_batch=B)
-    dev = lambda a: torch.tensor(a, dtype=torch.float64, device="cuda")      # noqa: E731
-    r_dev, cmd = dev(rbd), [dev(a) for a in cmd]
-    torch.cuda.synchronize()
-    plant.set_state(r_dev)
+        pk.use_parent_library(parent_lib)
+    _, plant, r_dev, cmd = pk.standing_plant(robot, B)
     if variant == "switched":
         plant.setSensorParams(bp.SensorParams(**IMU_GRADE).toRow())
         plant.seedSensors(1)
@@ -71,10 +50,8 @@ def measure(robot, B, variant, parent_lib, ticks, warmup, substeps, period):
         dt = time.perf_counter() - t0
         if k >= warmup:
             times.append(1e3 * dt)
-    p05, p95 = (float(x) for x in np.percentile(times, [5, 95]))
     line = dict(probe="timing", robot=robot, batch=B, variant=variant, ticks=ticks, substeps=substeps, period=period,
-                state_finite=bool(np.isfinite(plant.get_state()).all()), step_host_ms_median=float(np.median(times)), step_host_ms_min=float(np.min(times)),
-                step_host_ms_p05=p05, step_host_ms_p95=p95)
+                state_finite=bool(np.isfinite(plant.get_state()).all()), **pk.host_stats("step_host", times, "ms"))
     if variant == "switched":
         line["sensor_ticks"] = int(plant.sensorState()["tick"][0])
     return line
@@ -83,7 +60,7 @@ def measure(robot, B, variant, parent_lib, ticks, warmup, substeps, period):
 def estimate(robot, B, noisy, seconds, substeps, period):
     import numpy as np
     import bipedal_control_amd as bp
-    itf, rbd, cmd = _standing(robot, B)
+    itf, rbd, cmd = pk.standing(robot, B)
     nv = 6 + itf.actuatedDofNum
     plant = bp.BatchedPlant(itf, max_batch=B)
     est = bp.BatchedStateEstimate(itf, kind="kalman", max_batch=B)
@@ -118,44 +95,19 @@ def main():
     ap.add_argument("--parent-lib", help="libbpmpc.so built from the parent commit: timed beside this one on an untouched handle")
     ap.add_argument("--estimate", action="store_true", help="the Kalman estimate's error with and without noise instead of the timing")
     ap.add_argument("--seconds", type=float, default=1.0)
-    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
-    ap.add_argument("--limit", type=int, default=180, help="time limit of one child process [s]")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    ap.add_argument("--out")
+    pk.driver_options(ap, limit=180)
     a = ap.parse_args()
     if a.child:      # one measurement, in this process
         what, robot, B = a.child.split(":")
         if what in ("clean", "noisy"):
-            line = estimate(robot, int(B), what == "noisy", a.seconds, a.substeps, a.period)
-        else:
-            line = measure(robot, int(B), what, a.parent_lib, a.ticks, a.warmup, a.substeps, a.period)
-        if a.commit:
-            line["commit"] = a.commit
-        print(json.dumps(line), flush=True)
-        return 0
+            return pk.child_line(a, estimate(robot, int(B), what == "noisy", a.seconds, a.substeps, a.period))
+        return pk.child_line(a, measure(robot, int(B), what, a.parent_lib, a.ticks, a.warmup, a.substeps, a.period))
     if a.estimate:
         jobs = ["clean:h1:8", "noisy:h1:8"]
     else:
         variants = (["parent"] if a.parent_lib else []) + ["untouched", "switched"]
         jobs = ["%s:%s" % (v, shape) for shape in a.shapes.split(",") for _ in range(a.repeats) for v in variants]
-    lines = []
-    for job in jobs:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", job, "--ticks", str(a.ticks), "--warmup", str(a.warmup),
-               "--substeps", str(a.substeps), "--period", repr(a.period), "--seconds", repr(a.seconds)]
-        cmd += (["--parent-lib", a.parent_lib] if a.parent_lib else []) + (["--commit", a.commit] if a.commit else [])
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
-            print("plant_sensor_probe: %s ended with status %d; stopping" % (job, r.returncode), file=sys.stderr)
-            break
-        text = r.stdout.strip().splitlines()[-1]
-        print(text, flush=True)
-        lines.append(text)
-    if a.out and lines:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for text in lines:
-                f.write(text + "\n")
-    return 0 if len(lines) == len(jobs) else 1
+    return pk.run_jobs(__file__, jobs, pk.forwarded(a), a.limit, a.out)
 
 
 if __name__ == "__main__":

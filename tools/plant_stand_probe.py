@@ -22,12 +22,13 @@ usage (GPU box, repository root): python tools/plant_stand_probe.py [--seconds 2
 import argparse
 import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+from tools import probekit as pk      # noqa: E402
 
 PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
 
@@ -171,43 +172,18 @@ def main():
     ap.add_argument("--cmd-delay", type=float, default=0.0, metavar="SECONDS", help="command latency of the plant's input model on every robot (0: none)")
     ap.add_argument("--joint-preset", choices=["none", "mjcf"], default="none", help="joint rows of every robot: ideal joints, or the reference's MJCF defaults")
     ap.add_argument("--joint-limits", choices=["none", "urdf"], default="none", help="end stops: none, or the model's <limit> tags")
-    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
-    ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    ap.add_argument("--out")
+    pk.driver_options(ap, limit=300)
     a = ap.parse_args()
-    if a.child is not None:
+    if a.child is not None:      # one run, in this process
         record, line = run(a.child, a.batch, a.seconds, a.telemetry, a.telemetry_every, a.cmd_delay, a.joint_preset, a.joint_limits)
-        if a.commit:
-            line["commit"] = a.commit
         if record is not None:
             if a.commit:
                 record["commit"] = a.commit
             os.makedirs(os.path.dirname(os.path.abspath(a.telemetry_out)), exist_ok=True)
             with open(a.telemetry_out, "a") as f:
                 f.write(json.dumps(record) + "\n")
-        print(json.dumps(line), flush=True)
-        return 0
-    lines = []
-    kts = a.kts.split(",")
-    for kt in kts:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", kt, "--seconds", repr(a.seconds), "--batch", str(a.batch), "--cmd-delay", repr(a.cmd_delay),
-               "--joint-preset", a.joint_preset, "--joint-limits", a.joint_limits]
-        if a.telemetry is not None:
-            cmd += ["--telemetry", str(a.telemetry), "--telemetry-every", str(a.telemetry_every), "--telemetry-out", a.telemetry_out]
-        r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
-            print("plant_stand_probe: kt = %s ended with status %d; stopping" % (kt, r.returncode), file=sys.stderr)
-            break
-        text = r.stdout.strip().splitlines()[-1]
-        print(text, flush=True)
-        lines.append(text)
-    if a.out and lines:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for text in lines:
-                f.write(text + "\n")
-    return 0 if len(lines) == len(kts) else 1
+        return pk.child_line(a, line)
+    return pk.run_jobs(__file__, a.kts.split(","), pk.forwarded(a), a.limit, a.out)
 
 
 if __name__ == "__main__":

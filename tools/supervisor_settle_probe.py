@@ -19,18 +19,18 @@ stdout; --out appends them to a file (profiles/supervisor_settle_probe.jsonl is 
 usage (GPU box, repository root): python tools/supervisor_settle_probe.py [--seconds 2.0] [--batch 8] [--kt kn] [--joint-preset {none,mjcf}] [--joint-limits {none,urdf}] [--variants LIST] [--commit ID] [--out FILE]
 """
 import argparse
-import json
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-PERIOD, SUBSTEPS, REARM, NI = 0.002, 4, 10, 20
+from tools import probekit as pk      # noqa: E402
+from tools.probekit import PERIOD, POS_TOL, RAMP_TIME, SETTLE_TIME, SUBSTEPS, VEL_TOL  # noqa: E402
+
+REARM, NI = 10, 20
 GAINS = {"reference": None, "holding": (2000.0, 40.0)}
-RAMP_TIME, POS_TOL, VEL_TOL, SETTLE_TIME = 0.1, 0.05, 0.5, 0.2
 
 
 def settled(gains, kt, B, seconds, settle_seconds, joint_preset="none", joint_limits="none"):
@@ -154,40 +154,17 @@ def main():
     ap.add_argument("--joint-preset", choices=["none", "mjcf"], default="none", help="joint rows of every robot: ideal joints, or the reference's MJCF defaults")
     ap.add_argument("--joint-limits", choices=["none", "urdf"], default="none", help="end stops: none, or the model's <limit> tags")
     ap.add_argument("--variants", default=",".join(["plain"] + list(GAINS)), help="which runs: plain, reference, holding")
-    ap.add_argument("--commit", help="the commit the library was built from, recorded in every line")
-    ap.add_argument("--limit", type=int, default=300, help="time limit of one run's child process [s]")
-    ap.add_argument("--child", help=argparse.SUPPRESS)
-    ap.add_argument("--out")
+    pk.driver_options(ap, limit=300)
     a = ap.parse_args()
-    if a.child is not None:
+    if a.child is not None:      # one run, in this process
         if a.child == "plain":
             from tools.plant_stand_probe import run
             _, line = run(a.kt, a.batch, a.seconds, joint_preset=a.joint_preset, joint_limits=a.joint_limits)
             line["variant"] = "plain"
         else:
             line = settled(a.child, a.kt, a.batch, a.seconds, a.settle_seconds, a.joint_preset, a.joint_limits)
-        if a.commit:
-            line["commit"] = a.commit
-        print(json.dumps(line), flush=True)
-        return 0
-    jobs = a.variants.split(",")
-    lines = []
-    for job in jobs:
-        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--child", job, "--seconds", repr(a.seconds), "--settle-seconds",
-               repr(a.settle_seconds), "--batch", str(a.batch), "--kt", a.kt, "--joint-preset", a.joint_preset, "--joint-limits", a.joint_limits]
-        r = subprocess.run(cmd + (["--commit", a.commit] if a.commit else []), stdout=subprocess.PIPE, text=True)
-        if r.returncode != 0:      # a fault, an abort or the time limit: nothing more is started on the GPU
-            print("supervisor_settle_probe: %s ended with status %d; stopping" % (job, r.returncode), file=sys.stderr)
-            break
-        text = r.stdout.strip().splitlines()[-1]
-        print(text, flush=True)
-        lines.append(text)
-    if a.out and lines:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            for text in lines:
-                f.write(text + "\n")
-    return 0 if len(lines) == len(jobs) else 1
+        return pk.child_line(a, line)
+    return pk.run_jobs(__file__, a.variants.split(","), pk.forwarded(a), a.limit, a.out)
 
 
 if __name__ == "__main__":

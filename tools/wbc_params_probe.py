@@ -20,41 +20,19 @@ usage (GPU box, repository root): python tools/wbc_params_probe.py --parent-lib 
 """
 import argparse
 import ctypes as C
-import faulthandler
 import gc
 import json
 import os
 import sys
 import time
-from contextlib import contextmanager
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+from tools.probekit import library, step      # noqa: E402
+
 NI = 40
-
-
-@contextmanager
-def step(name, seconds):
-    """a step under its own time limit: past it the traceback of every thread is dumped and the process ends"""
-    print("# step %s (limit %d s)" % (name, seconds), file=sys.stderr, flush=True)
-    faulthandler.dump_traceback_later(seconds, exit=True)
-    try:
-        yield
-    finally:
-        faulthandler.cancel_dump_traceback_later()
-
-
-@contextmanager
-def library(api, lib):
-    """the Python mirror calls `lib` (a ctypes library with the C ABI) inside: a handle is created, used and destroyed by one library only"""
-    mine = api._LIB
-    api._LIB = lib
-    try:
-        yield
-    finally:
-        api._LIB = mine
 
 
 def fleet(B, stream, lib):
