@@ -296,7 +296,8 @@ class BipedalRobotInterface(_Handle):
     def sqpSettings(self):
         v = self.get("sqp")
         return dict(dt=v[0], sqpIteration=int(v[1]), deltaTol=v[2], g_max=v[3], g_min=v[4], useFeedbackPolicy=bool(v[5]),
-                    projectStateInputEqualityConstraints=bool(v[6]), integratorType="RK2")
+                    projectStateInputEqualityConstraints=bool(v[6]), integratorType="RK2",
+                    alpha_decay=v[8], alpha_min=v[9], gamma_c=v[10], armijoFactor=v[11], costTol=v[12])
 
     _IPM_FIELDS = ("dt", "ipmIteration", "deltaTol", "g_max", "g_min", "computeLagrangeMultipliers", "useFeedbackPolicy", "initialBarrierParameter",
                    "targetBarrierParameter", "barrierLinearDecreaseFactor", "barrierSuperlinearDecreasePower", "barrierReductionCostTol",

@@ -461,7 +461,8 @@ int bpmpc_model_get(const bpmpc_model* m, const char* name, double* out, int cap
     if (n == "swing") return list({r.swing.lift_off_velocity, r.swing.touch_down_velocity, r.swing.swing_height, r.swing.swing_time_scale});
     if (n == "rollout") return list({r.rollout.abs_tol, r.rollout.rel_tol, r.rollout.time_step, (double)r.rollout.max_steps_per_second, r.mrt_frequency, r.mpc_frequency});
     if (n == "sqp") return list({r.sqp.dt, (double)r.sqp.sqp_iteration, r.sqp.delta_tol, r.sqp.g_max, r.sqp.g_min, (double)r.sqp.use_feedback_policy,
-                                 1.0 /* projectStateInputEqualityConstraints */, 0.0 /* integratorType: 0 = RK2 */});
+                                 1.0 /* projectStateInputEqualityConstraints */, 0.0 /* integratorType: 0 = RK2 */,
+                                 r.sqp.alpha_decay, r.sqp.alpha_min, r.sqp.gamma_c, r.sqp.armijo_factor, r.sqp.cost_tol});
     // settings blocks the reference loads beside sqp (BipedalRobotInterface.cpp:98-100); field order documented in include/bpmpc.h
     if (n == "ipm") {
       const IpmConfig& p = r.ipm;

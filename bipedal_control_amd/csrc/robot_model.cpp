@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <map>
 #include <set>
 #include <stdexcept>
@@ -212,6 +213,30 @@ RobotModel load_robot_model(const std::string& urdf_path, const std::string& tas
   task->get("sqp.deltaTol", &m.sqp.delta_tol);
   task->get("sqp.g_max", &m.sqp.g_max);
   task->get("sqp.g_min", &m.sqp.g_min);
+  {
+    // the filter line search's own keys ([OCS2-upstream] sqp::loadSettings); optional, the defaults of SqpConfig are upstream's.  Values for
+    // which the back-tracking sequence 1, alpha_decay, alpha_decay^2, .. >= alpha_min does not end (or an acceptance test loses its meaning) are refused
+    SqpConfig& q = m.sqp;
+    task->get("sqp.alpha_decay", &q.alpha_decay);
+    task->get("sqp.alpha_min", &q.alpha_min);
+    task->get("sqp.gamma_c", &q.gamma_c);
+    task->get("sqp.armijoFactor", &q.armijo_factor);
+    task->get("sqp.costTol", &q.cost_tol);
+    auto num = [](double v) { char t[32]; std::snprintf(t, sizeof t, "%g", v); return std::string(t); };
+    auto refuse = [&](const char* key, double v, const char* range) {
+      throw Unsupported("task.info: sqp." + std::string(key) + " " + num(v) + " is outside " + range);
+    };
+    if (!(q.alpha_decay > 0.0 && q.alpha_decay < 1.0)) refuse("alpha_decay", q.alpha_decay, "(0, 1)");
+    if (!(q.alpha_min > 0.0 && q.alpha_min <= 1.0)) refuse("alpha_min", q.alpha_min, "(0, 1]");
+    if (!(q.gamma_c >= 0.0 && q.gamma_c <= 1.0)) refuse("gamma_c", q.gamma_c, "[0, 1]");
+    if (!(q.armijo_factor >= 0.0 && q.armijo_factor < 1.0)) refuse("armijoFactor", q.armijo_factor, "[0, 1)");
+    if (!(q.cost_tol >= 0.0)) refuse("costTol", q.cost_tol, "[0, inf)");
+    int trials = 0;
+    for (double a = 1.0; a >= q.alpha_min && trials <= kMaxLineSearchTrials; a *= q.alpha_decay) ++trials;
+    if (trials > kMaxLineSearchTrials)
+      throw Unsupported("task.info: sqp.alpha_decay " + num(q.alpha_decay) + " with sqp.alpha_min " + num(q.alpha_min) +
+                        " asks for more than " + std::to_string(kMaxLineSearchTrials) + " line-search trials");
+  }
   {
     // what the reference hands to SqpMpc as sqp::Settings (BipedalController.cpp:303-306, BipedalRobotInterface.cpp:99) and this engine
     // does not implement is refused, not ignored: a drop-in must not run a different optimiser silently

@@ -33,8 +33,9 @@ struct SqpConfig { double dt = 0.015; int sqp_iteration = 1; double delta_tol = 
                    // projectStateInputEqualityConstraints true only and refuses anything else; both values of useFeedbackPolicy
                    // (LinearController / FeedforwardController of the solution, of the warm start and of the policy rollout)
                    int use_feedback_policy = 1;
-                   // [OCS2-upstream] sqp::Settings defaults not present in task.info
+                   // [OCS2-upstream] sqp::Settings defaults; task.info may set them (sqp.alpha_decay, alpha_min, gamma_c, armijoFactor, costTol)
                    double alpha_decay = 0.5, alpha_min = 1e-4, gamma_c = 1e-6, armijo_factor = 1e-4, cost_tol = 1e-4; };
+constexpr int kMaxLineSearchTrials = 64;   // a task.info whose alpha_decay / alpha_min ask for more back-tracking trials is refused at load
 
 // rollout block of task.info (TimeTriggeredRollout, ODE45)
 struct RolloutConfig { double abs_tol = 1e-5, rel_tol = 1e-3, time_step = 0.015; int max_steps_per_second = 10000; };

@@ -62,7 +62,10 @@ int bpmpc_model_dims(const bpmpc_model* model, int* nx, int* nu, int* n_contacts
  * "contact_body", "contact_offset", "cone" (mu, regularization, gripper force, hessian shift, barrier mu, barrier delta),
  * "swing" (liftOffVelocity, touchDownVelocity, swingHeight, swingTimeScale), "sqp" (dt, sqpIteration, deltaTol, g_max, g_min,
  * useFeedbackPolicy, projectStateInputEqualityConstraints (always 1), integratorType (always 0 = RK2): bpmpc_model_create returns
- * BPMPC_ERR_UNSUPPORTED with the key in bpmpc_last_error() for a task.info that sets the latter two otherwise),
+ * BPMPC_ERR_UNSUPPORTED with the key in bpmpc_last_error() for a task.info that sets the latter two otherwise; then the filter line
+ * search's alpha_decay, alpha_min, gamma_c, armijoFactor, costTol (optional keys, upstream's defaults 0.5, 1e-4, 1e-6, 1e-4, 1e-4; refused
+ * with BPMPC_ERR_UNSUPPORTED: alpha_decay outside (0, 1), alpha_min outside (0, 1], gamma_c outside [0, 1], armijoFactor outside [0, 1),
+ * a negative costTol, and any pair for which 1, alpha_decay, alpha_decay^2, .. >= alpha_min has more than 64 terms)),
  * "time_horizon", "position_error_gain", "phase_transition_stance_time", "hard_cone" (flag, sqp.inequalityConstraintMu, Delta),
  * "rollout" (AbsTolODE, RelTolODE, timeStep, maxNumStepsPerSecond, mrt frequency, mpc frequency).
  * The other two solver-settings blocks the reference loads beside `sqp` (src/BipedalRobotInterface.cpp:98-100; accessors ddpSettings(),

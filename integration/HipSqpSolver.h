@@ -69,8 +69,8 @@ class HipSqpSolver final : public SolverBase {
     }
     check(bpmpc_model_dims(model_, &nx_, &nu_, nullptr, nullptr));
     if (settings_.useFeedbackPolicy < 0) {       // the file's sqp block decides (integratorType / projectStateInputEqualityConstraints the engine
-      double sqp[8] = {0}, ddp[20] = {0};        // does not implement were refused by bpmpc_model_create above: BPMPC_ERR_UNSUPPORTED)
-      check(bpmpc_model_get(model_, "sqp", sqp, 8) >= 6 ? BPMPC_OK : BPMPC_ERR_IO);
+      double sqp[13] = {0}, ddp[20] = {0};       // does not implement were refused by bpmpc_model_create above: BPMPC_ERR_UNSUPPORTED)
+      check(bpmpc_model_get(model_, "sqp", sqp, 13) >= 6 ? BPMPC_OK : BPMPC_ERR_IO);   // 13: the block's length since the line-search keys were appended
       check(bpmpc_model_get(model_, "ddp", ddp, 20) >= 13 ? BPMPC_OK : BPMPC_ERR_IO);
       settings_.useFeedbackPolicy = (settings_.solver == BPMPC_SOLVER_DDP ? ddp[12] : sqp[5]) != 0.0 ? 1 : 0;
     }

@@ -389,7 +389,11 @@ def build_model(urdf_path, task_path, reference_path, use_hard_friction_cone=Fal
                         timeStep=float(info_get(task, "rollout.timeStep", 0.015)), maxNumStepsPerSecond=int(info_get(task, "rollout.maxNumStepsPerSecond", 10000)))
     m["sqp"] = dict(dt=float(info_get(task, "sqp.dt")), sqpIteration=int(info_get(task, "sqp.sqpIteration")),
                     deltaTol=float(info_get(task, "sqp.deltaTol")), g_max=float(info_get(task, "sqp.g_max")),
-                    g_min=float(info_get(task, "sqp.g_min")))
+                    g_min=float(info_get(task, "sqp.g_min")),
+                    # [OCS2-upstream] sqp::loadSettings: optional, sqp::Settings defaults
+                    alpha_decay=float(info_get(task, "sqp.alpha_decay", 0.5)), alpha_min=float(info_get(task, "sqp.alpha_min", 1e-4)),
+                    gamma_c=float(info_get(task, "sqp.gamma_c", 1e-6)), armijoFactor=float(info_get(task, "sqp.armijoFactor", 1e-4)),
+                    costTol=float(info_get(task, "sqp.costTol", 1e-4)))
     m["mpc"] = dict(timeHorizon=float(info_get(task, "mpc.timeHorizon")))
     m["initial_mode_schedule"] = (load_std_vector(ref, "initialModeSchedule.eventTimes"),
                                   [MODE_NUMBER[s] for s in load_std_vector(ref, "initialModeSchedule.modeSequence", str)])

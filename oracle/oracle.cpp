@@ -1066,7 +1066,7 @@ int oracle_solve(const oracle_model* om, int N, const int* kind, const double* d
   const int iters = static_cast<int>(opts[0]);
   const double g_max = opts[1], g_min = opts[2], alpha_decay = opts[3], alpha_min = opts[4], gamma_c = opts[5], armijo = opts[6],
                delta_tol = opts[7], reg_prim = opts[8];
-  const double cost_tol = 1e-4;  // [OCS2-upstream] sqp::Settings default costTol
+  const double cost_tol = opts[9];  // [OCS2-upstream] sqp::Settings costTol (default 1e-4)
   Problem pb{N, kind, dt, mode, zref, zdref, xref};
   std::vector<double> x(x_init, x_init + (N + 1) * nx), u(u_init, u_init + N * nu), xn((N + 1) * nx), un(N * nu);
   StepOut so;

@@ -73,7 +73,7 @@ int oracle_lu_projection(int nc, int nx, int nu, const double* C, const double* 
                          int* rank);
 
 /* Full solve.  Node arrays have N entries (intervals); x_init (N+1)*nx, u_init N*nu.
- * opts[9] = {sqp_iterations, g_max, g_min, alpha_decay, alpha_min, gamma_c, armijo_factor, delta_tol}
+ * opts[10] = {sqp_iterations, g_max, g_min, alpha_decay, alpha_min, gamma_c, armijo_factor, delta_tol, reg_prim, cost_tol}
  * Outputs: x_out (N+1)*nx, u_out N*nu, K_out N*nu*nx (nullable), stats[16 * iterations]:
  *   per iteration {merit0, dyn0, eq0, alpha, merit1, dyn1, eq1, armijo_descent, dx_norm, du_norm, n_trials, decision_margin, 0...};
  *   decision_margin: the smallest relative distance |lhs - rhs| / |rhs| of any comparison of the iteration's line search and convergence test

@@ -151,11 +151,11 @@ class OracleModel:
         return dx, du, K
 
     def solve(self, nodes, x0, x_init, u_init, iterations=1, g_max=1e-2, g_min=1e-6, alpha_decay=0.5, alpha_min=1e-4, gamma_c=1e-6,
-              armijo_factor=1e-4, delta_tol=1e-4, reg_prim=0.0):
+              armijo_factor=1e-4, delta_tol=1e-4, reg_prim=0.0, cost_tol=1e-4):
         keep, args = self._node_args(nodes)
         N = int(nodes["N"])
         x0, x_init, u_init = _arr(x0), _arr(x_init), _arr(u_init)
-        opts = np.array([iterations, g_max, g_min, alpha_decay, alpha_min, gamma_c, armijo_factor, delta_tol, reg_prim], float)
+        opts = np.array([iterations, g_max, g_min, alpha_decay, alpha_min, gamma_c, armijo_factor, delta_tol, reg_prim, cost_tol], float)
         xo, uo, K = np.zeros((N + 1, self.nx)), np.zeros((N, self.nu)), np.zeros((N, self.nu, self.nx))
         stats = np.zeros((iterations, 16))
         rc = lib().oracle_solve(self.h, *args, _d(x0), _d(x_init), _d(u_init), _d(opts), _d(xo), _d(uo), _d(K), _d(stats))

@@ -12,7 +12,7 @@ def build(force=False, optimised=False, outdir=None):
     passes a scratch `outdir` so that a benchmark never writes next to the libraries of a test run in progress)."""
     csrc = os.path.join(ROOT, "bipedal_control_amd", "csrc")
     srcs = [os.path.join(HERE, "hostemu.cpp")] + [os.path.join(csrc, f) for f in ("info_tree.cpp", "urdf_tree.cpp", "robot_model.cpp", "device_model.cpp")]
-    newest = max(os.path.getmtime(p) for p in srcs)
+    newest = max(os.path.getmtime(p) for p in srcs + [os.path.join(HERE, "linesearch_emu.h")])
     for root, _, files in os.walk(os.path.join(csrc, "kernels")):
         newest = max([newest] + [os.path.getmtime(os.path.join(root, f)) for f in files])
     lib = LIB.replace(".so", "_native.so") if optimised else LIB

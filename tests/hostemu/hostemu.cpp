@@ -154,3 +154,7 @@ int emu_solve_iteration(void* mv, int N, const int* kind, const double* dt, cons
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// emu_linesearch: the decision code of the filter line search on caller-supplied numbers (shared with the stand-alone driver linesearch_driver.cpp)
+#include "linesearch_emu.h"
