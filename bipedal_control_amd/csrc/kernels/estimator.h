@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../device_model.h"
-#include "wbc.h"   // w_mat3_vec, w_mat3_mul, w_cross, lds_wave_sync, kWave
+#include "wbc.h"   // kinematics.h, lds_wave_sync, kWave
 
 namespace bpmpc {
 
@@ -132,28 +132,20 @@ __device__ __forceinline__ void estimate_robot(const DeviceModel& md, EstLds<NJ>
   if (l < kNumContacts) {
     int f;
     if (a.contact) f = a.contact[(size_t)b * kNumContacts + l] != 0;
-    else {
-      const int mode = a.mode[b];      // modeNumber2StanceLeg, MotionPhaseDefinition.h:57-76; a device value outside 0..3 counts as 0 (include/bpmpc.h)
-      f = (l < 2) ? (mode == 1 || mode == 3) : (mode == 2 || mode == 3);
-    }
+    else f = fused::stance_flag(a.mode[b], l);      // modeNumber2StanceLeg; a device value outside 0..3 counts as 0 (include/bpmpc.h)
     w.flag[l] = f;
   }
   if (l < NJ) {
-    double sg, cg;
+    double sg, cg, E[9];
     sincos(qj, &sg, &cg);
-    const double* ax = md.axis[l + 1];
-    const double vv = 1.0 - cg;
-    const double rot[9] = {cg + vv * ax[0] * ax[0],         vv * ax[0] * ax[1] - sg * ax[2], vv * ax[0] * ax[2] + sg * ax[1],
-                           vv * ax[1] * ax[0] + sg * ax[2], cg + vv * ax[1] * ax[1],         vv * ax[1] * ax[2] - sg * ax[0],
-                           vv * ax[2] * ax[0] - sg * ax[1], vv * ax[2] * ax[1] + sg * ax[0], cg + vv * ax[2] * ax[2]};
-    double E[9];
-    w_mat3_mul(md.Rfix[l + 1], rot, E);
+    fused::joint_rotation(md.Rfix[l + 1], md.axis[l + 1], sg, cg, E);
     for (int i = 0; i < 9; ++i) w.T[l][i] = E[i];
     w.col[0][l] = qdj;                  // the joint rates, read by the contact lanes (col is free until the solve)
   }
   lds_wave_sync();
 
-  const double Rb[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
+  double Rb[9];
+  fused::rot_zyx(sz, cz, sy, cy, sx, cx, Rb);
   // ---- predict: P- = A P A' + Q, x- = A x + B accel
   for (int e = l; e < N * N; e += kWave) {
     const int r = e / N, c = e % N;
@@ -176,7 +168,7 @@ __device__ __forceinline__ void estimate_robot(const DeviceModel& md, EstLds<NJ>
   if (l < N) {
     const double* al = a.acc_local + (size_t)b * 3;
     double acc[3];
-    w_mat3_vec(Rb, al, acc);
+    fused::mat3_vec(Rb, al, acc);
     acc[2] -= kEstGravity;
     double v = w.P[l][N];
     if (l < 3) {
@@ -197,23 +189,24 @@ __device__ __forceinline__ void estimate_robot(const DeviceModel& md, EstLds<NJ>
     for (int d = 0; d < depth; ++d) {
       const int j = md.path[body][d];
       double t[3], t2[3], E[9], ah[3];
-      w_mat3_vec(R, md.pfix[j], t);
-      w_cross(om, t, t2);
-      for (int i = 0; i < 3; ++i) { o[i] += t[i]; vo[i] += t2[i]; }
+      fused::mat3_vec(R, md.pfix[j], t);      // the arm of this step, for the velocity of the joint's origin: om x (R pfix)
+      fused::cross3(om, t, t2);
+      for (int i = 0; i < 3; ++i) vo[i] += t2[i];
       for (int i = 0; i < 9; ++i) E[i] = w.T[j - 1][i];
-      w_mat3_mul(R, E, R);
-      w_mat3_vec(R, md.axis[j], ah);
+      fused::chain_step(R, o, md.pfix[j], E);
+      fused::mat3_vec(R, md.axis[j], ah);
       const double qd = w.col[0][j - 1];
       for (int i = 0; i < 3; ++i) om[i] += ah[i] * qd;
     }
-    double t[3], t2[3];
-    w_mat3_vec(R, md.contact_off[l], t);
-    w_cross(om, t, t2);
+    double t[3], t2[3], pt[3];
+    fused::mat3_vec(R, md.contact_off[l], t);
+    fused::cross3(om, t, t2);
+    fused::point_on_body(R, o, md.contact_off[l], pt);
     const int f = w.flag[l];
     const double scale = f ? 1.0 : 100.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      w.y[3 * l + i] = -(o[i] + t[i]) + (i == 2 ? w.par[0] : 0.0);
+      w.y[3 * l + i] = -pt[i] + (i == 2 ? w.par[0] : 0.0);
       w.y[12 + 3 * l + i] = -(vo[i] + t2[i]);
       w.Rd[3 * l + i] = w.par[4];
       w.Rd[12 + 3 * l + i] = w.par[5] * scale;

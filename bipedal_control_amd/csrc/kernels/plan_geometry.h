@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "../device_model.h"
+#include "kinematics.h"        // the exact:: flavour: the host twin must give the kernels' bits
 #include "riccati_fast.h"      // lds_wave_sync, readlane_f64
 
 namespace bpmpc {
@@ -46,37 +47,18 @@ constexpr int kPsNodes = 0, kPsFootholds = 1, kPsPath = 2, kPsApex = 3, kPsDrift
 
 // ------------------------------------------------------------------------------------------------ the per-item arithmetic, host and device
 
-PG_HD void pg_mat3_mul(const double* A, const double* B, double* C) {      // C = A B, no aliasing
-#pragma clang fp contract(off)
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) C[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-}
-PG_HD void pg_mat3_vec(const double* A, const double* v, double* y) {
-#pragma clang fp contract(off)
-  y[0] = A[0] * v[0] + A[1] * v[1] + A[2] * v[2];
-  y[1] = A[3] * v[0] + A[4] * v[1] + A[5] * v[2];
-  y[2] = A[6] * v[0] + A[7] * v[1] + A[8] * v[2];
-}
-
-// contact_flag of reference_gen.h (points 0, 1: left foot; 2, 3: right foot); the last node's mode -1 has no contact
-PG_HD bool plan_contact_flag(int mode, int i) { return i < 2 ? (mode == 1 || mode == 3) : (mode == 2 || mode == 3); }
+// the contact points of a mode as a bit mask; the last node's mode -1 has no contact
 PG_HD int plan_contact_mask(int mode) {
   int m = 0;
-  for (int i = 0; i < kNumContacts; ++i) m |= plan_contact_flag(mode, i) ? 1 << i : 0;
+  for (int i = 0; i < kNumContacts; ++i) m |= exact::stance_flag(mode, i) ? 1 << i : 0;
   return m;
 }
 
 // E = Rfix[body] E(q): the joint-local rotation of joint `body` (1 .. nj) at the angle q (wbc_py.fk: Rfix_j axis_angle(axis_j, q_j))
 PG_HD void plan_joint_rotation(const DeviceModel& md, int body, double q, double* E) {
-#pragma clang fp contract(off)
-  const double* ax = md.axis[body];
   double sg, cg;
   sincos(q, &sg, &cg);
-  const double vv = 1.0 - cg;
-  const double rot[9] = {cg + vv * ax[0] * ax[0],         vv * ax[0] * ax[1] - sg * ax[2], vv * ax[0] * ax[2] + sg * ax[1],
-                         vv * ax[1] * ax[0] + sg * ax[2], cg + vv * ax[1] * ax[1],         vv * ax[1] * ax[2] - sg * ax[0],
-                         vv * ax[2] * ax[0] - sg * ax[1], vv * ax[2] * ax[1] + sg * ax[0], cg + vv * ax[2] * ax[2]};
-  pg_mat3_mul(md.Rfix[body], rot, E);
+  exact::joint_rotation(md.Rfix[body], md.axis[body], sg, cg, E);
 }
 
 // What the chain walks read of a model, gathered once (per wavefront into LDS; on the host into a local): a walk that fetched path, pfix and
@@ -105,23 +87,14 @@ PG_HD void plan_base_sincos(double angle, double* sc) { sincos(angle, sc, sc + 1
 // joint-local rotations of the configuration, joint j (1 .. nj) at T + 9 (j - 1).  wbc_py.fk / contact_points: o_j = o_parent + R_parent pfix_j,
 // R_j = R_parent Rfix_j E(q_j); point = o_body + R_body contact_off_i
 PG_HD void plan_chain_point(const PlanChains& ch, int i, const double* pos, const double* sc, const double* T, double* pt) {
-#pragma clang fp contract(off)
-  const double sy = sc[0], cy = sc[1], sp = sc[2], cp = sc[3], sr = sc[4], cr = sc[5];
-  double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
-  double o[3] = {pos[0], pos[1], pos[2]};
+  double R[9], o[3] = {pos[0], pos[1], pos[2]};
+  exact::rot_zyx(sc[0], sc[1], sc[2], sc[3], sc[4], sc[5], R);
   const int depth = ch.depth[i];
   for (int d = 0; d < depth; ++d) {
     const int j = ch.path[i][d];
-    double t[3], E[9], Rn[9];
-    pg_mat3_vec(R, ch.pfix[j - 1], t);
-    for (int k = 0; k < 3; ++k) o[k] += t[k];
-    for (int k = 0; k < 9; ++k) E[k] = T[9 * (j - 1) + k];
-    pg_mat3_mul(R, E, Rn);
-    for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+    exact::chain_step(R, o, ch.pfix[j - 1], T + 9 * (j - 1));
   }
-  double t[3];
-  pg_mat3_vec(R, ch.off[i], t);
-  for (int k = 0; k < 3; ++k) pt[k] = o[k] + t[k];
+  exact::point_on_body(R, o, ch.off[i], pt);
 }
 
 // Centre of pressure of four points p [4][3] under the normal forces fz [4]: sum_z = ((fz0 + fz1) + fz2) + fz3; with sum_z > 0

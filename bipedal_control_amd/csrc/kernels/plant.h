@@ -39,7 +39,7 @@
 #include <type_traits>
 
 #include "../device_model.h"
-#include "wbc.h"   // wbc_rbd_pass, wbc_on_chain, wbc_contact_jac_col, w_*, lds_wave_sync, kWave
+#include "wbc.h"   // wbc_rbd_pass, wbc_on_chain, wbc_contact_jac_col, kinematics.h, lds_wave_sync, kWave
 
 namespace bpmpc {
 
@@ -248,12 +248,12 @@ __device__ void plant_robot(const DeviceModel& md, PlantLdsOf<NJ, STICK, JOINT, 
     for (int idx = l; idx < NV * NV; idx += kWave) {
       const int hh = idx / NV, g = idx % NV;
       double val = 0.0;
-      if (wbc_on_chain(md, hh, g)) val = w_dot(r.S[hh], r.fc[g]) + w_dot(r.S[hh] + 3, r.fc[g] + 3);
-      else if (wbc_on_chain(md, g, hh)) val = w_dot(r.S[g], r.fc[hh]) + w_dot(r.S[g] + 3, r.fc[hh] + 3);
+      if (wbc_on_chain(md, hh, g)) val = fused::dot3(r.S[hh], r.fc[g]) + fused::dot3(r.S[hh] + 3, r.fc[g] + 3);
+      else if (wbc_on_chain(md, g, hh)) val = fused::dot3(r.S[g], r.fc[hh]) + fused::dot3(r.S[g] + 3, r.fc[hh] + 3);
       w.A[hh][g] = val;
     }
     double nle = 0.0;
-    if (l < NV) nle = w_dot(r.S[l], r.ws[l]) + w_dot(r.S[l] + 3, r.ws[l] + 3);
+    if (l < NV) nle = fused::dot3(r.S[l], r.ws[l]) + fused::dot3(r.S[l] + 3, r.ws[l] + 3);
 #pragma unroll 1
     for (int idx = l; idx < NC * NV; idx += kWave) {
       const int i = idx / NV, g = idx % NV;
@@ -420,7 +420,8 @@ __device__ void plant_robot(const DeviceModel& md, PlantLdsOf<NJ, STICK, JOINT, 
   // wave-uniform: orientation, Euler rates, angular velocity
   const double z = r.q[3], y = r.q[4], x = r.q[5];
   const double sz = sin(z), cz = cos(z), sy = sin(y), cy = cos(y), sx = sin(x), cx = cos(x);
-  const double Rb[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
+  double Rb[9];
+  fused::rot_zyx(sz, cz, sy, cy, sx, cx, Rb);
   const double r0 = r.v[3], r1 = r.v[4], r2 = r.v[5];
   const double wg[3] = {-sz * r1 + cy * cz * r2, cz * r1 + cy * sz * r2, r0 - sy * r2};      // E(zyx) thetadot
   const double hz = 0.5 * z, hy = 0.5 * y, hx = 0.5 * x;

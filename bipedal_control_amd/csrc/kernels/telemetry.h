@@ -83,12 +83,9 @@ __device__ __forceinline__ void telemetry_robot(const DeviceModel& md, Telemetry
     for (int p = 0; p < 2; ++p) {
       double sg, cg;
       sincos(p == 0 ? qd : qm, &sg, &cg);
-      const double vv = 1.0 - cg;
-      const double rot[9] = {cg + vv * ax[0] * ax[0],         vv * ax[0] * ax[1] - sg * ax[2], vv * ax[0] * ax[2] + sg * ax[1],
-                             vv * ax[1] * ax[0] + sg * ax[2], cg + vv * ax[1] * ax[1],         vv * ax[1] * ax[2] - sg * ax[0],
-                             vv * ax[2] * ax[0] - sg * ax[1], vv * ax[2] * ax[1] + sg * ax[0], cg + vv * ax[2] * ax[2]};
-      double E[9];
-      mat3_mul(md.Rfix[body], rot, E);
+      double rot[9], E[9];
+      exact::axis_angle(ax, sg, cg, rot);             // the literals are rounded product by product, the matrix products below are fused:
+      fused::mat3_mul(md.Rfix[body], rot, E);         // the bits this kernel has always produced ("Kinematic primitives")
       for (int i = 0; i < 9; ++i) w.T[sub][p][body - 1][i] = E[i];
     }
   }
@@ -105,21 +102,17 @@ __device__ __forceinline__ void telemetry_robot(const DeviceModel& md, Telemetry
     sincos(base[3], &sy, &cy);
     sincos(base[4], &sp, &cp);
     sincos(base[5], &sr, &cr);
-    double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
-    double o[3] = {base[0], base[1], base[2]};
+    double R[9], o[3] = {base[0], base[1], base[2]};
+    exact::rot_zyx(sy, cy, sp, cp, sr, cr, R);
     const int body = md.contact_body[i], depth = md.depth[body];
     for (int d = 0; d < depth; ++d) {
       const int j = md.path[body][d];
-      double t[3], E[9], Rn[9];
-      mat3_vec(R, md.pfix[j], t);
-      for (int k = 0; k < 3; ++k) o[k] += t[k];
+      double E[9];
       for (int k = 0; k < 9; ++k) E[k] = w.T[sub][p][j - 1][k];
-      mat3_mul(R, E, Rn);
-      for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+      fused::chain_step(R, o, md.pfix[j], E);
     }
-    double t[3];
-    mat3_vec(R, md.contact_off[i], t);
-    for (int k = 0; k < 3; ++k) { pt[k] = o[k] + t[k]; smp[12 + 3 * g + k] = pt[k]; }
+    fused::point_on_body(R, o, md.contact_off[i], pt);
+    for (int k = 0; k < 3; ++k) smp[12 + 3 * g + k] = pt[k];
   }
 
   // ---- errors.  Lane i < 4: contact i, against the measured point of lane 4 + i; the lane sums of the squared coordinate errors

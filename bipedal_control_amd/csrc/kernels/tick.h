@@ -14,6 +14,7 @@
 // oracle/wbc_py.py measured_state / centroidal_momentum_matrix, oracle/reference_py.py time_segment / primal_solution_arrays /
 // linear_controller_input / mode_at_time.
 #pragma once
+#include "kinematics.h"
 #include "rollout.h"
 
 namespace bpmpc {
@@ -67,10 +68,9 @@ __device__ __forceinline__ void tick_observation(const DeviceModel& md, TickLds<
   if (g < 3) { qg = rb[3 + g]; vg = rb[G + 3 + g]; }
   else if (g < 6) {
     qg = rb[g - 3];
-    // Euler-angle rates from the world angular velocity: E thetadot = omega, E = [e_z, Rz e_y, Rz Ry e_x] (as k_wbc)
-    const double wx = rb[G], wy = rb[G + 1], wz = rb[G + 2];
-    const double rr = (cy * wx + sy * wy) / cp, pr = -sy * wx + cy * wy;
-    vg = g == 3 ? wz + sp * rr : (g == 4 ? pr : rr);
+    double rates[3];
+    fused::euler_rates_from_world_omega(sy, cy, sp, cp, rb + G, rates);
+    vg = g == 3 ? rates[0] : (g == 4 ? rates[1] : rates[2]);
   } else if (g < G) { qg = rb[g]; vg = rb[G + g]; }
   const bool is_joint = g >= 6 && g < G, is_body = g >= 5 && g < G;
   const int body = is_body ? g - 5 : 0;
@@ -78,46 +78,26 @@ __device__ __forceinline__ void tick_observation(const DeviceModel& md, TickLds<
   if (is_joint) {
     double sg, cg;
     sincos(qg, &sg, &cg);
-    const double* ax = md.axis[body];
-    const double vv = 1.0 - cg;
-    const double rot[9] = {cg + vv * ax[0] * ax[0],         vv * ax[0] * ax[1] - sg * ax[2], vv * ax[0] * ax[2] + sg * ax[1],
-                           vv * ax[1] * ax[0] + sg * ax[2], cg + vv * ax[1] * ax[1],         vv * ax[1] * ax[2] - sg * ax[0],
-                           vv * ax[2] * ax[0] - sg * ax[1], vv * ax[2] * ax[1] + sg * ax[0], cg + vv * ax[2] * ax[2]};
     double E[9];
-    mat3_mul(md.Rfix[body], rot, E);
+    fused::joint_rotation(md.Rfix[body], md.axis[body], sg, cg, E);
     for (int i = 0; i < 9; ++i) w.T[sub][body - 1][i] = E[i];
   }
   lds_wave_sync();
-  double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
-  double o[3] = {pb[0], pb[1], pb[2]};
+  double R[9], o[3] = {pb[0], pb[1], pb[2]};
+  fused::rot_zyx(sy, cy, sp, cp, sr, cr, R);
   if (is_joint) {
     const int depth = md.depth[body];
     for (int d = 0; d < depth; ++d) {
       const int j = md.path[body][d];
-      double t[3], E[9], Rn[9];
-      mat3_vec(R, md.pfix[j], t);
-      for (int i = 0; i < 3; ++i) o[i] += t[i];
-      for (int i = 0; i < 9; ++i) E[i] = w.T[sub][j - 1][i];
-      mat3_mul(R, E, Rn);
-      for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+      fused::chain_step(R, o, md.pfix[j], w.T[sub][j - 1]);
     }
   }
   // ---- inertia of the lane's body about the base origin (eval_lane's composite form)
   if (is_body) {
-    double cb[3], dv[3];
-    mat3_vec(R, md.com[body], cb);
-    for (int i = 0; i < 3; ++i) dv[i] = o[i] + cb[i] - pb[i];
-    const double* I = md.inertia[body];
-    const double Ib[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
-    double Tm[9];
-    mat3_mul(R, Ib, Tm);
-    double Iw[6];
-    Iw[0] = Tm[0] * R[0] + Tm[1] * R[1] + Tm[2] * R[2];
-    Iw[1] = Tm[0] * R[3] + Tm[1] * R[4] + Tm[2] * R[5];
-    Iw[2] = Tm[0] * R[6] + Tm[1] * R[7] + Tm[2] * R[8];
-    Iw[3] = Tm[3] * R[3] + Tm[4] * R[4] + Tm[5] * R[5];
-    Iw[4] = Tm[3] * R[6] + Tm[4] * R[7] + Tm[5] * R[8];
-    Iw[5] = Tm[6] * R[6] + Tm[7] * R[7] + Tm[8] * R[8];
+    double cw[3], dv[3], Iw[6];
+    fused::point_on_body(R, o, md.com[body], cw);
+    for (int i = 0; i < 3; ++i) dv[i] = cw[i] - pb[i];
+    fused::world_inertia(R, md.inertia[body], Iw);
     const double m = md.mass[body], dd = dv[0] * dv[0] + dv[1] * dv[1] + dv[2] * dv[2];
     double* cm = w.comp[sub][body];
     cm[0] = m; cm[1] = m * dv[0]; cm[2] = m * dv[1]; cm[3] = m * dv[2];
@@ -149,17 +129,17 @@ __device__ __forceinline__ void tick_observation(const DeviceModel& md, TickLds<
   else if (g == 3) ah[2] = 1.0;
   else if (g == 4) { ah[0] = -sy; ah[1] = cy; }
   else if (g == 5) { ah[0] = cy * cp; ah[1] = sy * cp; ah[2] = -sp; }
-  else if (g < G) mat3_vec(R, md.axis[body], ah);
+  else if (g < G) fused::mat3_vec(R, md.axis[body], ah);
   double Ac[6];
   if (g < 3) {
     for (int i = 0; i < 3; ++i) { Ac[i] = ah[i] * Mtot; Ac[3 + i] = 0.0; }
   } else {
     const double rC[3] = {Cc[0] - o[0], Cc[1] - o[1], Cc[2] - o[2]};
     double vC[3], t[3], Iw[3];
-    cross3(ah, rC, vC);
+    fused::cross3(ah, rC, vC);
     const double dC[3] = {Cc[0] - com[0], Cc[1] - com[1], Cc[2] - com[2]};
-    cross3(dC, vC, t);
-    sym3_mul(Ic, ah, Iw);
+    fused::cross3(dC, vC, t);
+    fused::sym3_vec(Ic, ah, Iw);
     for (int i = 0; i < 3; ++i) { Ac[i] = Mc * vC[i]; Ac[3 + i] = Iw[i] + Mc * t[i]; }
   }
   // ---- h = A v (a reduction over the robot's lanes), normalised by the robot mass; q; the yaw unwrap of BipedalController.cpp:400-403

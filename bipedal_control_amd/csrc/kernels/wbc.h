@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../device_model.h"
+#include "kinematics.h"
 #include "riccati_fast.h"   // lds_wave_sync
 
 namespace bpmpc {
@@ -50,26 +51,6 @@ constexpr double kWbcGravity = 9.81;
 constexpr double kWbcFeasTol = 1e-8;   // relative: equality rows that cannot all hold (as the oracle)
 constexpr double kWbcActiveTol = 1e-9;
 
-__device__ __forceinline__ void w_cross(const double* a, const double* b, double* c) {
-  const double c0 = a[1] * b[2] - a[2] * b[1], c1 = a[2] * b[0] - a[0] * b[2], c2 = a[0] * b[1] - a[1] * b[0];
-  c[0] = c0; c[1] = c1; c[2] = c2;
-}
-__device__ __forceinline__ double w_dot(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-__device__ __forceinline__ void w_mat3_vec(const double* R, const double* v, double* out) {
-  const double a = R[0] * v[0] + R[1] * v[1] + R[2] * v[2], b = R[3] * v[0] + R[4] * v[1] + R[5] * v[2], c = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
-  out[0] = a; out[1] = b; out[2] = c;
-}
-__device__ __forceinline__ void w_mat3_mul(const double* A, const double* B, double* C) {
-  double t[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) t[3 * i + j] = A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j] + A[3 * i + 2] * B[6 + j];
-  for (int i = 0; i < 9; ++i) C[i] = t[i];
-}
-// symmetric 3x3 stored as xx, xy, xz, yy, yz, zz
-__device__ __forceinline__ void w_sym3_vec(const double* S, const double* v, double* out) {
-  const double a = S[0] * v[0] + S[1] * v[1] + S[2] * v[2], b = S[1] * v[0] + S[3] * v[1] + S[4] * v[2], c = S[2] * v[0] + S[4] * v[1] + S[5] * v[2];
-  out[0] = a; out[1] = b; out[2] = c;
-}
 __device__ __forceinline__ double wave_max(double x) {
   for (int m = 1; m < kWave; m <<= 1) x = fmax(x, __shfl_xor(x, m));
   return x;
@@ -122,54 +103,42 @@ __device__ void wbc_rbd_pass(const Model& model, WbcRbd<NJ>& r, bool gravity, in
   // ---- body frames by a chain walk per body
   if (l < NB) {
     const double cy = cos(r.q[3]), sy = sin(r.q[3]), cp = cos(r.q[4]), sp = sin(r.q[4]), cr = cos(r.q[5]), sr = sin(r.q[5]);
-    double R[9] = {cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr, sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr, -sp, cp * sr, cp * cr};
+    double R[9];
+    fused::rot_zyx(sy, cy, sp, cp, sr, cr, R);
     double o[3] = {r.q[0], r.q[1], r.q[2]};
     const int depth = md.depth[l];
     for (int d = 0; d < depth; ++d) {
       const int j = md.path[l][d];
-      const double* a = md.axis[j];
-      const double c = cos(r.q[5 + j]), s = sin(r.q[5 + j]), vv = 1.0 - c;
-      const double rot[9] = {c + vv * a[0] * a[0], vv * a[0] * a[1] - s * a[2], vv * a[0] * a[2] + s * a[1],
-                             vv * a[1] * a[0] + s * a[2], c + vv * a[1] * a[1], vv * a[1] * a[2] - s * a[0],
-                             vv * a[2] * a[0] - s * a[1], vv * a[2] * a[1] + s * a[0], c + vv * a[2] * a[2]};
-      double t[3], E[9];
-      w_mat3_vec(R, md.pfix[j], t);
+      // joint_rotation and chain_step in this pass's own order: which product of a sum is fused follows the order of definition
+      const double c = cos(r.q[5 + j]), s = sin(r.q[5 + j]);
+      double rot[9], t[3], E[9];
+      fused::axis_angle(md.axis[j], s, c, rot);
+      fused::mat3_vec(R, md.pfix[j], t);
       for (int i = 0; i < 3; ++i) o[i] += t[i];
-      w_mat3_mul(md.Rfix[j], rot, E);
-      w_mat3_mul(R, E, R);
+      fused::mat3_mul(md.Rfix[j], rot, E);
+      fused::mat3_mul(R, E, R);
     }
     for (int i = 0; i < 9; ++i) r.R[l][i] = R[i];
     for (int i = 0; i < 3; ++i) r.o[l][i] = o[i];
     // spatial axis of the coordinate that moves this body
     if (l >= 1) {
       double ah[3], sv[3];
-      w_mat3_vec(R, md.axis[l], ah);
-      w_cross(o, ah, sv);
+      fused::mat3_vec(R, md.axis[l], ah);
+      fused::cross3(o, ah, sv);
       for (int i = 0; i < 3; ++i) { r.S[5 + l][i] = ah[i]; r.S[5 + l][3 + i] = sv[i]; }
     } else {
       const double ax[3][3] = {{0.0, 0.0, 1.0}, {-sy, cy, 0.0}, {cy * cp, sy * cp, -sp}};     // world axes of the z, y', x'' rotations
       for (int g = 0; g < 3; ++g) {
         for (int i = 0; i < 3; ++i) { r.S[g][i] = 0.0; r.S[g][3 + i] = (i == g) ? 1.0 : 0.0; }
         double sv[3];
-        w_cross(o, ax[g], sv);
+        fused::cross3(o, ax[g], sv);
         for (int i = 0; i < 3; ++i) { r.S[3 + g][i] = ax[g][i]; r.S[3 + g][3 + i] = sv[i]; }
       }
     }
     // inertial quantities of the body in the world frame
-    double cb[3];
-    w_mat3_vec(R, in.com[l], cb);
-    const double c[3] = {o[0] + cb[0], o[1] + cb[1], o[2] + cb[2]};
-    const double* I = in.inertia[l];
-    const double Ib[9] = {I[0], I[1], I[2], I[1], I[3], I[4], I[2], I[4], I[5]};
-    double T[9];
-    w_mat3_mul(R, Ib, T);
-    double Iw[6];
-    Iw[0] = T[0] * R[0] + T[1] * R[1] + T[2] * R[2];
-    Iw[1] = T[0] * R[3] + T[1] * R[4] + T[2] * R[5];
-    Iw[2] = T[0] * R[6] + T[1] * R[7] + T[2] * R[8];
-    Iw[3] = T[3] * R[3] + T[4] * R[4] + T[5] * R[5];
-    Iw[4] = T[3] * R[6] + T[4] * R[7] + T[5] * R[8];
-    Iw[5] = T[6] * R[6] + T[7] * R[7] + T[8] * R[8];
+    double c[3], Iw[6];
+    fused::point_on_body(R, o, in.com[l], c);
+    fused::world_inertia(R, in.inertia[l], Iw);
     const double m = in.mass[l], cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
     for (int i = 0; i < 3; ++i) r.cw[l][i] = c[i];
     for (int i = 0; i < 6; ++i) r.Iw[l][i] = Iw[i];
@@ -188,9 +157,9 @@ __device__ void wbc_rbd_pass(const Model& model, WbcRbd<NJ>& r, bool gravity, in
       const double* s = r.S[g];
       const double vg = r.v[g];
       double t1[3], t2[3], t3[3];
-      w_cross(Vw, s, t1);            // w x s_w
-      w_cross(Vw, s + 3, t2);        // w x s_v
-      w_cross(Vo, s, t3);            // v_O x s_w
+      fused::cross3(Vw, s, t1);            // w x s_w
+      fused::cross3(Vw, s + 3, t2);        // w x s_v
+      fused::cross3(Vo, s, t3);            // v_O x s_w
       for (int i = 0; i < 3; ++i) { Aw[i] += t1[i] * vg; Ao[i] += (t2[i] + t3[i]) * vg; }
       for (int i = 0; i < 3; ++i) { Vw[i] += s[i] * vg; Vo[i] += s[3 + i] * vg; }
     }
@@ -198,16 +167,16 @@ __device__ void wbc_rbd_pass(const Model& model, WbcRbd<NJ>& r, bool gravity, in
     // bias wrench of the body about the origin
     const double* c = r.cw[l];
     double t[3], vc[3], ac[3], f[3], n[3], Iw_w[3], Ia[3], t4[3];
-    w_cross(Vw, c, t);
+    fused::cross3(Vw, c, t);
     for (int i = 0; i < 3; ++i) vc[i] = Vo[i] + t[i];
-    w_cross(Aw, c, t);
-    w_cross(Vw, vc, t4);
+    fused::cross3(Aw, c, t);
+    fused::cross3(Vw, vc, t4);
     for (int i = 0; i < 3; ++i) ac[i] = Ao[i] + t[i] + t4[i];
     for (int i = 0; i < 3; ++i) f[i] = in.mass[l] * ac[i];
-    w_cross(c, f, n);
-    w_sym3_vec(r.Iw[l], Aw, Ia);
-    w_sym3_vec(r.Iw[l], Vw, Iw_w);
-    w_cross(Vw, Iw_w, t);
+    fused::cross3(c, f, n);
+    fused::sym3_vec(r.Iw[l], Aw, Ia);
+    fused::sym3_vec(r.Iw[l], Vw, Iw_w);
+    fused::cross3(Vw, Iw_w, t);
     for (int i = 0; i < 3; ++i) { r.wr[l][i] = n[i] + Ia[i] + t[i]; r.wr[l][3 + i] = f[i]; }
   }
   lds_wave_sync();
@@ -227,9 +196,9 @@ __device__ void wbc_rbd_pass(const Model& model, WbcRbd<NJ>& r, bool gravity, in
     const double* s = r.S[l];
     const double h[3] = {c10[1], c10[2], c10[3]};
     double Ia[3], t1[3], t2[3];
-    w_sym3_vec(&c10[4], s, Ia);
-    w_cross(h, s + 3, t1);           // h x a_O
-    w_cross(s, h, t2);               // alpha x h
+    fused::sym3_vec(&c10[4], s, Ia);
+    fused::cross3(h, s + 3, t1);           // h x a_O
+    fused::cross3(s, h, t2);               // alpha x h
     for (int i = 0; i < 3; ++i) { r.fc[l][i] = Ia[i] + t1[i]; r.fc[l][3 + i] = c10[0] * s[3 + i] + t2[i]; }
     if (l == 0) { r.mass = c10[0]; for (int i = 0; i < 3; ++i) r.com[i] = c10[1 + i] / c10[0]; }
   }
@@ -237,12 +206,11 @@ __device__ void wbc_rbd_pass(const Model& model, WbcRbd<NJ>& r, bool gravity, in
   if (l < kNumContacts) {
     const int b = md.contact_body[l];
     double t[3], p[3], vp[3], t2[3], t3[3];
-    w_mat3_vec(r.R[b], md.contact_off[l], t);
-    for (int i = 0; i < 3; ++i) p[i] = r.o[b][i] + t[i];
-    w_cross(r.Vw[b], p, t);
+    fused::point_on_body(r.R[b], r.o[b], md.contact_off[l], p);
+    fused::cross3(r.Vw[b], p, t);
     for (int i = 0; i < 3; ++i) vp[i] = r.Vo[b][i] + t[i];
-    w_cross(r.Aw[b], p, t2);
-    w_cross(r.Vw[b], vp, t3);
+    fused::cross3(r.Aw[b], p, t2);
+    fused::cross3(r.Vw[b], vp, t3);
     for (int i = 0; i < 3; ++i) {
       r.cp[l][i] = p[i]; r.cv[l][i] = vp[i];
       r.ca[l][i] = r.Ao[b][i] - ((gravity && i == 2) ? kWbcGravity : 0.0) + t2[i] + t3[i];
@@ -257,7 +225,7 @@ __device__ __forceinline__ void wbc_contact_jac_col(const DeviceModel& md, const
   const bool moves = g < 6 || ((md.contact_path[i] >> (g - 5)) & 1u);
   if (!moves) { col[0] = col[1] = col[2] = 0.0; return; }
   double t[3];
-  w_cross(r.S[g], r.cp[i], t);
+  fused::cross3(r.S[g], r.cp[i], t);
   for (int a = 0; a < 3; ++a) col[a] = r.S[g][3 + a] + t[a];
 }
 
@@ -310,7 +278,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
   for (int i = l; i < NX; i += kWave) { w.xd[i] = a.state_des[(size_t)b * NX + i]; w.ud[i] = a.input_des[(size_t)b * NX + i]; }
   if (l < kNumContacts) {
     const int mode = a.mode[b];
-    w.flag[l] = (l < 2) ? ((mode == 1 || mode == 3) ? 1 : 0) : ((mode == 2 || mode == 3) ? 1 : 0);     // MotionPhaseDefinition.h:57-76
+    w.flag[l] = fused::stance_flag(mode, l) ? 1 : 0;
   }
   lds_wave_sync();
   if (l < NV) { r.q[l] = w.xd[6 + l]; r.v[l] = l >= 6 ? w.ud[12 + l - 6] : 0.0; }
@@ -322,14 +290,14 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
     for (int i = 0; i < 6; ++i) rhs[i] = md.robot_mass * w.xd[i];
     for (int g = 6; g < NV; ++g) {
       double t[3];
-      w_cross(r.com, &r.fc[g][3], t);
+      fused::cross3(r.com, &r.fc[g][3], t);
       for (int i = 0; i < 3; ++i) { rhs[i] -= r.fc[g][3 + i] * r.v[g]; rhs[3 + i] -= (r.fc[g][i] - t[i]) * r.v[g]; }
     }
     // Ab = [[m I, A12], [0, A22]] (translations carry no angular momentum about the com)
     double A12[9], A22[9];
     for (int g = 3; g < 6; ++g) {
       double t[3];
-      w_cross(r.com, &r.fc[g][3], t);
+      fused::cross3(r.com, &r.fc[g][3], t);
       for (int i = 0; i < 3; ++i) { A12[3 * i + (g - 3)] = r.fc[g][3 + i]; A22[3 * i + (g - 3)] = r.fc[g][i] - t[i]; }
     }
     const double* Mx = A22;
@@ -339,8 +307,8 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
                      c01 * idet, (Mx[0] * Mx[8] - Mx[2] * Mx[6]) * idet, (Mx[2] * Mx[3] - Mx[0] * Mx[5]) * idet,
                      c02 * idet, (Mx[1] * Mx[6] - Mx[0] * Mx[7]) * idet, (Mx[0] * Mx[4] - Mx[1] * Mx[3]) * idet};
     double th[3], t[3];
-    w_mat3_vec(X22, &rhs[3], th);
-    w_mat3_vec(A12, th, t);
+    fused::mat3_vec(X22, &rhs[3], th);
+    fused::mat3_vec(A12, th, t);
     const double im = 1.0 / r.mass;
     for (int i = 0; i < 3; ++i) { r.v[i] = (rhs[i] - t[i]) * im; r.v[3 + i] = th[i]; }
     // keep what the second pass overwrites: A12, X22 live in registers of this lane
@@ -360,15 +328,15 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
       const double* F = &w.ud[3 * i];
       const double rr[3] = {r.cp[i][0] - r.com[0], r.cp[i][1] - r.com[1], r.cp[i][2] - r.com[2]};
       double t[3];
-      w_cross(rr, F, t);
+      fused::cross3(rr, F, t);
       for (int k = 0; k < 3; ++k) { hd[k] += F[k]; hd[3 + k] += t[k]; }
     }
     double t[3];
-    w_cross(r.com, &r.ws[0][3], t);
+    fused::cross3(r.com, &r.ws[0][3], t);
     for (int k = 0; k < 3; ++k) { hd[k] -= r.ws[0][3 + k]; hd[3 + k] -= r.ws[0][k] - t[k]; }
     double thdd[3], t2[3], pdd[3];
-    w_mat3_vec(X22, &hd[3], thdd);
-    w_mat3_vec(A12, thdd, t2);
+    fused::mat3_vec(X22, &hd[3], thdd);
+    fused::mat3_vec(A12, thdd, t2);
     for (int k = 0; k < 3; ++k) pdd[k] = (hd[k] - t2[k]) * im;
     for (int k = 0; k < 6; ++k) pose_d[k] = r.q[k];
     for (int k = 0; k < 3; ++k) {
@@ -392,23 +360,19 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
     const double* rb = a.rbd_meas + (size_t)b * 2 * NV;
     for (int i = 0; i < 3; ++i) r.v[i] = rb[NV + 3 + i];
     for (int j = 0; j < NJ; ++j) r.v[6 + j] = rb[NV + 6 + j];
-    // Euler-angle rates from the world angular velocity: solve E thetadot = omega, E = [e_z, Rz e_y, Rz Ry e_x]
     const double cy = cos(r.q[3]), sy = sin(r.q[3]), cp = cos(r.q[4]), sp = sin(r.q[4]);
-    const double wx = rb[NV], wy = rb[NV + 1], wz = rb[NV + 2];
-    const double rr = (cy * wx + sy * wy) / cp;          // roll rate
-    const double pr = -sy * wx + cy * wy;                // pitch rate
-    r.v[3] = wz + sp * rr; r.v[4] = pr; r.v[5] = rr;
+    fused::euler_rates_from_world_omega(sy, cy, sp, cp, rb + NV, &r.v[3]);
   }
   wbc_rbd_pass<NJ>(md, r, true, l);
   // mass matrix, nonlinear effects, contact Jacobian and its bias, angular base Jacobian
   for (int idx = l; idx < NV * NV; idx += kWave) {
     const int h = idx / NV, g = idx % NV;
     double val = 0.0;
-    if (wbc_on_chain(md, h, g)) val = w_dot(r.S[h], r.fc[g]) + w_dot(r.S[h] + 3, r.fc[g] + 3);
-    else if (wbc_on_chain(md, g, h)) val = w_dot(r.S[g], r.fc[h]) + w_dot(r.S[g] + 3, r.fc[h] + 3);
+    if (wbc_on_chain(md, h, g)) val = fused::dot3(r.S[h], r.fc[g]) + fused::dot3(r.S[h] + 3, r.fc[g] + 3);
+    else if (wbc_on_chain(md, g, h)) val = fused::dot3(r.S[g], r.fc[h]) + fused::dot3(r.S[g] + 3, r.fc[h] + 3);
     w.M[h][g] = val;
   }
-  if (l < NV) w.nle[l] = w_dot(r.S[l], r.ws[l]) + w_dot(r.S[l] + 3, r.ws[l] + 3);
+  if (l < NV) w.nle[l] = fused::dot3(r.S[l], r.ws[l]) + fused::dot3(r.S[l] + 3, r.ws[l] + 3);
   for (int idx = l; idx < kNumContacts * NV; idx += kWave) {
     const int i = idx / NV, g = idx % NV;
     double col[3];
@@ -426,8 +390,7 @@ __device__ void wbc_robot(const DeviceModel& md, WbcLds<NJ>& w, const WbcArgs& a
     {
       const double z = pose_d[3], y = pose_d[4], x = pose_d[5];
       const double cz = cos(z), sz = sin(z), cyy = cos(y), syy = sin(y), cx = cos(x), sx = sin(x);
-      const double T[9] = {cz * cyy, cz * syy * sx - sz * cx, cz * syy * cx + sz * sx, sz * cyy, sz * syy * sx + cz * cx, sz * syy * cx - cz * sx, -syy, cyy * sx, cyy * cx};
-      for (int i = 0; i < 9; ++i) Rd[i] = T[i];
+      fused::rot_zyx(sz, cz, syy, cyy, sx, cx, Rd);
       for (int i = 0; i < 9; ++i) Rm[i] = r.R[0][i];
     }
     // rotationErrorInWorld(Rd, Rm) = rotation vector of Rd Rm'

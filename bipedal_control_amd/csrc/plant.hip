@@ -55,11 +55,10 @@ __global__ __launch_bounds__(256) void k_plant_set_state(int batch, int nv, cons
   else if (e < nv) val = rb[e];
   else if (e < nv + 3) val = rb[e + 3];
   else if (e < nv + 6) {
+    double rates[3];
     const double cy = cos(rb[0]), sy = sin(rb[0]), cp = cos(rb[1]), sp = sin(rb[1]);
-    const double wx = rb[nv], wy = rb[nv + 1], wz = rb[nv + 2];
-    const double rr = (cy * wx + sy * wy) / cp;          // roll rate
-    const double pr = -sy * wx + cy * wy;                // pitch rate
-    val = e == nv + 3 ? wz + sp * rr : (e == nv + 4 ? pr : rr);
+    fused::euler_rates_from_world_omega(sy, cy, sp, cp, rb + nv, rates);
+    val = e == nv + 3 ? rates[0] : (e == nv + 4 ? rates[1] : rates[2]);
   } else val = rb[e];
   state[i] = val;
 }
