@@ -4,6 +4,8 @@ Names follow the reference so that code reads like its call sites:
   BipedalRobotInterface(taskFile, urdfFile, referenceFile)   ocs2_bipedal_robot/include/ocs2_bipedal_robot/BipedalRobotInterface.h:56-127
   GaitSchedule.insertModeSequenceTemplate / getModeSchedule  ocs2_bipedal_robot/src/gait/GaitSchedule.cpp:46-102
   BatchedGaitSchedule.command                                one GaitReceiver per robot, ocs2_bipedal_robot/src/gait/GaitReceiver.cpp:49-59
+  BatchedCommands.start / cmdVel / goal / setTargets         one stored TargetTrajectories per robot: BipedalController::starting
+                                                             (BipedalController.cpp:145,153), TargetTrajectoriesPublisher.h:48-87
   loadModeSequenceTemplate                                   ocs2_bipedal_robot/src/gait/ModeSequenceTemplate.cpp:50-71
   cmdVelToTargetTrajectories / goalToTargetTrajectories      bipedal_controllers/src/TargetTrajectoriesPublisher.cpp:60-99
   BatchedSqpMpc(interface, ...)                              the SqpMpc construction sites bipedal_controllers/src/BipedalController.cpp:303-306
@@ -454,6 +456,98 @@ class BatchedGaitSchedule(_Handle):
         return ModeSchedule(ev[:n.value].copy(), ms[:n.value + 1].copy())
 
 
+def _on_device(a):
+    return a is not None and (bool(getattr(a, "is_cuda", False)) or hasattr(a, "__cuda_array_interface__"))
+
+
+class BatchedCommands(_Handle):
+    """One stored TargetTrajectories per robot of a BatchedSqpMpc, kept on the device (bpmpc_command_batch): `start` is
+    BipedalController::starting, `cmdVel` and `goal` are the two messages of TargetTrajectoriesPublisher - computed once, from the observation
+    passed with them - and `setTargets` stores any trajectory.  After mpc.attachCommands(commands) the solver's setup_commands and setup_gaits
+    take every robot's target from here.  Inputs are numpy arrays (validated; the call returns when they have been read) or device arrays -
+    DeviceArray, GPU tensors, anything with __cuda_array_interface__ (not validated, only enqueued on the solver's stream); never mixed.
+    Robots are 0 .. B - 1 with B = len(mask), else the rows of the inputs, else the solver's batch; mask[b] == 0 leaves robot b untouched."""
+
+    _DESTROY = "bpmpc_command_batch_destroy"
+    SOURCES = ("none", "start", "velocity", "goal", "trajectory")      # status()[:, 2]
+
+    def __init__(self, mpc, max_points=8):
+        self.mpc, self.max_batch, self.max_points, self.nx = mpc, mpc.max_batch, int(max_points), mpc.nx
+        super().__init__()
+        _check(load_library().bpmpc_command_batch_create(mpc._h, self.max_points, C.byref(self._h)))
+
+    def _message(self, name, rows, t, x, mask, *tail):
+        given = [a for a in (rows, t, x, mask) if a is not None]
+        if mask is not None:
+            B = int(np.prod(_shape(mask)))
+        else:
+            lead = [_shape(a)[0] for a, nd in ((rows, 2), (x, 2), (t, 1)) if a is not None and len(_shape(a)) == nd]
+            B = lead[0] if lead else (self.mpc.batch or self.max_batch)
+        if not any(_on_device(a) for a in given):
+            t = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
+            rows = None if rows is None else _f64(np.broadcast_to(np.asarray(rows, float), (B, 4)))
+            x = None if x is None else _f64(np.broadcast_to(np.asarray(x, float), (B, self.nx)))
+        (mp, rp, tp, xp), dev, keep = _restart_args((mask, C.c_int, B), (rows, C.c_double, B * 4), (t, C.c_double, B), (x, C.c_double, B * self.nx))
+        self._call(name, B, mp, *([] if rows is None else [rp]), tp, xp, *tail, dev)
+        del keep
+
+    def start(self, t, x=None, mask=None):
+        """The target becomes the single point (t[b], x[b]).  x=None: the observations already on the device (the last controller tick,
+        otherwise the end states of the last rollout), as setup_commands(x0=None) reads them."""
+        self._message("bpmpc_command_batch_start", None, t, x, mask)
+
+    def cmdVel(self, cmd, t, x=None, mask=None, time_to_target=0.0):
+        """cmdVelToTargetTrajectories(cmd[b] = (vx, vy, vz, yaw rate), (t[b], x[b])) reaching time_to_target ahead (<= 0: mpc.timeHorizon);
+        a message at t == 0.0 is dropped and counted, as the reference's publisher drops it."""
+        self._message("bpmpc_command_batch_cmd_vel", cmd, t, x, mask, float(time_to_target))
+
+    def goal(self, goal, t, x=None, mask=None):
+        """goalToTargetTrajectories(goal[b] = (x, y, unused, yaw), (t[b], x[b])): the reach time is fixed here, once."""
+        self._message("bpmpc_command_batch_goal", goal, t, x, mask)
+
+    def setTargets(self, times, states, n_points=None, mask=None):
+        """Stores trajectories as they are: times [B, P] (or [P]: one for every robot written), states [B, P, nx] with P <= max_points, of which
+        robot b uses the first n_points[b] (None: all P).  Device arrays have the handle's strides, [B, max_points] and [B, max_points, nx], and
+        come with n_points [B] (int32)."""
+        if any(_on_device(a) for a in (times, states, n_points, mask)):
+            B = _shape(times)[0]
+            if n_points is None or _shape(times) != (B, self.max_points):
+                raise ValueError("device trajectories need n_points and the strides [B, %d] / [B, %d, %d]" % (self.max_points, self.max_points, self.nx))
+        else:
+            times, states = np.asarray(times, float), np.asarray(states, float)
+            if times.ndim == 1:
+                B = int(np.prod(_shape(mask))) if mask is not None else (self.mpc.batch or self.max_batch)
+                times, states = np.broadcast_to(times, (B,) + times.shape), np.broadcast_to(states, (B,) + states.shape)
+            B, P = times.shape
+            if P > self.max_points or states.shape != (B, P, self.nx):
+                raise ValueError("times [B, P] and states [B, P, %d] with P <= %d, got %s and %s" % (self.nx, self.max_points, times.shape, states.shape))
+            n_points = np.ascontiguousarray(np.broadcast_to(np.asarray(P if n_points is None else n_points, np.int32), (B,)))
+            tt, xx = np.zeros((B, self.max_points)), np.zeros((B, self.max_points, self.nx))
+            tt[:, :P], xx[:, :P] = times, states
+            times, states = tt, xx
+        (mp, np_, tp, xp), dev, keep = _restart_args((mask, C.c_int, B), (n_points, C.c_int, B), (times, C.c_double, B * self.max_points),
+                                                     (states, C.c_double, B * self.max_points * self.nx))
+        self._call("bpmpc_command_batch_set_targets", B, mp, np_, tp, xp, dev)
+        del keep
+
+    def targets(self, robot):
+        """Robot's stored trajectory, (times [n], states [n, nx]); n = 0 after create / reset.  Synchronises."""
+        ts, xs, n = np.zeros(self.max_points), np.zeros((self.max_points, self.nx)), C.c_int()
+        self._call("bpmpc_command_batch_get_targets", int(robot), _d(ts), _d(xs), self.max_points, C.byref(n))
+        return TargetTrajectories(ts[:n.value].copy(), xs[:n.value].copy())
+
+    def status(self, batch=None):
+        """[B, 4] int32 per robot: messages applied, messages dropped, source of the stored target (an index into SOURCES), stored points."""
+        B = int(batch or self.max_batch)
+        st = np.zeros((B, 4), np.int32)
+        self._call("bpmpc_command_batch_get_status", B, _i(st))
+        return st
+
+    def reset(self):
+        """Every robot back to no target, counters 0."""
+        self._call("bpmpc_command_batch_reset")
+
+
 def swing_reference(interface, modeSchedule, times):
     """SwingTrajectoryPlanner::update + getZpositionConstraint / getZvelocityConstraint (SwingTrajectoryPlanner.cpp:50-118)."""
     ev, ms, t = _f64(modeSchedule.eventTimes), np.ascontiguousarray(modeSchedule.modeSequence, np.int32), _f64(times)
@@ -566,7 +660,7 @@ class BatchedSqpMpc(_Handle):
         t0 = _f64(np.broadcast_to(np.asarray(t0, float), (B,)))
         gop = np.ascontiguousarray(np.broadcast_to(np.asarray(gait_of_problem, np.int32), (B,)))
         gst = _f64(np.broadcast_to(np.asarray(gait_start, float), (B,)))
-        cmd = _f64(np.broadcast_to(np.asarray(cmd_vel, float), (B, 4)))
+        cmd = None if cmd_vel is None else _f64(np.broadcast_to(np.asarray(cmd_vel, float), (B, 4)))      # None: an attached BatchedCommands
         keep, tm = [], (_GaitTemplate * max(1, len(gaits)))()
         for i, g in enumerate(gaits):
             sw, mo = _f64(g.switchingTimes), np.ascontiguousarray(g.modeSequence, np.int32)
@@ -588,10 +682,16 @@ class BatchedSqpMpc(_Handle):
             x0 = _f64(x0).reshape(-1, self.nx)
             B = x0.shape[0]
         t0 = _f64(np.broadcast_to(np.asarray(t0, float), (B,)))
-        cmd = _f64(np.broadcast_to(np.asarray(cmd_vel, float), (B, 4)))
+        cmd = None if cmd_vel is None else _f64(np.broadcast_to(np.asarray(cmd_vel, float), (B, 4)))      # None: an attached BatchedCommands
         self._call("bpmpc_solver_setup_gaits", gait_schedules._h, B, horizon, _d(t0), _d(x0), _d(cmd), int(bool(goal)), time_to_target, int(bool(from_previous)))
         self.batch = B
         return self.layout()
+
+    def attachCommands(self, commands):
+        """setup_commands and setup_gaits take every robot's target from `commands` (a BatchedCommands of this solver) and ignore cmd_vel (None
+        is accepted), goal and time_to_target (bpmpc_solver_attach_commands); None detaches: the solver runs what it ran before.  The solver does
+        not keep `commands` alive: destroying it detaches it."""
+        self._call("bpmpc_solver_attach_commands", None if commands is None else commands._h)
 
     def rollout(self, duration, t_start=None, x_start=None, fetch=True):
         """MRT_BASE::rolloutPolicy for the batch (bpmpc_solver_rollout): returns (x_end, u_end, steps[batch, 2]); fetch=False only

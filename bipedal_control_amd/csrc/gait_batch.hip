@@ -215,7 +215,7 @@ void setup_gaits(bpmpc_solver* s, bpmpc_gait_batch* g, int batch, double horizon
   {
     const TransferPiece up[6] = {{g->grp_i, gi.data(), nullptr, gi.size() * sizeof(int)}, {g->grp_d, gd.data(), nullptr, gd.size() * sizeof(double)},
                                  {bf.p_grid, pgrid.data(), nullptr, pgrid.size() * sizeof(int)}, {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)},
-                                 {bf.p_cmd, cmd_vel, nullptr, (size_t)batch * 4 * sizeof(double)}, {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
+                                 {bf.p_cmd, cmd_vel, nullptr, cmd_vel ? (size_t)batch * 4 * sizeof(double) : 0}, {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
     upload_batch(s, up, 6);
   }
   GaitAdvanceArgs a{};

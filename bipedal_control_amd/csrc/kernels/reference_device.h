@@ -276,6 +276,38 @@ struct CommandTargetArgs {
   int* tgt_n;
 };
 
+// cmdVelToTargetTrajectories (TargetTrajectoriesPublisher.cpp:40-62 restated in reference_gen.cpp cmd_vel_to_targets) or, with a.goal,
+// goalToTargetTrajectories (:64-99, goal_to_targets) of one robot from the observation (t_now, x): the two points go to ts[2] and xs[2][nx].
+// One body for k_command_targets (solver.hip) and the message kernel of the command batch (kernels/command_batch.h)
+__device__ inline void ref_command_target(const CommandTargetArgs& a, double t_now, const double* x, const double* cmd, double* ts, double* xs) {
+  EXACT_FP_BODY
+  const int nx = a.nx;
+  const double T = a.time_to_target;
+  double v[3] = {0.0, 0.0, 0.0}, pose[6], t_reach;
+  if (a.goal) {
+    pose[0] = cmd[0]; pose[1] = cmd[1]; pose[2] = a.com_height; pose[3] = cmd[3]; pose[4] = 0.0; pose[5] = 0.0;
+    const double dx = pose[0] - x[6], dy = pose[1] - x[7], dyaw = pose[3] - x[9];
+    const double tr = fabs(dyaw) / a.rotation_velocity, td = sqrt(dx * dx + dy * dy) / a.displacement_velocity;
+    t_reach = t_now + (tr < td ? td : tr);
+  } else {
+    const double yz = x[9], yy = x[10], yx = x[11];
+    const double cz = cos(yz), sz = sin(yz), cy = cos(yy), sy = sin(yy), cx = cos(yx), sx = sin(yx);
+    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
+    for (int i = 0; i < 3; ++i) v[i] = R[3 * i] * cmd[0] + R[3 * i + 1] * cmd[1] + R[3 * i + 2] * cmd[2];
+    pose[0] = x[6] + v[0] * T; pose[1] = x[7] + v[1] * T; pose[2] = a.com_height; pose[3] = x[9] + cmd[3] * T; pose[4] = 0.0; pose[5] = 0.0;
+    t_reach = t_now + T;
+  }
+  for (int i = 0; i < 2 * nx; ++i) xs[i] = 0.0;
+  ts[0] = t_now;
+  ts[1] = t_reach;
+  for (int i = 0; i < 6; ++i) { xs[6 + i] = x[6 + i]; xs[nx + 6 + i] = pose[i]; }
+  xs[6 + 2] = a.com_height;
+  xs[6 + 4] = 0.0;
+  xs[6 + 5] = 0.0;
+  for (int j = 0; j < a.nj; ++j) xs[12 + j] = xs[nx + 12 + j] = a.default_joint_state[j];
+  if (!a.goal) for (int i = 0; i < 3; ++i) xs[i] = xs[nx + i] = v[i];
+}
+
 #undef EXACT_FP_BODY
 
 }  // namespace bpmpc

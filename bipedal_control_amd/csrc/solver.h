@@ -52,6 +52,8 @@ struct PinnedArena {
   void release() { if (base) (void)hipHostFree(base); base = nullptr; cap = used = demand = 0; }
 };
 
+struct bpmpc_command_batch;
+
 struct bpmpc_solver {
   HostStaging staging;
   PinnedArena pin_up, pin_down;
@@ -86,6 +88,10 @@ struct bpmpc_solver {
   // per-problem restarts (bpmpc_solver_restart, MPC_BASE::reset per problem): restart_flag[b] != 0 from the restart to the next accepted setup,
   // which keeps k_prepare's guess for those problems instead of the shifted solution.  restart_pending: flags recorded and not consumed yet;
   // restart_wait: tick, evaluate_policy and rollout are refused until the first run after that setup (a fresh handle before its first run)
+  // the attached command batch (bpmpc_solver_attach_commands, command_batch.hip): the device-side setups window its stored targets into p_tgt_*
+  // instead of launching k_command_targets; tgt_flag[b] is the window kernel's verdict (0 taken, < 0 no target, > 0 that many points in the window)
+  bpmpc_command_batch* commands = nullptr;
+  int* tgt_flag = nullptr;                                 // [max_batch]
   int* restart_flag = nullptr;                             // [max_batch]
   int* restart_mask = nullptr;                             // [max_batch] device copy of a host mask
   double* restart_x = nullptr;                             // [max_batch][nx] device copy of host states
@@ -223,6 +229,7 @@ void check_device_setup(bpmpc_solver* s, const char* what, int batch, double hor
                         int command_kind, bool invalid_other);
 ReferenceGenArgs reference_args(bpmpc_solver* s, const GaitLibraryView& lib, int G, double horizon);
 void copy_loop_x0(bpmpc_solver* s, int batch, const double* x0);
+CommandTargetArgs command_target_args(const bpmpc_solver* s, int batch, int command_kind, double time_to_target);
 void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int command_kind, double time_to_target);
 void preserve_previous(bpmpc_solver* s, int batch, bool warm_arrays);
 void accept_reference_grids(bpmpc_solver* s, int batch, int G, const std::vector<int>& pgrid);

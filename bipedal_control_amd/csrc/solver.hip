@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "solver.h"
+#include "command_batch.h"
 #include "reference_gen.h"
 #include "kernels/rollout.h"
 
@@ -329,6 +330,7 @@ void allocate(bpmpc_solver* s) {
     d.update_is = s->alloc<double>("ddp_update_is", B);
     d.accepted = s->alloc<int>(nullptr, B); d.failed = s->alloc<int>(nullptr, B); d.n_points = s->alloc<int>("ddp_points", B, true);
   }
+  s->tgt_flag = s->alloc<int>(nullptr, B);                // behind every other buffer: their order, and so their placement, stays what it was
 }
 
 template <typename T>
@@ -441,11 +443,12 @@ void check_device_setup(bpmpc_solver* s, const char* what, int batch, double hor
                         int command_kind, bool invalid_other) {
   const std::string w(what);
   if (batch < 1 || batch > s->settings.max_batch) throw std::length_error("batch exceeds the solver's max_batch");
-  if (!(horizon > 0) || !t0 || !cmd_vel || invalid_other) throw std::invalid_argument(w + ": null or invalid argument");
+  const bool attached = s->commands != nullptr;         // the targets come from the attached command batch: cmd_vel and command_kind are not read
+  if (!(horizon > 0) || !t0 || (!cmd_vel && !attached) || invalid_other) throw std::invalid_argument(w + ": null or invalid argument");
   if (!x0 && (!(s->has_rollout || s->loop_from_tick) || batch != s->batch))
     throw std::invalid_argument(w + ": x0 == NULL needs a rollout of the same batch on the handle (or a controller tick)");
   if (!x0 && !s->loop_from_tick && s->rollout_unchecked) check_rollout_status(s, nullptr);
-  if (command_kind != 0 && command_kind != 1) throw std::invalid_argument(w + ": command_kind is 0 (velocity) or 1 (goal pose)");
+  if (!attached && command_kind != 0 && command_kind != 1) throw std::invalid_argument(w + ": command_kind is 0 (velocity) or 1 (goal pose)");
 }
 
 // grid settings and node-table outputs of k_reference_grids / k_gait_advance
@@ -495,47 +498,28 @@ __global__ __launch_bounds__(64) void k_command_targets(CommandTargetArgs a) {
   EXACT_FP_BODY
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= a.batch) return;
-  const int nx = a.nx;
-  const double* x = a.x0 + (size_t)b * nx;
-  const double* cmd = a.cmd_vel + (size_t)b * 4;
-  const double T = a.time_to_target, t_now = a.t0[b];
-  double v[3] = {0.0, 0.0, 0.0}, pose[6], t_reach;
-  if (a.goal) {            // goalToTargetTrajectories (TargetTrajectoriesPublisher.cpp:64-99 restated in reference_gen.cpp goal_to_targets)
-    pose[0] = cmd[0]; pose[1] = cmd[1]; pose[2] = a.com_height; pose[3] = cmd[3]; pose[4] = 0.0; pose[5] = 0.0;
-    const double dx = pose[0] - x[6], dy = pose[1] - x[7], dyaw = pose[3] - x[9];
-    const double tr = fabs(dyaw) / a.rotation_velocity, td = sqrt(dx * dx + dy * dy) / a.displacement_velocity;
-    t_reach = t_now + (tr < td ? td : tr);
-  } else {
-    const double yz = x[9], yy = x[10], yx = x[11];
-    const double cz = cos(yz), sz = sin(yz), cy = cos(yy), sy = sin(yy), cx = cos(yx), sx = sin(yx);
-    const double R[9] = {cz * cy, cz * sy * sx - sz * cx, cz * sy * cx + sz * sx, sz * cy, sz * sy * sx + cz * cx, sz * sy * cx - cz * sx, -sy, cy * sx, cy * cx};
-    for (int i = 0; i < 3; ++i) v[i] = R[3 * i] * cmd[0] + R[3 * i + 1] * cmd[1] + R[3 * i + 2] * cmd[2];
-    pose[0] = x[6] + v[0] * T; pose[1] = x[7] + v[1] * T; pose[2] = a.com_height; pose[3] = x[9] + cmd[3] * T; pose[4] = 0.0; pose[5] = 0.0;
-    t_reach = t_now + T;
-  }
-  double* ts = a.tgt_t + (size_t)b * kMaxTargetPoints;
-  double* xs = a.tgt_x + (size_t)b * kMaxTargetPoints * nx;
-  for (int i = 0; i < 2 * nx; ++i) xs[i] = 0.0;
-  ts[0] = t_now;
-  ts[1] = t_reach;
-  for (int i = 0; i < 6; ++i) { xs[6 + i] = x[6 + i]; xs[nx + 6 + i] = pose[i]; }
-  xs[6 + 2] = a.com_height;
-  xs[6 + 4] = 0.0;
-  xs[6 + 5] = 0.0;
-  for (int j = 0; j < a.nj; ++j) xs[12 + j] = xs[nx + 12 + j] = a.default_joint_state[j];
-  if (!a.goal) for (int i = 0; i < 3; ++i) xs[i] = xs[nx + i] = v[i];
+  ref_command_target(a, a.t0[b], a.x0 + (size_t)b * a.nx, a.cmd_vel + (size_t)b * 4, a.tgt_t + (size_t)b * kMaxTargetPoints,
+                     a.tgt_x + (size_t)b * kMaxTargetPoints * a.nx);
   a.tgt_n[b] = 2;
 }
 
 #undef EXACT_FP_BODY
 
-// the target trajectories of the velocity commands / goal poses (k_command_targets)
-void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int command_kind, double time_to_target) {
-  Buffers& bf = s->buf;
+// the constants of ref_command_target for `batch` robots of this solver's model
+CommandTargetArgs command_target_args(const bpmpc_solver* s, int batch, int command_kind, double time_to_target) {
   CommandTargetArgs c{};
-  c.batch = batch; c.nx = s->nx; c.nj = s->rm.nj; c.time_to_target = time_to_target > 0 ? time_to_target : horizon; c.com_height = s->rm.com_height;
+  c.batch = batch; c.nx = s->nx; c.nj = s->rm.nj; c.time_to_target = time_to_target; c.com_height = s->rm.com_height;
   c.goal = command_kind; c.displacement_velocity = s->rm.target_displacement_velocity; c.rotation_velocity = s->rm.target_rotation_velocity;
   for (int j = 0; j < s->rm.nj; ++j) c.default_joint_state[j] = s->rm.default_joint_state[j];
+  return c;
+}
+
+// the target trajectories of a setup: the window of the attached command batch's stored ones (command_batch.hip), else those of the velocity
+// commands / goal poses (k_command_targets)
+void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int command_kind, double time_to_target) {
+  if (s->commands) { launch_command_window(s, batch, horizon); return; }
+  Buffers& bf = s->buf;
+  CommandTargetArgs c = command_target_args(s, batch, command_kind, time_to_target > 0 ? time_to_target : horizon);
   c.t0 = bf.p_t0; c.x0 = bf.p_x0; c.cmd_vel = bf.p_cmd; c.tgt_t = bf.p_tgt_t; c.tgt_x = bf.p_tgt_x; c.tgt_n = bf.p_tgt_n;
   hipLaunchKernelGGL(k_command_targets, dim3((batch + 63) / 64), dim3(64), 0, s->stream, c);
   HIP_CHECK(hipGetLastError());
@@ -546,12 +530,13 @@ void launch_command_targets(bpmpc_solver* s, int batch, double horizon, int comm
 void accept_reference_grids(bpmpc_solver* s, int batch, int G, const std::vector<int>& pgrid) {
   const int N = s->settings.max_nodes;
   const Buffers& bf = s->buf;
-  std::vector<int> nodes(G), status(G), rows(G), kind((size_t)G * N);
+  std::vector<int> nodes(G), status(G), rows(G), kind((size_t)G * N), window(s->commands ? batch : 0);
   std::vector<double> node_times((size_t)G * (N + 1), 0.0);   // becomes the handle's copy once every grid has been accepted
   {
     Downloads down;
     down.add(nodes.data(), bf.g_nodes, G * sizeof(int)); down.add(status.data(), bf.rg_status, G * sizeof(int)); down.add(rows.data(), bf.rg_rows, G * sizeof(int));
     down.add(kind.data(), bf.g_kind, kind.size() * sizeof(int)); down.add(node_times.data(), bf.g_time, node_times.size() * sizeof(double));
+    down.add(window.data(), s->tgt_flag, window.size() * sizeof(int));      // the window kernel of an attached command batch
     down.enqueue(s);
     HIP_CHECK(hipStreamSynchronize(s->stream));
     down.finish();
@@ -569,6 +554,11 @@ void accept_reference_grids(bpmpc_solver* s, int batch, int G, const std::vector
     nmax = std::max(nmax, nodes[g]);
     rows_max = std::max(rows_max, rows[g] & 255);
     vrows_max = std::max(vrows_max, rows[g] >> 8);
+  }
+  for (size_t b = 0; b < window.size(); ++b) {             // what the host path says of such a TargetTrajectories (setup), with the robot
+    if (window[b] < 0) throw std::invalid_argument("robot " + std::to_string(b) + ": target trajectories need at least one point (the command batch holds none for it)");
+    if (window[b] > 0)
+      throw std::invalid_argument("robot " + std::to_string(b) + ": target trajectory has " + std::to_string(window[b]) + " points inside the horizon, the solver holds " + std::to_string(kMaxTargetPoints));
   }
   s->node_times.swap(node_times);
   s->batch = batch; s->n_grids = G; s->n_nodes_max = nmax; s->cold = true; s->max_rows = rows_max; s->max_vel_rows = vrows_max;
@@ -750,7 +740,7 @@ void setup_commands(bpmpc_solver* s, int batch, double horizon, const double* t0
     const TransferPiece up[9] = {{bf.rg_t0, gt0.data(), nullptr, gt0.size() * sizeof(double)}, {bf.rg_gait, ggait.data(), nullptr, ggait.size() * sizeof(int)},
                                  {bf.rg_start, gstart.data(), nullptr, gstart.size() * sizeof(double)}, {bf.lib_d, lib.d.data(), nullptr, lib.d.size() * sizeof(double)},
                                  {bf.lib_i, lib.i.data(), nullptr, lib.i.size() * sizeof(int)}, {bf.p_grid, pgrid.data(), nullptr, pgrid.size() * sizeof(int)},
-                                 {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)}, {bf.p_cmd, cmd_vel, nullptr, (size_t)batch * 4 * sizeof(double)},
+                                 {bf.p_t0, t0, nullptr, (size_t)batch * sizeof(double)}, {bf.p_cmd, cmd_vel, nullptr, cmd_vel ? (size_t)batch * 4 * sizeof(double) : 0},
                                  {bf.p_x0, x0, nullptr, x0 ? (size_t)batch * NX * sizeof(double) : 0}};
     upload_batch(s, up, 9);
   }

@@ -286,6 +286,60 @@ int bpmpc_gait_batch_command(bpmpc_gait_batch* gaits, int batch, const int* gait
 int bpmpc_gait_batch_mode_schedule(bpmpc_gait_batch* gaits, int robot, double* event_times, int* modes, int capacity, int* n_events);
 int bpmpc_solver_setup_gaits(bpmpc_solver* solver, bpmpc_gait_batch* gaits, int batch, double horizon, const double* t0, const double* x0,
                              const double* cmd_vel /* [batch][4] */, int command_kind, double time_to_target, int from_previous);
+/* Device-resident target trajectories: one TargetTrajectories per robot kept on the device between setups, the other half of the reference
+ * manager beside the gait batch.  The reference changes a robot's target only when a command arrives - BipedalController::starting sets the
+ * single point at the current observation (BipedalController.cpp:145,153), TargetTrajectoriesPublisher turns a /cmd_vel or goal message into a
+ * two-point trajectory from the observation AT THE TIME OF THE MESSAGE (TargetTrajectoriesPublisher.h:48-87, .cpp:30-99) - and every MPC solve in
+ * between interpolates that same trajectory [OCS2-upstream, recalled: ReferenceManager::setTargetTrajectories / preSolverRun].  Per robot b:
+ *   storage          n points (n <= max_points, given at create, 2 .. 64), times[max_points], states[max_points][nx], and the status row
+ *                    status[b][4] = (messages applied, messages dropped, source of the stored target, n) with the sources 0 none, 1 start,
+ *                    2 velocity, 3 goal, 4 trajectory.  Robots at or beyond `batch` and robots with mask[b] == 0 (mask == NULL: every robot
+ *                    below batch) keep every bit of theirs.
+ *   create / reset   no target (n = 0), counters and source 0.
+ *   start            starting(): the target becomes the single point (t_obs[b], x_obs[b]).
+ *   cmd_vel          cmdVelToTargetTrajectories(cmd[b] = (vx, vy, vz, yaw rate), observation), reaching time_to_target ahead; <= 0 means
+ *                    mpc.timeHorizon of task.info, the reference's TIME_TO_TARGET.
+ *   goal             goalToTargetTrajectories(goal[b] = (x, y, unused, yaw), observation): the reach time t_obs + max(|dyaw| /
+ *                    targetRotationVelocity, distance / targetDisplacementVelocity) is fixed by this call.
+ *                    Both are computed ONCE, from the observation passed to the call, with the arithmetic of bpmpc_solver_setup_commands' targets;
+ *                    the stored points stay until the next call that touches the robot.  The reference's quirk is kept: a robot whose t_obs
+ *                    equals 0.0 ignores a velocity or goal message (TargetTrajectoriesPublisher.h:49,75) and its dropped counter goes up;
+ *                    start and set_targets are not messages and ignore nothing.
+ *   set_targets      an arbitrary TargetTrajectories (a waypoint route): the first n_points[b] entries of times[b] and states[b].
+ *   x_obs == NULL    the observations already on the device, what bpmpc_solver_setup_commands(x0 = NULL) starts from: the observations of the
+ *                    last controller tick, otherwise the end states of the last rollout.  Without such a source, or with another batch:
+ *                    BPMPC_ERR_INVALID_ARGUMENT.  t_obs is always given.
+ *   inputs_on_device != 0: mask, the command rows, t_obs, x_obs, n_points, times and states are device pointers, ordered on the solver's
+ *                    stream; nothing is validated (a count outside 0 .. max_points is held inside it) and the call only enqueues.  Host arrays
+ *                    are validated - every used entry finite, n_points in 1 .. max_points, times not decreasing; a bad value names the robot
+ *                    and the entry in bpmpc_last_error(), changes nothing and returns BPMPC_ERR_INVALID_ARGUMENT - and the call returns when
+ *                    they have been read.
+ *   get_targets      robot's stored trajectory: *n_points, then its times and states when n <= capacity (else BPMPC_ERR_CAPACITY); get_status
+ *                    the status rows of robots 0 .. batch - 1.  Both synchronise.
+ *   attach           bpmpc_solver_attach_commands(solver, commands): while attached, bpmpc_solver_setup_commands and bpmpc_solver_setup_gaits
+ *                    ignore cmd_vel (may be NULL), command_kind and time_to_target and take every robot's target from the command batch: the
+ *                    points the host path bpmpc_solver_setup keeps of a TargetTrajectories - the last one at or before t0, the ones inside
+ *                    [t0, t0 + horizon], the first one behind - so the references equal those of bpmpc_solver_setup given the stored trajectory.
+ *                    More than 8 such points, or a robot without a target, rejects the setup with the host path's message and the robot's
+ *                    number (BPMPC_ERR_INVALID_ARGUMENT).  A setup only reads the command batch: a rejected one leaves it bit for bit as it
+ *                    was.  NULL detaches; a detached solver runs what a solver that never had a command batch runs.  SQP and DDP alike.
+ * The handle is created on a solver, enqueues on its stream, and is destroyed before it.  Null handles, a handle of another solver, batch >
+ * max_batch, max_points outside 2 .. 64, a robot out of range, NULL pointers: BPMPC_ERR_INVALID_ARGUMENT. */
+typedef struct bpmpc_command_batch bpmpc_command_batch;
+int bpmpc_command_batch_create(bpmpc_solver* solver, int max_points, bpmpc_command_batch** out);
+void bpmpc_command_batch_destroy(bpmpc_command_batch* commands);
+int bpmpc_command_batch_reset(bpmpc_command_batch* commands);
+int bpmpc_command_batch_start(bpmpc_command_batch* commands, int batch, const int* mask, const double* t_obs, const double* x_obs, int inputs_on_device);
+int bpmpc_command_batch_cmd_vel(bpmpc_command_batch* commands, int batch, const int* mask, const double* cmd /* [batch][4] */, const double* t_obs,
+                                const double* x_obs, double time_to_target, int inputs_on_device);
+int bpmpc_command_batch_goal(bpmpc_command_batch* commands, int batch, const int* mask, const double* goal /* [batch][4]: x, y, unused, yaw */,
+                             const double* t_obs, const double* x_obs, int inputs_on_device);
+int bpmpc_command_batch_set_targets(bpmpc_command_batch* commands, int batch, const int* mask, const int* n_points /* [batch] */,
+                                    const double* times /* [batch][max_points] */, const double* states /* [batch][max_points][nx] */,
+                                    int inputs_on_device);
+int bpmpc_command_batch_get_targets(bpmpc_command_batch* commands, int robot, double* times, double* states, int capacity, int* n_points);
+int bpmpc_command_batch_get_status(bpmpc_command_batch* commands, int batch, int* status /* [batch][4] */);
+int bpmpc_solver_attach_commands(bpmpc_solver* solver, bpmpc_command_batch* commands);
 /* MRT side: MRT_BASE::rolloutPolicy for every problem of the batch - TimeTriggeredRollout::run from
  * (t_start[b], x_start[b]) over `duration` under the LinearController of the last solve (u = uff(t) + K(t) x), ODE45 with the
  * rollout block of task.info (AbsTolODE, RelTolODE, timeStep, maxNumStepsPerSecond), restarted at the mode-schedule events inside
