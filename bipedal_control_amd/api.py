@@ -255,6 +255,59 @@ class WbcParams:
                    weightSwingLeg=100.0, weightBaseAccel=1.0, weightContactForce=0.1, **rest)
 
 
+class MpcWeights:
+    """A cost-weight row of the MPC (include/bpmpc.h "Per-problem cost weights", BPMPC_SOLVER_WEIGHT_STRIDE): Q [nx, nx] followed by R [nu, nu],
+    dense and row major, zeros behind them.  `Q` and `R` are views into `row`, so either may be edited in place."""
+
+    STRIDE = 2 * 24 * 24
+
+    def __init__(self, nx, nu, row=None):
+        self.nx, self.nu = int(nx), int(nu)
+        self.row = np.zeros(self.STRIDE) if row is None else np.array(row, float).reshape(-1)
+        if self.row.size != self.STRIDE:
+            raise ValueError("a weight row has %d entries" % self.STRIDE)
+
+    @property
+    def Q(self):
+        return self.row[:self.nx * self.nx].reshape(self.nx, self.nx)
+
+    @property
+    def R(self):
+        return self.row[self.nx * self.nx:self.nx * self.nx + self.nu * self.nu].reshape(self.nu, self.nu)
+
+    @classmethod
+    def from_model(cls, interface):
+        """The model's own weights: what every problem solves under until a row is set."""
+        w = cls(interface.stateDim, interface.inputDim)
+        Q, R = interface.costMatrices()
+        w.Q[:], w.R[:] = Q, R
+        return w
+
+    @classmethod
+    def from_task(cls, interface, Q_task, R_task):
+        """From the two matrices as task.info spells them (bpmpc_model_compose_weights): Q_task [nx, nx] as given, R_task [24, 24] - contact forces,
+        then contact-point velocities - mapped as R = blkdiag(R_F, J^T R_v J) with the contact Jacobians at initialState, like the model's own R."""
+        q, r = _f64(Q_task).reshape(-1), _f64(R_task).reshape(-1)
+        if q.size != interface.stateDim ** 2 or r.size != 24 * 24:
+            raise ValueError("Q_task must be [%d, %d] and R_task [24, 24]" % (interface.stateDim, interface.stateDim))
+        w = cls(interface.stateDim, interface.inputDim)
+        interface._call("bpmpc_model_compose_weights", _d(q), _d(r), _d(w.row))
+        return w
+
+    def scaled(self, q=1.0, r=1.0):
+        """A copy with Q and R scaled: a factor, a vector of nx (nu) factors d - the congruence diag(sqrt d) W diag(sqrt d), which scales diagonal
+        entry i by d_i and keeps the weight symmetric and definite - or a full [n, n] array of per-entry factors."""
+        out = MpcWeights(self.nx, self.nu, self.row)
+        for block, f in ((out.Q, q), (out.R, r)):
+            f = np.asarray(f, float)
+            if f.ndim == 1:
+                if f.size != block.shape[0] or (f < 0).any():
+                    raise ValueError("per-coordinate factors: %d values that are not negative" % block.shape[0])
+                f = np.sqrt(np.outer(f, f))
+            block *= f
+        return out
+
+
 class BipedalRobotInterface(_Handle):
     """Problem definition: model constants + settings (BipedalRobotInterface.cpp:67-204)."""
 
@@ -810,6 +863,37 @@ class BatchedSqpMpc(_Handle):
         (mp, xp), dev, keep = _restart_args((mask, C.c_int, B), (x, C.c_double, B * self.nx))
         self._call("bpmpc_solver_restart", B, mp, xp, dev)
         del keep
+
+    def setWeights(self, rows, mask=None):
+        """Per-problem cost weights (bpmpc_solver_set_weights, include/bpmpc.h "Per-problem cost weights"): the problems with mask[b] != 0 (None:
+        every problem of the last setup) solve under rows[b] - [batch, MpcWeights.STRIDE] - or under the one row [STRIDE] / [1, STRIDE], from the
+        next run on and without a new setup.  rows: MpcWeights, a list of them, numpy arrays, or float64 device tensors (not checked; with them the
+        call only enqueues).  A host row that is not finite, not symmetric, off the model's non-zero pattern or not (semi)definite raises
+        BpmpcError(-1) and changes nothing.  The DDP solver and reference_kernels raise BpmpcError(-3)."""
+        if isinstance(rows, MpcWeights):
+            rows = rows.row
+        elif isinstance(rows, (list, tuple)) and rows and isinstance(rows[0], MpcWeights):
+            rows = np.stack([w.row for w in rows])
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], MpcWeights.STRIDE, self.batch or self.max_batch)
+        self._call("bpmpc_solver_set_weights", B, mp, rp, n_rows, dev)
+        del keep
+
+    def getWeights(self, robot=-1):
+        """The weight row of problem `robot`, or with robot < 0 the start row, the model's Q and R (bpmpc_solver_get_weights; synchronises)."""
+        row = np.zeros(MpcWeights.STRIDE)
+        self._call("bpmpc_solver_get_weights", int(robot), _d(row))
+        return MpcWeights(self.nx, self.nu, row)
+
+    def resetWeights(self):
+        """Every row back to the model's weights and the handle back to the kernels it launched before any row was set (bpmpc_solver_reset_weights)."""
+        self._call("bpmpc_solver_reset_weights")
+
+    def checkWeights(self, row):
+        """The host check of setWeights alone (bpmpc_solver_check_weights): raises BpmpcError(-1) with the entry and the reason, else returns None."""
+        r = _f64(row.row if isinstance(row, MpcWeights) else row).reshape(-1)
+        if r.size != MpcWeights.STRIDE:
+            raise ValueError("a weight row has %d entries" % MpcWeights.STRIDE)
+        self._call("bpmpc_solver_check_weights", _d(r))
 
     def evaluatePolicy(self, t, x):
         """MRT_BASE::evaluatePolicy(t, x) for every problem of the last run (bpmpc_solver_evaluate_policy): t[batch], x[batch, nx] ->

@@ -483,6 +483,17 @@ int bpmpc_model_get(const bpmpc_model* m, const char* name, double* out, int cap
   });
 }
 
+int bpmpc_model_compose_weights(const bpmpc_model* m, const double* Q_task, const double* R_task, double* row_out) {
+  if (!m || !Q_task || !R_task || !row_out) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_model_compose_weights: null argument");
+  return guarded(BPMPC_ERR_IO, [&] {
+    const RobotModel& r = m->rm;
+    const std::vector<double> R = compose_input_weight(r, R_task);      // what load_robot_model runs on the R of task.info
+    std::fill(row_out, row_out + BPMPC_SOLVER_WEIGHT_STRIDE, 0.0);
+    std::copy(Q_task, Q_task + r.nx * r.nx, row_out);
+    std::copy(R.begin(), R.end(), row_out + r.nx * r.nx);
+  });
+}
+
 int bpmpc_model_joint_name(const bpmpc_model* m, int j, char* out, int capacity) {
   if (!m || !out || j < 0 || j >= m->rm.nj) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_model_joint_name: bad argument");
   const std::string& s = m->rm.joint_names[j];

@@ -6,6 +6,7 @@
 
 #include "kernel_launchers.h"
 #include "launch.h"
+#include "node_kernels.h"
 #include "kernels/rollout.h"
 
 namespace bpmpc {
@@ -48,10 +49,7 @@ __global__ __launch_bounds__(kWave) void k_linearize(Launch L) {
   linearize_node<NJ>(*L.model, ws, in, out, L.ilqr != 0, L.ilqr_shift);
 }
 
-constexpr int kTrialWaves = 4; // same for the value-only trial kernel (smaller per-node LDS: four waves, 8 waves per CU)
-// wavefronts per workgroup of the linearisation kernel: they share one copy of the model block in LDS.  Four: 74.3 KB at nx = 22, 79.1 KB
-// at nx = 24 (a wave serves four nodes of 4.2 KB each, packed lanes, LinFastCfg) - two workgroups, eight waves per CU
-template <int NJ> constexpr int lin_waves() { return 4; }      // (five - ten waves per CU - was measured: 0.302 against 0.223 ms at batch 256; the kernel is not short of waves, experiments/LOG.md)
+// (the workgroup shapes kTrialWaves, lin_waves and kTailThreads: node_kernels.h, shared with the per-problem-weight twins of k_weights.hip)
 template <int NJ, bool MAT, bool CHAIN, bool ILQR = false>      // ILQR: the DDP solver's Euler-discretised model (linearize_fast.h)
 __global__ __launch_bounds__(lin_waves<NJ>() * kWave) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_linearize_fast(Launch L) {
   using C = LinFastCfg<NJ, true, CHAIN>;
@@ -323,7 +321,6 @@ __global__ __launch_bounds__(kDecideThreads) void k_ls_decide(Launch L, int look
 // up.  The host never reads a flag back inside a solve, so consecutive solves queue without a gap.  The few problems that back-track
 // are alone on their CUs and what they cost is the latency of their rounds: eight waves walk the horizon in half the chunks of four
 // (the sums are the ones of k_ls_decide term by term while the horizon has at most kDecideThreads nodes).
-constexpr int kTailThreads = 512;
 template <int NJ, bool CHAIN>
 __global__ __launch_bounds__(kTailThreads) void k_ls_tail(Launch L, int first_round, int max_trials, int pending) {
   using C = LinFastCfg<NJ, true, CHAIN>;

@@ -25,6 +25,14 @@ struct TickArgs;
 struct TickCommandArgs;
 struct RestartArgs;
 
+// The per-problem cost weights of a solver handle as the kernels read them (bpmpc_solver_set_weights): rows [batch][BPMPC_SOLVER_WEIGHT_STRIDE],
+// Q then R per problem; q_diag [batch][kWeightDim], the diagonals of Q derived from the rows.  rows == nullptr: the model's weights, the kernels of
+// k_node.hip / k_project.hip.
+struct WeightRows {
+  const double* rows = nullptr;
+  const double* q_diag = nullptr;
+};
+
 namespace kl {
 
 // ---- k_node.hip: per-node kernels in the lane-per-coordinate mapping, line search, warm start, policy rollout
@@ -47,6 +55,14 @@ void copy_pairs(int grid, hipStream_t st, const double* a_src, double* a_dst, si
 void project_reference(int nj, int slots, hipStream_t st, const Launch& L);
 void project_lu_s(int nj, int max_vel_rows, bool packed, int nodes, hipStream_t st, const Launch& L);
 void project_fast(int nj, bool packed, bool joint_rows, int nodes, hipStream_t st, const Launch& L);
+
+// ---- k_weights.hip: the kernels that read Q / R, on per-problem weight rows (same arguments as their namesakes; w.rows != nullptr).  The lineariser
+// maps ceil(nodes / 16) workgroups onto every problem, so it takes no node count
+void linearize_fast_w(int nj, bool materialise, hipStream_t st, const Launch& L, const WeightRows& w, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+void trial_fast_w(int nj, int nodes, hipStream_t st, const Launch& L, const WeightRows& w);
+void ls_tail_w(int nj, int batch, hipStream_t st, const Launch& L, int first_round, int max_trials, bool pending, const WeightRows& w);
+void project_fast_w(int nj, bool packed, bool joint_rows, int nodes, hipStream_t st, const Launch& L, const WeightRows& w);
+void weight_diagonals(hipStream_t st, const double* rows, double* q_diag, int n_rows, int nx);      // q_diag[b][c] = Q_b[c][c]
 
 // ---- k_riccati.hip: workgroup-per-problem sweeps
 void riccati_reference(int nj, int batch, hipStream_t st, const Launch& L);

@@ -1175,10 +1175,14 @@ __device__ __forceinline__ TrialPre trial_preload(const double* x, const double*
 }
 // LISTS = false: the dense cost sums whatever the model says (the back-tracking tail, k_ls_tail: 248 .. 256 registers before this choice existed,
 // and both sums in one kernel sent it to scratch memory; the same bits either way)
-template <int NJ, class Cfg = LinFastCfg<NJ, true>, bool EQV = false, class NL = LinFastNodeLds<NJ, false, Cfg::CHAIN>, bool LISTS = true>
+// ROWS: the cost sums read the node's own weights W - Q (stride NX) then R (stride NU), a row of bpmpc_solver_set_weights - densely, instead of the
+// model's (the per-problem kernels of k_weights.hip).  A compile-time branch: the instantiations without it must compile to what they compiled to
+// before it existed (profiles/solver_weights_isa_check.txt), and a run-time test of W, though constant after inlining, moved instructions of
+// k_ddp_cost_fast<12> and k_ls_tail<12>.
+template <int NJ, class Cfg = LinFastCfg<NJ, true>, bool EQV = false, class NL = LinFastNodeLds<NJ, false, Cfg::CHAIN>, bool LISTS = true, bool ROWS = false>
 __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastShared<NJ, false>& sh, NL& nl, bool valid,
                                            const NodeInputs& in, double alpha, const double* dx, const double* du, const double* dxn,
-                                           double* perf, int ln, double* eqv = nullptr, const TrialPre* pre = nullptr) {
+                                           double* perf, int ln, double* eqv = nullptr, const TrialPre* pre = nullptr, const double* W = nullptr) {
   using C = Cfg;
   constexpr int G = C::G, NX = C::NX, NU = C::NU, LPN = C::LPN, G0 = C::G0;
   const int g = ln + G0;
@@ -1316,6 +1320,18 @@ __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastS
   {
     const int cq = 6 + g, ch = ln, cf = ln, cj = 12 + g - 6, ct = 6 + ln;
     double accq = 0.0, acch = 0.0, accf = 0.0, accj = 0.0, acct = 0.0;
+    if constexpr (ROWS) {                                // the node's own weights (no lists: those hold the model's values), the dense sums of the last branch
+      const double* wq = W;
+      const double* wr = W + NX * NX;
+      for (int r = 0; r < NX; ++r) {
+        const double dxr = nl.dx[r], dur = nl.du[r];
+        if (g < G) accq += wq[cq * NX + r] * dxr;
+        if (tr) acct += wq[ct * NX + r] * dxr;
+        if (ln < 6) acch += wq[ch * NX + r] * dxr;
+        if (ln < 12) accf += wr[cf * NU + r] * dur;
+        if (is_joint) accj += wr[cj * NU + r] * dur;
+      }
+    } else
     if (LISTS && __builtin_amdgcn_readfirstlane(sc.w_compact)) {
       // the non-zero lists of the weights from global memory (cache resident, as the dense weights below): term j of the rows of sixteen lanes is one
       // 128-byte line - 26 coalesced requests on the 22-state robots where the dense rows, 176 bytes apart from lane to lane, took 110 that touch

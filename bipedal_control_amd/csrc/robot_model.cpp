@@ -141,6 +141,31 @@ void contact_points(const RobotModel& m, const double* q, double pos[kNumContact
   }
 }
 
+// R = blkdiag(R_task[forces], J^T R_task[feet] J) (the declaration in robot_model.h)
+std::vector<double> compose_input_weight(const RobotModel& m, const double* Rt) {
+  const int tc = 3 * kNumContacts;
+  std::vector<double> J(static_cast<size_t>(tc) * m.nj);
+  double pos[kNumContacts][3];
+  contact_points(m, m.initial_state.data() + 6, pos, J.data());
+  std::vector<double> R(static_cast<size_t>(m.nu) * m.nu, 0.0);
+  for (int i = 0; i < tc; ++i)
+    for (int j = 0; j < tc; ++j) R[i * m.nu + j] = Rt[i * 2 * tc + j];
+  std::vector<double> RJ(static_cast<size_t>(tc) * m.nj);
+  for (int i = 0; i < tc; ++i)
+    for (int j = 0; j < m.nj; ++j) {
+      double t = 0;
+      for (int l = 0; l < tc; ++l) t += Rt[(tc + i) * 2 * tc + tc + l] * J[l * m.nj + j];
+      RJ[i * m.nj + j] = t;
+    }
+  for (int i = 0; i < m.nj; ++i)
+    for (int j = 0; j < m.nj; ++j) {
+      double t = 0;
+      for (int l = 0; l < tc; ++l) t += J[l * m.nj + i] * RJ[l * m.nj + j];
+      R[(tc + i) * m.nu + tc + j] = t;
+    }
+  return R;
+}
+
 RobotModel load_robot_model(const std::string& urdf_path, const std::string& task_info, const std::string& reference_info) {
   const auto task = read_info_file(task_info);
   const auto ref = read_info_file(reference_info);
@@ -296,27 +321,7 @@ RobotModel load_robot_model(const std::string& urdf_path, const std::string& tas
   // cost weights: Q as given; R = blkdiag(R_task[forces], J^T R_task[feet] J) with J the contact-point Jacobians
   // w.r.t. the leg joints at initialState (BipedalRobotInterface.cpp:239-271)
   m.Q = load_matrix(*task, "Q", m.nx, m.nx);
-  const int tc = 3 * kNumContacts;
-  const std::vector<double> Rt = load_matrix(*task, "R", 2 * tc, 2 * tc);
-  std::vector<double> J(static_cast<size_t>(tc) * m.nj);
-  double pos[kNumContacts][3];
-  contact_points(m, m.initial_state.data() + 6, pos, J.data());
-  m.R.assign(static_cast<size_t>(m.nu) * m.nu, 0.0);
-  for (int i = 0; i < tc; ++i)
-    for (int j = 0; j < tc; ++j) m.R[i * m.nu + j] = Rt[i * 2 * tc + j];
-  std::vector<double> RJ(static_cast<size_t>(tc) * m.nj);
-  for (int i = 0; i < tc; ++i)
-    for (int j = 0; j < m.nj; ++j) {
-      double t = 0;
-      for (int l = 0; l < tc; ++l) t += Rt[(tc + i) * 2 * tc + tc + l] * J[l * m.nj + j];
-      RJ[i * m.nj + j] = t;
-    }
-  for (int i = 0; i < m.nj; ++i)
-    for (int j = 0; j < m.nj; ++j) {
-      double t = 0;
-      for (int l = 0; l < tc; ++l) t += J[l * m.nj + i] * RJ[l * m.nj + j];
-      m.R[(tc + i) * m.nu + tc + j] = t;
-    }
+  m.R = compose_input_weight(m, load_matrix(*task, "R", 6 * kNumContacts, 6 * kNumContacts).data());
 
   // gait bootstrap (BipedalRobotInterface.cpp:209-234, ModeSequenceTemplate.cpp:50-111)
   m.initial_mode_schedule.event_times = load_scalar_list(*ref, "initialModeSchedule.eventTimes");

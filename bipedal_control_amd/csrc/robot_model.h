@@ -107,4 +107,9 @@ ModeTemplate load_mode_template(const std::string& gait_info, const std::string&
 // q = [p(3), zyx(3), joints(nj)] (host double precision; used for the input-cost matrix and by tests).
 void contact_points(const RobotModel& m, const double* q, double pos[kNumContacts][3], double* jac_joints /*12 x nj or null*/);
 
+// The input weight of the model from the R of task.info (R_task: 24 x 24 row major, contact forces then contact-point velocities):
+// R = blkdiag(R_task[forces], J^T R_task[feet] J), nu x nu row major, with J the contact-point Jacobians w.r.t. the leg joints at initialState
+// (BipedalRobotInterface.cpp:239-271).  What load_robot_model runs at ingest and bpmpc_model_compose_weights on the caller's matrices.
+std::vector<double> compose_input_weight(const RobotModel& m, const double* R_task);
+
 }  // namespace bpmpc

@@ -132,6 +132,15 @@ struct bpmpc_solver {
   // finish_setup.  Everything else is fixed when the solver is created: d_model, dm, rm, sw, ls, and of settings max_nodes, reg_prim, solver and
   // feedback_policy (set_materialize and set_profile write fields no launch reads from here).
   Launch plan{};
+  // The part of the plan that changes BETWEEN setups: the per-problem cost weights (solver_weights.hip).  rows == nullptr - a handle that never had
+  // a row set, or has been reset - launches the kernels of k_node.hip / k_project.hip; from the first bpmpc_solver_set_weights on every kernel that
+  // reads Q or R (lineariser, trial, back-tracking tail, change of variables) is its twin of k_weights.hip, for every problem of the batch.
+  // build_plan leaves it alone: the weights enter neither the grids nor the references, so no setup is needed after a set.
+  WeightRows plan_weights{};
+  DeviceBuffers weight_mem;                                // the table's memory (allocated by the first set_weights, freed with the handle)
+  ParamTable weights;                                      // rows [max_batch][BPMPC_SOLVER_WEIGHT_STRIDE], start row = the model's Q, R
+  double* weight_q_diag = nullptr;                         // [max_batch][kWeightDim]: the diagonals of Q, derived behind every write (k_weight_diagonals)
+  int* weight_mask = nullptr;                              // [max_batch] device copy of a host mask
   void build_plan() {
     Launch& L = plan;
     L.model = d_model;
@@ -163,6 +172,11 @@ struct bpmpc_solver {
   // The lineariser's events are attached to its dispatch (kl::linearize_fast): their elapsed time is the kernel's duration, without the barrier
   // packets and the dispatch latency a pair of hipEventRecord calls brackets as well
   void launch_linearize_fast(hipStream_t on, const Launch& L, int nodes) {
+    if (plan_weights.rows) {                               // per-problem weights: kernel class "linearize_w" (bpmpc_solver_kernel_time)
+      if (!KernelTimers::timed(settings.profile, "linearize_w")) { kl::linearize_fast_w(nj(), settings.materialize_lq != 0, on, L, plan_weights); return; }
+      timers.attached("linearize_w", [&](hipEvent_t a, hipEvent_t b) { kl::linearize_fast_w(nj(), settings.materialize_lq != 0, on, L, plan_weights, a, b); });
+      return;
+    }
     if (!KernelTimers::timed(settings.profile, "linearize")) { kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L); return; }
     timers.attached("linearize", [&](hipEvent_t a, hipEvent_t b) { kl::linearize_fast(nj(), settings.materialize_lq != 0, nodes, on, L, a, b); });
   }
@@ -240,6 +254,7 @@ void refuse_while_restarting(const bpmpc_solver* s, const char* what);
 void check_policy(const bpmpc_solver* s);                 // controller tick / evaluate_policy: SQP, no restart pending, a completed run, the gains
 void check_restart(const bpmpc_solver* s, int batch);
 void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device);
+void release_weights(bpmpc_solver* s);                    // solver_weights.hip: the weight table's memory (bpmpc_solver_destroy)
 
 // The guard of the entry points on a solver handle (guarded): the handle's device is set before the body, BPMPC_ERR_IO for an exception of no
 // class of its own.

@@ -76,7 +76,8 @@ void bpmpc_solver::launch_project(hipStream_t on, const Launch& L, int nodes) {
   // packed joint rows of [Px | Pe | Pu] when the input weight allows the change of variables to generate the force rows; Px, Pu, Pe for the
   // general one (which packs the joint rows for the sweeps' loaders itself)
   TIMED_ON(on, "project_lu", kl::project_lu_s(nj(), max_vel_rows, structured_project, nodes, on, L));
-  TIMED_ON(on, "project", kl::project_fast(nj(), structured_project, joint_rows(), nodes, on, L));
+  if (plan_weights.rows) TIMED_ON(on, "project_w", kl::project_fast_w(nj(), structured_project, joint_rows(), nodes, on, L, plan_weights));
+  else TIMED_ON(on, "project", kl::project_fast(nj(), structured_project, joint_rows(), nodes, on, L));
 }
 void bpmpc_solver::stage_project() {
   if (settings.reference_kernels) TIMED("project", kl::project_reference(nj(), batch * settings.max_nodes, stream, plan));
@@ -102,7 +103,9 @@ void bpmpc_solver::stage_linesearch() {
   const Launch& L = plan;
   if (settings.reference_kernels) HIP_CHECK(hipMemsetAsync(buf.remaining, 0, sizeof(int), stream));   // only the host loop below reads the counter
   hipEvent_t ev_a, ev_b;
-  timers.begin(settings.profile, stream, "linesearch", &ev_a, &ev_b);
+  const WeightRows& w = plan_weights;                     // per-problem weights: the twins of the trial and of the tail, kernel class "linesearch_w"
+  const char* cls = w.rows ? "linesearch_w" : "linesearch";
+  timers.begin(settings.profile, stream, cls, &ev_a, &ev_b);
   if (settings.reference_kernels) kl::ls_begin(nj(), batch, stream, L);   // fast path: done inside the Riccati kernel
   // alpha = 1, 1/2, ... >= alpha_min  ([OCS2-upstream] SqpSolver::takeStep do-while)
   int max_trials = 0;
@@ -116,13 +119,15 @@ void bpmpc_solver::stage_linesearch() {
     int round = 0;
     bool pending = false;                                  // the last of these rounds is judged by k_ls_tail (the workgroups of the few problems still open)
     for (; round < wide_rounds && round < max_trials; ++round) {
-      kl::trial_fast(nj(), nodes, stream, L);
+      if (w.rows) kl::trial_fast_w(nj(), nodes, stream, L, w);
+      else kl::trial_fast(nj(), nodes, stream, L);
       pending = round > 0 && (round + 1 == wide_rounds || round + 1 == max_trials);
       if (!pending) kl::ls_decide(nj(), batch, stream, L, round > 0);
     }
-    kl::ls_tail(nj(), batch, stream, L, round, max_trials, pending);
+    if (w.rows) kl::ls_tail_w(nj(), batch, stream, L, round, max_trials, pending, w);
+    else kl::ls_tail(nj(), batch, stream, L, round, max_trials, pending);
     HIP_CHECK(hipGetLastError());
-    timers.end(settings.profile, stream, "linesearch", ev_a, ev_b);
+    timers.end(settings.profile, stream, cls, ev_a, ev_b);
     return;
   }
   for (int t = 0; t < max_trials; ++t) {
@@ -134,7 +139,7 @@ void bpmpc_solver::stage_linesearch() {
     HIP_CHECK(hipStreamSynchronize(stream));
     if (*h_remaining <= 0) break;
   }
-  timers.end(settings.profile, stream, "linesearch", ev_a, ev_b);
+  timers.end(settings.profile, stream, cls, ev_a, ev_b);
 }
 // Linearisation, projection and Riccati sweep of one SQP iteration with the horizon cut into chunks: the producers
 // (linearise, LU, change of variables) of chunk c+1 run on their own stream while the latency-bound Riccati sweep of
@@ -936,6 +941,7 @@ void bpmpc_solver_destroy(bpmpc_solver* s) {
   if (s->ev_go) (void)hipEventDestroy(s->ev_go);
   for (hipEvent_t e : s->ev_chunk) if (e) (void)hipEventDestroy(e);
   for (void* p : s->allocations) (void)hipFree(p);
+  release_weights(s);
   if (s->d_model) (void)hipFree(s->d_model);
   if (s->h_remaining) (void)hipHostFree(s->h_remaining);
   s->pin_up.release(); s->pin_down.release();

@@ -545,7 +545,9 @@ int bpmpc_controller_restart(bpmpc_controller* controller, int batch, const int*
  *               which with zero gains is the WBC torque bit for bit.  bpmpc_controller_joint_outputs: every argument nullable; host_*
  *               [batch*nj] receive the last tick's joint_torque and the current gains and make the call synchronise; dev_* receive the handle's
  *               buffers (leading dimension the WBC's max_batch, like bpmpc_controller_device_outputs).
- * Not reproduced: per-robot MPC cost weights, UpperJointController (the MPC models carry no upper-body joints).  The SafetyChecker limits and
+ * Not reproduced: per-robot MPC cost weights, UpperJointController (the MPC models carry no upper-body joints).  (The reference's server has no
+ * MPC weights to reproduce; per-problem weights of the solver handle are this engine's own extension, "Per-problem cost weights" below, and no
+ * part of this interface.)  The SafetyChecker limits and
  * InitialJointController are the supervisor's ("Supervisor" below).
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_WBC_PARAM_STRIDE 32
@@ -567,6 +569,45 @@ int bpmpc_controller_set_joint_gains(bpmpc_controller* controller, int batch, co
                                      int inputs_on_device);
 int bpmpc_controller_joint_outputs(bpmpc_controller* controller, int batch, double* host_torque, double* host_kp, double* host_kd,
                                    double** dev_torque, double** dev_kp, double** dev_kd);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-problem cost weights: every problem of an SQP solver handle solves under a weight row of its own, settable at run time like the rows above
+ * (this engine's extension: the reference fixes Q and R when BipedalRobotInterface reads task.info).  One handle, one setup and one run then
+ * cover a sweep of Q / R candidates or a fleet whose robots weigh tracking differently.
+ *   row         BPMPC_SOLVER_WEIGHT_STRIDE = 2 * 24 * 24 doubles, dense and row major: Q (nx x nx, stride nx) followed by R (nu x nu, stride nu) -
+ *               the blocks bpmpc_model_get "Q" / "R" return; nx*nx + nu*nu entries are used, the rest reads 0.  The start row is the model's Q, R.
+ *   set         bpmpc_solver_set_weights: the rows of the problems with mask[b] != 0 (mask NULL: every problem) become rows[b] (n_rows == batch) or
+ *               rows[0] (n_rows == 1); batch must equal the batch of the last setup.  Every bpmpc_solver_run enqueued after the call solves under
+ *               the new rows; no new setup is needed (the weights enter neither the grids nor the references).  With host arrays the call
+ *               synchronises; inputs_on_device != 0: mask and rows are device pointers and the call only enqueues on the solver's stream (the
+ *               first set on a handle also allocates the table: 2 * max_batch rows).  From the first set on, the handle launches the
+ *               per-problem kernels for EVERY problem of the batch (lineariser, line-search trials, change of variables: k_weights.hip; kernel
+ *               classes "linearize_w", "linesearch_w", "project_w" of bpmpc_solver_kernel_time), also for rows equal to the model's.
+ *   check       a host row is refused with BPMPC_ERR_INVALID_ARGUMENT - the entry and the reason in bpmpc_last_error(), nothing written, nothing
+ *               enqueued, the kernels unchanged - when an entry is not finite; when Q or R is not symmetric (relative 1e-9); when it has a non-zero
+ *               where the model's Q or R has a structural zero (the PATTERN rule: the hot kernels and the solver's choice of kernels are built on
+ *               the model's pattern - non-zero lists, a diagonal Q, R without force / joint-velocity cross terms - and stay valid for every row
+ *               this way; zeroing an entry the model has is allowed); when a diagonal Q has a negative entry (a model whose Q is not diagonal: when
+ *               Q is not positive semidefinite); when R is not positive definite (pivoted Cholesky on the host; a model whose own R is only positive
+ *               semidefinite - six joints per leg: J^T R_v J has rank 10 - asks its rows for semidefiniteness).  bpmpc_solver_check_weights runs this
+ *               check alone.  Device rows are NOT checked: a device row outside these rules gives undefined results for its own problem only.
+ *   get / reset bpmpc_solver_get_weights: row[BPMPC_SOLVER_WEIGHT_STRIDE] = the start row (robot < 0) or the problem's current row; synchronises.
+ *               bpmpc_solver_reset_weights: every row back to the start row, and the handle back to the kernels it launched before any row was
+ *               set.  bpmpc_solver_reset and the restarts keep the rows.
+ *   compose     bpmpc_model_compose_weights (host only, no device): a row from the two matrices as task.info spells them - Q_task nx x nx as
+ *               given, R_task 24 x 24 (contact forces, then contact-point velocities) mapped as R = blkdiag(R_F, J^T R_v J) with the contact
+ *               Jacobians at initialState, by the function the model's own R is built with (BipedalRobotInterface.cpp:239-271): the Q and R of
+ *               the task file reproduce bpmpc_model_get "Q" / "R" bit for bit.
+ * BPMPC_ERR_UNSUPPORTED: the DDP solver (its cost of recorded points and its ILQR lineariser stay on the model's weights) and
+ * settings.reference_kernels (the lane-emulation bodies read the model's Q and R), like reg_prim and bpmpc_solver_restart on those paths.
+ * Not per problem: the cone parameters (friction, barrier mu / delta), kinematic and inertial constants of the MPC model.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_SOLVER_WEIGHT_STRIDE (2 * 24 * 24)
+int bpmpc_solver_set_weights(bpmpc_solver* solver, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_solver_get_weights(bpmpc_solver* solver, int robot, double* row);
+int bpmpc_solver_reset_weights(bpmpc_solver* solver);
+int bpmpc_solver_check_weights(const bpmpc_solver* solver, const double* row);
+int bpmpc_model_compose_weights(const bpmpc_model* model, const double* Q_task, const double* R_task, double* row_out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * State estimation = BipedalController::updateStateEstimation (bipedal_controllers/src/BipedalController.cpp:188, :360-405) for a BATCH of robots:
