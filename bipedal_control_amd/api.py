@@ -905,6 +905,57 @@ class BatchedSqpMpc(_Handle):
         self._call("bpmpc_solver_evaluate_policy", B, _d(t), _d(x), _d(x_opt), _d(u_opt), _i(mode))
         return x_opt, u_opt, mode
 
+    # ---- the value function of the QP a run has solved (include/bpmpc.h "Value function")
+    def enableValueFunction(self, on=True):
+        """From the next run on, every backward pass is followed by the value function of its QP, V_k(dx) = v_k + s_k'dx + dx'S_k dx / 2 around the
+        expansion point x_lin,k of every node (bpmpc_solver_enable_value_function).  The handle then linearises in materialised form (the solution
+        keeps its bits).  on=False stops the launches and keeps the buffers.  The DDP solver raises BpmpcError(-3)."""
+        self._call("bpmpc_solver_enable_value_function", int(bool(on)))
+
+    def valueFunction(self):
+        """(S [B, N + 1, nx, nx], s [B, N + 1, nx], v [B, N + 1], x_lin [B, N + 1, nx], status [B]) of the last run, N = max_nodes
+        (bpmpc_solver_value_function; synchronises).  status: 0 none yet, 1 valid, 2 the problem's sweep failed (rows as they were); entries beyond
+        n_nodes[b] are never written."""
+        B, K, nx = self.layout()["batch"], self.max_nodes + 1, self.nx      # the library copies the batch of ITS last setup
+        S, s, v, x_lin, status = np.zeros((B, K, nx, nx)), np.zeros((B, K, nx)), np.zeros((B, K)), np.zeros((B, K, nx)), np.zeros(B, np.int32)
+        self._call("bpmpc_solver_value_function", _d(S), _d(s), _d(v), _d(x_lin), _i(status))
+        return S, s, v, x_lin, status
+
+    def valueFunctionDevice(self):
+        """The same five arrays where they live: a dict of DeviceArray over max_batch problems (bpmpc_solver_device_value_function; no
+        synchronisation)."""
+        S, s, v, xl, st = _dp(), _dp(), _dp(), _dp(), _ip()
+        self._call("bpmpc_solver_device_value_function", C.byref(S), C.byref(s), C.byref(v), C.byref(xl), C.byref(st))
+        B, K, nx = self.max_batch, self.max_nodes + 1, self.nx
+        ptr = lambda p: C.cast(p, C.c_void_p).value
+        return {"S": DeviceArray(ptr(S), (B, K, nx, nx), "<f8"), "s": DeviceArray(ptr(s), (B, K, nx), "<f8"), "v": DeviceArray(ptr(v), (B, K), "<f8"),
+                "x_lin": DeviceArray(ptr(xl), (B, K, nx), "<f8"), "status": DeviceArray(ptr(st), (B,), "<i4")}
+
+    def evaluateValue(self, t, x, hessian=True):
+        """V(t, x) of every problem of the last run, its gradient and Hessian (bpmpc_solver_evaluate_value): t[batch], x[batch, nx] ->
+        (f [batch], dfdx [batch, nx], dfdxx [batch, nx, nx] or None).  t is clamped to the solution's span; S, s, v and the expansion point are
+        interpolated as evaluatePolicy interpolates the states.  numpy inputs: numpy results, the call synchronises.  float64 device tensors (e.g.
+        the observations of BatchedController.device_outputs()): the call only enqueues on the solver's stream and the results are DeviceArray
+        over torch tensors it allocates - synchronise the solver before another stream reads them."""
+        B, nx = self.batch, self.nx
+        if all(getattr(a, "is_cuda", False) or hasattr(a, "__cuda_array_interface__") for a in (t, x)):
+            import torch
+            (tp, xp), dev, keep = _restart_args((t, C.c_double, B), (x, C.c_double, B * nx))
+            out = [torch.empty(shape, dtype=torch.float64, device="cuda") for shape in ((B,), (B, nx)) + (((B, nx, nx),) if hessian else ())]
+            ptrs = [C.cast(C.c_void_p(o.data_ptr()), _dp) for o in out] + ([] if hessian else [None])
+            self._call("bpmpc_solver_evaluate_value", B, tp, xp, 1, *ptrs)
+            del keep
+            views = []
+            for o in out:
+                views.append(DeviceArray(o.data_ptr(), o.shape, "<f8"))
+                views[-1].owner = o                     # the tensor lives as long as its view
+            return tuple(views) + (() if hessian else (None,))
+        t = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
+        x = _f64(x).reshape(B, nx)
+        f, g, h = np.zeros(B), np.zeros((B, nx)), np.zeros((B, nx, nx)) if hessian else None
+        self._call("bpmpc_solver_evaluate_value", B, _d(t), _d(x), 0, _d(f), _d(g), _d(h))
+        return f, g, h
+
 
 class WeightedWbc(_Handle):
     """A batch of WeightedWbc instances on one MI355X (bipedal_wbc/include/bipedal_wbc/WeightedWbc.h; construction + loadTasksSetting as

@@ -17,6 +17,7 @@
 #include "kernel_timers.h"
 #include "launch.h"
 #include "sweep_plan.h"
+#include "value_kernels.h"
 #include "kernels/reference_device.h"
 
 using namespace bpmpc;
@@ -141,6 +142,14 @@ struct bpmpc_solver {
   ParamTable weights;                                      // rows [max_batch][BPMPC_SOLVER_WEIGHT_STRIDE], start row = the model's Q, R
   double* weight_q_diag = nullptr;                         // [max_batch][kWeightDim]: the diagonals of Q, derived behind every write (k_weight_diagonals)
   int* weight_mask = nullptr;                              // [max_batch] device copy of a host mask
+  // The value function (solver_value.hip, include/bpmpc.h "Value function"): its buffers exist from the first bpmpc_solver_enable_value_function
+  // on (value.S == nullptr before: nothing allocated, nothing launched); value_on: every backward pass is followed by the two kernels of
+  // k_value.hip.  While it is on the handle linearises in materialised form; own_materialize is the setting it goes back to.
+  ValueArgs value{};
+  DeviceBuffers value_mem;
+  bool value_on = false;
+  int own_materialize = 0;
+  void launch_value();                                     // solver_value.hip: k_value_terms, k_value_sweep on the current buffers, on `stream`
   void build_plan() {
     Launch& L = plan;
     L.model = d_model;
@@ -255,6 +264,7 @@ void check_policy(const bpmpc_solver* s);                 // controller tick / e
 void check_restart(const bpmpc_solver* s, int batch);
 void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device);
 void release_weights(bpmpc_solver* s);                    // solver_weights.hip: the weight table's memory (bpmpc_solver_destroy)
+void release_value(bpmpc_solver* s);                      // solver_value.hip: the value buffers (bpmpc_solver_destroy)
 
 // The guard of the entry points on a solver handle (guarded): the handle's device is set before the body, BPMPC_ERR_IO for an exception of no
 // class of its own.

@@ -166,6 +166,7 @@ void bpmpc_solver::pipelined_backward() {
     if (c == 0) { L.klen = settings.max_nodes - lo; }   // problems on longer grids than n_nodes_max do not exist; keep k_hi >= N
     launch_riccati(L);
   }
+  if (value_on) launch_value();                          // behind the last chunk: the whole horizon's model, gains and step are in place
 }
 
 void bpmpc_solver::run_iterations() {
@@ -184,6 +185,7 @@ void bpmpc_solver::run_iterations() {
       stage_linearize();
       stage_project();
       stage_riccati();
+      if (value_on) launch_value();                        // before the line search moves x: the value function of this iteration's QP
     }
     stage_linesearch();
   }
@@ -878,6 +880,7 @@ int bpmpc_solver_create(const bpmpc_model* model, const bpmpc_settings* settings
     if (!(settings->reg_prim >= 0.0)) { set_last_error("reg_prim must be >= 0"); return BPMPC_ERR_INVALID_ARGUMENT; }
     s->dm = make_device_model(s->rm);
     s->settings = *settings;
+    s->own_materialize = settings->materialize_lq;
     if (settings->solver != BPMPC_SOLVER_SQP && settings->solver != BPMPC_SOLVER_DDP) { set_last_error("bpmpc_solver_create: unknown solver"); return BPMPC_ERR_INVALID_ARGUMENT; }
     if (settings->feedback_policy < 0 || settings->feedback_policy > 2) { set_last_error("bpmpc_solver_create: feedback_policy must be 0, 1 or 2"); return BPMPC_ERR_INVALID_ARGUMENT; }
     if (settings->solver == BPMPC_SOLVER_DDP) {
@@ -942,6 +945,7 @@ void bpmpc_solver_destroy(bpmpc_solver* s) {
   for (hipEvent_t e : s->ev_chunk) if (e) (void)hipEventDestroy(e);
   for (void* p : s->allocations) (void)hipFree(p);
   release_weights(s);
+  release_value(s);
   if (s->d_model) (void)hipFree(s->d_model);
   if (s->h_remaining) (void)hipHostFree(s->h_remaining);
   s->pin_up.release(); s->pin_down.release();
@@ -987,7 +991,8 @@ int bpmpc_solver_rollout(bpmpc_solver* s, const double* t_start, const double* x
 }
 int bpmpc_solver_set_materialize(bpmpc_solver* s, int materialize_lq) {
   if (!s) { set_last_error("bpmpc_solver_set_materialize: null solver handle"); return BPMPC_ERR_INVALID_ARGUMENT; }
-  s->settings.materialize_lq = materialize_lq != 0;
+  s->own_materialize = materialize_lq != 0;
+  if (!s->value_on) s->settings.materialize_lq = s->own_materialize;      // the value function reads the materialised model: remembered until it is off
   return BPMPC_OK;
 }
 int bpmpc_solver_set_profile(bpmpc_solver* s, int level) {
@@ -1015,6 +1020,10 @@ int bpmpc_solver_stage(bpmpc_solver* s, const char* stage) {
     else if (n == "project") s->stage_project();
     else if (n == "riccati") s->stage_riccati();
     else if (n == "linesearch") s->stage_linesearch();
+    else if (n == "value") {
+      if (!s->value_on) throw std::invalid_argument("bpmpc_solver_stage: \"value\" needs bpmpc_solver_enable_value_function");
+      s->launch_value();
+    }
     else throw std::invalid_argument("unknown stage " + n);
   });
 }

@@ -355,7 +355,7 @@ int bpmpc_solver_run(bpmpc_solver* solver);     /* enqueue the SQP iteration(s) 
 int bpmpc_solver_sync(bpmpc_solver* solver);
 int bpmpc_solver_fetch(bpmpc_solver* solver, double* out_t, double* out_x, double* out_u, double* out_K, bpmpc_stats* stats);
 /* Run one stage of an iteration on the current iterate (parity tests, roofline measurement):
- * "linearize", "project", "riccati", "linesearch". */
+ * "linearize", "project", "riccati", "linesearch"; "value" with the value function enabled ("Value function" below). */
 int bpmpc_solver_stage(bpmpc_solver* solver, const char* stage);
 /* Copy a named device buffer to the host (tests): "x","u","xref","A","B","b","Q","R","P","q","r","c","C","D","e","nc","perf",
  * "Px","Pu","Pe","nut","dx","du","K","Acl","summary","stats","g_kind","g_mode","g_nodes","g_dt","g_start","g_zref","g_zdref","g_time",
@@ -608,6 +608,52 @@ int bpmpc_solver_get_weights(bpmpc_solver* solver, int robot, double* row);
 int bpmpc_solver_reset_weights(bpmpc_solver* solver);
 int bpmpc_solver_check_weights(const bpmpc_solver* solver, const double* row);
 int bpmpc_model_compose_weights(const bpmpc_model* model, const double* Q_task, const double* R_task, double* row_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Value function: the cost-to-go of the QP an SQP solver handle has just solved, per node of every problem and on query (this engine's
+ * extension; what SolverBase::getValueFunction asks for, and the one SolverBase query a multiple-shooting SQP can answer exactly).
+ *   definition  Take the QP of the LAST SWEPT SQP iteration of problem b in the unprojected LQ model - A, B, b, Q, R, P, q, r, c per node as
+ *               bpmpc_solver_read names them, the cost already times dt, event nodes identity jumps (the stored b) without cost.  The sweep's
+ *               optimal feasible policy is du = K_k dx + kappa_k with kappa_k = du_k - K_k dx_k from the stored K, dx, du; the equality
+ *               constraints live inside K, so the cost-to-go of that policy is the QP's value function for EVERY dx, not only on the optimal
+ *               trajectory:
+ *                   V_k(dx) = v_k + s_k' dx + dx' S_k dx / 2        k = 0 .. n_nodes[b],   V_n = 0 (there is no final cost)
+ *                   Acl = A + B K     bcl = b + B kappa     Qcl = Q + K'(R K + P) + P'K     qcl = q + K'r + (P' + K'R) kappa
+ *                   ccl = c + r'kappa + kappa'R kappa / 2
+ *                   S_k = Qcl + Acl' S+ Acl     s_k = qcl + Acl'(s+ + S+ bcl)     v_k = ccl + v+ + s+'bcl + bcl' S+ bcl / 2
+ *               S_k is stored symmetrised as computed, (S + S') / 2.  dx is measured from the EXPANSION POINT x_lin,k: the iterate the model was
+ *               linearised at, i.e. x before the line search of that iteration moved it; the handle keeps its own copy.  Nothing is assumed of
+ *               the sparsity of Q, R or P: the kernels read what the lineariser wrote (hard-cone model, per-problem weights included).
+ *   enable      bpmpc_solver_enable_value_function(on != 0) allocates the buffers (once, at the first such call) and from then on every
+ *               bpmpc_solver_run computes the value function behind the backward pass of every iteration (behind the last chunk with
+ *               pipeline_chunks > 1) and before that iteration's line search touches x: two kernels on the solver's stream (k_value.hip; kernel
+ *               classes "value_terms", "value_sweep" of bpmpc_solver_kernel_time), nothing read back or waited for.  Such a handle linearises in
+ *               MATERIALISED form: a handle created with materialize_lq = 0 switches as bpmpc_solver_set_materialize(solver, 1) would - the
+ *               solution stays the same bits, which is the contract of the two modes - and a bpmpc_solver_set_materialize while the feature is
+ *               on is remembered, not applied.  on == 0 stops the launches, puts the handle's own materialise setting back and keeps the
+ *               buffers (they describe the last run that computed them).  A problem the sweep skipped (converged earlier) keeps the value
+ *               function of its last sweep.  A handle that never enables the feature launches and allocates nothing for it.
+ *               BPMPC_ERR_UNSUPPORTED: the DDP solver.  BPMPC_ERR_INVALID_ARGUMENT: settings.reference_kernels without return_gains.
+ *   fetch       bpmpc_solver_value_function (synchronises; every pointer nullable): S[batch][max_nodes+1][nx*nx] full storage, row major;
+ *               s[batch][max_nodes+1][nx]; v[batch][max_nodes+1]; x_lin[batch][max_nodes+1][nx]; status[batch]: 0 = no value function yet,
+ *               1 = valid, 2 = the sweep of that problem failed (bpmpc_stats.status == 2) and its rows are left as they were.  Entries beyond
+ *               n_nodes[b] are never written.  bpmpc_solver_device_value_function: the device pointers of the same arrays, same layouts, no
+ *               synchronisation (valid for the handle's life once enabled).
+ *   query       bpmpc_solver_evaluate_value: t[batch], x[batch][nx] -> f[batch], dfdx[batch][nx], dfdxx[batch][nx*nx] (nullable).  Per problem t
+ *               is clamped to the solution's time span, (i, a) = LinearInterpolation::timeSegment as bpmpc_solver_evaluate_policy uses it for
+ *               the states (an event time, stored twice, belongs to the interval that ends there); S, s, v, x_lin are interpolated with a and
+ *               re-centred with delta = x - x_lin(t): f = v + s'delta + delta'S delta / 2, dfdx = s + S delta, dfdxx = S.  inputs_on_device != 0:
+ *               all five are device pointers and the call only enqueues on the solver's stream; otherwise it synchronises.  The rows are
+ *               evaluated as they are: look at status for a problem whose sweep failed.  BPMPC_ERR_INVALID_ARGUMENT: the feature not enabled, no
+ *               completed run since the last setup, a batch other than that setup's; BPMPC_ERR_UNSUPPORTED: the DDP solver.
+ *   stage       bpmpc_solver_stage(solver, "value") runs the two kernels on the current buffers (stage-wise parity tests).
+ * setup_from_previous, the restarts, the policy buffer and sharding are not involved: the buffers describe the last run until the next one.
+ * ------------------------------------------------------------------------------------------------------------- */
+int bpmpc_solver_enable_value_function(bpmpc_solver* solver, int on);
+int bpmpc_solver_value_function(bpmpc_solver* solver, double* S, double* s, double* v, double* x_lin, int* status);
+int bpmpc_solver_device_value_function(bpmpc_solver* solver, double** S_dev, double** s_dev, double** v_dev, double** x_lin_dev, int** status_dev);
+int bpmpc_solver_evaluate_value(bpmpc_solver* solver, int batch, const double* t, const double* x, int inputs_on_device, double* f, double* dfdx,
+                                double* dfdxx);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * State estimation = BipedalController::updateStateEstimation (bipedal_controllers/src/BipedalController.cpp:188, :360-405) for a BATCH of robots:

@@ -38,6 +38,8 @@ struct HipSqpSolverSettings {
                                    // policy rollout AND for the controller getPrimalSolution() returns alike (bpmpc_settings.feedback_policy)
   bool computeSolutionMetrics = false;   // fill getSolutionMetrics() after every run (one more kernel and a read-back: for solver observers)
   bool useHardFrictionConeConstraint = false;   // the interface's fourth constructor argument (BipedalRobotInterface.h:66-69): cones as inequality constraints
+  bool createValueFunction = false;      // getValueFunction(t, x) answers with the value function of the last run's QP (include/bpmpc.h "Value function":
+                                         // two more kernels behind every backward pass, the LQ model in materialised form); false: it throws, as SqpSolver does
 };
 
 class HipSqpSolver final : public SolverBase {
@@ -68,6 +70,17 @@ class HipSqpSolver final : public SolverBase {
       throw std::runtime_error("[HipSqpSolver] " + why);
     }
     check(bpmpc_model_dims(model_, &nx_, &nu_, nullptr, nullptr));
+    if (settings_.createValueFunction) {
+      const int on = bpmpc_solver_enable_value_function(solver_, 1);      // (the DDP solver refuses: BPMPC_ERR_UNSUPPORTED)
+      if (on != BPMPC_OK) {
+        const std::string why = bpmpc_last_error();
+        bpmpc_solver_destroy(solver_);
+        bpmpc_model_destroy(model_);
+        solver_ = nullptr;
+        model_ = nullptr;
+        throw std::runtime_error("[HipSqpSolver] " + why);
+      }
+    }
     if (settings_.useFeedbackPolicy < 0) {       // the file's sqp block decides (integratorType / projectStateInputEqualityConstraints the engine
       double sqp[13] = {0}, ddp[20] = {0};       // does not implement were refused by bpmpc_model_create above: BPMPC_ERR_UNSUPPORTED)
       check(bpmpc_model_get(model_, "sqp", sqp, 13) >= 6 ? BPMPC_OK : BPMPC_ERR_IO);   // 13: the block's length since the line-search keys were appended
@@ -104,8 +117,21 @@ class HipSqpSolver final : public SolverBase {
     return performanceIndeces_;
   }
   // not provided by a multiple-shooting solver; SqpSolver throws from the same entry points
-  ScalarFunctionQuadraticApproximation getValueFunction(scalar_t, const vector_t&) const override {
-    throw std::runtime_error("[HipSqpSolver] getValueFunction() not available yet.");
+  /** With Settings::createValueFunction: the cost-to-go of the QP the last run solved, interpolated at `time` and re-centred at `state`
+   *  (bpmpc_solver_evaluate_value; the definition that holds is the one in include/bpmpc.h "Value function").  f, dfdx and dfdxx are filled, the
+   *  input terms stay empty.  [OCS2-upstream, recalled] SolverBase::getValueFunction(time, state) of the DDP solvers returns the quadratic model
+   *  of their own value function around the nominal state at `time`, in the same three members; that reading is unpinned - no OCS2 source was at
+   *  hand - and nothing here depends on it. */
+  ScalarFunctionQuadraticApproximation getValueFunction(scalar_t time, const vector_t& state) const override {
+    if (!settings_.createValueFunction) throw std::runtime_error("[HipSqpSolver] getValueFunction() not available yet.");
+    if (static_cast<int>(state.size()) != nx_) throw std::runtime_error("[HipSqpSolver] state dimension does not match the model");
+    ScalarFunctionQuadraticApproximation v;
+    v.dfdx = vector_t(nx_);
+    std::vector<double> hessian(static_cast<size_t>(nx_) * nx_);
+    check(bpmpc_solver_evaluate_value(solver_, 1, &time, state.data(), 0, &v.f, v.dfdx.data(), hessian.data()));
+    using RowMajorMap = Eigen::Map<const Eigen::Matrix<scalar_t, Eigen::Dynamic, Eigen::Dynamic, Eigen::RowMajor>>;
+    v.dfdxx = RowMajorMap(hessian.data(), nx_, nx_);
+    return v;
   }
   ScalarFunctionQuadraticApproximation getHamiltonian(scalar_t, const vector_t&, const vector_t&) override {
     throw std::runtime_error("[HipSqpSolver] getHamiltonian() not available yet.");
@@ -119,6 +145,8 @@ class HipSqpSolver final : public SolverBase {
 
   /** Statistics of the last solve (PerformanceIndex of the reference + step size). */
   const bpmpc_stats& lastStats() const { return stats_; }
+  /** The engine's handle, for what the C ABI offers beyond SolverBase (device pointers of the value function, kernel times); owned by this object. */
+  bpmpc_solver* engineHandle() const { return solver_; }
 
  private:
   void runImpl(scalar_t initTime, const vector_t& initState, scalar_t finalTime) override {

@@ -33,7 +33,8 @@ class FeedforwardController final : public ControllerBase {
 struct ModeSchedule { scalar_array_t eventTimes; size_array_t modeSequence; };
 struct TargetTrajectories { scalar_array_t timeTrajectory; vector_array_t stateTrajectory; vector_array_t inputTrajectory; };
 struct PerformanceIndex { scalar_t merit = 0, cost = 0, dualFeasibilitiesSSE = 0, dynamicsViolationSSE = 0, equalityConstraintsSSE = 0, inequalityConstraintsSSE = 0, equalityLagrangian = 0, inequalityLagrangian = 0; };
-struct ScalarFunctionQuadraticApproximation {};
+// [OCS2-upstream, recalled] ocs2_core/Types.h: f + dfdx' dx + dx' dfdxx dx / 2 (+ the input terms, which the adaptor leaves empty).  Only what it fills.
+struct ScalarFunctionQuadraticApproximation { scalar_t f = 0; vector_t dfdx; matrix_t dfdxx; };
 struct MultiplierCollection {};
 // [OCS2-upstream, recalled] ocs2_oc/oc_data/ProblemMetrics.h: one Metrics per node; the equality-constraint members hold one vector per TERM of
 // the constraint collection, in registration order (empty for a term that is not active at that time).  Only what the adaptor fills.
