@@ -5,7 +5,7 @@ include/bpmpc.h); all arithmetic of the hot path runs in hand-written HIP kernel
 There is no CPU fallback: constructing a solver without the HIP library or without a GPU raises.
 """
 from .api import (BatchedController, BatchedDdpMpc, BatchedPlant, BatchedStateEstimate, BatchedSupervisor, SupervisorParams, BatchedTelemetry, TelemetrySample, PlanGeometry, PlanNode, KalmanParams, PlantParams, PolicyBuffer, SensorParams, InputParams, JointParams, BodyParams, BatchedCommands, BatchedGaitSchedule, BatchedSqpMpc, DeviceArray, BipedalRobotInterface, BpmpcError, GaitSchedule, ModeSchedule, ModeSequenceTemplate,  # noqa: F401
-                  TargetTrajectories, MpcWeights, WbcParams, WeightedWbc, load_library, loadModeSequenceTemplate, swing_reference, time_discretization_with_events)
+                  TargetTrajectories, MpcWeights, ConeParams, WbcParams, WeightedWbc, load_library, loadModeSequenceTemplate, swing_reference, time_discretization_with_events)
 
 __all__ = ["BatchedController", "BatchedDdpMpc", "BatchedPlant", "BatchedStateEstimate", "BatchedSupervisor", "SupervisorParams", "BatchedTelemetry", "TelemetrySample", "PlanGeometry", "PlanNode", "KalmanParams", "PlantParams", "PolicyBuffer", "SensorParams", "InputParams", "JointParams", "BodyParams", "BatchedCommands", "BatchedGaitSchedule", "BatchedSqpMpc", "DeviceArray", "BipedalRobotInterface", "BpmpcError", "GaitSchedule", "ModeSchedule", "ModeSequenceTemplate",
-           "TargetTrajectories", "MpcWeights", "WbcParams", "WeightedWbc", "load_library", "loadModeSequenceTemplate", "swing_reference", "time_discretization_with_events"]
+           "TargetTrajectories", "MpcWeights", "ConeParams", "WbcParams", "WeightedWbc", "load_library", "loadModeSequenceTemplate", "swing_reference", "time_discretization_with_events"]

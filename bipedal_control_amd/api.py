@@ -308,6 +308,33 @@ class MpcWeights:
         return out
 
 
+class ConeParams(_RowParams):
+    """A friction-cone row of the MPC (include/bpmpc.h "Per-problem cone parameters", BPMPC_SOLVER_CONE_*): frictionCoefficient, regularization,
+    gripperForce and hessianShift of the cone (frictionConeSoftConstraint of task.info and the constants behind it), mu and delta of its relaxed
+    barrier (with the hard cone: of the SQP solver's inequality penalty).  `row` is the row of STRIDE doubles, two zeros behind the six values."""
+
+    STRIDE = 8
+    FIELDS = ("frictionCoefficient", "regularization", "gripperForce", "hessianShift", "mu", "delta")
+
+    @property
+    def row(self):
+        return self.toRow()
+
+    @classmethod
+    def from_model(cls, interface):
+        """The model's own parameters as the solver's kernels read them - what every problem solves under until a row is set: with the hard cone
+        sqp.inequalityConstraintMu / Delta as the barrier and no Hessian shift."""
+        p = cls.fromRow(np.concatenate([interface.get("cone"), np.zeros(2)]))
+        hard = interface.get("hard_cone")
+        if hard[0] != 0.0:
+            p.hessianShift, p.mu, p.delta = 0.0, float(hard[1]), float(hard[2])
+        return p
+
+    def replaced(self, **fields):
+        """A copy with the named fields replaced."""
+        return ConeParams(**dict({n: getattr(self, n) for n in self.FIELDS}, **fields))
+
+
 class BipedalRobotInterface(_Handle):
     """Problem definition: model constants + settings (BipedalRobotInterface.cpp:67-204)."""
 
@@ -403,6 +430,14 @@ class BipedalRobotInterface(_Handle):
     def costMatrices(self):
         nx, nu = self.stateDim, self.inputDim
         return self.get("Q").reshape(nx, nx), self.get("R").reshape(nu, nu)
+
+    def checkConeParams(self, row):
+        """The host check of BatchedSqpMpc.setConeParams alone (bpmpc_model_check_cone_params; no device): raises BpmpcError(-1) with the entry and
+        the reason, else returns None."""
+        r = _f64(row.row if isinstance(row, ConeParams) else row).reshape(-1)
+        if r.size != ConeParams.STRIDE:
+            raise ValueError("a cone row has %d entries" % ConeParams.STRIDE)
+        self._call("bpmpc_model_check_cone_params", _d(r))
 
     # --- target trajectories (TargetTrajectoriesPublisher.cpp:60-99)
     def cmdVelToTargetTrajectories(self, cmdVel, time, state, timeToTarget=None):
@@ -894,6 +929,31 @@ class BatchedSqpMpc(_Handle):
         if r.size != MpcWeights.STRIDE:
             raise ValueError("a weight row has %d entries" % MpcWeights.STRIDE)
         self._call("bpmpc_solver_check_weights", _d(r))
+
+    def setConeParams(self, rows, mask=None):
+        """Per-problem friction-cone parameters (bpmpc_solver_set_cone_params, include/bpmpc.h "Per-problem cone parameters"): the problems with
+        mask[b] != 0 (None: every problem of the last setup) solve under rows[b] - [batch, ConeParams.STRIDE] - or under the one row [STRIDE] /
+        [1, STRIDE], from the next run on and without a new setup.  rows: ConeParams, a list of them, numpy arrays, or float64 device tensors (not
+        checked; with them the call only enqueues).  A host row that BipedalRobotInterface.checkConeParams refuses raises BpmpcError(-1) and
+        changes nothing.  The DDP solver and reference_kernels raise BpmpcError(-3)."""
+        if isinstance(rows, ConeParams):
+            rows = rows.row
+        elif isinstance(rows, (list, tuple)) and rows and isinstance(rows[0], ConeParams):
+            rows = np.stack([p.row for p in rows])
+        B, n_rows, (mp, rp), dev, keep = _rows_args(mask, [rows], ConeParams.STRIDE, self.batch or self.max_batch)
+        self._call("bpmpc_solver_set_cone_params", B, mp, rp, n_rows, dev)
+        del keep
+
+    def getConeParams(self, robot=-1):
+        """The cone row of problem `robot`, or with robot < 0 the start row, the model's parameters (bpmpc_solver_get_cone_params; synchronises)."""
+        row = np.zeros(ConeParams.STRIDE)
+        self._call("bpmpc_solver_get_cone_params", int(robot), _d(row))
+        return ConeParams.fromRow(row)
+
+    def resetConeParams(self):
+        """Every row back to the model's parameters; the handle goes back to the kernels it launched before any row was set unless a weight row is
+        set (bpmpc_solver_reset_cone_params)."""
+        self._call("bpmpc_solver_reset_cone_params")
 
     def evaluatePolicy(self, t, x):
         """MRT_BASE::evaluatePolicy(t, x) for every problem of the last run (bpmpc_solver_evaluate_policy): t[batch], x[batch, nx] ->

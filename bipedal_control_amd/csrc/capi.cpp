@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "cone_params.h"
 #include "estimator.h"
 #include "info_tree.h"
 #include "plant.h"
@@ -491,6 +492,14 @@ int bpmpc_model_compose_weights(const bpmpc_model* m, const double* Q_task, cons
     std::fill(row_out, row_out + BPMPC_SOLVER_WEIGHT_STRIDE, 0.0);
     std::copy(Q_task, Q_task + r.nx * r.nx, row_out);
     std::copy(R.begin(), R.end(), row_out + r.nx * r.nx);
+  });
+}
+
+int bpmpc_model_check_cone_params(const bpmpc_model* m, const double* row) {
+  if (!m || !row) return fail(BPMPC_ERR_INVALID_ARGUMENT, "bpmpc_model_check_cone_params: null model handle or row");
+  return guarded(BPMPC_ERR_IO, [&] {
+    const std::string why = check_cone_row(row, m->rm.hard_friction_cone);
+    if (!why.empty()) throw std::invalid_argument("bpmpc_model_check_cone_params: " + why);
   });
 }
 

@@ -1,7 +1,9 @@
-// Per-problem cost weights (bpmpc_solver_set_weights): the twins of the three kernel families that read Q / R - lineariser, value-only trial
-// (wide rounds and back-tracking tail), change of variables in fused mode - under names of their own in a translation unit of their own, so the
-// kernels of k_node.hip and k_project.hip keep their bits.  The launch plan (bpmpc_solver::plan_weights) selects them for every problem of the batch
-// once a row has been set.  Bodies: node_kernels.h, project_kernels.h.  W: the weight table [batch][kWeightRowStride], row b = Q then R of problem b.
+// Per-problem cost weights and cone parameters (bpmpc_solver_set_weights, bpmpc_solver_set_cone_params): the twins of the three kernel families
+// that read Q / R or the friction cone - lineariser, value-only trial (wide rounds and back-tracking tail), change of variables in fused mode - under
+// names of their own in a translation unit of their own, so the kernels of k_node.hip and k_project.hip keep their bits.  ONE family with two
+// operands: the launch plan (bpmpc_solver::plan_weights) selects it for every problem of the batch once a row of EITHER table has been set, and the
+// table that never was holds the model's row in every row.  Bodies: node_kernels.h, project_kernels.h.  W: the weight table
+// [batch][kWeightRowStride], row b = Q then R of problem b.  Cone: the cone table [batch][kConeRowStride], row b = the six cone scalars of problem b.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -24,7 +26,7 @@ __host__ __device__ constexpr int lin_slots() { return lin_waves<NJ>() * LinFast
 __host__ __device__ inline int lin_w_workgroups_per_problem(int nodes, int per_wg) { return (nodes + per_wg - 1) / per_wg; }
 
 template <int NJ, bool MAT, bool CHAIN>
-__global__ __launch_bounds__(lin_waves<NJ>() * kWave) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_linearize_fast_w(Launch L, const double* W) {
+__global__ __launch_bounds__(lin_waves<NJ>() * kWave) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_linearize_fast_w(Launch L, const double* W, const double* Cone) {
   using C = LinFastCfg<NJ, true, CHAIN>;
   constexpr int LPN = C::LPN, NPW = C::NPW, kLinWaves = lin_waves<NJ>(), per_wg = kLinWaves * NPW;
   using NL = typename LinKernelLds<NJ, CHAIN>::NL;
@@ -68,27 +70,28 @@ __global__ __launch_bounds__(lin_waves<NJ>() * kWave) __attribute__((amdgpu_wave
     k = valid ? L.k0 + j : 0;
   }
   const double* row = W + (size_t)b * kWeightRowStride;      // workgroup-uniform (unused by an event workgroup)
+  const double* cone = Cone + (size_t)b * kConeRowStride;
   linearize_fast_slot<NJ, MAT, CHAIN, false>(L, shared, lds[sub], valid, b, k, event_wg, g, tl0,
-                                             [&] { load_shared_model_weights<kLinWaves * kWave>(*L.model, row, shared, threadIdx.x); });
+                                             [&] { load_shared_model_rows<kLinWaves * kWave, NJ, true>(*L.model, cone, row, shared, threadIdx.x); });
 }
 
 template <int NJ, bool CHAIN>
 __global__ __launch_bounds__(kTrialWaves * kWave) __attribute__((amdgpu_waves_per_eu(3, 3)))
-void k_trial_fast_w(Launch L, const double* W) {
-  __shared__ LinFastNodeLds<NJ, false, CHAIN> lds[kTrialWaves * LinFastCfg<NJ, true, CHAIN>::NPW];
+void k_trial_fast_w(Launch L, const double* W, const double* Cone) {
+  __shared__ TrialConeNodeLds<NJ, CHAIN> lds[kTrialWaves * LinFastCfg<NJ, true, CHAIN>::NPW];
   __shared__ LinFastShared<NJ, false> shared;
-  trial_fast_rows_workgroup<NJ, CHAIN>(L, shared, lds, W);
+  trial_fast_rows_workgroup<NJ, CHAIN>(L, shared, lds, W, Cone);
 }
 
 template <int NJ, bool CHAIN>
-__global__ __launch_bounds__(kTailThreads) void k_ls_tail_w(Launch L, int first_round, int max_trials, int pending, const double* W) {
+__global__ __launch_bounds__(kTailThreads) void k_ls_tail_w(Launch L, int first_round, int max_trials, int pending, const double* W, const double* Cone) {
   __shared__ LinFastNodeLds<NJ, false, CHAIN> lds[(kTailThreads / kWave) * LinFastCfg<NJ, true, CHAIN>::NPW];
   __shared__ LinFastShared<NJ, false> shared;
   __shared__ double partial[3 * kTailThreads + 5];
-  ls_tail_rows_problem<NJ, CHAIN>(L, first_round, max_trials, pending, shared, lds, partial, W);
+  ls_tail_rows_problem<NJ, CHAIN>(L, first_round, max_trials, pending, shared, lds, partial, W, Cone);
 }
 
-// One node per wave: the pointers into the problem's row are wave-uniform
+// One node per wave: the pointers into the problem's row are wave-uniform (the change of variables reads no cone parameter)
 template <int NJ, bool PK, bool WJ>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PK ? 3 : 2, 4))) void k_project_fast_w(Launch L, const double* W) {
   __shared__ ProjectMfmaWorkspace<NJ, PK> ws;
@@ -122,8 +125,8 @@ void linearize_fast_w(int nj, bool materialise, hipStream_t st, const Launch& L,
                                     : L.batch * lin_w_workgroups_per_problem(L.klen, per_wg);
     const dim3 grid(wgs), block(lin_waves<NJ>() * kWave);
     auto launch = [&](auto kernel) {
-      if (ev_start && ev_stop) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, ev_start, ev_stop, 0, L, w.rows);
-      else hipLaunchKernelGGL(kernel, grid, block, 0, st, L, w.rows);
+      if (ev_start && ev_stop) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, ev_start, ev_stop, 0, L, w.rows, w.cone);
+      else hipLaunchKernelGGL(kernel, grid, block, 0, st, L, w.rows, w.cone);
     };
     if (L.serial_legs) {
       if (materialise) launch(k_linearize_fast_w<NJ, true, true>);
@@ -137,14 +140,14 @@ void linearize_fast_w(int nj, bool materialise, hipStream_t st, const Launch& L,
 void trial_fast_w(int nj, int nodes, hipStream_t st, const Launch& L, const WeightRows& w) {
   const int grid = trial_fast_workgroups(nj, nodes);
   KL_NJ(nj, {
-    if (L.serial_legs) hipLaunchKernelGGL((k_trial_fast_w<NJ, true>), dim3(grid), dim3(kTrialWaves * kWave), 0, st, L, w.rows);
-    else hipLaunchKernelGGL((k_trial_fast_w<NJ, false>), dim3(grid), dim3(kTrialWaves * kWave), 0, st, L, w.rows);
+    if (L.serial_legs) hipLaunchKernelGGL((k_trial_fast_w<NJ, true>), dim3(grid), dim3(kTrialWaves * kWave), 0, st, L, w.rows, w.cone);
+    else hipLaunchKernelGGL((k_trial_fast_w<NJ, false>), dim3(grid), dim3(kTrialWaves * kWave), 0, st, L, w.rows, w.cone);
   });
 }
 void ls_tail_w(int nj, int batch, hipStream_t st, const Launch& L, int first_round, int max_trials, bool pending, const WeightRows& w) {
   KL_NJ(nj, {
-    if (L.serial_legs) hipLaunchKernelGGL((k_ls_tail_w<NJ, true>), dim3(batch), dim3(kTailThreads), 0, st, L, first_round, max_trials, pending ? 1 : 0, w.rows);
-    else hipLaunchKernelGGL((k_ls_tail_w<NJ, false>), dim3(batch), dim3(kTailThreads), 0, st, L, first_round, max_trials, pending ? 1 : 0, w.rows);
+    if (L.serial_legs) hipLaunchKernelGGL((k_ls_tail_w<NJ, true>), dim3(batch), dim3(kTailThreads), 0, st, L, first_round, max_trials, pending ? 1 : 0, w.rows, w.cone);
+    else hipLaunchKernelGGL((k_ls_tail_w<NJ, false>), dim3(batch), dim3(kTailThreads), 0, st, L, first_round, max_trials, pending ? 1 : 0, w.rows, w.cone);
   });
 }
 void project_fast_w(int nj, bool packed, bool joint_rows, int nodes, hipStream_t st, const Launch& L, const WeightRows& w) {

@@ -25,12 +25,14 @@ struct TickArgs;
 struct TickCommandArgs;
 struct RestartArgs;
 
-// The per-problem cost weights of a solver handle as the kernels read them (bpmpc_solver_set_weights): rows [batch][BPMPC_SOLVER_WEIGHT_STRIDE],
-// Q then R per problem; q_diag [batch][kWeightDim], the diagonals of Q derived from the rows.  rows == nullptr: the model's weights, the kernels of
+// The per-problem rows of a solver handle as the kernels read them: rows [batch][BPMPC_SOLVER_WEIGHT_STRIDE], Q then R per problem
+// (bpmpc_solver_set_weights); q_diag [batch][kWeightDim], the diagonals of Q derived from the rows; cone [batch][BPMPC_SOLVER_CONE_STRIDE], the cone
+// parameters per problem (bpmpc_solver_set_cone_params).  All three or none: rows == nullptr: the model's weights and cone, the kernels of
 // k_node.hip / k_project.hip.
 struct WeightRows {
   const double* rows = nullptr;
   const double* q_diag = nullptr;
+  const double* cone = nullptr;
 };
 
 namespace kl {
@@ -56,8 +58,8 @@ void project_reference(int nj, int slots, hipStream_t st, const Launch& L);
 void project_lu_s(int nj, int max_vel_rows, bool packed, int nodes, hipStream_t st, const Launch& L);
 void project_fast(int nj, bool packed, bool joint_rows, int nodes, hipStream_t st, const Launch& L);
 
-// ---- k_weights.hip: the kernels that read Q / R, on per-problem weight rows (same arguments as their namesakes; w.rows != nullptr).  The lineariser
-// maps ceil(nodes / 16) workgroups onto every problem, so it takes no node count
+// ---- k_weights.hip: the kernels that read Q / R or the friction cone, on per-problem rows (same arguments as their namesakes; w.rows and w.cone
+// != nullptr).  The lineariser maps ceil(nodes / 16) workgroups onto every problem, so it takes no node count
 void linearize_fast_w(int nj, bool materialise, hipStream_t st, const Launch& L, const WeightRows& w, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 void trial_fast_w(int nj, int nodes, hipStream_t st, const Launch& L, const WeightRows& w);
 void ls_tail_w(int nj, int batch, hipStream_t st, const Launch& L, int first_round, int max_trials, bool pending, const WeightRows& w);

@@ -58,6 +58,17 @@ struct LinFastScalars {
   // row of Q / of R.  (The lineariser keeps its dense sums: they run under its row stores and the lists bought it nothing, experiments/LOG.md.)
   int w_compact, w_kq, w_kr, w_pad;
 };
+// The cone parameters of ONE problem as cone_terms reads them (the field names of LinFastScalars): a cone row of bpmpc_solver_set_cone_params -
+// kConeRowStride doubles, the six values in the order of LinFastScalars, two zeros - with the model's cone_gauss_newton where the first zero stood.
+// The kernels whose workgroups lie inside one problem overlay the six values on the model block (node_kernels.h load_shared_model_rows); the trial
+// kernel, whose workgroups straddle problems, keeps one of these per node slot (TrialConeNodeLds).
+constexpr int kConeRowStride = 8, kConeRowUsed = 6;
+struct ConeScalars {
+  double friction, cone_reg, cone_grip, cone_shift, barrier_mu, barrier_delta;
+  int cone_gauss_newton, pad;
+  double pad1;
+};
+static_assert(sizeof(ConeScalars) == kConeRowStride * sizeof(double), "a cone row");
 // Layout: the scalars and the kinematic constants first, the cost weights LAST - the block of the value-only kernels (COST = false) is a prefix of the
 // full one, so both are staged from one image by a flat copy.
 template <int NJ, bool COST = true>   // COST = false: without the cost weights (the value-only kernels read them from global memory)
@@ -128,6 +139,7 @@ struct LinFastNodeLds {
   using C = LinFastCfg<NJ>;
   static constexpr int NT = CHAIN ? 1 : NJ, NBT = CHAIN ? 1 : C::NB, NW = CHAIN ? 3 : C::G - 3;   // CHAIN: no walk tables, only the Euler rates
   static constexpr bool kFull = FULL;
+  static constexpr bool kCone = false;  // the cone parameters are the model block's (true: the slot's own, TrialConeNodeLds of node_kernels.h)
   // node inputs, staged once so that nothing is loaded from global memory after the first output store
   double x[C::NX], u[C::NU];
   union {
@@ -1182,7 +1194,8 @@ __device__ __forceinline__ TrialPre trial_preload(const double* x, const double*
 template <int NJ, class Cfg = LinFastCfg<NJ, true>, bool EQV = false, class NL = LinFastNodeLds<NJ, false, Cfg::CHAIN>, bool LISTS = true, bool ROWS = false>
 __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastShared<NJ, false>& sh, NL& nl, bool valid,
                                            const NodeInputs& in, double alpha, const double* dx, const double* du, const double* dxn,
-                                           double* perf, int ln, double* eqv = nullptr, const TrialPre* pre = nullptr, const double* W = nullptr) {
+                                           double* perf, int ln, double* eqv = nullptr, const TrialPre* pre = nullptr, const double* W = nullptr,
+                                           double cone_pre = 0.0 /* NL::kCone: lane ln < kConeRowUsed: entry ln of the node's cone row */) {
   using C = Cfg;
   constexpr int G = C::G, NX = C::NX, NU = C::NU, LPN = C::LPN, G0 = C::G0;
   const int g = ln + G0;
@@ -1213,6 +1226,10 @@ __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastS
     xn_q = g < G ? pre->x.xn_q + alpha * pre->d.xn_q : 0.0; xn_h = ln < 6 ? pre->x.xn_h + alpha * pre->d.xn_h : 0.0;
     xn_t = tr ? pre->x.xn_t + alpha * pre->d.xn_t : 0.0;
     xr_q = pre->x.xr_q; xr_h = pre->x.xr_h; xr_t = pre->x.xr_t;
+    if constexpr (NL::kCone) {          // the slot's cone parameters wait in LDS like the node record: read as broadcasts where the cone is evaluated
+      if (ln < kConeRowUsed) reinterpret_cast<double*>(&nl.cone_sc)[ln] = cone_pre;
+      if (ln == kConeRowUsed) nl.cone_sc.cone_gauss_newton = sc.cone_gauss_newton;
+    }
   } else {
     for (int idx = ln; idx < NX; idx += LPN) {
       nl.x[idx] = in.x[idx] + alpha * dx[idx];
@@ -1253,6 +1270,8 @@ __device__ __forceinline__ void trial_fast(const DeviceModel& md, const LinFastS
         for (int a = 0; a < 3; ++a) nl.cvel_v[i][a] = kin.vog[a] + t[a];
       }
   double cone_own[4] = {0.0, 0.0, 0.0, 0.0};          // h, barrier value, first and second derivative of this lane's contact
+  if constexpr (NL::kCone) { if (ln < kNumContacts && stance_flag(mode, ln)) cone_terms(nl.cone_sc, &nl.u[3 * ln], false, cone_own); }
+  else
   if (ln < kNumContacts && stance_flag(mode, ln)) cone_terms(sc, &nl.u[3 * ln], false, cone_own);
   lds_wave_sync();
   double eq_sse = 0.0;

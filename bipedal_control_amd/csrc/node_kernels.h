@@ -1,6 +1,7 @@
-// The per-node kernels of k_weights.hip (per-problem cost weights, bpmpc_solver_set_weights) behind their (problem, node) mappings, and the workgroup
-// shapes they share with k_node.hip.  The three bodies restate what k_linearize_fast, k_trial_fast and k_ls_tail of k_node.hip do behind their
-// mappings, with the cost weights from the problem's row instead of the model: linearize_fast.h's bodies do the work in both.  They are NOT shared
+// The per-node kernels of k_weights.hip (per-problem cost weights and cone parameters, bpmpc_solver_set_weights / bpmpc_solver_set_cone_params)
+// behind their (problem, node) mappings, and the workgroup shapes they share with k_node.hip.  The three bodies restate what k_linearize_fast,
+// k_trial_fast and k_ls_tail of k_node.hip do behind their mappings, with the cost weights and the cone parameters from the problem's rows
+// instead of the model: linearize_fast.h's bodies do the work in both.  They are NOT shared
 // with those kernels on purpose.  Routed through these functions with a null row, the kernels of k_node.hip computed the same but no longer
 // compiled to the same instructions (21 of 150 functions moved; a kernel's bits follow the text of its translation unit, DESIGN.md "plant_stick"),
 // and an untouched handle has to launch the parent's machine code: profiles/solver_weights_isa_check.txt.  A change to one side belongs on the other.
@@ -80,31 +81,59 @@ __device__ __forceinline__ void linearize_fast_slot(const Launch& L, LinFastShar
 #endif
 }
 
-// The model block with the Q / R tail from a weight row: the scalar and kinematic prefix from the model image, the tail - Q then R, the layout of
-// the row's used part - from `row`, through the one flat 16-byte copy of load_shared_model with every request in flight before the first LDS store.
-template <int NT, int NJ>
-__device__ __forceinline__ void load_shared_model_weights(const DeviceModel& md, const double* row, LinFastShared<NJ, true>& sh, int tid) {
+// The model block of ONE problem: the scalar and kinematic prefix from the model image, except the six cone scalars of LinFastScalars - three
+// 16-byte pieces, from the problem's cone row `cone` (bpmpc_solver_set_cone_params) - and, COST, the tail - Q then R, the layout of a weight row's
+// used part - from `row`.  All of it through the one flat 16-byte copy of load_shared_model: a piece picks its source ADDRESS, so every request is
+// in flight before the first LDS store and the rows cost no round trip of their own.
+template <int NT, int NJ, bool COST>
+__device__ __forceinline__ void load_shared_model_rows(const DeviceModel& md, const double* cone, const double* row, LinFastShared<NJ, COST>& sh, int tid) {
   using S = LinFastShared<NJ, true>;
   static_assert(offsetof(S, Q) % 16 == 0 && offsetof(S, R) == offsetof(S, Q) + sizeof(S::Q) && sizeof(S) == offsetof(S, R) + sizeof(S::R),
                 "the weights are the tail of the block, Q then R without a gap: the used part of a weight row");
   static_assert(sizeof(S::Q) + sizeof(S::R) <= kWeightRowStride * sizeof(double), "the tail fits a weight row");
-  constexpr int N16 = sizeof(S) / 16, P16 = offsetof(S, Q) / 16, K = (N16 + NT - 1) / NT;
+  constexpr size_t kCone = offsetof(S, sc) + offsetof(LinFastScalars, friction);
+  static_assert(kCone % 16 == 0 && kConeRowUsed % 2 == 0 && offsetof(LinFastScalars, cone_reg) == offsetof(LinFastScalars, friction) + 8 &&
+                offsetof(LinFastScalars, cone_grip) == offsetof(LinFastScalars, friction) + 16 && offsetof(LinFastScalars, cone_shift) == offsetof(LinFastScalars, friction) + 24 &&
+                offsetof(LinFastScalars, barrier_mu) == offsetof(LinFastScalars, friction) + 32 && offsetof(LinFastScalars, barrier_delta) == offsetof(LinFastScalars, friction) + 40,
+                "the cone scalars are whole 16-byte pieces of the block in the order of a cone row");
+  using S0 = LinFastShared<NJ, false>;
+  static_assert(offsetof(S, sc) == offsetof(S0, sc), "one place in both blocks");
+  constexpr int N16 = sizeof(LinFastShared<NJ, COST>) / 16, P16 = COST ? offsetof(S, Q) / 16 : N16, C16 = kCone / 16, CN = kConeRowUsed / 2, K = (N16 + NT - 1) / NT;
+  static_assert(C16 + CN <= P16, "the cone scalars lie in the prefix");
   const uint4* img = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(&md) + kLinImageOffset);
   const uint4* w = reinterpret_cast<const uint4*>(row);
+  const uint4* c = reinterpret_cast<const uint4*>(cone);
   uint4* dst = reinterpret_cast<uint4*>(&sh);
   uint4 v[K];
 #pragma unroll
-  for (int k = 0; k < K; ++k) { const int i = tid + k * NT, ii = i < N16 ? i : 0; v[k] = *(ii < P16 ? img + ii : w + (ii - P16)); }
+  for (int k = 0; k < K; ++k) {
+    const int i = tid + k * NT, ii = i < N16 ? i : 0;
+    const uint4* src = (COST && ii >= P16) ? w + (ii - P16) : img + ii;
+    if (k * NT < C16 + CN) src = (ii >= C16 && ii < C16 + CN) ? c + (ii - C16) : src;      // (the first pass only, known when compiled)
+    v[k] = *src;
+  }
 #pragma unroll
   for (int k = 0; k < K; ++k) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y), "+v"(v[k].z), "+v"(v[k].w));   // all of them in flight before the first store
 #pragma unroll
   for (int k = 0; k < K; ++k) { const int i = tid + k * NT; if (i < N16) dst[i] = v[k]; }
 }
 
+// The per-node tables of the trial kernel with the slot's own cone parameters behind them: the workgroups of that kernel run in launch order and
+// straddle problems, so the shared model block is NOT one problem's and cone_terms reads the slot's copy instead (trial_fast, NL::kCone) - from
+// LDS, as broadcasts at the one place the cone is evaluated, not from registers held across the evaluation (the kernel lives at three waves per
+// SIMD without scratch).  pos_gain and robot_mass stay the model's.
+template <int NJ, bool CHAIN>
+struct TrialConeNodeLds : LinFastNodeLds<NJ, false, CHAIN> {
+  static constexpr bool kCone = true;
+  ConeScalars cone_sc;
+};
+
 // The value-only trial of one workgroup (k_trial_fast): its node slots in the launch-index mapping.  W: the weight table (the slot's lane
-// group sums over the row of ITS problem, dense, from global memory as the model's dense weights).
+// group sums over the row of ITS problem, dense, from global memory as the model's dense weights).  Cone: the cone table; lane l of a slot
+// requests entry l % 8 of its problem's row (entries 6 and 7 are zeros) together with its entries of the iterate.
 template <int NJ, bool CHAIN, class NL>
-__device__ __forceinline__ void trial_fast_rows_workgroup(const Launch& L, LinFastShared<NJ, false>& shared, NL* lds, const double* W) {
+__device__ __forceinline__ void trial_fast_rows_workgroup(const Launch& L, LinFastShared<NJ, false>& shared, NL* lds, const double* W, const double* Cone) {
+  static_assert(NL::kCone, "the slots carry their cone parameters");
   using C = LinFastCfg<NJ, true, CHAIN>;
   constexpr int NX = 12 + NJ, NU = 12 + NJ, LPN = C::LPN, NPW = C::NPW;
   const int sub = threadIdx.x / LPN, g = threadIdx.x % LPN;
@@ -127,6 +156,7 @@ __device__ __forceinline__ void trial_fast_rows_workgroup(const Launch& L, LinFa
     const size_t s0 = (size_t)b * L.N + k;
     const double* xk = L.buf.x + ((size_t)b * (L.N + 1) + k) * NX;
     const TrialPre pre = trial_preload<C>(xk, xk + NX, L.buf.u + s0 * NU, L.buf.xref + s0 * NX, dx, dx + NX, L.buf.du + s0 * NU, g, L.buf.n_aux + s0 * kNodeAux);
+    const double cone_pre = Cone[(size_t)b * kConeRowStride + g % kConeRowStride];
     load_shared_model<kTrialWaves * kWave>(*L.model, shared, threadIdx.x);
     NodeInputs in;                      // dt and the swing references come with the node record (TrialPre::x.aux)
     in.kind = info & 1; in.mode = (info >> 1) & 3; in.dt = 0.0;
@@ -135,14 +165,15 @@ __device__ __forceinline__ void trial_fast_rows_workgroup(const Launch& L, LinFa
     valid = valid && fin == 0 && info != 0;
     const size_t s = valid ? s0 : 0;
     trial_fast<NJ, C, false, NL, false, true>(*L.model, shared, lds[sub], valid, in, alpha, dx, L.buf.du + s * NU, dx + NX, L.buf.trial_perf + s * 3, g, nullptr, &pre,
-                                              W + (size_t)b * kWeightRowStride);
+                                              W + (size_t)b * kWeightRowStride, cone_pre);
   }
 }
 
-// Back-tracking rounds after the first one of one problem (k_ls_tail).  W: as trial_fast_rows_workgroup.
+// Back-tracking rounds after the first one of one problem (k_ls_tail).  W: as trial_fast_rows_workgroup.  Cone: the cone table; the workgroup
+// serves one problem, whose row is overlaid on the model block as in the lineariser.
 template <int NJ, bool CHAIN, class NL>
 __device__ __forceinline__ void ls_tail_rows_problem(const Launch& L, int first_round, int max_trials, int pending, LinFastShared<NJ, false>& shared, NL* lds,
-                                                double* partial, const double* W) {
+                                                double* partial, const double* W, const double* Cone) {
   using C = LinFastCfg<NJ, true, CHAIN>;
   constexpr int NX = 12 + NJ, NU = 12 + NJ, LPN = C::LPN, NPW = C::NPW, CHUNK = (kTailThreads / kWave) * NPW;
   const int b = blockIdx.x;
@@ -159,7 +190,7 @@ __device__ __forceinline__ void ls_tail_rows_problem(const Launch& L, int first_
     __syncthreads();
     if (*done) return;
   }
-  load_shared_model<kTailThreads>(*L.model, shared, threadIdx.x);
+  load_shared_model_rows<kTailThreads, NJ, false>(*L.model, Cone + (size_t)b * kConeRowStride, nullptr, shared, threadIdx.x);
   __syncthreads();
   const int sub = threadIdx.x / LPN, g = threadIdx.x % LPN;
   const int n = L.buf.g_nodes[L.buf.p_grid[b]];

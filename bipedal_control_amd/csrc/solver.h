@@ -133,15 +133,22 @@ struct bpmpc_solver {
   // finish_setup.  Everything else is fixed when the solver is created: d_model, dm, rm, sw, ls, and of settings max_nodes, reg_prim, solver and
   // feedback_policy (set_materialize and set_profile write fields no launch reads from here).
   Launch plan{};
-  // The part of the plan that changes BETWEEN setups: the per-problem cost weights (solver_weights.hip).  rows == nullptr - a handle that never had
-  // a row set, or has been reset - launches the kernels of k_node.hip / k_project.hip; from the first bpmpc_solver_set_weights on every kernel that
-  // reads Q or R (lineariser, trial, back-tracking tail, change of variables) is its twin of k_weights.hip, for every problem of the batch.
-  // build_plan leaves it alone: the weights enter neither the grids nor the references, so no setup is needed after a set.
+  // The part of the plan that changes BETWEEN setups: the per-problem cost weights (solver_weights.hip) and cone parameters (solver_cone.hip).
+  // rows == nullptr - a handle that never had a row of either table set, or has had both reset - launches the kernels of k_node.hip /
+  // k_project.hip; from the first bpmpc_solver_set_weights or bpmpc_solver_set_cone_params on every kernel that reads Q, R or the cone
+  // (lineariser, trial, back-tracking tail, change of variables) is its twin of k_weights.hip, for every problem of the batch.  ONE switch
+  // (select_row_kernels): the family takes both tables, and both exist from the first set of either - the one that was never set filled with the
+  // model's row (an allocated table, not one row at stride 0: the kernels keep compile-time strides, and the change of variables its body).
+  // build_plan leaves it alone: the rows enter neither the grids nor the references, so no setup is needed after a set.
   WeightRows plan_weights{};
-  DeviceBuffers weight_mem;                                // the table's memory (allocated by the first set_weights, freed with the handle)
+  bool weights_set = false, cone_set = false;              // a row set since the table's own reset
+  void select_row_kernels() { plan_weights = (weights_set || cone_set) ? WeightRows{weights.d_params, weight_q_diag, cone.d_params} : WeightRows{}; }
+  DeviceBuffers weight_mem;                                // the memory of both tables (allocated by the first set of either, freed with the handle)
   ParamTable weights;                                      // rows [max_batch][BPMPC_SOLVER_WEIGHT_STRIDE], start row = the model's Q, R
   double* weight_q_diag = nullptr;                         // [max_batch][kWeightDim]: the diagonals of Q, derived behind every write (k_weight_diagonals)
   int* weight_mask = nullptr;                              // [max_batch] device copy of a host mask
+  ParamTable cone;                                         // rows [max_batch][BPMPC_SOLVER_CONE_STRIDE], start row = the DeviceModel's cone scalars (in weight_mem)
+  int* cone_mask = nullptr;                                // [max_batch] device copy of a host mask
   // The value function (solver_value.hip, include/bpmpc.h "Value function"): its buffers exist from the first bpmpc_solver_enable_value_function
   // on (value.S == nullptr before: nothing allocated, nothing launched); value_on: every backward pass is followed by the two kernels of
   // k_value.hip.  While it is on the handle linearises in materialised form; own_materialize is the setting it goes back to.
@@ -263,7 +270,9 @@ void refuse_while_restarting(const bpmpc_solver* s, const char* what);
 void check_policy(const bpmpc_solver* s);                 // controller tick / evaluate_policy: SQP, no restart pending, a completed run, the gains
 void check_restart(const bpmpc_solver* s, int batch);
 void restart(bpmpc_solver* s, int batch, const int* mask, const double* x_new, bool on_device);
-void release_weights(bpmpc_solver* s);                    // solver_weights.hip: the weight table's memory (bpmpc_solver_destroy)
+void release_weights(bpmpc_solver* s);                    // solver_weights.hip: the memory of the weight and cone tables (bpmpc_solver_destroy)
+void ensure_weight_table(bpmpc_solver* s);                // solver_weights.hip / solver_cone.hip: the tables of the per-problem kernel family, allocated and
+void ensure_cone_table(bpmpc_solver* s);                  // filled from their start rows by the first set of either
 void release_value(bpmpc_solver* s);                      // solver_value.hip: the value buffers (bpmpc_solver_destroy)
 
 // The guard of the entry points on a solver handle (guarded): the handle's device is set before the body, BPMPC_ERR_IO for an exception of no

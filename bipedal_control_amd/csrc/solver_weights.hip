@@ -38,22 +38,24 @@ void check_host_row(const bpmpc_solver* s, const char* who, const double* row, i
                               weight_fault_text(v.fault));
 }
 
-// the table exists from the first bpmpc_solver_set_weights on (2 x max_batch rows of 9 KB); every row starts as the model's
-void ensure_table(bpmpc_solver* s) {
-  if (s->weights.d_params) return;
-  const int B = s->settings.max_batch;
-  s->weights.create(s->weight_mem, B, kStride, s->nx * s->nx + s->nu * s->nu, model_row(s).data());
-  s->weight_q_diag = s->weight_mem.alloc<double>((size_t)B * kWeightDim);
-  s->weight_mask = s->weight_mem.alloc<int>(B);
-  s->weights.fill_from_start(s->stream, B);
-}
-
 void derive_diagonals(bpmpc_solver* s) {
   kl::weight_diagonals(s->stream, s->weights.d_params, s->weight_q_diag, s->settings.max_batch, s->nx);
   HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace
+
+// the table exists from the first set of EITHER table on (bpmpc_solver_set_weights, bpmpc_solver_set_cone_params: one kernel family reads both;
+// 2 x max_batch rows of 9 KB); every row starts as the model's
+void ensure_weight_table(bpmpc_solver* s) {
+  if (s->weights.d_params) return;
+  const int B = s->settings.max_batch;
+  s->weights.create(s->weight_mem, B, kStride, s->nx * s->nx + s->nu * s->nu, model_row(s).data());
+  s->weight_q_diag = s->weight_mem.alloc<double>((size_t)B * kWeightDim);
+  s->weight_mask = s->weight_mem.alloc<int>(B);
+  s->weights.fill_from_start(s->stream, B);
+  derive_diagonals(s);
+}
 
 void release_weights(bpmpc_solver* s) { s->weight_mem.release(); }
 
@@ -72,10 +74,12 @@ int bpmpc_solver_set_weights(bpmpc_solver* s, int batch, const int* mask, const 
     if (!on_device)      // before anything is allocated or enqueued
       for (int r = 0; r < n_rows; ++r)
         if (n_rows == 1 || !mask || mask[r]) check_host_row(s, who, rows + (size_t)r * kStride, r);
-    ensure_table(s);
+    ensure_weight_table(s);
+    ensure_cone_table(s);                          // the family's other operand: the model's cone parameters in every row unless set
     s->weights.set(who, s->stream, batch, mask, s->weight_mask, rows, n_rows, on_device, [](const double*, int) {});
     derive_diagonals(s);
-    s->plan_weights = WeightRows{s->weights.d_params, s->weight_q_diag};      // every run enqueued from here on: the per-problem kernels
+    s->weights_set = true;
+    s->select_row_kernels();                       // every run enqueued from here on: the per-problem kernels
     if (!on_device) HIP_CHECK(hipStreamSynchronize(s->stream));               // the caller's host arrays
   });
 }
@@ -95,7 +99,8 @@ int bpmpc_solver_get_weights(bpmpc_solver* s, int robot, double* row) {
 
 int bpmpc_solver_reset_weights(bpmpc_solver* s) {
   return guarded(s, [&] {
-    s->plan_weights = WeightRows{};                // the kernels of a handle that never had a row set
+    s->weights_set = false;
+    s->select_row_kernels();                       // the kernels of a handle that never had a row set, unless a cone row is set
     if (!s->weights.d_params) return;
     s->weights.fill_from_start(s->stream, s->settings.max_batch);
     derive_diagonals(s);

@@ -600,7 +600,7 @@ int bpmpc_controller_joint_outputs(bpmpc_controller* controller, int batch, doub
  *               the task file reproduce bpmpc_model_get "Q" / "R" bit for bit.
  * BPMPC_ERR_UNSUPPORTED: the DDP solver (its cost of recorded points and its ILQR lineariser stay on the model's weights) and
  * settings.reference_kernels (the lane-emulation bodies read the model's Q and R), like reg_prim and bpmpc_solver_restart on those paths.
- * Not per problem: the cone parameters (friction, barrier mu / delta), kinematic and inertial constants of the MPC model.
+ * Not per problem: the kinematic and inertial constants of the MPC model.  (The cone parameters are: "Per-problem cone parameters" below.)
  * ------------------------------------------------------------------------------------------------------------- */
 #define BPMPC_SOLVER_WEIGHT_STRIDE (2 * 24 * 24)
 int bpmpc_solver_set_weights(bpmpc_solver* solver, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
@@ -608,6 +608,46 @@ int bpmpc_solver_get_weights(bpmpc_solver* solver, int robot, double* row);
 int bpmpc_solver_reset_weights(bpmpc_solver* solver);
 int bpmpc_solver_check_weights(const bpmpc_solver* solver, const double* row);
 int bpmpc_model_compose_weights(const bpmpc_model* model, const double* Q_task, const double* R_task, double* row_out);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Per-problem cone parameters: every problem of an SQP solver handle solves under friction-cone parameters of its own, settable at run time like
+ * the weight rows above (this engine's extension: the reference fixes them when BipedalRobotInterface reads task.info).  One handle, one setup
+ * and one run then cover a fleet that stands on different ground, or a sweep of the barrier's mu / delta next to one of Q / R.
+ *   row         BPMPC_SOLVER_CONE_STRIDE = 8 doubles: the six values of bpmpc_model_get "cone" in that order (BPMPC_SOLVER_CONE_*: friction
+ *               coefficient, regularisation, gripper force, Hessian diagonal shift, barrier mu, barrier delta), then two entries that must be 0.
+ *               The start row is what the solver's kernels read of the model: for a model created with the hard friction cone
+ *               (bpmpc_model_create_ex) entries 4 and 5 are sqp.inequalityConstraintMu / Delta and entry 3 is 0.
+ *   set         bpmpc_solver_set_cone_params: the contract of bpmpc_solver_set_weights - the rows of the problems with mask[b] != 0 (mask NULL:
+ *               every problem) become rows[b] (n_rows == batch) or rows[0] (n_rows == 1); batch must equal the batch of the last setup.  Every
+ *               bpmpc_solver_run enqueued after the call solves under the new rows; no new setup is needed.  With host arrays the call
+ *               synchronises; inputs_on_device != 0: mask and rows are device pointers and the call only enqueues on the solver's stream.  Host
+ *               rows are checked before anything is allocated or enqueued; device rows are NOT checked.
+ *   kernels     ONE per-problem kernel family serves the weight rows and the cone rows (k_weights.hip; kernel classes "linearize_w",
+ *               "linesearch_w", "project_w").  The handle launches it for every problem from the first bpmpc_solver_set_weights OR
+ *               bpmpc_solver_set_cone_params on, and returns to the default kernels when neither table has had a row set since its own reset.
+ *               The first set of either allocates BOTH tables (2 * max_batch rows each); the one that was never set holds the model's row.
+ *   check       bpmpc_model_check_cone_params (host only, no device): the check of a host row.  BPMPC_ERR_INVALID_ARGUMENT, the entry and the
+ *               reason in bpmpc_last_error(), for: an entry that is not finite; friction <= 0; regularisation <= 0 (sqrt(Fx^2 + Fy^2 +
+ *               regularisation) is a divisor at zero force); gripper force < 0; shift < 0; shift != 0 on a hard-cone model; mu <= 0; delta <= 0;
+ *               entry 6 or 7 != 0.  A refused set writes nothing, enqueues nothing and leaves the kernels unchanged.
+ *   get / reset bpmpc_solver_get_cone_params: row[BPMPC_SOLVER_CONE_STRIDE] = the start row (robot < 0, or a handle that never had a row set) or
+ *               the problem's current row; synchronises.  bpmpc_solver_reset_cone_params: every row back to the start row.
+ *               bpmpc_solver_reset and the restarts keep the rows.
+ * BPMPC_ERR_UNSUPPORTED: the DDP solver and settings.reference_kernels, for the reasons of the weight rows.
+ * Not per problem: pos_gain and the robot's mass (the model's in every kernel), the WBC's and the plant's friction (rows of their own handles).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define BPMPC_SOLVER_CONE_STRIDE 8
+#define BPMPC_SOLVER_CONE_FRICTION 0
+#define BPMPC_SOLVER_CONE_REGULARIZATION 1
+#define BPMPC_SOLVER_CONE_GRIPPER_FORCE 2
+#define BPMPC_SOLVER_CONE_HESSIAN_SHIFT 3
+#define BPMPC_SOLVER_CONE_BARRIER_MU 4
+#define BPMPC_SOLVER_CONE_BARRIER_DELTA 5
+#define BPMPC_SOLVER_CONE_RESERVED 6
+int bpmpc_solver_set_cone_params(bpmpc_solver* solver, int batch, const int* mask, const double* rows, int n_rows, int inputs_on_device);
+int bpmpc_solver_get_cone_params(bpmpc_solver* solver, int robot, double* row);
+int bpmpc_solver_reset_cone_params(bpmpc_solver* solver);
+int bpmpc_model_check_cone_params(const bpmpc_model* model, const double* row);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Value function: the cost-to-go of the QP an SQP solver handle has just solved, per node of every problem and on query (this engine's
