@@ -399,6 +399,44 @@ def test_reg_prim_setting_matches_oracle(ctx):
         bp.BatchedSqpMpc(itf, max_batch=1, max_nodes=8, reg_prim=1e-12, reference_kernels=True)
 
 
+def _modes_seen(got, n):
+    kind = got["g_kind"][:n].astype(int)
+    return set(got["g_mode"][:n].astype(int)[kind == 0] & 3)
+
+
+def _structured_against_dense(structured, dense, B, N, n, nx):
+    """The packed projected model Wt, Qp, Mt of the first n nodes in the region the sweep reads, a handle on the structured path against one under
+    BPMPC_DENSE_PROJECT=1 (each the dict of buffers test_structured_and_dense_change_of_variables_agree reads): the worst relative difference.
+    Also used by tests/test_gpu_row_kernel_edges.py."""
+    wp = ((2 * nx + 1 + 15) // 16) * 16
+    got = {"0": structured, "1": dense}
+    nut = got["0"]["nut"].reshape(B, N)[:, :n].astype(int)
+    assert np.array_equal(nut, got["1"]["nut"].reshape(B, N)[:, :n])
+    kind = got["0"]["g_kind"][:n].astype(int)
+    W = {d: got[d]["Wt"].reshape(B, N, nx, wp)[:, :n] for d in got}
+    Q = {d: got[d]["Qp"].reshape(B, N, nx, 32)[:, :n] for d in got}
+    M = {d: got[d]["Mt"].reshape(B, N, nx, wp)[:, :n] for d in got}
+    Vt = got["0"]["Vt"].reshape(B, N, nx - 12, wp)[:, :n]
+    bb = got["0"]["b"].reshape(B, N, nx)[:, :n]
+    dt = got["0"]["g_dt"][:n]
+    worst = 0.0
+    for other in ("0",):
+        for b in range(B):
+            for k in range(n):
+                nt = nut[b, k]
+                cend = 16 * ((nx + 1 + nt + 15) // 16) if kind[k] == 0 else 32
+                # the structured path leaves the joint rows of Wt to the sweep (round 4, every regime but the four-wave kernel): rows 0..11 are compared
+                # as written, the joint rows of the dense path against what the sweep's loaders complete: [I | b | 0] + dt x (joint rows of [Px | Pe | Pu]) = Vt
+                done = dt[k] * Vt[b, k, :, :cend]
+                done[:, 12:nx] += np.eye(nx - 12); done[:, nx] += bb[b, k, 12:]
+                pairs = [(W[other][b, k, :12, :cend], W["1"][b, k, :12, :cend]), (done, W["1"][b, k, 12:, :cend]), (Q[other][b, k, :, :nx + 1], Q["1"][b, k, :, :nx + 1])]
+                if kind[k] == 0:
+                    pairs.append((M[other][b, k, :nt, :cend], M["1"][b, k, :nt, :cend]))
+                for a, d in pairs:
+                    worst = max(worst, _rel(a, d))
+    return worst
+
+
 @pytest.mark.parametrize("robot,gait", [("h1", "trot"), ("h1", "standing_trot"), ("h1", "flying_trot"), ("hunter", "trot"), ("g1", "standing_trot"),
                                          ("openloong", "flying_trot")])
 def test_structured_and_dense_change_of_variables_agree(ctx, robot, gait, monkeypatch):
@@ -421,32 +459,9 @@ def test_structured_and_dense_change_of_variables_agree(ctx, robot, gait, monkey
         mpc.stage("linearize"); mpc.stage("project"); mpc.synchronize()
         got[dense] = {k: mpc.read(k) for k in ("Wt", "Qp", "Mt", "nut", "g_kind", "g_mode", "Vt", "b", "g_dt")}
         n = lay["n_nodes_max"]
-    nut = got["0"]["nut"].reshape(B, N)[:, :n].astype(int)
-    assert np.array_equal(nut, got["1"]["nut"].reshape(B, N)[:, :n])
-    kind = got["0"]["g_kind"][:n].astype(int)
-    modes = set(got["0"]["g_mode"][:n].astype(int)[kind == 0] & 3)
+    modes = _modes_seen(got["0"], n)
     assert modes >= ({0, 1, 2} if "flying" in gait else ({1, 2} if gait == "trot" else {1, 2, 3}))
-    W = {d: got[d]["Wt"].reshape(B, N, nx, wp)[:, :n] for d in got}
-    Q = {d: got[d]["Qp"].reshape(B, N, nx, 32)[:, :n] for d in got}
-    M = {d: got[d]["Mt"].reshape(B, N, nx, wp)[:, :n] for d in got}
-    Vt = got["0"]["Vt"].reshape(B, N, nx - 12, wp)[:, :n]
-    bb = got["0"]["b"].reshape(B, N, nx)[:, :n]
-    dt = got["0"]["g_dt"][:n]
-    worst = 0.0
-    for other in ("0",):
-        for b in range(B):
-            for k in range(n):
-                nt = nut[b, k]
-                cend = 16 * ((nx + 1 + nt + 15) // 16) if kind[k] == 0 else 32
-                # the structured path leaves the joint rows of Wt to the sweep (round 4, every regime but the four-wave kernel): rows 0..11 are compared
-                # as written, the joint rows of the dense path against what the sweep's loaders complete: [I | b | 0] + dt x (joint rows of [Px | Pe | Pu]) = Vt
-                done = dt[k] * Vt[b, k, :, :cend]
-                done[:, 12:nx] += np.eye(nx - 12); done[:, nx] += bb[b, k, 12:]
-                pairs = [(W[other][b, k, :12, :cend], W["1"][b, k, :12, :cend]), (done, W["1"][b, k, 12:, :cend]), (Q[other][b, k, :, :nx + 1], Q["1"][b, k, :, :nx + 1])]
-                if kind[k] == 0:
-                    pairs.append((M[other][b, k, :nt, :cend], M["1"][b, k, :nt, :cend]))
-                for a, d in pairs:
-                    worst = max(worst, _rel(a, d))
+    worst = _structured_against_dense(got["0"], got["1"], B, N, n, nx)
     assert worst < 1e-12, worst
 
 

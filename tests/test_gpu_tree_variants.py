@@ -114,12 +114,13 @@ def _solve_floor(name, shape, iterations, b, prob):
     return _CACHE[key]
 
 
-def _tolerances(name, shape, iterations, b, prob, inherited, merit=1e-9):
+def _tolerances(name, shape, iterations, b, prob, inherited, merit=1e-9, floor=None):
     """The inherited tolerances; for the cases of tree_variants.FLOOR_CASES - and only for them - ten times the reference's own floor for this problem where that
-    is larger (module docstring).  Everywhere else a floor that rose would fail here as it does in the CPU tier."""
+    is larger (module docstring).  Everywhere else a floor that rose would fail here as it does in the CPU tier.  floor(b): the floor of another reference
+    than the cold-start solve under the model."""
     if (name, shape, b, iterations) not in tv.FLOOR_CASES:
         return tuple(inherited), merit
-    floor, fm = _solve_floor(name, shape, iterations, b, prob)
+    floor, fm = floor(b) if floor is not None else _solve_floor(name, shape, iterations, b, prob)
     return tuple(max(t, tv.FLOOR_FACTOR * f) for t, f in zip(inherited, floor)), max(merit, tv.FLOOR_FACTOR * fm)
 
 
@@ -323,16 +324,18 @@ def test_reference_and_fast_kernels_agree(robots, name, shape):
     assert [(s.status, s.n_nodes, s.iterations) for s in ra[4]] == [(s.status, s.n_nodes, s.iterations) for s in rb[4]]
 
 
-def _compare_solve(name, shape, iterations, prob, out, key):
+def _compare_solve(name, shape, iterations, prob, out, key, oracle=None, floor=None):
+    """oracle: the solves to compare with instead of the cold-start solves under the model (tests/test_gpu_row_kernel_edges.py: under a cone row per
+    problem); floor(b) -> ((x, u, K), merit): the reference floor of THAT oracle for the cases of tree_variants.FLOOR_CASES."""
     t, x, u, K, stats = out
     report, steps, missed = {}, [], []
-    for b, (xo, uo, Ko, st) in enumerate(_oracle_solves(name, shape, iterations, prob)):
+    for b, (xo, uo, Ko, st) in enumerate(oracle if oracle is not None else _oracle_solves(name, shape, iterations, prob)):
         n = stats[b].n_nodes
         assert n == xo.shape[0] - 1 and stats[b].status == 0
         its = int(sum(1 for r in st if r[10] > 0))
         assert its == iterations and stats[b].iterations == its
         steps.append((stats[b].step_size, float(st[its - 1][3])))
-        (tx, tu, tK), tm = _tolerances(name, shape, iterations, b, prob, (1e-11, 1e-11, 1e-10))
+        (tx, tu, tK), tm = _tolerances(name, shape, iterations, b, prob, (1e-11, 1e-11, 1e-10), floor=floor)
         ex, eu, eK = rel_x(x[b, :n + 1], xo, report), rel_u(u[b, :n], uo, report), rel_K(K[b, :n], Ko, report)
         em = _rel(stats[b].merit_after, st[its - 1][4])
         report["merit"] = max(report.get("merit", 0.0), em)

@@ -184,20 +184,22 @@ def oracle_qp_floor(name, nodes, x0, x, u):
     return dict(whole=tuple(float(v) for v in whole), blocks=tuple(float(v) for v in blocks))
 
 
-def oracle_solve_floor(name, prob, b, iterations):
+def oracle_solve_floor(name, prob, b, iterations, solve=None, start=None):
     """The same for a whole solve from the cold start: ((x, u, K) per physical block as tests/tolerances.py measures, merit, steps_stable) - the oracle's
-    solve against its solve from the cold start moved by 1e-15 relative.  steps_stable: every sample accepts the same step lengths."""
+    solve against its solve from the cold start moved by 1e-15 relative.  steps_stable: every sample accepts the same step lengths.
+    solve(x, u) -> (x, u, K, record): another oracle of the same problem (tests/row_kernel_cases.py: under a cone row); start = (x, u): another iterate
+    than the cold start."""
     from oracle import reference_py as rp
     from tests import oracle_bridge as ob
     from tests.tolerances import rel_K, rel_u, rel_x
-    m = ob.model(name)
-    nodes = ob.oracle_nodes(prob, b, robot=name)
-    x, u = rp.cold_start(m, nodes, prob["x0"][b])
-    xo, uo, Ko, st = ob.oracle_solve_like(prob, b, iterations=iterations, x_init=x, u_init=u, robot=name)
+    if solve is None:
+        def solve(x, u):
+            return ob.oracle_solve_like(prob, b, iterations=iterations, x_init=x, u_init=u, robot=name)
+    x, u = start if start is not None else rp.cold_start(ob.model(name), ob.oracle_nodes(prob, b, robot=name), prob["x0"][b])
+    xo, uo, Ko, st = solve(x, u)
     floor, merit, stable = np.zeros(3), 0.0, True
     for s in range(FLOOR_SAMPLES):
-        x2, u2, K2, st2 = ob.oracle_solve_like(prob, b, iterations=iterations, x_init=x * (1.0 + 1e-15 * _signs(x.shape, s)),
-                                               u_init=u * (1.0 + 1e-15 * _signs(u.shape, 100 + s)), robot=name)
+        x2, u2, K2, st2 = solve(x * (1.0 + 1e-15 * _signs(x.shape, s)), u * (1.0 + 1e-15 * _signs(u.shape, 100 + s)))
         floor = np.maximum(floor, [rel_x(x2, xo), rel_u(u2, uo), rel_K(K2, Ko)])
         merit = max(merit, abs(st2[iterations - 1][4] - st[iterations - 1][4]) / max(1.0, abs(st[iterations - 1][4])))
         stable = stable and np.array_equal(st2[:, 3], st[:, 3])
