@@ -29,6 +29,9 @@ _LIB = None
 ModeSchedule = namedtuple("ModeSchedule", ["eventTimes", "modeSequence"])
 ModeSequenceTemplate = namedtuple("ModeSequenceTemplate", ["switchingTimes", "modeSequence"])
 TargetTrajectories = namedtuple("TargetTrajectories", ["timeTrajectory", "stateTrajectory"])
+# BatchedSqpMpc.dualSolution (include/bpmpc.h "Dual solution"); the fields are named as the C arrays, `lambda` being a keyword
+DualSolution = namedtuple("DualSolution", ["costate", "nu", "nu0", "nu_gain", "residual", "gain_residual", "summary", "status"])
+DUAL_ROWS = 16
 
 MODE_NUMBER = {"FLY": 0, "LF": 1, "RF": 2, "STANCE": 3}
 
@@ -1015,6 +1018,62 @@ class BatchedSqpMpc(_Handle):
         f, g, h = np.zeros(B), np.zeros((B, nx)), np.zeros((B, nx, nx)) if hessian else None
         self._call("bpmpc_solver_evaluate_value", B, _d(t), _d(x), 0, _d(f), _d(g), _d(h))
         return f, g, h
+
+    # ---- the dual solution of the QP a run has solved (include/bpmpc.h "Dual solution")
+    def enableDualSolution(self, on=True):
+        """From the next run on, the value function's kernels are followed by the dual solution of the same QP: the costates lambda_k = s_k + S_k dx_k,
+        the minimum-norm multipliers nu_k = nu0_k + N_k dx_k of the state-input equality rows, and the two residuals that certify the step and the
+        gains (bpmpc_solver_enable_dual_solution).  The value function is on while this is on.  on=False stops the launches and keeps the
+        buffers.  The DDP solver raises BpmpcError(-3)."""
+        self._call("bpmpc_solver_enable_dual_solution", int(bool(on)))
+
+    def dualSolution(self):
+        """DualSolution(costate [B, N + 1, nx], nu [B, N, 16], nu0 [B, N, 16], nu_gain [B, N, 16, nx], residual [B, N], gain_residual [B, N],
+        summary [B, 6], status [B]) of the last run, N = max_nodes (bpmpc_solver_dual_solution; synchronises).  summary: the maxima over a problem's
+        nodes of residual, |g_u|, gain_residual, |Hux|, |nu|, |lambda|; status as valueFunction's.  Nodes beyond n_nodes[b] are never written."""
+        B, N, nx, R = self.layout()["batch"], self.max_nodes, self.nx, DUAL_ROWS
+        out = DualSolution(np.zeros((B, N + 1, nx)), np.zeros((B, N, R)), np.zeros((B, N, R)), np.zeros((B, N, R, nx)), np.zeros((B, N)), np.zeros((B, N)),
+                           np.zeros((B, 6)), np.zeros(B, np.int32))
+        self._call("bpmpc_solver_dual_solution", *[_d(a) for a in out[:7]], _i(out.status))
+        return out
+
+    def dualSolutionDevice(self):
+        """The same eight arrays where they live: a dict of DeviceArray over max_batch problems, keyed as the C arrays ("lambda", "nu", ...)
+        (bpmpc_solver_device_dual_solution; no synchronisation)."""
+        names = ("lambda", "nu", "nu0", "nu_gain", "residual", "gain_residual", "summary")
+        ptrs, st = [_dp() for _ in names], _ip()
+        self._call("bpmpc_solver_device_dual_solution", *[C.byref(p) for p in ptrs], C.byref(st))
+        B, N, nx, R = self.max_batch, self.max_nodes, self.nx, DUAL_ROWS
+        shapes = ((B, N + 1, nx), (B, N, R), (B, N, R), (B, N, R, nx), (B, N), (B, N), (B, 6))
+        ptr = lambda p: C.cast(p, C.c_void_p).value
+        out = {n: DeviceArray(ptr(p), shp, "<f8") for n, p, shp in zip(names, ptrs, shapes)}
+        out["status"] = DeviceArray(ptr(st), (B,), "<i4")
+        return out
+
+    def evaluateDual(self, t, x):
+        """The multipliers and the costate of every problem of the last run at (t, x) (bpmpc_solver_evaluate_dual): t[batch], x[batch, nx] ->
+        (costate [batch, nx], nu [batch, 16], rows [batch]): nu = nu0_i + N_i (x - x_lin(t)) of the interval i that holds t, its first rows[b]
+        entries meaningful; the costate is evaluateValue's dfdx.  numpy inputs: numpy results, the call synchronises.  float64 device tensors: the
+        call only enqueues on the solver's stream and the results are DeviceArray over torch tensors it allocates."""
+        B, nx = self.batch, self.nx
+        if all(getattr(a, "is_cuda", False) or hasattr(a, "__cuda_array_interface__") for a in (t, x)):
+            import torch
+            (tp, xp), dev, keep = _restart_args((t, C.c_double, B), (x, C.c_double, B * nx))
+            lam, nu = (torch.empty(shape, dtype=torch.float64, device="cuda") for shape in ((B, nx), (B, DUAL_ROWS)))
+            rows = torch.empty((B,), dtype=torch.int32, device="cuda")
+            self._call("bpmpc_solver_evaluate_dual", B, tp, xp, 1, C.cast(C.c_void_p(lam.data_ptr()), _dp), C.cast(C.c_void_p(nu.data_ptr()), _dp),
+                       C.cast(C.c_void_p(rows.data_ptr()), _ip))
+            del keep
+            views = []
+            for o, ts in ((lam, "<f8"), (nu, "<f8"), (rows, "<i4")):
+                views.append(DeviceArray(o.data_ptr(), o.shape, ts))
+                views[-1].owner = o                     # the tensor lives as long as its view
+            return tuple(views)
+        t = _f64(np.broadcast_to(np.asarray(t, float), (B,)))
+        x = _f64(x).reshape(B, nx)
+        lam, nu, rows = np.zeros((B, nx)), np.zeros((B, DUAL_ROWS)), np.zeros(B, np.int32)
+        self._call("bpmpc_solver_evaluate_dual", B, _d(t), _d(x), 0, _d(lam), _d(nu), _i(rows))
+        return lam, nu, rows
 
 
 class WeightedWbc(_Handle):

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libbpmpc.so")
-SOURCES = ["k_node.hip", "k_weights.hip", "k_project.hip", "k_riccati.hip", "k_riccati_wave.hip", "k_ddp.hip", "solver.hip", "solver_weights.hip", "solver_cone.hip", "k_value.hip", "solver_value.hip", "gait_batch.hip", "command_batch.hip", "transfer.hip", "wbc.hip", "estimator.hip", "plant.hip", "plant_stick.hip", "plant_joint.hip", "plant_body.hip", "plant_sense.hip", "plant_input.hip", "policy.hip", "telemetry.hip", "plan_geometry.hip", "supervisor.hip", "device_handle.hip", "k_tick.hip", "controller.cpp", "capi.cpp", "info_tree.cpp", "urdf_tree.cpp",
+SOURCES = ["k_node.hip", "k_weights.hip", "k_project.hip", "k_riccati.hip", "k_riccati_wave.hip", "k_ddp.hip", "solver.hip", "solver_weights.hip", "solver_cone.hip", "k_value.hip", "solver_value.hip", "k_dual.hip", "solver_dual.hip", "gait_batch.hip", "command_batch.hip", "transfer.hip", "wbc.hip", "estimator.hip", "plant.hip", "plant_stick.hip", "plant_joint.hip", "plant_body.hip", "plant_sense.hip", "plant_input.hip", "policy.hip", "telemetry.hip", "plan_geometry.hip", "supervisor.hip", "device_handle.hip", "k_tick.hip", "controller.cpp", "capi.cpp", "info_tree.cpp", "urdf_tree.cpp",
            "robot_model.cpp", "reference_gen.cpp", "device_model.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
 

@@ -18,6 +18,7 @@
 #include "launch.h"
 #include "sweep_plan.h"
 #include "value_kernels.h"
+#include "dual_kernels.h"
 #include "kernels/reference_device.h"
 
 using namespace bpmpc;
@@ -157,6 +158,13 @@ struct bpmpc_solver {
   bool value_on = false;
   int own_materialize = 0;
   void launch_value();                                     // solver_value.hip: k_value_terms, k_value_sweep on the current buffers, on `stream`
+  // The dual solution (solver_dual.hip, include/bpmpc.h "Dual solution"): buffers from the first bpmpc_solver_enable_dual_solution on
+  // (dual.lambda == nullptr before: nothing allocated, nothing launched); dual_on: the kernels of k_dual.hip follow every launch_value.  It reads
+  // the value function's rows, so the value function runs while either the caller asked for it (value_own) or dual_on: value_on = value_own || dual_on.
+  DualArgs dual{};
+  DeviceBuffers dual_mem;
+  bool dual_on = false, value_own = false;
+  void launch_dual();                                      // solver_dual.hip: k_dual_node, k_dual_summary behind launch_value(), on `stream`
   void build_plan() {
     Launch& L = plan;
     L.model = d_model;
@@ -274,6 +282,8 @@ void release_weights(bpmpc_solver* s);                    // solver_weights.hip:
 void ensure_weight_table(bpmpc_solver* s);                // solver_weights.hip / solver_cone.hip: the tables of the per-problem kernel family, allocated and
 void ensure_cone_table(bpmpc_solver* s);                  // filled from their start rows by the first set of either
 void release_value(bpmpc_solver* s);                      // solver_value.hip: the value buffers (bpmpc_solver_destroy)
+void apply_value_state(bpmpc_solver* s, const char* who); // solver_value.hip: value_on = value_own || dual_on, with the buffers and the materialise setting that go with it
+void release_dual(bpmpc_solver* s);                       // solver_dual.hip: the dual buffers (bpmpc_solver_destroy)
 
 // The guard of the entry points on a solver handle (guarded): the handle's device is set before the body, BPMPC_ERR_IO for an exception of no
 // class of its own.

@@ -167,6 +167,7 @@ void bpmpc_solver::pipelined_backward() {
     launch_riccati(L);
   }
   if (value_on) launch_value();                          // behind the last chunk: the whole horizon's model, gains and step are in place
+  if (dual_on) launch_dual();
 }
 
 void bpmpc_solver::run_iterations() {
@@ -186,6 +187,7 @@ void bpmpc_solver::run_iterations() {
       stage_project();
       stage_riccati();
       if (value_on) launch_value();                        // before the line search moves x: the value function of this iteration's QP
+      if (dual_on) launch_dual();                          // ... and its dual solution, from the rows the value kernels have just written
     }
     stage_linesearch();
   }
@@ -946,6 +948,7 @@ void bpmpc_solver_destroy(bpmpc_solver* s) {
   for (void* p : s->allocations) (void)hipFree(p);
   release_weights(s);
   release_value(s);
+  release_dual(s);
   if (s->d_model) (void)hipFree(s->d_model);
   if (s->h_remaining) (void)hipHostFree(s->h_remaining);
   s->pin_up.release(); s->pin_down.release();
@@ -1023,6 +1026,10 @@ int bpmpc_solver_stage(bpmpc_solver* s, const char* stage) {
     else if (n == "value") {
       if (!s->value_on) throw std::invalid_argument("bpmpc_solver_stage: \"value\" needs bpmpc_solver_enable_value_function");
       s->launch_value();
+    }
+    else if (n == "dual") {
+      if (!s->dual_on) throw std::invalid_argument("bpmpc_solver_stage: \"dual\" needs bpmpc_solver_enable_dual_solution");
+      s->launch_dual();
     }
     else throw std::invalid_argument("unknown stage " + n);
   });

@@ -36,6 +36,21 @@ void check_enabled(const bpmpc_solver* s, const char* who) {
 
 void release_value(bpmpc_solver* s) { s->value_mem.release(); }
 
+// The value function runs while the caller asked for it (value_own) or the dual solution, which reads its rows, is on (dual_on)
+void apply_value_state(bpmpc_solver* s, const char* who) {
+  check_supported(s, who);
+  if (s->settings.reference_kernels && !s->settings.return_gains)
+    throw std::invalid_argument(std::string(who) + ": the value function needs the feedback gains (return_gains with reference kernels)");
+  const bool on = s->value_own || s->dual_on;
+  if (on) {
+    ensure_buffers(s);
+    s->settings.materialize_lq = 1;                        // the kernels read A .. c as the lineariser writes them in this mode
+  } else {
+    s->settings.materialize_lq = s->own_materialize;
+  }
+  s->value_on = on;
+}
+
 }  // namespace bpmpc
 
 // the model, gains and step of the backward pass that has just been enqueued, as the handle's buffers stand now (x, K trade places with their
@@ -61,17 +76,9 @@ extern "C" {
 
 int bpmpc_solver_enable_value_function(bpmpc_solver* s, int on) {
   return guarded(s, [&] {
-    const char* who = "bpmpc_solver_enable_value_function";
-    check_supported(s, who);
-    if (s->settings.reference_kernels && !s->settings.return_gains)
-      throw std::invalid_argument(std::string(who) + ": the value function needs the feedback gains (return_gains with reference kernels)");
-    if (on) {
-      ensure_buffers(s);
-      s->settings.materialize_lq = 1;                      // the kernels read A .. c as the lineariser writes them in this mode
-    } else {
-      s->settings.materialize_lq = s->own_materialize;
-    }
-    s->value_on = on != 0;
+    const bool before = s->value_own;
+    s->value_own = on != 0;
+    try { apply_value_state(s, "bpmpc_solver_enable_value_function"); } catch (...) { s->value_own = before; throw; }
   });
 }
 

@@ -355,7 +355,8 @@ int bpmpc_solver_run(bpmpc_solver* solver);     /* enqueue the SQP iteration(s) 
 int bpmpc_solver_sync(bpmpc_solver* solver);
 int bpmpc_solver_fetch(bpmpc_solver* solver, double* out_t, double* out_x, double* out_u, double* out_K, bpmpc_stats* stats);
 /* Run one stage of an iteration on the current iterate (parity tests, roofline measurement):
- * "linearize", "project", "riccati", "linesearch"; "value" with the value function enabled ("Value function" below). */
+ * "linearize", "project", "riccati", "linesearch"; "value" with the value function enabled ("Value function" below); "dual" with the dual
+ * solution enabled ("Dual solution" below; behind "value"). */
 int bpmpc_solver_stage(bpmpc_solver* solver, const char* stage);
 /* Copy a named device buffer to the host (tests): "x","u","xref","A","B","b","Q","R","P","q","r","c","C","D","e","nc","perf",
  * "Px","Pu","Pe","nut","dx","du","K","Acl","summary","stats","g_kind","g_mode","g_nodes","g_dt","g_start","g_zref","g_zdref","g_time",
@@ -694,6 +695,59 @@ int bpmpc_solver_value_function(bpmpc_solver* solver, double* S, double* s, doub
 int bpmpc_solver_device_value_function(bpmpc_solver* solver, double** S_dev, double** s_dev, double** v_dev, double** x_lin_dev, int** status_dev);
 int bpmpc_solver_evaluate_value(bpmpc_solver* solver, int batch, const double* t, const double* x, int inputs_on_device, double* f, double* dfdx,
                                 double* dfdxx);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Dual solution: the costates of the dynamics and the Lagrange multipliers of the state-input equality rows of the QP an SQP solver handle has just
+ * solved, per node of every problem and on query, with two residuals that certify the step and the gains without any oracle (this engine's
+ * extension; what SolverBase::getStateInputEqualityConstraintLagrangian asks for).
+ *   definition  The QP of the LAST SWEPT SQP iteration of problem b in the unprojected LQ model, as "Value function" above takes it.  Lagrangian:
+ *                   cost + sum_k lambda_{k+1}'(A dx_k + B du_k + b - dx_{k+1}) + sum_k nu_k'(C dx_k + D du_k + e)
+ *               with the rows of C, D, e as bpmpc_solver_read returns them: nc[k] rows in registration order (zero force, zero velocity, normal
+ *               velocity per contact point), 16 slots.  With S, s of the value function, and + for node k + 1:
+ *                   lambda_k = s_k + S_k dx_k        k = 0 .. n_nodes[b],   lambda_n = 0
+ *               and per intermediate node, event nodes excepted, under the sweep's policy du = K dx + kappa:
+ *                   Hux = P + R K + B'S+ Acl     g0 = r + R kappa + B'(s+ + S+ bcl)     g_u(dx) = Hux dx + g0
+ *               (the input gradient of the Hamiltonian as a function of dx), and
+ *                   [N | nu0] = -pinv(D') [Hux | g0]        nu_k = nu0 + N dx_k
+ *               D is NEVER of full row rank while a foot stands: the two contact points of a rigid foot cannot move along the line between them
+ *               (single stance: 14 rows of rank 13, double stance: 12 of rank 10; only a flight node's 16 rows have rank 16).  nu is therefore
+ *               not unique, and this is the MINIMUM-NORM solution, which is: the component of every column of [N | nu0] in null(D') is zero.
+ *               Singular values of D below 1e-6 of the largest count as zero - equivalently eigenvalues of D D' below 1e-12 of the largest; on
+ *               these robots the smallest kept singular value is above 0.05 of the largest and the dropped ones are rounding noise.
+ *               nu belongs to the QP, whose cost is already times dt (divide by the node's dt for a multiplier of the continuous-time cost).
+ *               With the hard-cone model the cone inequalities are in the cost, as the SQP treats them: they have no multiplier here.
+ *               Certificates: residual_k = |g_u(dx_k) + D'nu_k|_inf is zero exactly when the step (dx, du) the sweep returned is stationary in
+ *               du on the constraint set - the Riccati sweep, the constraint elimination and the change of variables together returned the QP's
+ *               minimiser; gain_residual_k = max |Hux + D'N| says the same of the gains K for every dx.
+ *               CAVEAT, stationarity in x: lambda_k = q + Q dx + P'du + A'lambda+ + C'nu holds at nodes where D has full row rank only.  At a
+ *               rank-deficient node off convergence the linearised redundant row is inconsistent in its state part, the elimination drops it,
+ *               and the QP that was solved does not contain it; what always holds is lambda_k = q + Q dx + P'du + A'lambda+ + K'g_u(dx_k).
+ *   enable      bpmpc_solver_enable_dual_solution(on != 0) allocates the buffers (once, at the first such call), turns the value function on as
+ *               bpmpc_solver_enable_value_function(solver, 1) would and keeps it on while this is on (a bpmpc_solver_enable_value_function(solver,
+ *               0) in between is remembered and applies once this is off).  From then on two more kernels follow the value function's behind
+ *               every backward pass (k_dual.hip: k_dual_node, one wave per node - kernel class "dual" of bpmpc_solver_kernel_time -, and
+ *               k_dual_summary).  on == 0 stops the launches and keeps the buffers.  A problem the sweep skipped keeps its rows.  A handle that
+ *               never enables the feature launches and allocates nothing for it.  Memory: per node 16 nx doubles of nu_gain (at max_batch 4096,
+ *               max_nodes 100, nx = 22: 1.2 GB) and about 37 + nx more.  BPMPC_ERR_UNSUPPORTED: the DDP solver.
+ *   fetch       bpmpc_solver_dual_solution (synchronises; every pointer nullable): lambda[batch][max_nodes+1][nx]; nu, nu0[batch][max_nodes][16];
+ *               nu_gain[batch][max_nodes][16][nx]; residual, gain_residual[batch][max_nodes]; summary[batch][6]: the maxima over the problem's
+ *               nodes of residual, |g_u(dx_k)|_inf, gain_residual, |Hux|, |nu|, |lambda|; status[batch] as the value function's: 0 none yet,
+ *               1 valid, 2 the sweep of that problem failed and its rows are left as they were.  Rows at and beyond nc[k] are exact zeros; at an
+ *               event node nu, nu0 and nu_gain are zero.  Nodes beyond n_nodes[b] are never written.  bpmpc_solver_device_dual_solution: the
+ *               device pointers of the same arrays, no synchronisation.
+ *   query       bpmpc_solver_evaluate_dual: t[batch], x[batch][nx] -> lambda[batch][nx], nu[batch][16], rows[batch].  (i, a) of the time segment
+ *               as bpmpc_solver_evaluate_value; multipliers belong to intervals: the rows of node i are taken (an event time belongs to the
+ *               interval that ends there; behind the last node: node n - 1), nu = nu0_i + N_i delta with delta = x - x_lin(t) interpolated as
+ *               in the value query, rows = nc_i, and lambda is that query's dfdx.  inputs_on_device, refusals: as bpmpc_solver_evaluate_value.
+ *   stage       bpmpc_solver_stage(solver, "dual") runs the two kernels on the current buffers, behind a "value" stage.
+ * ------------------------------------------------------------------------------------------------------------- */
+int bpmpc_solver_enable_dual_solution(bpmpc_solver* solver, int on);
+int bpmpc_solver_dual_solution(bpmpc_solver* solver, double* lambda, double* nu, double* nu0, double* nu_gain, double* residual, double* gain_residual,
+                               double* summary, int* status);
+int bpmpc_solver_device_dual_solution(bpmpc_solver* solver, double** lambda_dev, double** nu_dev, double** nu0_dev, double** nu_gain_dev,
+                                      double** residual_dev, double** gain_residual_dev, double** summary_dev, int** status_dev);
+int bpmpc_solver_evaluate_dual(bpmpc_solver* solver, int batch, const double* t, const double* x, int inputs_on_device, double* lambda, double* nu,
+                               int* rows);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * State estimation = BipedalController::updateStateEstimation (bipedal_controllers/src/BipedalController.cpp:188, :360-405) for a BATCH of robots:

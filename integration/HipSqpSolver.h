@@ -40,6 +40,8 @@ struct HipSqpSolverSettings {
   bool useHardFrictionConeConstraint = false;   // the interface's fourth constructor argument (BipedalRobotInterface.h:66-69): cones as inequality constraints
   bool createValueFunction = false;      // getValueFunction(t, x) answers with the value function of the last run's QP (include/bpmpc.h "Value function":
                                          // two more kernels behind every backward pass, the LQ model in materialised form); false: it throws, as SqpSolver does
+  bool createDualSolution = false;       // getStateInputEqualityConstraintLagrangian(t, x) answers with the minimum-norm multipliers of the last run's QP
+                                         // (include/bpmpc.h "Dual solution": the value function's kernels and two more); false: it throws, as SqpSolver does
 };
 
 class HipSqpSolver final : public SolverBase {
@@ -70,8 +72,9 @@ class HipSqpSolver final : public SolverBase {
       throw std::runtime_error("[HipSqpSolver] " + why);
     }
     check(bpmpc_model_dims(model_, &nx_, &nu_, nullptr, nullptr));
-    if (settings_.createValueFunction) {
-      const int on = bpmpc_solver_enable_value_function(solver_, 1);      // (the DDP solver refuses: BPMPC_ERR_UNSUPPORTED)
+    if (settings_.createValueFunction || settings_.createDualSolution) {
+      int on = settings_.createValueFunction ? bpmpc_solver_enable_value_function(solver_, 1) : BPMPC_OK;      // (the DDP solver refuses: BPMPC_ERR_UNSUPPORTED)
+      if (on == BPMPC_OK && settings_.createDualSolution) on = bpmpc_solver_enable_dual_solution(solver_, 1);
       if (on != BPMPC_OK) {
         const std::string why = bpmpc_last_error();
         bpmpc_solver_destroy(solver_);
@@ -133,12 +136,23 @@ class HipSqpSolver final : public SolverBase {
     v.dfdxx = RowMajorMap(hessian.data(), nx_, nx_);
     return v;
   }
+  // A discrete-time QP defines no continuous-time Hamiltonian: getHamiltonian keeps throwing.
   ScalarFunctionQuadraticApproximation getHamiltonian(scalar_t, const vector_t&, const vector_t&) override {
     throw std::runtime_error("[HipSqpSolver] getHamiltonian() not available yet.");
   }
-  vector_t getStateInputEqualityConstraintLagrangian(scalar_t, const vector_t&) const override {
-    throw std::runtime_error("[HipSqpSolver] getStateInputEqualityConstraintLagrangian() not available yet.");
+  /** With Settings::createDualSolution: the Lagrange multipliers of the state-input equality rows of the QP the last run solved, for the interval
+   *  that holds `time`, at `state` (bpmpc_solver_evaluate_dual; the definition that holds - minimum norm, the QP's dt-scaled cost - is the one in
+   *  include/bpmpc.h "Dual solution").  One entry per active row in registration order, as getSolutionMetrics() lays the terms out. */
+  vector_t getStateInputEqualityConstraintLagrangian(scalar_t time, const vector_t& state) const override {
+    if (!settings_.createDualSolution) throw std::runtime_error("[HipSqpSolver] getStateInputEqualityConstraintLagrangian() not available yet.");
+    if (static_cast<int>(state.size()) != nx_) throw std::runtime_error("[HipSqpSolver] state dimension does not match the model");
+    std::vector<double> costate(nx_);
+    double nu[16] = {0};
+    int rows = 0;
+    check(bpmpc_solver_evaluate_dual(solver_, 1, &time, state.data(), 0, costate.data(), nu, &rows));
+    return Eigen::Map<const vector_t>(nu, rows);
   }
+  // The per-term layout of MultiplierCollection is unpinned (no OCS2 source at hand): getIntermediateDualSolution keeps throwing.
   MultiplierCollection getIntermediateDualSolution(scalar_t) const override {
     throw std::runtime_error("[HipSqpSolver] getIntermediateDualSolution() not available yet.");
   }
